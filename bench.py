@@ -1,8 +1,13 @@
 #!/usr/bin/env python3
 """bench.py -- BASELINE.json's metric on its named workload, on N MI355X of one node.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C] [--extra-configs 3,4,5|none]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C] [--dump-outputs DIR] [--full [--extra-configs 3,4,5|none]]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K headline steps, writes the last step's surfaces if --dump-outputs is given and
+prints the result line.  Everything below that is not the headline (the rays actually traced, the free-running / cold /
+scene-update / raster-order / pipelined modes, the CPU baselines, `configs_extra`; at N > 1 the per-rank kernel share, the
+latency split, the assembled-frame self-check and `peer_store`) is measured only with --full.
 
 A "step" is one frame: one pass of the ray-tracing hot path over the workload's pixels, with the scene, textures
 and output surfaces already resident in HBM (the reference re-uploads its <= 4 KB of SSBOs per frame; the
@@ -160,8 +165,26 @@ def roofline_record(cfg, sc, n_px, rays_ref, step_ms, counters, src_hash):
     return out
 
 
-def measure_single(cfg, steps, warmup, variant, dev_index, with_modes=True):
-    """One config on one GPU: fixed-frameCount headline, kernel-only duration, free-running and cold modes."""
+DUMP_PIXELS = 1 << 20                 # 48 MB of float32 for the three rgba surfaces
+DUMP_SEED = 0
+
+
+def dump_outputs(out_dir, col, pos, nrm):
+    """--dump-outputs: the three surfaces of the last timed step (gColor, gPosition rgba32f; gNormal rgba16f, widened exactly)
+    as DIR/<name>.npy, float32 [n, 4].  n = every pixel in raster order up to 2^20 pixels; larger frames (all whole
+    surfaces of 1080p are 99 MB as float32) give the same seeded sample of 2^20 pixels, in raster order, in every run."""
+    n_px = col.shape[0] * col.shape[1]
+    idx = (np.sort(np.random.default_rng(DUMP_SEED).choice(n_px, size=DUMP_PIXELS, replace=False))
+           if n_px > DUMP_PIXELS else np.arange(n_px))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in (("gColor", col), ("gPosition", pos), ("gNormal", nrm)):
+        a = t.cpu().numpy().reshape(n_px, 4)[idx].astype(np.float32)
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+
+
+def measure_single(cfg, steps, warmup, variant, dev_index, with_modes=True, full=True, dump_dir=None):
+    """One config on one GPU: fixed-frameCount headline; with `full` also the rays actually traced, and with `with_modes`
+    the free-running, cold, scene-update, raster-order and pipelined modes."""
     import torch
     from opengl_raytracing_amd import dist as D
     from opengl_raytracing_amd import host, scenes, layout as L
@@ -183,7 +206,7 @@ def measure_single(cfg, steps, warmup, variant, dev_index, with_modes=True):
         rt.render_to(p, col.data_ptr(), pos.data_ptr(), nrm.data_ptr(), stream=stream.cuda_stream)
 
     rays_ref = rt.count_rays(base)
-    rays_traced = rt.count_rays_traced(base)
+    rays_traced = rt.count_rays_traced(base) if full else None
     for _ in range(warmup):
         render(base)
     torch.cuda.synchronize()
@@ -202,6 +225,8 @@ def measure_single(cfg, steps, warmup, variant, dev_index, with_modes=True):
                frame_ms={"median": round(float(np.median(per_frame)), 4), "p10": round(float(np.percentile(per_frame, 10)), 4),
                          "p90": round(float(np.percentile(per_frame, 90)), 4), "min": round(float(per_frame.min()), 4),
                          "max": round(float(per_frame.max()), 4)})
+    if dump_dir:
+        dump_outputs(dump_dir, col, pos, nrm)
     if with_modes:
         # (1) frameCount advancing every frame, as in the reference with TAA on (ForwardShadingPipeline.cpp:254).  Every frame's inputs
         #     are new and its rays differ, so each timed frame is counted.  The bounce sample all pixels share is (nearly) periodic in
@@ -304,10 +329,12 @@ def single_record(cfg, r, steps, warmup, src_hash):
     ms = r["elapsed"] / steps * 1e3
     out = {"workload": workload_name(cfg, sc), "steps": steps, "warmup": warmup, "ms_per_step": round(ms, 4),
            "value_mray_s": round(r["rays_ref"] * steps / r["elapsed"] / 1e6, 1),
-           "mray_s_traced": round(r["rays_traced"] * steps / r["elapsed"] / 1e6, 1),
            "mpx_per_s": round(n_px * steps / r["elapsed"] / 1e6, 1),
-           "rays_reference_per_frame": r["rays_ref"], "rays_traced_per_frame": r["rays_traced"],
+           "rays_reference_per_frame": r["rays_ref"],
            "step_ms_device": round(r["step_ms_dev"], 4), "frame_ms": r["frame_ms"]}
+    if r["rays_traced"] is not None:
+        out["mray_s_traced"] = round(r["rays_traced"] * steps / r["elapsed"] / 1e6, 1)
+        out["rays_traced_per_frame"] = r["rays_traced"]
     # the roofline's duration is the timed region's own (the one `value` is computed from), by HIP events on the launch stream
     out.update(roofline_record(cfg, sc, n_px, r["rays_ref"], r["step_ms_dev"], load_counters(cfg), src_hash))
     for k in ("free_running", "free_running_first_period", "cold_frame_ms", "cold_frame_rays_reference_mean", "scene_update_every_frame_ms",
@@ -403,15 +430,19 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--config", type=int, default=2, help="headline BASELINE.json config 1..5 (default 2 = the metric's)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write the surfaces of the last one as DIR/gColor.npy, gPosition.npy, "
+                         "gNormal.npy (float32 [pixels, 4]; frames above 2^20 pixels: a fixed seeded sample of 2^20)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what is not the headline: rays traced, the N = 1 modes, the CPU baselines, "
+                         "`configs_extra`; at N > 1 the kernel share, latency, assembled-frame check and peer store")
     ap.add_argument("--extra-configs", default="3,4,5",
-                    help="further configs measured after the headline and reported under `configs_extra` "
+                    help="with --full: further configs measured after the headline and reported under `configs_extra` "
                          "(N = 1: comma list, default 3,4,5; N > 1: default 5 = the 8K frame the tiling was designed for); 'none' skips")
     ap.add_argument("--no-modes", action="store_true",
-                    help="N = 1: skip the free-running-frameCount and raster-order (cold) measurements, so that every launch of the "
-                         "dominant kernel in the process belongs to the headline loop (profiles/run_profile.sh uses this: "
-                         "rocprofv3's per-kernel average is then the headline's step_ms_device minus the launch gaps)")
+                    help="with --full, N = 1: skip the free-running-frameCount and raster-order (cold) measurements")
     ap.add_argument("--strip-rows", type=int, default=0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--variant", type=int, default=1, help="1 = packet kernel (default), 0 = exhaustive loop")
     ap.add_argument("--frames-in-flight", type=int, default=0,
                     help="frames overlapping on the device, each on its own render stream (1..4; default 3 at N>1, "
@@ -454,7 +485,8 @@ def main():
 
     # ------------------------------------------------------------------------------------------------ N = 1
     if world == 1 and (args.frames_in_flight or 0) <= 1:
-        r = measure_single(args.config, args.steps, args.warmup, args.variant, local_rank, with_modes=not args.no_modes)
+        r = measure_single(args.config, args.steps, args.warmup, args.variant, local_rank,
+                           with_modes=args.full and not args.no_modes, full=args.full, dump_dir=args.dump_outputs)
         rec = single_record(args.config, r, args.steps, args.warmup, src_hash)
         sc = r["sc"]
         out = {"metric": "Mray/s", "value": rec["value_mray_s"], "unit": "Mray/s", "n_gpus": 1, "steps": args.steps,
@@ -476,7 +508,7 @@ def main():
                                    "peak_TFLOPs": FP32_VALU_PEAK_TFLOPS,
                                    "note": "flops of the EXHAUSTIVE traversal (SURVEY.md 8(d)); packet culling skips most of "
                                            "them, so this is work-equivalent throughput, not a utilisation"}
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             from oracle import binding as O   # checker / reported baseline only
             O.load()
             threads = host_threads()
@@ -493,12 +525,13 @@ def main():
                                    "sample": f"{n_frames} whole frame(s) of the same workload ({r_cpu} rays each) in "
                                              f"{t_cpu:.1f} s; scalar fp32 C restatement (oracle/rt_oracle.c), OpenMP over rows",
                                    "ms_per_frame": round(t_cpu / n_frames * 1e3, 1)}
-        try:      # the reference's own GLSL on llvmpipe: static record from the build container (cannot run on the box)
-            ref = json.load(open(os.path.join(REPO, "profiles", "reference_llvmpipe_timing.json")))
-            out["cpu_baseline_reference"] = ref.get(f"c{args.config}", ref)
-        except Exception:
-            out["cpu_baseline_reference"] = None
-        if extra:
+        if args.full:
+            try:      # the reference's own GLSL on llvmpipe: a static record (the reference is not present on GPU hosts)
+                ref = json.load(open(os.path.join(REPO, "profiles", "reference_llvmpipe_timing.json")))
+                out["cpu_baseline_reference"] = ref.get(f"c{args.config}", ref)
+            except Exception:
+                out["cpu_baseline_reference"] = None
+        if args.full and extra:
             out["configs_extra"] = {}
             for c in extra:
                 k = max(5, min(args.steps, 20))
@@ -541,7 +574,7 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    def run_config(cfg, steps, warmup, autotune):
+    def run_config(cfg, steps, warmup, autotune, dump_dir=None):
         sc = scenes.make_scene(cfg, host.generate_aabb)
         W, H = sc.width, sc.height
         base = sc.params()
@@ -640,7 +673,7 @@ def main():
         s_col, s_pos, s_nrm = pipe.views[0]
 
         # exact ray counts of this rank's pixels (instrumented launches, outside the timed region)
-        counts = torch.tensor([rt.count_rays(p), rt.count_rays_traced(p)], dtype=torch.int64, device=red_dev)
+        counts = torch.tensor([rt.count_rays(p), rt.count_rays_traced(p) if args.full else 0], dtype=torch.int64, device=red_dev)
         my_rays = int(counts[0].item())
         if world > 1:
             dist.all_reduce(counts)
@@ -667,20 +700,24 @@ def main():
         if world > 1:
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+        step_ms_dev = ev0.elapsed_time(ev1) / steps
+        if dump_dir and rank == 0:        # the last step's frame: assembled on rank 0 at N > 1, else the slot rendered last
+            dump_outputs(dump_dir, *(full if world > 1 else pipe.views[(pipe.k - 1) % F]))
 
         # this rank's render share: kernel launches only, back to back on one stream (HIP events)
-        kev0, kev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        kev0.record(stream)
-        for _ in range(steps):
-            rt.render_to(p, s_col.data_ptr(), s_pos.data_ptr(), s_nrm.data_ptr(), stream=stream.cuda_stream)
-        kev1.record(stream)
-        torch.cuda.synchronize()
-        kernel_ms = kev0.elapsed_time(kev1) / steps
-        step_ms_dev = ev0.elapsed_time(ev1) / steps
+        kernel_ms = None
+        if args.full:
+            kev0, kev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            kev0.record(stream)
+            for _ in range(steps):
+                rt.render_to(p, s_col.data_ptr(), s_pos.data_ptr(), s_nrm.data_ptr(), stream=stream.cuda_stream)
+            kev1.record(stream)
+            torch.cuda.synchronize()
+            kernel_ms = kev0.elapsed_time(kev1) / steps
 
         # frame LATENCY (one frame at a time, nothing overlapped) and its parts, per rank
         lat = None
-        if world > 1:
+        if world > 1 and args.full:
             n_lat = max(3, min(steps, 10))
             e = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
             t_lat, t_render, t_comm = 0.0, 0.0, 0.0
@@ -713,7 +750,7 @@ def main():
 
         # untimed self-check at N > 1: the assembled frame must equal a single-GPU render bit for bit
         assembled_ok = None
-        if world > 1 and rank == 0:
+        if world > 1 and rank == 0 and args.full:
             one = D.StripPlan(W, H, H, 1)
             ref_buf = D.alloc_rank_buffer(one, dev)
             rc, rp, rn = D.surface_views(ref_buf, one)
@@ -729,10 +766,8 @@ def main():
             rec = {"workload": workload_name(cfg, sc), "steps": steps, "warmup": warmup,
                    "ms_per_step": round(elapsed / steps * 1e3, 4),
                    "value_mray_s": round(frame_rays * steps / elapsed / 1e6, 1),
-                   "mray_s_traced": round(frame_traced * steps / elapsed / 1e6, 1),
                    "mpx_per_s": round(n_px * steps / elapsed / 1e6, 1),
-                   "rays_reference_per_frame": frame_rays, "rays_traced_per_frame": frame_traced,
-                   "rank0_render_share_kernel_ms": round(kernel_ms, 4), "step_ms_device": round(step_ms_dev, 4),
+                   "rays_reference_per_frame": frame_rays, "step_ms_device": round(step_ms_dev, 4),
                    "width": W, "height": H, "max_ray_depth": sc.max_ray_depth,
                    "parallelism": (f"{world} ranks x interleaved {strip_rows}-row strips, rank 0 owns {root_weight} of every "
                                    f"{root_weight + world - 1} (its rows stay local), one RCCL gather/frame of the 30 B/px "
@@ -743,18 +778,23 @@ def main():
                    "bytes_into_rank0_per_frame": (plan.wire_bytes * (world - 1)) if world > 1 else 0,
                    "rank0_pixels": my_px, "rank0_rays_reference": my_rays,
                    "assembled_frame_equals_single_gpu_render": assembled_ok, "latency": lat}
+            if args.full:
+                rec.update({"mray_s_traced": round(frame_traced * steps / elapsed / 1e6, 1), "rays_traced_per_frame": frame_traced,
+                            "rank0_render_share_kernel_ms": round(kernel_ms, 4)})
         rt.close()
         return rec
 
-    head = run_config(args.config, args.steps, args.warmup, autotune=True)
+    head = run_config(args.config, args.steps, args.warmup, autotune=True, dump_dir=args.dump_outputs)
     extras = {}
     if world > 1 and args.extra_configs == "3,4,5":
         extra = [5] if args.config != 5 else []          # the frame the tiling was designed for
+    if not args.full:
+        extra = []
     for c in extra:
         k = max(3, min(args.steps, 10))
         extras[f"c{c}"] = run_config(c, k, 2, autotune=False)
     peer = None
-    if world > 1 and not args.no_peer_store:
+    if world > 1 and args.full and not args.no_peer_store:
         # the other ranks wait on the rendezvous store (host side): an RCCL barrier would spin on their GPUs meanwhile
         torch.cuda.synchronize()
         dist.barrier()

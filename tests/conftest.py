@@ -1,3 +1,4 @@
+import glob
 import os
 import sys
 
@@ -76,11 +77,25 @@ class GoldenScene:
         self.skybox = scenes.procedural_skybox(512) if self.use_skybox else None
 
 
+class Fixture(dict):
+    """The arrays of one golden fixture, by name (as np.load's NpzFile gives them)."""
+
+    @property
+    def files(self):
+        return list(self)
+
+
 def load_golden(name):
-    path = os.path.join(GOLDEN_DIR, f"{name}.npz")
-    if not os.path.exists(path):
+    """tests/golden/<name>.npz, or the union of its shards <name>.part1.npz, <name>.part2.npz, ... (make_golden.py splits
+    a fixture that would pass the repository's 1 MiB file limit)."""
+    paths = sorted(glob.glob(os.path.join(GOLDEN_DIR, f"{name}.part*.npz"))) or [os.path.join(GOLDEN_DIR, f"{name}.npz")]
+    if not os.path.exists(paths[0]):
         pytest.skip(f"golden fixture {name}.npz not generated")
-    return np.load(path)
+    out = Fixture()
+    for path in paths:
+        with np.load(path) as z:
+            out.update({k: z[k] for k in z.files})
+    return out
 
 
 def params_from_bytes(b):

@@ -33,6 +33,19 @@ from opengl_raytracing_amd import host, scenes  # noqa: E402
 from oracle import binding as O  # noqa: E402
 
 OUT = os.path.dirname(os.path.abspath(__file__))
+SHARDS = {"c5_8k": [["objects", "lights", "params", "tan_bits", "frame_count", "max_ray_depth", "strip_dispatch_s",
+                     "column_dispatch_s", "win8k_origins", "win8k_color", "renderer"], ["win8k_pos", "win8k_normal"]],
+          "trig": [["trig_in", "trig_out"], ["fov_in", "fov_tan", "explog_in"], ["explog_out"]]}
+
+
+def save_sharded(name, data):
+    """<name>.part1.npz, <name>.part2.npz, ... with the keys of SHARDS[name] (conftest.load_golden joins them): every
+    committed file stays under 1 MiB."""
+    assert sorted(k for part in SHARDS[name] for k in part) == sorted(data)
+    for i, keys in enumerate(SHARDS[name], 1):
+        np.savez_compressed(os.path.join(OUT, f"{name}.part{i}.npz"), **{k: data[k] for k in keys})
+
+
 WIN = 32
 WINDOW_FRACS = [(0.10, 0.10), (0.50, 0.20), (0.80, 0.15), (0.30, 0.45),
                 (0.60, 0.50), (0.45, 0.30), (0.20, 0.70), (0.70, 0.75)]
@@ -408,12 +421,12 @@ def make_c5_8k(strip_groups_y=24, column_groups_x=4, win=48):
     data["win8k_origins"] = np.array(origins, dtype=np.int32)
     data["win8k_color"], data["win8k_pos"], data["win8k_normal"] = np.stack(cols), np.stack(poss), np.stack(nrms)
     data["renderer"] = np.array(info["renderer"] + " / " + info["version"])
-    np.savez_compressed(os.path.join(OUT, "c5_8k.npz"), **data)
+    save_sharded("c5_8k", data)
     print(f"  [c5_8k] {len(origins)} windows of {win}x{win} written", flush=True)
 
 
 def make_trig():
-    """llvmpipe's sin / cos / tan / log2 / exp2 / pow(x,5) / exp, bitwise (trig.npz).  Pins oracle/rt_oracle.c's
+    """llvmpipe's sin / cos / tan / log2 / exp2 / pow(x,5) / exp, bitwise (trig.part*.npz).  Pins oracle/rt_oracle.c's
     mesa_* restatements (gallivm's cephes-style sincos with fused multiply-adds, polynomial log2 / exp2): the
     camera's tan(radians(fov)*0.5), cosineWeightedHemisphere's cos/sin(phi), random()'s sin(large), SSS's exp."""
     rng = np.random.default_rng(7)
@@ -451,7 +464,7 @@ void main(){ uint i=gl_GlobalInvocationID.x; float a=xin[i]; xout[4u*i]=log2(a);
 """
     out["explog_in"] = y
     out["explog_out"] = O.run_probe(glsl, y, np.float32, 4 * n, n // 64).reshape(n, 4)
-    np.savez_compressed(os.path.join(OUT, "trig.npz"), **out)
+    save_sharded("trig", out)
     print("  [trig] written", flush=True)
 
 

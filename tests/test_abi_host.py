@@ -11,7 +11,7 @@ import subprocess
 import numpy as np
 import pytest
 
-from conftest import load_golden
+from conftest import GOLDEN_DIR, load_golden
 from opengl_raytracing_amd import layout as L
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -167,12 +167,10 @@ def test_scene_writer_round_trip(host):
         np.testing.assert_allclose(l2[fld], lts[fld], rtol=1e-5, err_msg=fld)
 
 
-@pytest.mark.reference
 def test_scene_parser_on_the_reference_scene_files(host):
-    """The three shipped scenes (/root/reference/res/Scene) parse to the counts SURVEY.md lists."""
-    root = "/root/reference/res/Scene"
-    if not os.path.isdir(root):
-        pytest.skip("reference not mounted")
+    """The three scenes the reference ships (res/Scene, copied verbatim to tests/golden/scenes) parse to the counts
+    SURVEY.md lists."""
+    root = os.path.join(GOLDEN_DIR, "scenes")
     want = {"default.scene": (4, 3), "SIMPLE.scene": (15, 3), "performance_test.scene": (15, 8)}
     for name, (no, nl) in want.items():
         objs, lts = host.parse_scene(open(os.path.join(root, name)).read())
