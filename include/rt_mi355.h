@@ -236,6 +236,37 @@ int rt_debug_shadow_tables(rt_context *ctx, uint32_t *out, size_t capDwords, siz
  * sin, cos, tan, exp of in[i].  Test hook (no GPU needed), no reference counterpart. */
 int rt_debug_mesa_math(const float *in, float *out, int n);
 
+/* ---- ray queries on the scene of the last rt_set_scene: the shader's intersectObjects (raytracingCs.glsl:155-196)
+ *      outside a frame, for the questions a host asks about the scene (which object is under the mouse, is a segment
+ *      blocked, where does a ray first hit).  No reference counterpart: the reference's editor can only pick from a list
+ *      (ImGUIManager::DrawObjectsList).  Same fp32 arithmetic as the render kernels, bit for bit.
+ *
+ * rt_ray (32 B): the ray o + d*t, 0 < t < tMax.  d need not be normalised.  reserved is ignored (write 0).
+ * rt_hit (32 B), RT_QUERY_CLOSEST: intersectObjects with maxRayDistance replaced by the ray's tMax -- the AABB cull
+ *      uses tMax, minT starts at tMax, equal t keeps the lower object index.  Hit: object = index into the caller's
+ *      object array, t = hit distance, position = o + d*t, normal = normalize(o + d*t - centre) for a sphere and the
+ *      raw (unnormalised) plane normal for a plane -- the render kernels' P and N.  Miss: object = -1, t = tMax
+ *      (the shader's minT), position and normal 0.  A ray whose tMax is <= 0 or NaN misses.
+ * RT_QUERY_ANY: one int32_t per ray, 1 iff some object passes the AABB cull and the shape test with 0 < t < tMax,
+ *      else 0; equal to (closest.object >= 0) for every ray. */
+typedef struct rt_ray { float origin[3]; float tMax; float direction[3]; int32_t reserved; } rt_ray;
+typedef struct rt_hit { float position[3]; float t; float normal[3]; int32_t object; } rt_hit;
+typedef enum rt_query_mode { RT_QUERY_CLOSEST = 0, RT_QUERY_ANY = 1 } rt_query_mode;
+
+/* nRays rays (device, rt_ray) -> nRays rt_hit (CLOSEST) or int32_t (ANY) (device).  Both pointers 16-byte aligned.
+ * nRays == 0 is a no-op.  RT_ERR_INVALID_ARG: NULL / misaligned pointer, unknown mode, no scene set.  Asynchronous
+ * on hipStream (NULL = the context's stream), ordered with rt_set_scene like rt_render_to. */
+int rt_trace_rays(rt_context *ctx, const void *dRays, size_t nRays, int mode, void *dOut, void *hipStream);
+/* The primary rays of rt_render_to(p): regionW x regionH rt_ray (device, 16-byte aligned) in exactly the surface
+ * layout rt_render_to writes for the same p (local rows, window, strips), bit-identical to the rays the renderer
+ * traces (noise jitter, frameCount, the GL's tan); tMax = p->maxRayDistance.  Window pixels outside the image get an
+ * all-zero record (zero direction, tMax = 0: they miss).  Asynchronous on hipStream (NULL = the context's stream). */
+int rt_camera_rays(rt_context *ctx, const rt_params *p, void *dRays, void *hipStream);
+/* Closest hit of the primary ray of IMAGE pixel (px, py) (row 0 = bottom, as in the surfaces; the window and strip
+ * fields of p are ignored) -- click-to-select.  Synchronous on the context's stream.  A pixel outside the image or
+ * no scene set: RT_ERR_INVALID_ARG. */
+int rt_pick(rt_context *ctx, const rt_params *p, int px, int py, rt_hit *hit);
+
 const char *rt_last_error(rt_context *ctx);
 
 /* ---- host-side feeders of the byte contract (no GPU needed) */
@@ -420,6 +451,10 @@ RT_SA(offsetof(rt_light, shadowSoftness) == 72 && offsetof(rt_light, shadowType)
 RT_SA(offsetof(rt_light, pcfSamples) == 80 && offsetof(rt_light, lightSize) == 84, "Light.pcfSamples/lightSize");
 RT_SA(offsetof(rt_light, angularRadius) == 88, "Light.angularRadius");
 RT_SA(sizeof(rt_params) == 128, "rt_params is 128 B");
+RT_SA(sizeof(rt_ray) == 32 && offsetof(rt_ray, tMax) == 12 && offsetof(rt_ray, direction) == 16 && offsetof(rt_ray, reserved) == 28,
+      "rt_ray layout");
+RT_SA(sizeof(rt_hit) == 32 && offsetof(rt_hit, t) == 12 && offsetof(rt_hit, normal) == 16 && offsetof(rt_hit, object) == 28,
+      "rt_hit layout");
 #undef RT_SA
 #endif
 

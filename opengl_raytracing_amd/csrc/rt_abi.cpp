@@ -118,6 +118,9 @@ struct rt_context {
     bool phaseOn = true;                       // RT_PHASE_ORDER=0 switches it off (measurements)
     bool haveLastFc = false;
     int lastFc = 0, freeRun = 0;               // consecutive scheduled launches whose frameCount differed from the previous one's
+    // rt_pick: the hit record on the device and its pinned host copy
+    float4 *dPick = nullptr;
+    rt_hit *hPick = nullptr;
     std::string err;
 };
 
@@ -532,6 +535,8 @@ int rt_destroy(rt_context *c) {
     if (c->evStart) (void)hipEventDestroy(c->evStart);
     if (c->evStop) (void)hipEventDestroy(c->evStop);
     if (c->evScene) (void)hipEventDestroy(c->evScene);
+    if (c->dPick) (void)hipFree(c->dPick);
+    if (c->hPick) (void)hipHostFree(c->hPick);
     for (int k = 0; k < 2; k++)
         if (c->evSort[k]) (void)hipEventDestroy(c->evSort[k]);
     for (int k = 0; k < 2; k++) {
@@ -699,6 +704,82 @@ int rt_render_into_image(rt_context *c, const rt_params *p, void *dColorImage, v
     hipStream_t s = hipStream ? (hipStream_t)hipStream : c->stream;
     if (s != c->stream) HIP_TRY(c, hipStreamWaitEvent(s, c->evScene, 0));
     return launch(c, p, (float4 *)dColorImage, (float4 *)dPositionImage, (uint2 *)dNormalImage, nullptr, s, true, 1, true);
+}
+
+// ---- ray queries (rt_query.inc).  They read the compiled scene, so they join the render launches' stream protocol: a
+// foreign stream first waits for the last scene upload, and every launch records its stream's `last` event, which
+// rt_set_scene orders the next rewrite behind.  No scheduling state, timing event or feedback buffer is touched.
+static int query_stream(rt_context *c, void *hipStream, hipStream_t *out) {
+    hipStream_t s = hipStream ? (hipStream_t)hipStream : c->stream;
+    if (s != c->stream) HIP_TRY(c, hipStreamWaitEvent(s, c->evScene, 0));
+    *out = s;
+    return RT_OK;
+}
+
+static int query_record(rt_context *c, hipStream_t s) {
+    rt_context::FbStream *mine = nullptr;
+    const int rc = stream_record(c, s, &mine);
+    if (rc) return rc;
+    HIP_TRY(c, hipEventRecord(mine->last, s));
+    return RT_OK;
+}
+
+int rt_trace_rays(rt_context *c, const void *dRays, size_t nRays, int mode, void *dOut, void *hipStream) {
+    if (!c) return RT_ERR_INVALID_ARG;
+    if (mode != RT_QUERY_CLOSEST && mode != RT_QUERY_ANY) return fail(c, RT_ERR_INVALID_ARG, "unknown query mode");
+    if (!c->dCompiled) return fail(c, RT_ERR_INVALID_ARG, "rt_set_scene has not been called");
+    if (nRays == 0) return RT_OK;
+    if (!dRays || !dOut) return fail(c, RT_ERR_INVALID_ARG, "NULL ray or result pointer");
+    if (((uintptr_t)dRays | (uintptr_t)dOut) & 15u) return fail(c, RT_ERR_INVALID_ARG, "ray and result pointers must be 16-byte aligned");
+    if (nRays > ((size_t)0x7fffffff) * 256) return fail(c, RT_ERR_TOO_LARGE, "too many rays in one call");
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t s;
+    int rc = query_stream(c, hipStream, &s);
+    if (rc) return rc;
+    HIP_TRY(c, rt_launch_trace_rays((const float4 *)dRays, nRays, c->dCompiled, c->nObj, mode == RT_QUERY_ANY, dOut, s));
+    return query_record(c, s);
+}
+
+int rt_camera_rays(rt_context *c, const rt_params *p, void *dRays, void *hipStream) {
+    if (!c) return RT_ERR_INVALID_ARG;
+    int rc = validate_params(c, p);
+    if (rc) return rc;
+    if (!dRays) return fail(c, RT_ERR_INVALID_ARG, "NULL ray pointer");
+    if ((uintptr_t)dRays & 15u) return fail(c, RT_ERR_INVALID_ARG, "ray pointer must be 16-byte aligned");
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t s;
+    if ((rc = query_stream(c, hipStream, &s))) return rc;
+    RtFrame f;
+    build_frame(c, p, &f);
+    HIP_TRY(c, rt_launch_camera_rays(f, c->dNoise, (float4 *)dRays, s));
+    return query_record(c, s);      // rt_set_noise drains it before freeing the texture
+}
+
+int rt_pick(rt_context *c, const rt_params *p, int px, int py, rt_hit *hit) {
+    if (!c) return RT_ERR_INVALID_ARG;
+    if (!hit) return fail(c, RT_ERR_INVALID_ARG, "NULL hit pointer");
+    if (!p) return fail(c, RT_ERR_INVALID_ARG, "params is NULL");
+    // only the camera, image size and ray fields matter: validate them with an identity window
+    rt_params q = *p;
+    q.x0 = q.y0 = 0;
+    q.regionW = q.width;
+    q.regionH = q.height;
+    q.stripRows = q.stripCount = 1;
+    q.stripIndex = q.stripCycleRows = q.stripOffsetRows = 0;
+    int rc = validate_params(c, &q);
+    if (rc) return rc;
+    if (px < 0 || py < 0 || px >= q.width || py >= q.height) return fail(c, RT_ERR_INVALID_ARG, "pixel outside the image");
+    if (!c->dCompiled) return fail(c, RT_ERR_INVALID_ARG, "rt_set_scene has not been called");
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (!c->dPick) HIP_TRY(c, hipMalloc((void **)&c->dPick, 2 * sizeof(float4)));
+    if (!c->hPick) HIP_TRY(c, hipHostMalloc((void **)&c->hPick, sizeof(rt_hit), hipHostMallocDefault));
+    RtFrame f;
+    build_frame(c, &q, &f);
+    HIP_TRY(c, rt_launch_pick(f, c->dNoise, c->dCompiled, px, py, c->dPick, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->hPick, c->dPick, sizeof(rt_hit), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    memcpy(hit, c->hPick, sizeof(rt_hit));
+    return RT_OK;
 }
 
 int rt_context_stream(rt_context *c, void **hipStream) {

@@ -106,3 +106,9 @@ hipError_t rt_launch_wire_unpack(const void *dWire, size_t rankStrideBytes, size
                                  void *dNormal, int width, int height, int stripRows, int stripCount, hipStream_t s);
 hipError_t rt_launch_deinterleave(const void *src, void *dst, int width, int height, int bytesPerPixel,
                                   int stripRows, int stripCount, size_t rankStrideBytes, hipStream_t s);
+// Ray queries (rt_query.inc).  dRays / dOut: 2 float4 per ray / hit (rt_ray / rt_hit), anyHit: one int per ray.
+hipError_t rt_launch_trace_rays(const float4 *dRays, size_t nRays, const float4 *dCompiled, int nObj, int anyHit, void *dOut,
+                                hipStream_t s);
+hipError_t rt_launch_camera_rays(const RtFrame &f, const uint8_t *dNoise, float4 *dRays, hipStream_t s);
+hipError_t rt_launch_pick(const RtFrame &f, const uint8_t *dNoise, const float4 *dCompiled, int px, int py, float4 *dOut,
+                          hipStream_t s);

@@ -1273,3 +1273,8 @@ hipError_t rt_launch_wire_unpack(const void *dWire, size_t rankStrideBytes, size
                        (float4 *)dColor, (float4 *)dPos, (uint2 *)dNormal, width, height, stripRows, stripCount);
     return hipGetLastError();
 }
+
+// =========================================================================================
+// Ray queries (rt_trace_rays / rt_camera_rays / rt_pick): same helpers, separate kernels.
+// =========================================================================================
+#include "rt_query.inc"

@@ -18,6 +18,7 @@ blue-noise texture                     ``RayTracer.set_noise(r8)``
 There is no CPU fallback: if the HIP library is missing or no GPU is present the calls
 raise ``RtError``.
 """
+import collections
 import ctypes
 import os
 
@@ -37,7 +38,7 @@ EXPORTS = [
     "rt_wire_bytes", "rt_wire_pack", "rt_wire_unpack", "rt_debug_mesa_math", "rt_debug_shadow_tables", "rt_debug_predicted_classes",
     "rt_render_into_image", "rt_context_stream", "rt_mgpu_create", "rt_mgpu_destroy", "rt_mgpu_device_count", "rt_mgpu_set_scene", "rt_mgpu_set_noise",
     "rt_mgpu_set_skybox", "rt_mgpu_set_strip_rows", "rt_mgpu_render", "rt_mgpu_sync", "rt_mgpu_get_surfaces", "rt_mgpu_readback", "rt_mgpu_last_ms",
-    "rt_mgpu_last_error",
+    "rt_mgpu_last_error", "rt_trace_rays", "rt_camera_rays", "rt_pick",
 ]
 
 
@@ -148,6 +149,9 @@ def load_library(build_if_missing=True):
     lib.rt_mgpu_last_ms.argtypes = [vp, P(ctypes.c_float), ci]
     lib.rt_mgpu_last_error.argtypes = [vp]
     lib.rt_mgpu_last_error.restype = ctypes.c_char_p
+    lib.rt_trace_rays.argtypes = [vp, vp, ctypes.c_size_t, ci, vp, vp]
+    lib.rt_camera_rays.argtypes = [vp, P(L.RtParams), vp, vp]
+    lib.rt_pick.argtypes = [vp, P(L.RtParams), ci, ci, P(L.RtHit)]
     for name in EXPORTS:
         if name not in ("rt_last_error", "rt_mgpu_last_error", "rt_wire_bytes"):
             getattr(lib, name).restype = ci
@@ -265,6 +269,18 @@ def strip_local_rows(height, strip_rows, strip_count, strip_index):
     return n
 
 
+PickHit = collections.namedtuple("PickHit", "object t position normal")
+PickHit.__doc__ = """rt_pick's answer: object index (-1 = nothing under the pixel), hit distance (tMax on a miss), hit position and
+normal (float32[3] each; zero on a miss)."""
+
+
+def _query_mode(mode):
+    m = {"closest": L.QUERY_CLOSEST, "any": L.QUERY_ANY}.get(mode, mode)
+    if m not in (L.QUERY_CLOSEST, L.QUERY_ANY):
+        raise ValueError(f"mode must be 'closest' or 'any', not {mode!r}")
+    return m
+
+
 # ---- the device context ---------------------------------------------------------------------
 class RayTracer:
     def __init__(self, device=0):
@@ -340,6 +356,74 @@ class RayTracer:
         self._check(self.lib.rt_render_to(self.ctx, ctypes.byref(params), ctypes.c_void_p(d_color),
                                           ctypes.c_void_p(d_position), ctypes.c_void_p(d_normal),
                                           ctypes.c_void_p(stream) if stream else None), "rt_render_to")
+
+    # ---- ray queries -------------------------------------------------------------------------
+    def _on_torch_stream(self, stream, launch):
+        """launch(hipStream_t) asynchronously in the order of torch stream `stream` (default: the current one).  torch's
+        default stream has the handle 0, which the C ABI reads as "the context's stream": then the launch goes to the
+        context's stream, fenced on both sides with events against torch's stream."""
+        import torch
+        s = stream if stream is not None else torch.cuda.current_stream()
+        h = s.cuda_stream if hasattr(s, "cuda_stream") else int(s)
+        if h:
+            launch(h)
+            return
+        if not hasattr(self, "_ctx_stream"):
+            cs = ctypes.c_void_p()
+            self._check(self.lib.rt_context_stream(self.ctx, ctypes.byref(cs)), "rt_context_stream")
+            self._ctx_stream = torch.cuda.ExternalStream(cs.value)
+        self._ctx_stream.wait_stream(s)
+        launch(self._ctx_stream.cuda_stream)
+        s.wait_stream(self._ctx_stream)
+
+    def trace_rays(self, rays, mode="closest", out=None, stream=None):
+        """Closest-hit ("closest") or any-hit ("any") query of the current scene.
+
+        rays: a CUDA torch tensor float32 [..., 8] (rt_ray per row: origin, tMax, direction, reserved) -> a CUDA torch
+        tensor, asynchronous on `stream` (default torch.cuda.current_stream()): closest float32 [..., 8] (rt_hit: position,
+        t, normal, object -- the last column holds int32 bits, `.view(torch.int32)[..., 7]`), any int32 [...].  `out`
+        may supply it.  Or a numpy array (RAY_DTYPE records or float32 [..., 8]) -> numpy HIT_DTYPE records / int32,
+        synchronously."""
+        m = _query_mode(mode)
+        if isinstance(rays, np.ndarray):
+            import torch
+            a = np.ascontiguousarray(rays)
+            if a.dtype == L.RAY_DTYPE:
+                shape, flat = a.shape, a.view(np.float32).reshape(-1, 8)
+            else:
+                assert a.dtype == np.float32 and a.shape[-1] == 8, "numpy rays: RAY_DTYPE records or float32 [..., 8]"
+                shape, flat = a.shape[:-1], a.reshape(-1, 8)
+            d = self.trace_rays(torch.from_numpy(flat.copy()).cuda(), m)
+            torch.cuda.current_stream().synchronize()
+            h = d.cpu().numpy()
+            return h.view(L.HIT_DTYPE).reshape(shape) if m == L.QUERY_CLOSEST else h.reshape(shape)
+        import torch
+        assert rays.is_cuda and rays.dtype == torch.float32 and rays.shape[-1] == 8, "rays: CUDA float32 [..., 8]"
+        rays = rays.contiguous()
+        shape = tuple(rays.shape[:-1])
+        if out is None:
+            out = (torch.empty(shape + (8,), dtype=torch.float32, device=rays.device) if m == L.QUERY_CLOSEST
+                   else torch.empty(shape, dtype=torch.int32, device=rays.device))
+        assert out.is_contiguous() and out.numel() * out.element_size() == rays.numel() // 8 * (32 if m == L.QUERY_CLOSEST else 4)
+        n = rays.numel() // 8
+        self._on_torch_stream(stream, lambda h: self._check(self.lib.rt_trace_rays(
+            self.ctx, ctypes.c_void_p(rays.data_ptr()), n, m, ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(h)), "rt_trace_rays"))
+        return out
+
+    def camera_rays(self, params, stream=None):
+        """The primary rays of render(params): CUDA float32 [regionH, regionW, 8] (rt_ray, surface layout),
+        asynchronous on `stream` (default torch.cuda.current_stream())."""
+        import torch
+        out = torch.empty((params.regionH, params.regionW, 8), dtype=torch.float32, device="cuda")
+        self._on_torch_stream(stream, lambda h: self._check(self.lib.rt_camera_rays(
+            self.ctx, ctypes.byref(params), ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(h)), "rt_camera_rays"))
+        return out
+
+    def pick(self, params, x, y):
+        """Closest hit of the primary ray of image pixel (x, y), row 0 = bottom (rt_pick) -> PickHit."""
+        h = L.RtHit()
+        self._check(self.lib.rt_pick(self.ctx, ctypes.byref(params), int(x), int(y), ctypes.byref(h)), "rt_pick")
+        return PickHit(h.object, h.t, np.array(h.position, dtype=np.float32), np.array(h.normal, dtype=np.float32))
 
     def sync(self):
         self._check(self.lib.rt_sync(self.ctx), "rt_sync")

@@ -170,3 +170,29 @@ def copy_params(p, **updates):
         else:
             setattr(q, k, v)
     return q
+
+
+# ---- ray queries (rt_trace_rays / rt_camera_rays / rt_pick, include/rt_mi355.h) ---------------
+QUERY_CLOSEST, QUERY_ANY = 0, 1
+
+RAY_DTYPE = np.dtype({"names": ["origin", "tMax", "direction", "reserved"],
+                      "formats": [("<f4", 3), "<f4", ("<f4", 3), "<i4"],
+                      "offsets": [0, 12, 16, 28], "itemsize": 32})
+HIT_DTYPE = np.dtype({"names": ["position", "t", "normal", "object"],
+                      "formats": [("<f4", 3), "<f4", ("<f4", 3), "<i4"],
+                      "offsets": [0, 12, 16, 28], "itemsize": 32})
+
+
+class RtRay(ctypes.Structure):
+    """``rt_ray``: the ray origin + direction * t, 0 < t < tMax."""
+    _fields_ = [("origin", ctypes.c_float * 3), ("tMax", ctypes.c_float), ("direction", ctypes.c_float * 3),
+                ("reserved", ctypes.c_int32)]
+
+
+class RtHit(ctypes.Structure):
+    """``rt_hit``: closest hit (object -1 = miss, then t = tMax and position / normal 0)."""
+    _fields_ = [("position", ctypes.c_float * 3), ("t", ctypes.c_float), ("normal", ctypes.c_float * 3),
+                ("object", ctypes.c_int32)]
+
+
+assert ctypes.sizeof(RtRay) == RAY_DTYPE.itemsize == 32 and ctypes.sizeof(RtHit) == HIT_DTYPE.itemsize == 32
