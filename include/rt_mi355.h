@@ -267,6 +267,36 @@ int rt_camera_rays(rt_context *ctx, const rt_params *p, void *dRays, void *hipSt
  * no scene set: RT_ERR_INVALID_ARG. */
 int rt_pick(rt_context *ctx, const rt_params *p, int px, int py, rt_hit *hit);
 
+/* ---- ray shading on the scene of the last rt_set_scene: main() of raytracingCs.glsl (:509-584) on caller-supplied rays,
+ *      for what a frame's pinhole camera cannot ask (cubemap / environment probes, panoramas, stereo, fisheye or
+ *      orthographic views, re-shading a sparse set of pixels).  No reference counterpart.  Same fp32 arithmetic as the
+ *      render kernels, bit for bit.
+ *
+ * rt_pixel (8 B): the gl_GlobalInvocationID.xy ray k is shaded as.  It feeds only the noise tap sample_noise(x, y) that
+ *      PCF's jitter reads (:359) and the Russian roulette's random(gid + depth) (:547).
+ * Ray k runs main() with generateCameraRay replaced by the ray's (origin, direction), taken as given (no normalisation,
+ *      no jitter).  The primary segment (depth 0) runs intersectObjects with maxRayDistance replaced by the ray's tMax --
+ *      the AABB cull and where minT starts, as rt_trace_rays CLOSEST; every later bounce and every shadow, PCSS-blocker
+ *      and SSS ray uses p->maxRayDistance.  p->frameCount (hammersley rows, noise offset), maxRayDepth, maxRayDistance,
+ *      useSkybox and noiseScale keep their meaning; the camera fields are ignored when dPixels != NULL, but p is still
+ *      validated as for rt_render_to.  Outputs in rt_render_to's per-pixel formats: colour (finalColor, 1), position
+ *      (P, 1), normal (N, 1) as fp16 rounded toward zero; P / N are the last hit's.  A miss on the primary segment gives
+ *      P = N = 0 and colour skybox(d) (or 0 without a skybox / useSkybox).
+ * dPixels == NULL: the rays are in rt_camera_rays(p)'s surface layout, nRays must equal regionW * regionH, and ray k is
+ *      shaded as the image pixel rt_render_to(p) writes at surface index k (window, local rows, strips); window pixels
+ *      outside the image get the all-zero records rt_render_to writes.  So rt_shade_rays(p, rt_camera_rays(p), NULL)
+ *      equals rt_render_to(p) bit for bit on all three surfaces. */
+typedef struct rt_pixel { uint32_t x, y; } rt_pixel;
+
+/* nRays rays (device, rt_ray, 16-byte aligned) and pixels (device, rt_pixel, 8-byte aligned, or NULL: see above) ->
+ * nRays float4 colours (required), float4 positions and 4 x fp16 normals (each NULL = not stored), all device and
+ * 16- / 16- / 8-byte aligned.  nRays == 0 is a no-op.  RT_ERR_INVALID_ARG: no scene set, NULL required / misaligned
+ * pointer, dPixels == NULL with nRays != regionW * regionH, p failing rt_render_to's checks (e.g. maxRayDepth > 32);
+ * RT_ERR_TOO_LARGE: more rays than one grid holds (as rt_trace_rays).  Asynchronous on hipStream (NULL = the context's
+ * stream), ordered with rt_set_scene like rt_render_to; rt_set_noise / rt_set_skybox wait for it. */
+int rt_shade_rays(rt_context *ctx, const rt_params *p, const void *dRays, const void *dPixels, size_t nRays, void *dColor,
+                  void *dPosition, void *dNormal, void *hipStream);
+
 const char *rt_last_error(rt_context *ctx);
 
 /* ---- host-side feeders of the byte contract (no GPU needed) */
@@ -455,6 +485,7 @@ RT_SA(sizeof(rt_ray) == 32 && offsetof(rt_ray, tMax) == 12 && offsetof(rt_ray, d
       "rt_ray layout");
 RT_SA(sizeof(rt_hit) == 32 && offsetof(rt_hit, t) == 12 && offsetof(rt_hit, normal) == 16 && offsetof(rt_hit, object) == 28,
       "rt_hit layout");
+RT_SA(sizeof(rt_pixel) == 8 && offsetof(rt_pixel, y) == 4, "rt_pixel layout");
 #undef RT_SA
 #endif
 

@@ -755,6 +755,32 @@ int rt_camera_rays(rt_context *c, const rt_params *p, void *dRays, void *hipStre
     return query_record(c, s);      // rt_set_noise drains it before freeing the texture
 }
 
+// ---- ray shading (rt_shade.inc): the query stream protocol; it also reads the noise texture and the skybox, which
+// rt_set_noise / rt_set_skybox / an installing rt_equirect_to_cubemap free only after draining every recorded stream.
+int rt_shade_rays(rt_context *c, const rt_params *p, const void *dRays, const void *dPixels, size_t nRays, void *dColor,
+                  void *dPosition, void *dNormal, void *hipStream) {
+    if (!c) return RT_ERR_INVALID_ARG;
+    int rc = validate_params(c, p);
+    if (rc) return rc;
+    if (!c->dCompiled) return fail(c, RT_ERR_INVALID_ARG, "rt_set_scene has not been called");
+    if (!dPixels && nRays != (size_t)p->regionW * (size_t)p->regionH)
+        return fail(c, RT_ERR_INVALID_ARG, "without pixels, nRays must equal regionW * regionH");
+    if (nRays == 0) return RT_OK;
+    if (!dRays || !dColor) return fail(c, RT_ERR_INVALID_ARG, "NULL ray or colour pointer");
+    if (((uintptr_t)dRays | (uintptr_t)dColor | (uintptr_t)dPosition) & 15u)
+        return fail(c, RT_ERR_INVALID_ARG, "ray, colour and position pointers must be 16-byte aligned");
+    if (((uintptr_t)dPixels | (uintptr_t)dNormal) & 7u) return fail(c, RT_ERR_INVALID_ARG, "pixel and normal pointers must be 8-byte aligned");
+    if (nRays > ((size_t)0x7fffffff) * 256) return fail(c, RT_ERR_TOO_LARGE, "too many rays in one call");
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t s;
+    if ((rc = query_stream(c, hipStream, &s))) return rc;
+    RtFrame f;
+    build_frame(c, p, &f);
+    HIP_TRY(c, rt_launch_shade_rays(f, c->dCompiled, c->dNoise, c->dSky, (const float4 *)dRays, (const uint2 *)dPixels, nRays,
+                                    (float4 *)dColor, (float4 *)dPosition, (uint2 *)dNormal, s));
+    return query_record(c, s);
+}
+
 int rt_pick(rt_context *c, const rt_params *p, int px, int py, rt_hit *hit) {
     if (!c) return RT_ERR_INVALID_ARG;
     if (!hit) return fail(c, RT_ERR_INVALID_ARG, "NULL hit pointer");
@@ -994,6 +1020,11 @@ int rt_equirect_to_cubemap(rt_context *c, const float *hEquirectRGB, int width, 
         return fail(c, RT_ERR_HIP, "rt_equirect_to_cubemap", e);
     }
     if (install) {
+        e = fb_sync_all(c);            // frames and shades on every stream read the old skybox
+        if (e != hipSuccess) {
+            (void)hipFree(dFaces);
+            return fail(c, RT_ERR_HIP, "fb_sync_all", e);
+        }
         c->texGen++;
         if (c->dSky) (void)hipFree(c->dSky);
         c->dSky = (decltype(c->dSky))dFaces;

@@ -1278,3 +1278,8 @@ hipError_t rt_launch_wire_unpack(const void *dWire, size_t rankStrideBytes, size
 // Ray queries (rt_trace_rays / rt_camera_rays / rt_pick): same helpers, separate kernels.
 // =========================================================================================
 #include "rt_query.inc"
+
+// =========================================================================================
+// Ray shading (rt_shade_rays): main() on caller-supplied rays, same helpers, separate kernel.
+// =========================================================================================
+#include "rt_shade.inc"

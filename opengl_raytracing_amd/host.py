@@ -38,7 +38,7 @@ EXPORTS = [
     "rt_wire_bytes", "rt_wire_pack", "rt_wire_unpack", "rt_debug_mesa_math", "rt_debug_shadow_tables", "rt_debug_predicted_classes",
     "rt_render_into_image", "rt_context_stream", "rt_mgpu_create", "rt_mgpu_destroy", "rt_mgpu_device_count", "rt_mgpu_set_scene", "rt_mgpu_set_noise",
     "rt_mgpu_set_skybox", "rt_mgpu_set_strip_rows", "rt_mgpu_render", "rt_mgpu_sync", "rt_mgpu_get_surfaces", "rt_mgpu_readback", "rt_mgpu_last_ms",
-    "rt_mgpu_last_error", "rt_trace_rays", "rt_camera_rays", "rt_pick",
+    "rt_mgpu_last_error", "rt_trace_rays", "rt_camera_rays", "rt_pick", "rt_shade_rays",
 ]
 
 
@@ -152,6 +152,7 @@ def load_library(build_if_missing=True):
     lib.rt_trace_rays.argtypes = [vp, vp, ctypes.c_size_t, ci, vp, vp]
     lib.rt_camera_rays.argtypes = [vp, P(L.RtParams), vp, vp]
     lib.rt_pick.argtypes = [vp, P(L.RtParams), ci, ci, P(L.RtHit)]
+    lib.rt_shade_rays.argtypes = [vp, P(L.RtParams), vp, vp, ctypes.c_size_t, vp, vp, vp, vp]
     for name in EXPORTS:
         if name not in ("rt_last_error", "rt_mgpu_last_error", "rt_wire_bytes"):
             getattr(lib, name).restype = ci
@@ -418,6 +419,52 @@ class RayTracer:
         self._on_torch_stream(stream, lambda h: self._check(self.lib.rt_camera_rays(
             self.ctx, ctypes.byref(params), ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(h)), "rt_camera_rays"))
         return out
+
+    def shade_rays(self, params, rays, pixels=None, out=None, stream=None, position=True, normal=True):
+        """main() of the shader on the given rays (rt_shade_rays): what the renderer computes along each ray.
+
+        rays: CUDA float32 [..., 8] (rt_ray per row, e.g. from camera_rays).  pixels: CUDA int32 / uint32 [..., 2], the
+        (x, y) each ray is shaded as (bits read as uint32), or None: rays in camera_rays(params)' surface layout, shaded as
+        render(params)'s pixels.  -> (colour float32 [..., 4], position float32 [..., 4] or None, normal float16 [..., 4]
+        or None), asynchronous on `stream` (default torch.cuda.current_stream()).  `out` may supply the three tensors (None
+        entries are allocated when requested)."""
+        import torch
+        # every shape / dtype check first, then the device: nothing reaches the ABI unchecked
+        if not isinstance(rays, torch.Tensor) or rays.dtype != torch.float32 or rays.ndim < 1 or rays.shape[-1] != 8:
+            raise ValueError("rays: a CUDA float32 tensor [..., 8] (rt_ray rows)")
+        shape = tuple(rays.shape[:-1])
+        n = rays.numel() // 8
+        tensors = [rays]
+        if pixels is None:
+            if n != params.regionW * params.regionH:
+                raise ValueError(f"pixels=None: {n} rays, but the window has regionW * regionH = {params.regionW * params.regionH} pixels")
+        else:
+            ok_dtypes = (torch.int32,) + ((torch.uint32,) if hasattr(torch, "uint32") else ())
+            if not isinstance(pixels, torch.Tensor) or pixels.dtype not in ok_dtypes or pixels.ndim < 1 or pixels.shape[-1] != 2:
+                raise ValueError("pixels: a CUDA int32 / uint32 tensor [..., 2]")
+            if pixels.numel() != 2 * n:
+                raise ValueError(f"pixels: {tuple(pixels.shape)} does not give one (x, y) per ray ({n} rays)")
+            tensors.append(pixels)
+        col, pos, nrm = out if out is not None else (None, None, None)
+        res = []
+        for t, on, dt in ((col, True, torch.float32), (pos, position, torch.float32), (nrm, normal, torch.float16)):
+            if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != dt or not t.is_contiguous() or t.numel() != 4 * n):
+                raise ValueError(f"out: expected a contiguous CUDA {dt} tensor of {n} x 4 elements")
+            if t is not None:
+                tensors.append(t)
+            res.append(t)
+        if not all(t.is_cuda and t.device == rays.device for t in tensors):
+            raise ValueError("shade_rays: rays, pixels and out must be CUDA tensors on one device")
+        rays = rays.contiguous()
+        pixels = pixels.contiguous() if pixels is not None else None
+        for k, (on, dt) in enumerate(((True, torch.float32), (position, torch.float32), (normal, torch.float16))):
+            if res[k] is None and on:
+                res[k] = torch.empty(shape + (4,), dtype=dt, device=rays.device)
+        ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
+        self._on_torch_stream(stream, lambda h: self._check(self.lib.rt_shade_rays(
+            self.ctx, ctypes.byref(params), ptr(rays), ptr(pixels), n, ptr(res[0]), ptr(res[1]), ptr(res[2]),
+            ctypes.c_void_p(h)), "rt_shade_rays"))
+        return tuple(res)
 
     def pick(self, params, x, y):
         """Closest hit of the primary ray of image pixel (x, y), row 0 = bottom (rt_pick) -> PickHit."""

@@ -196,3 +196,15 @@ class RtHit(ctypes.Structure):
 
 
 assert ctypes.sizeof(RtRay) == RAY_DTYPE.itemsize == 32 and ctypes.sizeof(RtHit) == HIT_DTYPE.itemsize == 32
+
+
+# ---- ray shading (rt_shade_rays, include/rt_mi355.h) ------------------------------------------
+PIXEL_DTYPE = np.dtype({"names": ["x", "y"], "formats": ["<u4", "<u4"], "offsets": [0, 4], "itemsize": 8})
+
+
+class RtPixel(ctypes.Structure):
+    """``rt_pixel``: the gl_GlobalInvocationID.xy a shaded ray stands for."""
+    _fields_ = [("x", ctypes.c_uint32), ("y", ctypes.c_uint32)]
+
+
+assert ctypes.sizeof(RtPixel) == PIXEL_DTYPE.itemsize == 8
