@@ -1,0 +1,108 @@
+// rt_sched.h -- the packet kernel's tile scheduler, held by value in rt_context (rt_abi.cpp).  It keeps the record of every
+// stream a launch has been issued on (the stream protocol that renders, queries, shading and the scene / texture setters share)
+// and decides the tile order of each frame: begin() before rt_launch_render, end() after it.  Not part of the public ABI.
+#pragma once
+#include "rt_devbuf.h"
+#include "rt_device.h"
+
+struct RtTileScheduler {
+    // Every stream a launch has been issued on (the context's own and the callers'): `last` = its most recent
+    // launch (recorded on EVERY launch, feedback or not: rt_set_scene orders the scene rewrite behind all of
+    // them), `seenGen` = the tile-order adoption it has already ordered itself behind.
+    struct StreamRec {
+        hipStream_t s = nullptr;
+        DevEvent last;
+        unsigned seenGen = 0;
+        // predicted tile order of the last frame issued on this stream, and the inputs it was predicted from
+        // (predOrder: the order, then 32 class segments of predCls.cap tile ids each; predCounts: two sets of 32 class sizes, used
+        // alternately -- a prediction clears the other set)
+        DevBuf<unsigned> predOrder, predCounts;
+        DevBuf<unsigned char> predCls;
+        unsigned long long predKey = 0;
+        bool predValid = false;
+        int predSet = 0;
+    };
+    // What begin() decided for one launch; end() takes it back.
+    struct Plan {
+        StreamRec *rec = nullptr;
+        int nTiles = 0, tilesX = 0, bt = 0;
+        int phase = -1;                        // frameCount mod 64 when the frame records into (and sorts) its phase's buffers
+        bool sortAfter = false;                // the frame was scheduled: the measured order's bookkeeping runs after it
+    };
+
+    void init(hipStream_t contextStream);      // + the environment overrides (RT_FB_PERIOD, RT_PRED_MIN_TILES, RT_PHASE_ORDER, RT_DEBUG_PRED_CLASSES)
+    void setMode(int variant);                 // rt_set_variant's bits 8 and 9; forgets the geometry
+
+    // ---- stream protocol
+    hipError_t record(hipStream_t s, StreamRec **out);                  // the record of stream s (created on first use)
+    hipError_t recordLaunch(hipStream_t s);                             // s's last launch is whatever was just enqueued on it
+    hipError_t waitForLaunches(hipStream_t t, bool ownToo = false);     // t waits for every recorded stream's last launch (its own record only if asked)
+    hipError_t drain();                                                 // the host waits for every stream and every sort
+
+    // ---- one frame.  `packet`: the launch is one the scheduler may order (packet kernel, no ray counter); `inputsGen`
+    // changes whenever the scene or a texture does.  begin() fills sc.tileOrder / sc.tileCost.
+    hipError_t begin(const RtFrame &f, RtDeviceScene &sc, hipStream_t s, bool packet, unsigned long long inputsGen, Plan *plan);
+    hipError_t end(const Plan &plan, hipStream_t s);
+
+    // ---- debug read-outs (rt_debug_tile_costs, rt_debug_predicted_classes)
+    hipError_t tileCosts(unsigned *out, int cap, int *nTiles, int *tilesX);
+    hipError_t predictedClasses(unsigned char *out, int cap, int *nTiles);
+
+    const char *failedCall = "";               // the HIP call behind the last error returned
+
+private:
+    hipError_t measuredBegin(RtDeviceScene &sc, hipStream_t s, Plan *plan, bool *newGeometry);
+    hipError_t measuredEnd(const Plan &plan);
+    hipError_t predictedBegin(const RtFrame &f, RtDeviceScene &sc, hipStream_t s, unsigned long long inputsGen, const Plan &plan);
+    hipError_t phaseBegin(const RtFrame &f, RtDeviceScene &sc, Plan *plan);
+    hipError_t phaseEnd(const Plan &plan);
+    void phaseForget();
+
+    hipStream_t own = nullptr;                 // the context's stream: the periodic sort runs on it
+    // schedMode 2 (default): tiles run longest-first by their MEASURED cost over the last frames of the same window geometry (the
+    // feedback of rounds 1-2); while no measured order exists yet, frames of >= predMinTiles tiles run in the heavy-first order
+    // PREDICTED from their own inputs (rt_predict_tiles_kernel, in the frame's own stream, buffers per stream in StreamRec).
+    // 1: measured costs only.  0: raster order.
+    int schedMode = 2;
+
+    static constexpr int kMaxStreams = 8;
+    StreamRec recs[kMaxStreams];
+    int nRecs = 0;
+
+    // ---- measured order.  Frames may be issued on several streams (frames in flight overlapping on the device), so the order
+    // is double-buffered: a sort writes the buffer no launch is reading, and later launches wait for it.
+    DevBuf<unsigned> dTileCost, dTileSnap, dTileOrder[2];
+    DevEvent evSort[2];                        // completion of the rt_lpt_sort that wrote dTileOrder[k]
+    int fbCur = -1;                            // order buffer new launches read (-1 = raster order)
+    int fbNext = 0;                            // order buffer the pending sort is writing
+    bool sortPending = false;                  // a sort has been enqueued on the context's own stream, not yet adopted
+    unsigned sortAge = 0;                      // fbAge at which it was enqueued
+    int fbTiles = 0, fbTilesX = 0, fbBt = 0;   // geometry the current order was measured on (0 = none)
+    unsigned fbAge = 0;                        // frames since that geometry was first seen
+    unsigned adoptGen = 0;                     // bumped whenever fbCur changes to a freshly sorted buffer
+    unsigned fbPeriod = 32;                    // re-sort period in frames (RT_FB_PERIOD overrides, for measurements)
+
+    // ---- predicted order
+    int predMinTiles = 49152;                  // frames of at least this many tiles get a predicted order while no measured one exists (RT_PRED_MIN_TILES)
+    bool dbgWantCls = false;                   // RT_DEBUG_PRED_CLASSES=1: predictions also store each tile's class
+    const unsigned char *dbgPredCls = nullptr; // class buffer of the last predicted launch (rt_debug_predicted_classes)
+    int dbgPredTiles = 0;
+
+    // ---- per-phase orders.  Free-running frameCount (the reference with TAA on, ForwardShadingPipeline.cpp:254): frameCount
+    // enters the frame through hammersley(depth*64 + frameCount, 64) (:557) -- the bounce sample ALL pixels share -- whose azimuth
+    // is periodic in frameCount with period 64 and whose cos^2(theta) = halton2 repeats to within 2^-6.  A frame's tile costs
+    // therefore repeat, nearly, every 64 frames, while consecutive frames differ a lot (tools/gpu_phase_costs.py: list-scheduling
+    // makespan over the ideal, C2: 1.04 in the frame's own order, 1.06-1.09 in the order of the frame 64 earlier, 1.07-1.17 in the
+    // all-phase average order, 1.29-1.34 in raster order).  So once frameCount is seen advancing, every frame's costs go to its
+    // PHASE's buffer (frameCount mod 64) and are sorted, beside the following frames on a stream of their own, into that phase's
+    // order, which the frame 64 later runs in; phases not seen yet use the all-phase average order as before (the per-phase
+    // sorts feed it).
+    DevStream phaseStream;
+    DevBuf<unsigned> dPhaseCost, dPhaseOrder, dPhaseSnap;   // [64][phaseTiles], [64][phaseTiles], [phaseTiles]
+    int phaseTiles = 0;                        // tiles per phase of the current geometry (0 = none)
+    DevEvent evPhase[64];                      // completion of the last sort into phase k's order
+    unsigned char phaseState[64] = {};         // 0 = no order, 1 = sort issued, 2 = seen complete
+    bool phaseOn = true;                       // RT_PHASE_ORDER=0 switches it off (measurements)
+    bool haveLastFc = false;
+    int lastFc = 0, freeRun = 0;               // consecutive scheduled launches whose frameCount differed from the previous one's
+};

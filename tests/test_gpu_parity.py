@@ -605,6 +605,88 @@ def test_scene_updates_between_frames_in_flight_on_three_streams(host, oracle):
             assert_bit_exact(tuple(t.cpu().numpy() for t in bufs[k]), want, f"frame {k} (scene {k % 4})")
 
 
+def _zeroed_targets(w, h, n):
+    import torch
+    return [(torch.zeros((h, w, 4), dtype=torch.float32, device="cuda"), torch.zeros((h, w, 4), dtype=torch.float32, device="cuda"),
+             torch.zeros((h, w, 4), dtype=torch.float16, device="cuda")) for _ in range(n)]
+
+
+def test_more_render_streams_than_stream_records(host, monkeypatch):
+    """The scheduler keeps one record per stream frames were issued on, eight at most; a ninth stream drains everything
+    and starts the records over, after which a record (its `last` event, its prediction buffers) belongs to another stream
+    than before.  Nine streams round-robin, the host running ahead: 27 frames of one geometry, then 18 of a second one, into
+    zeroed targets; every frame must equal the raster-order render bit for bit.  RT_PRED_MIN_TILES=1 lets these small frames
+    take the predicted order too, so the first frame of each geometry predicts into the buffers of whichever record its stream
+    holds by then."""
+    import torch
+    monkeypatch.setenv("RT_PRED_MIN_TILES", "1")      # read when the context is created
+    sc = scenes.make_scene(2, host.generate_aabb)
+    with host.RayTracer(0) as rt, host.RayTracer(0) as ref_rt:
+        rt.load(sc)
+        ref_rt.load(sc)
+        ref_rt.set_variant(0x101)                # packet kernel, raster order: no scheduler state
+        streams = [torch.cuda.Stream() for _ in range(9)]
+        issued = 0
+        for (w, h), n_frames in [((320, 200), 27), ((328, 136), 18)]:
+            p = sc.params(width=w, height=h)
+            ref_rt.render(p)
+            ref = ref_rt.readback()
+            bufs = _zeroed_targets(w, h, n_frames)
+            torch.cuda.synchronize()
+            for k in range(n_frames):            # nothing synchronises between the launches
+                c, q, n = bufs[k]
+                rt.render_to(p, c.data_ptr(), q.data_ptr(), n.data_ptr(), stream=streams[(issued + k) % 9].cuda_stream)
+            issued += n_frames
+            torch.cuda.synchronize()
+            for k in range(n_frames):
+                for got, want in zip(bufs[k], ref):
+                    assert bits_equal(got.cpu().numpy(), want), f"{w}x{h} frame {k}"
+
+
+def test_mode_switches_in_mid_run_on_three_streams(host):
+    """rt_set_variant between frames in flight: 12 frames in each of the modes 1 (predicted, measured and per-phase orders),
+    0x201 (measured only), 0x101 (raster), 1 again, on three streams with frameCount advancing and nothing synchronised at the
+    switches; every frame must equal the raster-order render of its frameCount bit for bit.  A mode switch forgets the
+    geometry: rt_debug_tile_costs reports zero tiles right after it (which returns before touching the device).  A read-out
+    of real costs drains every stream, so it comes after the run: one more block in mode 0x201 must report the geometry's
+    25 x 40 tiles of 8 x 8 pixels with a non-zero sum."""
+    import torch
+    sc = scenes.make_scene(2, host.generate_aabb)
+    w, h = 320, 200
+    base = sc.params(width=w, height=h)
+    with host.RayTracer(0) as rt, host.RayTracer(0) as ref_rt:
+        rt.load(sc)
+        ref_rt.load(sc)
+        ref_rt.set_variant(0x101)
+        streams = [torch.cuda.Stream() for _ in range(3)]
+        modes = [1, 0x201, 0x101, 1, 0x201]
+        bufs = _zeroed_targets(w, h, 12 * len(modes))
+        torch.cuda.synchronize()
+
+        def block(b):
+            rt.set_variant(modes[b])
+            assert rt.tile_costs().size == 0, f"block {b}: the geometry survived the mode switch"
+            for k in range(12 * b, 12 * b + 12):
+                c, q, n = bufs[k]
+                rt.render_to(L.copy_params(base, frameCount=5 + k), c.data_ptr(), q.data_ptr(), n.data_ptr(), stream=streams[k % 3].cuda_stream)
+
+        for b in range(4):
+            block(b)
+        torch.cuda.synchronize()
+        block(4)
+        costs = rt.tile_costs()
+        assert costs.shape == ((h + 7) // 8, (w + 7) // 8)
+        assert int(costs.sum(dtype=np.uint64)) > 0
+        rt.set_variant(1)
+        assert rt.tile_costs().size == 0
+        torch.cuda.synchronize()
+        for k in range(len(bufs)):
+            ref_rt.render(L.copy_params(base, frameCount=5 + k))
+            ref = ref_rt.readback()
+            for got, want in zip(bufs[k], ref):
+                assert bits_equal(got.cpu().numpy(), want), f"mode {modes[k // 12]:#x} frameCount {5 + k}"
+
+
 def _grazing_scene(kind, scale, offset, samples, softness, ltype, seed):
     """Shadow rays that graze: a floor under a light, 40 spheres between them whose shadow limbs cross the view -- every pixel on
     a shadow's edge is a ray within rounding of a sphere's limb.  kind: 'tiny' (radii 1e-3..1e-2 of the scene's scale), 'mixed',
