@@ -236,6 +236,36 @@ int rt_debug_shadow_tables(rt_context *ctx, uint32_t *out, size_t capDwords, siz
  * sin, cos, tan, exp of in[i].  Test hook (no GPU needed), no reference counterpart. */
 int rt_debug_mesa_math(const float *in, float *out, int n);
 
+/* The device-side arithmetic primitives of the render kernels, one call each on caller-supplied operands: the inline
+ * functions of csrc/rt_fastmath.h, the DEVICE instantiation of csrc/rt_mesa_math.h and the small helpers of
+ * csrc/rt_kernels.hip, compiled in the render kernels' translation unit with their flags (no copy of the arithmetic).
+ * dIn / dOut: n records of four 32-bit words (device, 16-byte aligned); in = (a, b, c, d) as float bit patterns unless
+ * stated, out words not listed are 0:
+ *   RCP       rtf::rcp(a),  rtf::rcp_fast(a, ok),  ok (0 / 1)
+ *   RCP3      rtf::rcp3(a, b, c): 1/a, 1/b, 1/c
+ *   SQRT      rtf::sqrt(a),  rtf::sqrt_fast(a, ok),  ok
+ *   RCP_SQRT  rtf::rcp_sqrt(a),  rtf::rcp_sqrt_fast(a, ok),  ok
+ *   DIV2      rtf::div2(a, b, c): a/c, b/c;  rtf::div_fast(a, c, y = rtf::rcp_fast(c, oky), ok0),  oky & ok0
+ *   DIV3      rtf::div3(a, b, c, d): a/d, b/d, c/d
+ *   MESA      rtm::sin_(a), cos_(a), tan_(a), exp_(a)
+ *   F2H       f2h_rtz(a) (the fp16 bits, round toward zero, as a uint32),  half_bits_to_float(low 16 bits of b)
+ *   POW5      pow5(a)
+ *   HALTON    halton_eval(index = a as int32, base = b as int32); a base < 2 (the loop would not end) gives 0 uncalled
+ * LAUNCH GEOMETRY (fixed; tests/test_device_math.py composes wavefronts with it): 256-thread blocks, exactly one record per
+ * thread, record i is processed by lane i % 64 of wavefront i / 64, no grid-stride loop.  n need not be a multiple of 64:
+ * the tail lanes of the last wavefront exit BEFORE the primitive is called, so they take no part in its ballot, and
+ * nothing past record n - 1 is written.  The rtf:: functions replace their fast path by the IEEE sequence for a whole
+ * wavefront when any of its lanes needs it (wave-uniform branch), so what a lane's operand exercises depends on its 63
+ * neighbours; the *_fast outputs are the lane's own fast-path value and its guard.
+ * n == 0 is a no-op.  RT_ERR_INVALID_ARG: NULL context, unknown op, NULL / misaligned pointer; RT_ERR_TOO_LARGE: more
+ * records than one grid holds.  Asynchronous on hipStream (NULL = the context's stream).  Test hook, no reference
+ * counterpart. */
+typedef enum rt_device_math_op {
+    RT_DM_RCP = 0, RT_DM_RCP3 = 1, RT_DM_SQRT = 2, RT_DM_RCP_SQRT = 3, RT_DM_DIV2 = 4, RT_DM_DIV3 = 5, RT_DM_MESA = 6,
+    RT_DM_F2H = 7, RT_DM_POW5 = 8, RT_DM_HALTON = 9, RT_DM_OP_COUNT = 10
+} rt_device_math_op;
+int rt_debug_device_math(rt_context *ctx, int op, const void *dIn, void *dOut, size_t n, void *hipStream);
+
 /* ---- ray queries on the scene of the last rt_set_scene: the shader's intersectObjects (raytracingCs.glsl:155-196)
  *      outside a frame, for the questions a host asks about the scene (which object is under the mouse, is a segment
  *      blocked, where does a ray first hit).  No reference counterpart: the reference's editor can only pick from a list

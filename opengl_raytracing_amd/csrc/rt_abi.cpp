@@ -629,6 +629,21 @@ int rt_debug_mesa_math(const float *in, float *out, int n) {
     return RT_OK;
 }
 
+// The device-side primitives on caller-supplied operands (rt_kernels.hip).  It reads nothing the context owns, so it takes
+// no part in the scene streams' protocol: ordered on the given stream like the post passes.
+int rt_debug_device_math(rt_context *c, int op, const void *dIn, void *dOut, size_t n, void *hipStream) {
+    if (!c) return RT_ERR_INVALID_ARG;
+    if (op < 0 || op >= RT_DM_OP_COUNT) return fail(c, RT_ERR_INVALID_ARG, "unknown device math op");
+    if (n == 0) return RT_OK;
+    if (!dIn || !dOut) return fail(c, RT_ERR_INVALID_ARG, "NULL input or output pointer");
+    if (((uintptr_t)dIn | (uintptr_t)dOut) & 15u) return fail(c, RT_ERR_INVALID_ARG, "input and output pointers must be 16-byte aligned");
+    if (n > ((size_t)0x7fffffff) * 256) return fail(c, RT_ERR_TOO_LARGE, "too many records in one call");
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t s = hipStream ? (hipStream_t)hipStream : c->stream;
+    HIP_TRY(c, rt_launch_device_math(op, (const uint4 *)dIn, (uint4 *)dOut, n, s));
+    return RT_OK;
+}
+
 int rt_equirect_to_cubemap(rt_context *c, const float *hEquirectRGB, int width, int height, int size, void *dFacesOut,
                            int install) {
     if (!c) return RT_ERR_INVALID_ARG;

@@ -112,6 +112,8 @@ hipError_t rt_launch_trace_rays(const float4 *dRays, size_t nRays, const float4 
 hipError_t rt_launch_camera_rays(const RtFrame &f, const uint8_t *dNoise, float4 *dRays, hipStream_t s);
 hipError_t rt_launch_pick(const RtFrame &f, const uint8_t *dNoise, const float4 *dCompiled, int px, int py, float4 *dOut,
                           hipStream_t s);
+// rt_debug_device_math: one rt_device_math_op on n records of four words, one record per thread (rt_kernels.hip).
+hipError_t rt_launch_device_math(int op, const uint4 *dIn, uint4 *dOut, size_t n, hipStream_t s);
 // Ray shading (rt_shade.inc).  dRays: 2 float4 per ray (rt_ray); dPixels: one uint2 per ray, or null = rt_render_to(f.p)'s
 // surface layout; dColor / dPos: one float4 per ray, dNormal: one packed half4 per ray (dPos / dNormal may be null).
 hipError_t rt_launch_shade_rays(const RtFrame &f, const float4 *dCompiled, const uint8_t *dNoise, const uint16_t *dSky,

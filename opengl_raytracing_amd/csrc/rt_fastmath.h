@@ -14,7 +14,10 @@
 // itself); the square root is exact for every x >= 2^-100 (below, the residual underflows), x = +-0 passes through.
 // Everything else -- denormals, |x| >= 2^126, tiny radicands -- takes the compiler's IEEE sequence through a
 // WAVE-UNIFORM branch (one v_cmp_class + one scalar branch on the fast path), so the functions are exact for every
-// input, which the same tool verifies.
+// input.  tests/test_device_math.py is the regression gate for that (pytest -m gpu): it calls these functions through
+// rt_debug_device_math on every exponent and guard boundary, in wavefronts where nobody, one lane or 63 lanes vote for the
+// fallback, and checks the *_fast values and their `ok` guards on their own; the tool above is the full 2^32 sweep, run by
+// hand.
 #pragma once
 #include <hip/hip_runtime.h>
 

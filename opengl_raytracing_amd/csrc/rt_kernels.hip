@@ -1275,6 +1275,90 @@ hipError_t rt_launch_wire_unpack(const void *dWire, size_t rankStrideBytes, size
 }
 
 // =========================================================================================
+// rt_debug_device_math: the arithmetic primitives above on caller-supplied operands (tests/test_device_math.py).  The
+// kernel calls the very inline functions the render kernels call, in this translation unit, under its flags.  One record
+// per thread and NO grid-stride loop: record i runs in lane i % 64 of wavefront i / 64, so a caller decides which operands
+// share a wavefront -- and with it whether rtf::'s wave-uniform IEEE fallbacks run for a lane that does not itself need
+// them.  Tail lanes leave before the primitive, so its ballot never sees them.
+// =========================================================================================
+template <int OP>
+__device__ __forceinline__ uint4 device_math_op(const uint4 u) {
+    const float a = __uint_as_float(u.x), b = __uint_as_float(u.y), c = __uint_as_float(u.z), d = __uint_as_float(u.w);
+    float r0 = 0.0f, r1 = 0.0f, r2 = 0.0f, r3 = 0.0f;
+    uint4 o = make_uint4(0u, 0u, 0u, 0u);
+    bool ok = false, oky = false;
+    if constexpr (OP == RT_DM_RCP) {
+        r0 = rtf::rcp(a);
+        r1 = rtf::rcp_fast(a, ok);
+        o.z = ok ? 1u : 0u;
+    } else if constexpr (OP == RT_DM_RCP3) {
+        rtf::rcp3(a, b, c, r0, r1, r2);
+        o.z = __float_as_uint(r2);
+    } else if constexpr (OP == RT_DM_SQRT) {
+        r0 = rtf::sqrt(a);
+        r1 = rtf::sqrt_fast(a, ok);
+        o.z = ok ? 1u : 0u;
+    } else if constexpr (OP == RT_DM_RCP_SQRT) {
+        r0 = rtf::rcp_sqrt(a);
+        r1 = rtf::rcp_sqrt_fast(a, ok);
+        o.z = ok ? 1u : 0u;
+    } else if constexpr (OP == RT_DM_DIV2) {
+        rtf::div2(a, b, c, r0, r1);
+        const float y = rtf::rcp_fast(c, oky);
+        r2 = rtf::div_fast(a, c, y, ok);
+        o.z = __float_as_uint(r2);
+        o.w = (oky & ok) ? 1u : 0u;
+    } else if constexpr (OP == RT_DM_DIV3) {
+        rtf::div3(a, b, c, d, r0, r1, r2);
+        o.z = __float_as_uint(r2);
+    } else if constexpr (OP == RT_DM_MESA) {
+        r0 = rtm::sin_(a);
+        r1 = rtm::cos_(a);
+        r2 = rtm::tan_(a);
+        r3 = rtm::exp_(a);
+        o.z = __float_as_uint(r2);
+        o.w = __float_as_uint(r3);
+    } else if constexpr (OP == RT_DM_F2H) {
+        o.x = f2h_rtz(a);
+        o.y = __float_as_uint(half_bits_to_float((uint16_t)(u.y & 0xffffu)));
+        return o;
+    } else if constexpr (OP == RT_DM_POW5) {
+        r0 = pow5(a);
+    } else {
+        static_assert(OP == RT_DM_HALTON, "unknown rt_device_math_op");
+        const int index = (int)u.x, base = (int)u.y;
+        r0 = base >= 2 ? halton_eval(index, base) : 0.0f;       // base 0 / 1: haltonSequence's loop would not end
+    }
+    o.x = __float_as_uint(r0);
+    o.y = __float_as_uint(r1);
+    return o;
+}
+
+template <int OP>
+__global__ __launch_bounds__(256) void rt_device_math_kernel(const uint4 *__restrict__ in, uint4 *__restrict__ out, size_t n) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    out[i] = device_math_op<OP>(in[i]);
+}
+
+template <int OP>
+static hipError_t launch_device_math(int op, unsigned blocks, const uint4 *dIn, uint4 *dOut, size_t n, hipStream_t s) {
+    if (op == OP) {
+        hipLaunchKernelGGL(rt_device_math_kernel<OP>, dim3(blocks), dim3(256), 0, s, dIn, dOut, n);
+        return hipGetLastError();
+    }
+    if constexpr (OP + 1 < RT_DM_OP_COUNT) return launch_device_math<OP + 1>(op, blocks, dIn, dOut, n, s);
+    return hipErrorInvalidValue;
+}
+
+hipError_t rt_launch_device_math(int op, const uint4 *dIn, uint4 *dOut, size_t n, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    const size_t blocks = (n + 255) / 256;
+    if (blocks > 0x7fffffffull) return hipErrorInvalidValue;
+    return launch_device_math<0>(op, (unsigned)blocks, dIn, dOut, n, s);
+}
+
+// =========================================================================================
 // Ray queries (rt_trace_rays / rt_camera_rays / rt_pick): same helpers, separate kernels.
 // =========================================================================================
 #include "rt_query.inc"

@@ -11,8 +11,10 @@
 // sse_mathfun single-precision sincos with llvm.fmuladd in the reduction and the polynomials; exp(x) =
 // exp2(x*log2 e) with lp_build_exp2's degree-5 polynomial by the even/odd Horner split) -- restated from the
 // published algorithm, NOT libm.  The CPU oracle carries its own restatement (oracle/rt_oracle.c), which is pinned
-// bitwise against llvmpipe (tests/golden/trig.npz); the GPU tests pin this one against the oracle's through the
-// rendered pixels (bit-exact surfaces on every config) and tests/test_abi_host.py::test_mesa_trig_host.
+// bitwise against llvmpipe (tests/golden/trig.npz).  This one is pinned against the same fixture directly: the host
+// instantiation by tests/test_abi_host.py::test_mesa_trig_host, the device instantiation by tests/test_device_math.py
+// (rt_debug_device_math), which also compares device with host bit for bit far outside the fixture's range -- every
+// exponent, |a| beyond 2^31 * pi/4, NaN / inf, exp across its clamp points.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>

@@ -38,7 +38,7 @@ EXPORTS = [
     "rt_wire_bytes", "rt_wire_pack", "rt_wire_unpack", "rt_debug_mesa_math", "rt_debug_shadow_tables", "rt_debug_predicted_classes",
     "rt_render_into_image", "rt_context_stream", "rt_mgpu_create", "rt_mgpu_destroy", "rt_mgpu_device_count", "rt_mgpu_set_scene", "rt_mgpu_set_noise",
     "rt_mgpu_set_skybox", "rt_mgpu_set_strip_rows", "rt_mgpu_render", "rt_mgpu_sync", "rt_mgpu_get_surfaces", "rt_mgpu_readback", "rt_mgpu_last_ms",
-    "rt_mgpu_last_error", "rt_trace_rays", "rt_camera_rays", "rt_pick", "rt_shade_rays",
+    "rt_mgpu_last_error", "rt_trace_rays", "rt_camera_rays", "rt_pick", "rt_shade_rays", "rt_debug_device_math",
 ]
 
 
@@ -153,6 +153,7 @@ def load_library(build_if_missing=True):
     lib.rt_camera_rays.argtypes = [vp, P(L.RtParams), vp, vp]
     lib.rt_pick.argtypes = [vp, P(L.RtParams), ci, ci, P(L.RtHit)]
     lib.rt_shade_rays.argtypes = [vp, P(L.RtParams), vp, vp, ctypes.c_size_t, vp, vp, vp, vp]
+    lib.rt_debug_device_math.argtypes = [vp, ci, vp, vp, ctypes.c_size_t, vp]
     for name in EXPORTS:
         if name not in ("rt_last_error", "rt_mgpu_last_error", "rt_wire_bytes"):
             getattr(lib, name).restype = ci
@@ -273,6 +274,10 @@ def strip_local_rows(height, strip_rows, strip_count, strip_index):
 PickHit = collections.namedtuple("PickHit", "object t position normal")
 PickHit.__doc__ = """rt_pick's answer: object index (-1 = nothing under the pixel), hit distance (tMax on a miss), hit position and
 normal (float32[3] each; zero on a miss)."""
+
+
+# rt_device_math_op of include/rt_mi355.h
+DEVICE_MATH_OPS = {"rcp": 0, "rcp3": 1, "sqrt": 2, "rcp_sqrt": 3, "div2": 4, "div3": 5, "mesa": 6, "f2h": 7, "pow5": 8, "halton": 9}
 
 
 def _query_mode(mode):
@@ -465,6 +470,33 @@ class RayTracer:
             self.ctx, ctypes.byref(params), ptr(rays), ptr(pixels), n, ptr(res[0]), ptr(res[1]), ptr(res[2]),
             ctypes.c_void_p(h)), "rt_shade_rays"))
         return tuple(res)
+
+    def device_math(self, op, inputs, n=None, out=None):
+        """One device-side arithmetic primitive (rt_debug_device_math; `op` a DEVICE_MATH_OPS name or number) on numpy
+        records of four 32-bit words: inputs [m, 4] uint32 / int32 / float32 (bits taken as they are) -> uint32 [m, 4],
+        synchronously.  Record i runs in lane i % 64 of wavefront i / 64.  `n` < m launches the first n records only and
+        `out` (uint32 [>= n, 4]) supplies what the rows the launch does not write keep: the tail tests' sentinels."""
+        import torch
+        o = DEVICE_MATH_OPS.get(op, op)
+        a = np.ascontiguousarray(inputs)
+        if a.ndim != 2 or a.shape[1] != 4 or a.dtype.itemsize != 4:
+            raise ValueError("inputs: [m, 4] records of 32-bit words")
+        n = len(a) if n is None else int(n)
+        if not 0 <= n <= len(a):
+            raise ValueError(f"n = {n} outside 0..{len(a)}")
+        d_in = torch.from_numpy(a.view(np.int32).copy()).cuda()
+        if out is None:
+            d_out = torch.zeros((len(a), 4), dtype=torch.int32, device="cuda")
+        else:
+            h = np.ascontiguousarray(out)
+            if h.ndim != 2 or h.shape[1] != 4 or h.dtype.itemsize != 4 or len(h) < n:
+                raise ValueError("out: [>= n, 4] records of 32-bit words")
+            d_out = torch.from_numpy(h.view(np.int32).copy()).cuda()
+        self._on_torch_stream(None, lambda s: self._check(self.lib.rt_debug_device_math(
+            self.ctx, int(o), ctypes.c_void_p(d_in.data_ptr()), ctypes.c_void_p(d_out.data_ptr()), n, ctypes.c_void_p(s)),
+            "rt_debug_device_math"))
+        torch.cuda.current_stream().synchronize()
+        return d_out.cpu().numpy().view(np.uint32)
 
     def pick(self, params, x, y):
         """Closest hit of the primary ray of image pixel (x, y), row 0 = bottom (rt_pick) -> PickHit."""

@@ -201,7 +201,8 @@ def test_strip_bookkeeping(host):
 def test_mesa_trig_host(host):
     """csrc/rt_mesa_math.h (host instantiation, the one rt_abi.cpp uses for tan(radians(fov)/2) and the bounce
     sample's cos / sin) against the llvmpipe fixture directly: sin, cos, tan and exp BIT FOR BIT.  The device
-    instantiation of the same header is pinned through the rendered pixels by the GPU parity tests."""
+    instantiation of the same header is pinned by tests/test_device_math.py: against this fixture, and against this host
+    instantiation on every exponent, beyond the int32 range of the reduction and across exp's clamp points."""
     g = load_golden("trig")
     x, ref = g["trig_in"], g["trig_out"]
     got = host.mesa_math(x)

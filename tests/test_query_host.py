@@ -69,3 +69,28 @@ def test_null_context_and_null_pointers_are_invalid_arguments(host):
     assert lib.rt_camera_rays(None, None, None, None) == RT_ERR_INVALID_ARG
     assert lib.rt_pick(None, ctypes.byref(p), 0, 0, ctypes.byref(hit)) == RT_ERR_INVALID_ARG
     assert lib.rt_pick(None, None, 0, 0, None) == RT_ERR_INVALID_ARG
+
+
+def test_device_math_entry_refuses_bad_arguments_without_a_device(host, tmp_path):
+    """rt_debug_device_math (the test hook behind tests/test_device_math.py): exported, declared with the documented C
+    signature and op numbers, and a NULL context -- with or without pointers, for every op -- is an invalid argument
+    before any device is touched."""
+    lib = host.load_library()
+    assert hasattr(lib, "rt_debug_device_math") and "rt_debug_device_math" in host.EXPORTS
+    buf = ctypes.create_string_buffer(64)
+    for op in list(host.DEVICE_MATH_OPS.values()) + [-1, len(host.DEVICE_MATH_OPS)]:
+        assert lib.rt_debug_device_math(None, op, buf, buf, 1, None) == RT_ERR_INVALID_ARG
+        assert lib.rt_debug_device_math(None, op, None, None, 1, None) == RT_ERR_INVALID_ARG
+        assert lib.rt_debug_device_math(None, op, None, buf, 0, None) == RT_ERR_INVALID_ARG
+    src = tmp_path / "m.c"
+    names = dict(rcp="RCP", rcp3="RCP3", sqrt="SQRT", rcp_sqrt="RCP_SQRT", div2="DIV2", div3="DIV3", mesa="MESA", f2h="F2H",
+                 pow5="POW5", halton="HALTON")
+    assert set(names) == set(host.DEVICE_MATH_OPS)
+    checks = " && ".join(f"RT_DM_{c} == {host.DEVICE_MATH_OPS[k]}" for k, c in names.items())
+    src.write_text(
+        '#include <stddef.h>\n#include "rt_mi355.h"\n'
+        f'_Static_assert({checks} && RT_DM_OP_COUNT == {len(names)}, "rt_device_math_op");\n'
+        'int main(void) { int (*f)(rt_context *, int, const void *, void *, size_t, void *) = rt_debug_device_math;\n'
+        '  return f ? 0 : 1; }\n')
+    subprocess.run(["gcc", "-std=c11", "-Wall", "-Werror", "-c", "-I", os.path.join(REPO, "include"), str(src), "-o",
+                    str(tmp_path / "m.o")], check=True)

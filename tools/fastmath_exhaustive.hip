@@ -1,10 +1,13 @@
 // Exhaustive check (all 2^32 float bit patterns, ~1 s on an MI355X) of the correctly-rounded fast paths for 1/x and sqrt(x)
 // used by csrc/rt_fastmath.h against the compiler's IEEE sequences (hipcc default -fhip-fp32-correctly-rounded-divide-sqrt).
 //   hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -o /tmp/fm tools/fastmath_exhaustive.hip && /tmp/fm
+// The header is included as the library builds it: the *_fast functions are called directly to see where they need the
+// fallback, the full functions keep theirs.  The regression gate is tests/test_device_math.py (pytest -m gpu: the same
+// functions through the library's own kernel, chosen operands and wavefront compositions, a few seconds); this tool is the
+// full sweep -- all 2^32 operands, 6 x 2^33 quotient pairs -- run by hand after a change to the header or the compiler.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <stdint.h>
-#define RT_FASTMATH_NO_FALLBACK 1      // test the fast paths alone: report where they need the fallback
 #include "../opengl_raytracing_amd/csrc/rt_fastmath.h"
 __device__ __forceinline__ bool same(float a, float b) { return __float_as_uint(a) == __float_as_uint(b) || (a != a && b != b); }
 // signed zeros distinguished (a quotient's -0 must stay -0)
