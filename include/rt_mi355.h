@@ -353,8 +353,18 @@ int rt_scene_write(const void *objects, int nObj, const void *lights, int nLt,
  *      dCurrent = gColor of this frame (rgba32f, sampled LINEAR/REPEAT), dHistory = the previous
  *      resolve (rgba32f, LINEAR/CLAMP_TO_EDGE), dNormal = gNormal (rgba16f, NEAREST/REPEAT), all
  *      width x height device surfaces as produced by rt_render; dOut = the new history (rgba32f).
- *      The caller ping-pongs dHistory/dOut like historyTex[2] (:233, :248).  Asynchronous on
- *      hipStream (NULL = the context's stream). */
+ *      The caller ping-pongs dHistory/dOut like historyTex[2] (:233, :248); dOut == dCurrent or
+ *      dOut == dHistory is refused (RT_ERR_INVALID_ARG).  Asynchronous on hipStream (NULL = the
+ *      context's stream).
+ *
+ *      Streams and the post passes (rt_taa_resolve, rt_bloom, rt_ssao, rt_ssao_blur): they may be issued
+ *      on any streams concurrently, and next to rt_frame on the context's stream.  A pass is ordered
+ *      on its stream like any kernel there, so the caller orders its own surfaces (inputs written
+ *      before, outputs read after, on that stream or behind an event).  The scratch a pass keeps inside
+ *      the context (rt_bloom's rgba16f targets, rt_ssao's depth plane) is one per context: the library
+ *      orders each pass behind the previous user of that scratch with an event, on the device, whichever
+ *      streams the two ran on -- such passes run one after another -- and waits for the last user on
+ *      the host only when the scratch has to grow for a larger frame, and in rt_destroy. */
 int rt_taa_resolve(rt_context *ctx, const void *dCurrent, const void *dHistory, const void *dNormal,
                    void *dOut, int width, int height, float blendFactor, float jitterX,
                    float jitterY, void *hipStream);
@@ -366,7 +376,10 @@ int rt_taa_jitter(int frameCount, int width, int height, float *jitterX, float *
  *      (/root/reference/shader/{brightness_extractFS,gaussian_blurFs,bloom_combineFs}.glsl;
  *      ForwardShadingPipeline.cpp:189-228 uses threshold 1.0, 10 iterations, strength 0.5).
  *      dScene = gColor (rgba32f), dOut = combined rgba32f (what the reference draws to the default
- *      framebuffer, before display quantisation); may not alias.  Asynchronous on hipStream. */
+ *      framebuffer, before display quantisation); dOut == dScene is refused (RT_ERR_INVALID_ARG: a
+ *      fused pass reads neighbouring tiles' scene texels while other workgroups store theirs), and the
+ *      surfaces may not overlap in any other way either.  Asynchronous on hipStream (NULL = the
+ *      context's stream). */
 int rt_bloom(rt_context *ctx, const void *dScene, void *dOut, int width, int height, float threshold,
              float strength, int iterations, void *hipStream);
 
@@ -376,9 +389,11 @@ int rt_bloom(rt_context *ctx, const void *dScene, void *dOut, int width, int hei
  *      hSamples = the 64 kernel samples (AO.cpp:23-36), hProjection / hView = column-major mat4 (the glm
  *      matrices AO.cpp:91-92 uploads; rt_camera_matrices builds them like Camera.h:36-42); all four are HOST
  *      pointers, copied at the call.  dOut = width*height floats: the value the fragment shader writes (the
- *      reference renders it into FBOs without attachments, so upstream nothing consumes it).
+ *      reference renders it into FBOs without attachments, so upstream nothing consumes it); dOut ==
+ *      dPosition or dOut == dNormal is refused (RT_ERR_INVALID_ARG: every pixel samples its neighbours'
+ *      G-buffer).
  *      rt_ssao_blur: one separable 9-tap pass (the reference draws a single pass and never sets `horizontal`,
- *      i.e. vertical).  Asynchronous on hipStream. */
+ *      i.e. vertical); dOut == dIn is refused.  Asynchronous on hipStream (NULL = the context's stream). */
 int rt_ssao(rt_context *ctx, const void *dPosition, const void *dNormal, void *dOut, int width, int height,
             const float *hNoise, int noiseW, int noiseH, const float *hSamples, const float *hProjection,
             const float *hView, void *hipStream);

@@ -15,6 +15,23 @@
 #include "rt_mesa_math.h"
 #include "rt_sched.h"
 
+// Last use of a context-owned scratch that post passes on any stream work in (rt_bloom's ping-pong targets, rt_ssao's depth
+// plane).  The scratch is one per context, so its users run one after another: a pass orders its stream behind the previous
+// use (acquire), launches, and records its own (release).  Every use waits for the one before it, so the event of the last
+// one stands for all of them: the host waits on it alone before the scratch is freed (drain).  Nothing here blocks the host
+// in steady state; behind a use on the same stream the wait is already met by stream order.
+struct ScratchUse {
+    DevEvent ev;
+    bool used = false;
+    hipError_t create() { return ev.create(hipEventDisableTiming); }
+    hipError_t acquire(hipStream_t s) { return used ? hipStreamWaitEvent(s, ev, 0) : hipSuccess; }
+    hipError_t release(hipStream_t s) {
+        used = true;
+        return hipEventRecord(ev, s);
+    }
+    hipError_t drain() { return used ? hipEventSynchronize(ev) : hipSuccess; }
+};
+
 // Everything the context allocates is held by an owner (rt_devbuf.h): after rt_destroy has drained the streams, `delete`
 // releases it all.  The stream comes first so that it goes last.
 struct rt_context {
@@ -48,6 +65,7 @@ struct rt_context {
     RtTileScheduler sched;                     // tile order of the packet kernel's frames; the record of every stream launches go to
     DevBuf<uint2> dBloom[2];                   // rgba16f ping-pong targets of rt_bloom
     DevBuf<float> dSsaoDepth;                  // gPosition.z plane of rt_ssao
+    ScratchUse bloomUse, ssaoUse;              // who ran last in dBloom / dSsaoDepth, on whichever stream
     // rt_frame: AO result (raw, blurred), TAA history ping-pong, bloom-combined image when the caller passes none
     DevBuf<float> dFrameAO[2];
     DevBuf<float4> dHistory[2];
@@ -232,7 +250,7 @@ int rt_create(rt_context **out, int deviceId) {
     }
     if (c->stream.create() != hipSuccess || c->evStart.create(hipEventDefault) != hipSuccess ||
         c->evStop.create(hipEventDefault) != hipSuccess || c->evScene.create(hipEventDisableTiming) != hipSuccess ||
-        c->dRayCounter.grow(32) != hipSuccess) {
+        c->bloomUse.create() != hipSuccess || c->ssaoUse.create() != hipSuccess || c->dRayCounter.grow(32) != hipSuccess) {
         rt_destroy(c);
         return RT_ERR_HIP;
     }
@@ -245,6 +263,8 @@ int rt_destroy(rt_context *c) {
     if (!c) return RT_ERR_INVALID_ARG;
     (void)hipSetDevice(c->device);
     (void)c->sched.drain();            // the context's stream, the phase stream, every stream's last launch
+    (void)c->bloomUse.drain();         // post passes on caller streams: the scratch they work in goes with the context
+    (void)c->ssaoUse.drain();
     delete c;
     return RT_OK;
 }
@@ -604,15 +624,18 @@ int rt_bloom(rt_context *c, const void *dScene, void *dOut, int width, int heigh
              int iterations, void *hipStream) {
     if (!c) return RT_ERR_INVALID_ARG;
     if (!dScene || !dOut || width <= 0 || height <= 0 || iterations < 0) return fail(c, RT_ERR_INVALID_ARG, "bad rt_bloom arguments");
+    if (dOut == dScene) return fail(c, RT_ERR_INVALID_ARG, "rt_bloom cannot run in place");     // the fused passes read neighbouring tiles' scene texels
     HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t s = hipStream ? (hipStream_t)hipStream : c->stream;
     const size_t npx = (size_t)width * height;
     if (!(c->dBloom[0].holds(npx) && c->dBloom[1].holds(npx))) {
-        HIP_TRY(c, hipStreamSynchronize(s));
+        HIP_TRY(c, c->bloomUse.drain());       // the last pass in the old targets, on whichever stream it ran
         HIP_TRY(c, c->dBloom[0].grow(npx));
         HIP_TRY(c, c->dBloom[1].grow(npx));
     }
+    HIP_TRY(c, c->bloomUse.acquire(s));
     HIP_TRY(c, rt_launch_bloom(dScene, c->dBloom[0], c->dBloom[1], dOut, width, height, threshold, strength, iterations, s));
+    HIP_TRY(c, c->bloomUse.release(s));
     return RT_OK;
 }
 
@@ -678,15 +701,18 @@ int rt_ssao(rt_context *c, const void *dPosition, const void *dNormal, void *dOu
     if (!dPosition || !dNormal || !dOut || !hNoise || !hSamples || !hProjection || !hView || width <= 0 || height <= 0)
         return fail(c, RT_ERR_INVALID_ARG, "bad rt_ssao arguments");
     if (noiseW <= 0 || noiseH <= 0 || noiseW * noiseH > 16) return fail(c, RT_ERR_TOO_LARGE, "rotation texture larger than 16 texels");
+    if (dOut == dPosition || dOut == dNormal) return fail(c, RT_ERR_INVALID_ARG, "rt_ssao cannot run in place");   // samples read other pixels' G-buffer
     HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t s = hipStream ? (hipStream_t)hipStream : c->stream;
     const size_t npx = (size_t)width * height;
     if (!c->dSsaoDepth.holds(npx)) {
-        HIP_TRY(c, hipDeviceSynchronize());
+        HIP_TRY(c, c->ssaoUse.drain());        // the last pass that read the old plane, on whichever stream it ran
         HIP_TRY(c, c->dSsaoDepth.grow(npx));
     }
+    HIP_TRY(c, c->ssaoUse.acquire(s));
     HIP_TRY(c, rt_launch_ssao(dPosition, dNormal, c->dSsaoDepth, dOut, width, height, hNoise, noiseW, noiseH, hSamples, hProjection,
                               hView, s));
+    HIP_TRY(c, c->ssaoUse.release(s));
     return RT_OK;
 }
 
