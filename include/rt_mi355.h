@@ -438,6 +438,60 @@ int rt_frame(rt_context *ctx, const rt_params *p, const rt_frame_desc *desc, voi
  * pass has not run. */
 int rt_frame_surfaces(rt_context *ctx, void **dColor, void **dPosition, void **dNormal, void **dAO, void **dHistory);
 
+/* ---- the last step of Render(): the default framebuffer and glfwSwapBuffers (ForwardShadingPipeline.cpp:220-228 draws
+ *      bloom_combineFs.glsl into the 8-bit default framebuffer, glfwSwapBuffers at :267 puts it on the screen).  This card has no display
+ *      engine: the frame reaches a screen, an encoder or a file through host memory, as the 4 B per pixel those consume.
+ *      rt_display_pack: dImage (device, width*height rgba32f: gColor, rt_frame's dDisplay -- the image BEFORE this
+ *      quantisation --, a TAA history slot, rt_shade_rays' colour) -> dOut (device, width*height*4 bytes: R, G, B, A in byte
+ *      order, rows tightly packed).  Both pointers 16-byte aligned; the two ranges must not overlap.  Asynchronous on
+ *      hipStream (NULL = the context's stream).  Per colour channel x, all in fp32:
+ *        y = x * exposure;  NaN -> 0;  y <= 0 (with -0, -inf) -> 0;  y >= 1 (with +inf) -> 255;  otherwise
+ *        RT_DISPLAY_RGBA8_LINEAR  q = rint(y * 255.0f), round to nearest even: GL's float -> UNORM8 conversion, what the
+ *                                 reference's framebuffer stores (it never enables GL_FRAMEBUFFER_SRGB);
+ *        RT_DISPLAY_RGBA8_SRGB    q = the number of i in 1..255 with T[i] <= y, T[i] = the fp32 nearest to
+ *                                 f((i - 0.5) / 255) evaluated in double, f(s) = s / 12.92 for s <= 0.04045, else
+ *                                 ((s + 0.055) / 1.055)^2.4: the sRGB code whose decoded value interval holds y.
+ *      Alpha out is 255: every surface's alpha is the constant 1.0 (raytracingCs.glsl:581-583, bloom_combineFs.glsl:13).
+ *      exposure must be finite and > 0; unknown format or flag bits and non-zero reserved words are refused.
+ *      rt_display_srgb_thresholds: the table T (out[0] = 0), built on the host; needs no GPU. */
+typedef enum rt_display_format { RT_DISPLAY_RGBA8_LINEAR = 0, RT_DISPLAY_RGBA8_SRGB = 1 } rt_display_format;
+#define RT_DISPLAY_FLIP_ROWS 1u   /* output row 0 = TOP image row (file / encoder order); default keeps row 0 = bottom */
+typedef struct rt_display_desc {
+    int32_t width, height;
+    int32_t format;                  /* rt_display_format */
+    uint32_t flags;                  /* RT_DISPLAY_FLIP_ROWS */
+    float exposure;
+    int32_t reserved[3];             /* zero */
+} rt_display_desc;
+int rt_display_pack(rt_context *ctx, const void *dImage, void *dOut, const rt_display_desc *desc, void *hipStream);
+int rt_display_srgb_thresholds(float out[256]);
+
+/* ---- pipelined delivery of packed frames to the host.  A ring of `slots` (2..8, default 3) entries, each a device staging
+ *      buffer, a pinned host buffer and an event.  rt_present_submit packs dImage (as rt_display_pack) into the next slot on
+ *      hipStream (NULL = the context's stream) and has a context-owned non-blocking copy stream move the 4 B per pixel to the
+ *      slot's pinned buffer behind it; it returns a ticket (0, 1, 2, ...; slot = ticket % slots) and does not block the host
+ *      in steady state.  Two consequences:
+ *        - dImage is consumed in hipStream's order: work enqueued on hipStream after rt_present_submit returns may overwrite
+ *          it at once (the next frame's render into the same surface, for one);
+ *        - the copy is not in hipStream's order: it overlaps whatever the caller launches next.
+ *      rt_present_wait blocks the host until THAT ticket's copy is complete, and on nothing else; it returns the slot's pinned
+ *      pixels (rt_display_pack's layout) and width*height*4.  The pointer stays valid until the submit of ticket + slots,
+ *      which reuses the slot; a ticket older than that has expired and, like one not issued yet, gives RT_ERR_INVALID_ARG.
+ *      Waiting twice on a live ticket is allowed.  rt_present_poll: the same rules without blocking (*ready = 0 or 1).
+ *      A slot's buffers grow when the slot is next used for a larger frame, after a host wait for that slot's own last copy
+ *      (the rule of the post passes' scratch); other slots' tickets stay valid.  rt_present_configure changes the slot count
+ *      and expires every ticket issued so far; it is refused (RT_ERR_INVALID_ARG) while a ticket is outstanding: live and not
+ *      yet seen complete by the host (returned by rt_present_wait, or reported ready by rt_present_poll).  rt_destroy waits
+ *      for the copies in flight.  The loop of a host that shows frame k - 1 while frame k renders:
+ *          rt_frame(ctx, &p, &d, dDisplay);                                (or any producer of an rgba32f surface)
+ *          rt_present_submit(ctx, dDisplay, &desc, NULL, &t);  if (t) rt_present_wait(ctx, t - 1, &pixels, &bytes);
+ *      Multi-GPU frames (rt_mgpu_*) have no delivery of their own: the root's surfaces and stream (rt_mgpu_get_surfaces) can
+ *      be passed to rt_present_submit of a context on the root device. */
+int rt_present_configure(rt_context *ctx, int slots);
+int rt_present_submit(rt_context *ctx, const void *dImage, const rt_display_desc *desc, void *hipStream, uint64_t *ticket);
+int rt_present_poll(rt_context *ctx, uint64_t ticket, int *ready);
+int rt_present_wait(rt_context *ctx, uint64_t ticket, const void **hostPixels, size_t *bytes);
+
 /* ---- multi-GPU strip helpers */
 /* Number of local rows a rank owns for interleaved strips. */
 int rt_strip_local_rows(int height, int stripRows, int stripCount, int stripIndex);
@@ -531,6 +585,8 @@ RT_SA(sizeof(rt_ray) == 32 && offsetof(rt_ray, tMax) == 12 && offsetof(rt_ray, d
 RT_SA(sizeof(rt_hit) == 32 && offsetof(rt_hit, t) == 12 && offsetof(rt_hit, normal) == 16 && offsetof(rt_hit, object) == 28,
       "rt_hit layout");
 RT_SA(sizeof(rt_pixel) == 8 && offsetof(rt_pixel, y) == 4, "rt_pixel layout");
+RT_SA(sizeof(rt_display_desc) == 32 && offsetof(rt_display_desc, flags) == 12 && offsetof(rt_display_desc, exposure) == 16,
+      "rt_display_desc is 32 B");
 #undef RT_SA
 #endif
 

@@ -32,6 +32,29 @@ struct ScratchUse {
     hipError_t drain() { return used ? hipEventSynchronize(ev) : hipSuccess; }
 };
 
+// The ring rt_present_submit delivers packed frames through.  Ticket t lives in slot t % slots: the pack kernel writes the
+// slot's device staging buffer on the caller's stream, the copy stream moves it to the slot's pinned buffer behind `packed`
+// and records `done`.  The next user of the slot orders its pack behind `done` on the device; the host waits on `done` only
+// for the ticket it asks for, before the slot's buffers grow, and (the copy stream as a whole) before the ring goes.
+struct PresentRing {
+    static constexpr int kMaxSlots = 8;
+    struct Slot {
+        DevBuf<uint8_t> dStage;
+        PinnedBuf<uint8_t> hPixels;
+        DevEvent packed, done;
+        bool used = false;               // `done` has been recorded at least once
+        bool seen = false;               // the host has seen the slot's current ticket complete (wait, or a ready poll)
+        uint64_t ticket = 0;
+        size_t bytes = 0;
+    };
+    DevStream copy;                      // created by the first submit: a context that never presents opens no second stream
+    Slot slot[kMaxSlots];
+    int slots = 3;
+    uint64_t next = 0;                   // the ticket the next submit returns
+    uint64_t base = 0;                   // tickets below it were expired by rt_present_configure
+    bool live(uint64_t t) const { return t < next && t >= base && next - t <= (uint64_t)slots; }
+};
+
 // Everything the context allocates is held by an owner (rt_devbuf.h): after rt_destroy has drained the streams, `delete`
 // releases it all.  The stream comes first so that it goes last.
 struct rt_context {
@@ -83,6 +106,7 @@ struct rt_context {
     // rt_pick: the hit record on the device and its pinned host copy
     DevBuf<float4> dPick;
     PinnedBuf<rt_hit> hPick;
+    PresentRing present;                       // rt_present_*: staging, pinned buffers and events of the frames on their way to the host
     std::string err;
 };
 
@@ -265,6 +289,7 @@ int rt_destroy(rt_context *c) {
     (void)c->sched.drain();            // the context's stream, the phase stream, every stream's last launch
     (void)c->bloomUse.drain();         // post passes on caller streams: the scratch they work in goes with the context
     (void)c->ssaoUse.drain();
+    if (c->present.copy) (void)hipStreamSynchronize(c->present.copy);   // frames on their way to the pinned buffers (and, before them, their packs)
     delete c;
     return RT_OK;
 }
@@ -723,6 +748,134 @@ int rt_ssao_blur(rt_context *c, const void *dIn, void *dOut, int width, int heig
     HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t s = hipStream ? (hipStream_t)hipStream : c->stream;
     HIP_TRY(c, rt_launch_ssao_blur(dIn, dOut, width, height, horizontal, s));
+    return RT_OK;
+}
+
+// ---- display packing and delivery (the header has the contract)
+static int validate_display(rt_context *c, const void *dImage, const rt_display_desc *d) {
+    if (!d) return fail(c, RT_ERR_INVALID_ARG, "display description is NULL");
+    if (d->width <= 0 || d->height <= 0) return fail(c, RT_ERR_INVALID_ARG, "width/height must be positive");
+    if (d->format != RT_DISPLAY_RGBA8_LINEAR && d->format != RT_DISPLAY_RGBA8_SRGB) return fail(c, RT_ERR_INVALID_ARG, "unknown display format");
+    if (d->flags & ~RT_DISPLAY_FLIP_ROWS) return fail(c, RT_ERR_INVALID_ARG, "unknown display flag bits");
+    if (!(d->exposure > 0.0f) || !(d->exposure < HUGE_VALF)) return fail(c, RT_ERR_INVALID_ARG, "exposure must be finite and > 0");
+    if (d->reserved[0] || d->reserved[1] || d->reserved[2]) return fail(c, RT_ERR_INVALID_ARG, "reserved words must be zero");
+    if (!dImage || ((uintptr_t)dImage & 15u)) return fail(c, RT_ERR_INVALID_ARG, "the image pointer must be non-NULL and 16-byte aligned");
+    if ((((uint64_t)d->width + 3) / 4) * (uint64_t)d->height > 0xffffff00ull) return fail(c, RT_ERR_TOO_LARGE, "frame too large for one pack launch");
+    return RT_OK;
+}
+
+int rt_display_srgb_thresholds(float out[256]) {
+    if (!out) return RT_ERR_INVALID_ARG;
+    memcpy(out, rt_display_thresholds(), 256 * sizeof(float));
+    return RT_OK;
+}
+
+int rt_display_pack(rt_context *c, const void *dImage, void *dOut, const rt_display_desc *d, void *hipStream) {
+    if (!c) return RT_ERR_INVALID_ARG;
+    int rc = validate_display(c, dImage, d);
+    if (rc) return rc;
+    if (!dOut || ((uintptr_t)dOut & 15u)) return fail(c, RT_ERR_INVALID_ARG, "the output pointer must be non-NULL and 16-byte aligned");
+    const size_t npx = (size_t)d->width * d->height;
+    const uintptr_t i0 = (uintptr_t)dImage, o0 = (uintptr_t)dOut;
+    if (i0 < o0 + npx * 4 && o0 < i0 + npx * 16) return fail(c, RT_ERR_INVALID_ARG, "rt_display_pack cannot run in place: image and output overlap");
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t s = hipStream ? (hipStream_t)hipStream : c->stream;
+    HIP_TRY(c, rt_launch_display_pack(dImage, dOut, d->width, d->height, d->format == RT_DISPLAY_RGBA8_SRGB,
+                                      (d->flags & RT_DISPLAY_FLIP_ROWS) != 0, d->exposure, s));
+    return RT_OK;
+}
+
+int rt_present_configure(rt_context *c, int slots) {
+    if (!c) return RT_ERR_INVALID_ARG;
+    PresentRing &r = c->present;
+    if (slots < 2 || slots > PresentRing::kMaxSlots) return fail(c, RT_ERR_INVALID_ARG, "rt_present_configure: 2..8 slots");
+    for (int k = 0; k < r.slots; k++)
+        if (r.slot[k].used && r.live(r.slot[k].ticket) && !r.slot[k].seen)
+            return fail(c, RT_ERR_INVALID_ARG, "rt_present_configure: a ticket is outstanding (wait for it first)");
+    // every live ticket's copy has been seen complete, older ones finished before them (one copy stream): nothing reads the buffers
+    HIP_TRY(c, hipSetDevice(c->device));
+    for (int k = slots; k < PresentRing::kMaxSlots; k++) {
+        HIP_TRY(c, r.slot[k].dStage.release());
+        HIP_TRY(c, r.slot[k].hPixels.release());
+    }
+    r.slots = slots;
+    r.base = r.next;
+    return RT_OK;
+}
+
+int rt_present_submit(rt_context *c, const void *dImage, const rt_display_desc *d, void *hipStream, uint64_t *ticket) {
+    if (!c) return RT_ERR_INVALID_ARG;
+    if (!ticket) return fail(c, RT_ERR_INVALID_ARG, "ticket is NULL");
+    int rc = validate_display(c, dImage, d);
+    if (rc) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    PresentRing &r = c->present;
+    PresentRing::Slot &sl = r.slot[r.next % (uint64_t)r.slots];
+    hipStream_t s = hipStream ? (hipStream_t)hipStream : c->stream;
+    HIP_TRY(c, r.copy.create());
+    HIP_TRY(c, sl.packed.create(hipEventDisableTiming));
+    HIP_TRY(c, sl.done.create(hipEventDisableTiming));
+    const size_t bytes = (size_t)d->width * d->height * 4;
+    if (!(sl.dStage.holds(bytes) && sl.hPixels.holds(bytes))) {
+        if (sl.used) HIP_TRY(c, hipEventSynchronize(sl.done));      // this slot's own last copy; the other slots are untouched
+        HIP_TRY(c, sl.dStage.grow(bytes));
+        HIP_TRY(c, sl.hPixels.grow(bytes));
+    }
+    if (sl.used) HIP_TRY(c, hipStreamWaitEvent(s, sl.done, 0));     // the copy of ticket - slots has left the staging buffer
+    HIP_TRY(c, rt_launch_display_pack(dImage, sl.dStage, d->width, d->height, d->format == RT_DISPLAY_RGBA8_SRGB,
+                                      (d->flags & RT_DISPLAY_FLIP_ROWS) != 0, d->exposure, s));
+    HIP_TRY(c, hipEventRecord(sl.packed, s));
+    HIP_TRY(c, hipStreamWaitEvent(r.copy, sl.packed, 0));
+    HIP_TRY(c, hipMemcpyAsync(sl.hPixels, sl.dStage, bytes, hipMemcpyDeviceToHost, r.copy));
+    HIP_TRY(c, hipEventRecord(sl.done, r.copy));
+    sl.used = true;
+    sl.seen = false;
+    sl.ticket = r.next;
+    sl.bytes = bytes;
+    *ticket = r.next++;
+    return RT_OK;
+}
+
+static int present_slot(rt_context *c, uint64_t ticket, PresentRing::Slot **out) {
+    PresentRing &r = c->present;
+    if (ticket >= r.next) return fail(c, RT_ERR_INVALID_ARG, "ticket has not been issued");
+    if (!r.live(ticket)) return fail(c, RT_ERR_INVALID_ARG, "ticket has expired (its slot was reused or the ring reconfigured)");
+    *out = &r.slot[ticket % (uint64_t)r.slots];
+    return RT_OK;
+}
+
+int rt_present_poll(rt_context *c, uint64_t ticket, int *ready) {
+    if (!c) return RT_ERR_INVALID_ARG;
+    if (!ready) return fail(c, RT_ERR_INVALID_ARG, "ready is NULL");
+    *ready = 0;
+    PresentRing::Slot *sl;
+    int rc = present_slot(c, ticket, &sl);
+    if (rc) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const hipError_t e = hipEventQuery(sl->done);
+    if (e == hipErrorNotReady) {
+        (void)hipGetLastError();           // not an error: keep it out of the next launch's hipGetLastError()
+        return RT_OK;
+    }
+    if (e != hipSuccess) return fail(c, RT_ERR_HIP, "hipEventQuery(done)", e);
+    sl->seen = true;
+    *ready = 1;
+    return RT_OK;
+}
+
+int rt_present_wait(rt_context *c, uint64_t ticket, const void **hostPixels, size_t *bytes) {
+    if (!c) return RT_ERR_INVALID_ARG;
+    if (!hostPixels) return fail(c, RT_ERR_INVALID_ARG, "hostPixels is NULL");
+    *hostPixels = nullptr;
+    if (bytes) *bytes = 0;
+    PresentRing::Slot *sl;
+    int rc = present_slot(c, ticket, &sl);
+    if (rc) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipEventSynchronize(sl->done));
+    sl->seen = true;
+    *hostPixels = sl->hPixels.ptr;
+    if (bytes) *bytes = sl->bytes;
     return RT_OK;
 }
 

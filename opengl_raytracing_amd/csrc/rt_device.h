@@ -99,6 +99,9 @@ hipError_t rt_launch_ssao_blur(const void *in, void *out, int W, int H, int hori
 hipError_t rt_launch_equirect_to_cubemap(const float *dRgb, void *dTex, int W, int H, int S, void *dFaces, hipStream_t s);
 hipError_t rt_launch_bloom(const void *scene, void *tmpA, void *tmpB, void *out, int W, int H, float threshold, float strength,
                            int iterations, hipStream_t s);
+// rgba32f -> RGBA8 (rt_post.hip); `out` rows tightly packed, both pointers 16-byte aligned, W * H below 2^32 quads of 4 pixels
+hipError_t rt_launch_display_pack(const void *image, void *out, int W, int H, int srgb, int flip, float exposure, hipStream_t s);
+const float *rt_display_thresholds();      // the 256 sRGB decision thresholds ([0] = 0), built on the host on first use
 hipError_t rt_launch_wire_pack(const void *dColor, const void *dPos, const void *dNormal, void *dWire, size_t nPixels,
                                hipStream_t s);
 hipError_t rt_launch_wire_unpack(const void *dWire, size_t rankStrideBytes, size_t rankPixels, const void *dRootColor,

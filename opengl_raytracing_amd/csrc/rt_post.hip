@@ -10,6 +10,7 @@
 // LDS instead: measured equal).
 #include <hip/hip_fp16.h>
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stdint.h>
 #include <string.h>
 
@@ -838,5 +839,113 @@ hipError_t rt_launch_equirect_to_cubemap(const float *dRgb, void *dTex, int W, i
     hipLaunchKernelGGL(rt_equirect_upload_kernel, dim3((unsigned)blocks), dim3(256), 0, s, dRgb, (uint2 *)dTex, n);
     dim3 grid((S + 31) / 32, (S + 7) / 8, 6);
     hipLaunchKernelGGL(rt_equirect_to_cubemap_kernel, grid, dim3(256), 0, s, (const uint2 *)dTex, W, H, S, (unsigned short *)dFaces);
+    return hipGetLastError();
+}
+
+// =========================================================================================
+// Display packing: any rgba32f surface -> RGBA8, the quantisation an 8-bit default framebuffer applies to what
+// bloom_combineFs.glsl draws into it (ForwardShadingPipeline.cpp:220-228, then glfwSwapBuffers).
+// Purely bandwidth-bound: 16 B read + 4 B written per pixel.  A lane owns four consecutive pixels of ONE row (a "quad";
+// the last quad of a row is short when W % 4 != 0, so a lane never straddles rows): four 16-B loads issued together,
+// one 16-B store; consecutive lanes take consecutive quads, so a wave reads 4 KiB and writes 1 KiB contiguously.
+// FLIP_ROWS only changes the row the store goes to.  Per colour channel (include/rt_mi355.h has the definition):
+// y = x * exposure; NaN and y <= 0 -> 0, y >= 1 -> 255; LINEAR q = rint(y * 255) (v_rndne_f32: nearest even);
+// SRGB q = #{i in 1..255 : T[i] <= y}, T the host-built table of rt_display_thresholds().  The kernel finds that
+// count with a branch-free 8-step descent of the table laid out as an implicit search tree in LDS (node n's
+// children are 2n and 2n + 1, level d occupies the 2^d consecutive entries from 2^d): after 8 steps the node
+// number minus 256 IS the count, and the lanes of a wave spread over consecutive banks at every level where a
+// sorted layout would put levels 2..5 on one or two banks.  No transcendental runs on the device.
+// =========================================================================================
+struct RtDisplayTree { float node[256]; };       // node[0] unused; 1 KiB of kernel arguments, staged into LDS by each workgroup
+
+namespace {
+struct DisplayTables {
+    float thresholds[256];
+    RtDisplayTree tree;
+};
+const DisplayTables &display_tables() {
+    static const DisplayTables tables = [] {               // built once, on first use (thread-safe: a function-local static)
+        DisplayTables t;
+        t.thresholds[0] = 0.0f;
+        for (int i = 1; i < 256; i++) {          // the sRGB EOTF at the midpoint between codes i - 1 and i, in double
+            const double s = ((double)i - 0.5) / 255.0;
+            const double f = s <= 0.04045 ? s / 12.92 : pow((s + 0.055) / 1.055, 2.4);
+            t.thresholds[i] = (float)f;
+        }
+        t.tree.node[0] = 0.0f;
+        for (int d = 0; d < 8; d++)              // level d, position p: the key of rank (2p + 1) * 2^(7 - d)
+            for (int p = 0; p < (1 << d); p++) t.tree.node[(1 << d) + p] = t.thresholds[(2 * p + 1) << (7 - d)];
+        return t;
+    }();
+    return tables;
+}
+
+template <bool SRGB>
+__device__ __forceinline__ unsigned display_code(float x, float exposure, const float *tree) {
+    const float y = x * exposure;
+    const float yc = !(y > 0.0f) ? 0.0f : (y >= 1.0f ? 1.0f : y);     // NaN, -0, -inf -> 0; +inf -> 1
+    if constexpr (SRGB) {
+        unsigned n = 1;
+#pragma unroll
+        for (int d = 0; d < 8; d++) n = 2 * n + (tree[n] <= yc ? 1u : 0u);
+        return n - 256u;
+    } else {
+        return (unsigned)rintf(yc * 255.0f);
+    }
+}
+}  // namespace
+
+const float *rt_display_thresholds() { return display_tables().thresholds; }
+
+// QUADS: W % 4 == 0 -- every quad is whole and every output quad 16-B aligned: no predicate anywhere, one 16-B store.
+// Otherwise the rows of the output are only 4-B aligned and the last quad of a row is short: predicated loads, 4-B stores.
+template <bool SRGB, bool QUADS>
+__global__ __launch_bounds__(256) void rt_display_pack_kernel(const float4 *__restrict__ in, unsigned *__restrict__ out, int W, int H,
+                                                              unsigned quadsPerRow, unsigned nQuads, int flip, float exposure,
+                                                              const RtDisplayTree tree) {
+    __shared__ float lds[SRGB ? 256 : 1];
+    const unsigned g = blockIdx.x * 256u + threadIdx.x;
+    const bool valid = g < nQuads;                           // (no early return: the sRGB form has a barrier below)
+    const unsigned j = g / quadsPerRow, q = g - j * quadsPerRow;
+    const int x0 = (int)(q * 4u);
+    const int r = !valid ? 0 : (QUADS ? 4 : min(4, W - x0)); // pixels of this quad: 4, or 1..3 at a ragged row end
+    const float4 *src = in + (size_t)j * W + x0;
+    float4 p[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) p[k] = k < r ? src[k] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if constexpr (SRGB) {                                    // the table goes to LDS while the pixels are on their way
+        lds[threadIdx.x] = tree.node[threadIdx.x];
+        __syncthreads();
+    }
+    if (!valid) return;
+    unsigned px[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++)
+        px[k] = display_code<SRGB>(p[k].x, exposure, lds) | (display_code<SRGB>(p[k].y, exposure, lds) << 8) |
+                (display_code<SRGB>(p[k].z, exposure, lds) << 16) | 0xff000000u;
+    const unsigned jo = flip ? (unsigned)(H - 1) - j : j;
+    unsigned *dst = out + (size_t)jo * W + x0;
+    if constexpr (QUADS) {
+        *(uint4 *)dst = make_uint4(px[0], px[1], px[2], px[3]);
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; k++)
+            if (k < r) dst[k] = px[k];
+    }
+}
+
+hipError_t rt_launch_display_pack(const void *image, void *out, int W, int H, int srgb, int flip, float exposure, hipStream_t s) {
+    const unsigned quadsPerRow = ((unsigned)W + 3u) / 4u;
+    const unsigned long long nQuads = (unsigned long long)quadsPerRow * (unsigned)H;
+    if (nQuads > 0xffffff00ull) return hipErrorInvalidValue;       // (callers refuse such frames first)
+    const dim3 grid((unsigned)((nQuads + 255) / 256));
+    const RtDisplayTree &tree = display_tables().tree;
+    auto go = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, (const float4 *)image, (unsigned *)out, W, H, quadsPerRow, (unsigned)nQuads,
+                           flip, exposure, tree);
+    };
+    const bool quads = (W & 3) == 0;
+    if (srgb) quads ? go(rt_display_pack_kernel<true, true>) : go(rt_display_pack_kernel<true, false>);
+    else quads ? go(rt_display_pack_kernel<false, true>) : go(rt_display_pack_kernel<false, false>);
     return hipGetLastError();
 }

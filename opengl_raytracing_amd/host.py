@@ -39,6 +39,7 @@ EXPORTS = [
     "rt_render_into_image", "rt_context_stream", "rt_mgpu_create", "rt_mgpu_destroy", "rt_mgpu_device_count", "rt_mgpu_set_scene", "rt_mgpu_set_noise",
     "rt_mgpu_set_skybox", "rt_mgpu_set_strip_rows", "rt_mgpu_render", "rt_mgpu_sync", "rt_mgpu_get_surfaces", "rt_mgpu_readback", "rt_mgpu_last_ms",
     "rt_mgpu_last_error", "rt_trace_rays", "rt_camera_rays", "rt_pick", "rt_shade_rays", "rt_debug_device_math",
+    "rt_display_pack", "rt_display_srgb_thresholds", "rt_present_configure", "rt_present_submit", "rt_present_poll", "rt_present_wait",
 ]
 
 
@@ -154,6 +155,12 @@ def load_library(build_if_missing=True):
     lib.rt_pick.argtypes = [vp, P(L.RtParams), ci, ci, P(L.RtHit)]
     lib.rt_shade_rays.argtypes = [vp, P(L.RtParams), vp, vp, ctypes.c_size_t, vp, vp, vp, vp]
     lib.rt_debug_device_math.argtypes = [vp, ci, vp, vp, ctypes.c_size_t, vp]
+    lib.rt_display_pack.argtypes = [vp, vp, vp, P(L.RtDisplayDesc), vp]
+    lib.rt_display_srgb_thresholds.argtypes = [P(cf)]
+    lib.rt_present_configure.argtypes = [vp, ci]
+    lib.rt_present_submit.argtypes = [vp, vp, P(L.RtDisplayDesc), vp, P(ctypes.c_uint64)]
+    lib.rt_present_poll.argtypes = [vp, ctypes.c_uint64, P(ci)]
+    lib.rt_present_wait.argtypes = [vp, ctypes.c_uint64, P(vp), P(ctypes.c_size_t)]
     for name in EXPORTS:
         if name not in ("rt_last_error", "rt_mgpu_last_error", "rt_wire_bytes"):
             getattr(lib, name).restype = ci
@@ -269,6 +276,21 @@ def strip_local_rows(height, strip_rows, strip_count, strip_index):
     if n < 0:
         raise RtError(n, "rt_strip_local_rows")
     return n
+
+
+def display_srgb_thresholds():
+    """The 256 decision thresholds of the sRGB display format (rt_display_srgb_thresholds): float32, [0] = 0; a colour value
+    y in (0, 1) becomes the number of entries 1..255 that are <= y.  Needs no GPU."""
+    out = np.zeros(256, dtype=np.float32)
+    rc = load_library().rt_display_srgb_thresholds(out.ctypes.data_as(ctypes.POINTER(ctypes.c_float)))
+    if rc:
+        raise RtError(rc, "rt_display_srgb_thresholds")
+    return out
+
+
+def _dev_ptr(x):
+    """A device address: a raw pointer (int) or anything with data_ptr() (a torch tensor)."""
+    return ctypes.c_void_p(x.data_ptr() if hasattr(x, "data_ptr") else x)
 
 
 PickHit = collections.namedtuple("PickHit", "object t position normal")
@@ -548,6 +570,54 @@ class RayTracer:
         """Bloom chain on device surfaces (raw device pointers as ints)."""
         self._check(self.lib.rt_bloom(self.ctx, ctypes.c_void_p(d_scene), ctypes.c_void_p(d_out), width, height, threshold,
                                       strength, iterations, ctypes.c_void_p(stream) if stream else None), "rt_bloom")
+
+    # ---- display packing and delivery to the host ------------------------------------------
+    def display_pack(self, d_image, d_out, width, height, format="linear", flip=False, exposure=1.0, stream=None):
+        """rgba32f surface -> RGBA8 on the device (rt_display_pack).  d_image / d_out: raw device pointers (ints) or CUDA
+        tensors, 16-byte aligned, not overlapping; d_out holds height * width * 4 bytes (R, G, B, A), row 0 = bottom unless
+        `flip`.  format "linear" or "srgb".  Asynchronous on torch stream `stream` (default torch.cuda.current_stream())."""
+        d = L.make_display_desc(width, height, format, flip, exposure)
+        self._on_torch_stream(stream, lambda h: self._check(self.lib.rt_display_pack(
+            self.ctx, _dev_ptr(d_image), _dev_ptr(d_out), ctypes.byref(d), ctypes.c_void_p(h)), "rt_display_pack"))
+
+    def present_configure(self, slots):
+        """Number of frames that can be on their way to the host at once (2..8, default 3); expires every earlier ticket and
+        is refused while one is outstanding (submitted, not yet waited for or polled ready)."""
+        self._check(self.lib.rt_present_configure(self.ctx, int(slots)), "rt_present_configure")
+
+    def present_submit(self, d_image, width, height, format="linear", flip=False, exposure=1.0, stream=None):
+        """Pack the rgba32f surface d_image (raw device pointer or CUDA tensor) as display_pack does and start its copy into a
+        pinned host buffer -> ticket (0, 1, 2, ...).  Ordered on torch stream `stream` (default torch.cuda.current_stream()):
+        later work on that stream may overwrite d_image at once, and the copy overlaps it.  Does not block the host."""
+        d = L.make_display_desc(width, height, format, flip, exposure)
+        t = ctypes.c_uint64()
+        self._on_torch_stream(stream, lambda h: self._check(self.lib.rt_present_submit(
+            self.ctx, _dev_ptr(d_image), ctypes.byref(d), ctypes.c_void_p(h), ctypes.byref(t)), "rt_present_submit"))
+        self._present_shapes = getattr(self, "_present_shapes", {})
+        self._present_shapes[t.value] = (int(height), int(width))
+        for old in [k for k in self._present_shapes if k + 16 <= t.value]:     # (more than any ring holds)
+            del self._present_shapes[old]
+        return t.value
+
+    def present_poll(self, ticket):
+        """True once present_wait(ticket) would not block."""
+        ready = ctypes.c_int(0)
+        self._check(self.lib.rt_present_poll(self.ctx, int(ticket), ctypes.byref(ready)), "rt_present_poll")
+        return bool(ready.value)
+
+    def present_wait(self, ticket, copy=True):
+        """Block until the frame of `ticket` is in host memory -> uint8 [height, width, 4].  copy=False returns a read-only
+        view of the ring's pinned slot instead: valid until the present_submit that returns ticket + slots (or
+        present_configure, or close()), after which its memory is rewritten or gone -- copy what must outlive that."""
+        p, n = ctypes.c_void_p(), ctypes.c_size_t(0)
+        self._check(self.lib.rt_present_wait(self.ctx, int(ticket), ctypes.byref(p), ctypes.byref(n)), "rt_present_wait")
+        h, w = self._present_shapes[int(ticket)]
+        assert n.value == h * w * 4
+        view = np.frombuffer((ctypes.c_uint8 * n.value).from_address(p.value), dtype=np.uint8).reshape(h, w, 4)
+        if copy:
+            return view.copy()
+        view.flags.writeable = False
+        return view
 
     def tile_costs(self):
         """(costs[tilesY, tilesX] uint32, cycles/64 per tile) of the last feedback-scheduled launch."""

@@ -208,3 +208,24 @@ class RtPixel(ctypes.Structure):
 
 
 assert ctypes.sizeof(RtPixel) == PIXEL_DTYPE.itemsize == 8
+
+
+# ---- display packing and delivery (rt_display_pack / rt_present_*, include/rt_mi355.h) --------
+DISPLAY_RGBA8_LINEAR, DISPLAY_RGBA8_SRGB = 0, 1
+DISPLAY_FLIP_ROWS = 1
+
+
+class RtDisplayDesc(ctypes.Structure):
+    """``rt_display_desc``: size of the rgba32f surface, output format, flags, exposure."""
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("format", ctypes.c_int32), ("flags", ctypes.c_uint32),
+                ("exposure", ctypes.c_float), ("reserved", ctypes.c_int32 * 3)]
+
+
+assert ctypes.sizeof(RtDisplayDesc) == 32
+
+
+def make_display_desc(width, height, format="linear", flip=False, exposure=1.0):
+    f = {"linear": DISPLAY_RGBA8_LINEAR, "srgb": DISPLAY_RGBA8_SRGB}.get(format, format)
+    d = RtDisplayDesc()
+    d.width, d.height, d.format, d.flags, d.exposure = int(width), int(height), int(f), DISPLAY_FLIP_ROWS if flip else 0, float(exposure)
+    return d
