@@ -492,6 +492,86 @@ int rt_present_submit(rt_context *ctx, const void *dImage, const rt_display_desc
 int rt_present_poll(rt_context *ctx, uint64_t ticket, int *ready);
 int rt_present_wait(rt_context *ctx, uint64_t ticket, const void **hostPixels, size_t *bytes);
 
+/* ---- exposure metering: what turns the HDR surfaces above into an `exposure` for the pack without a read-back.  The
+ *      reference has no counterpart (it clips at 1); this is the auto-exposure with eye adaptation every HDR display path has.
+ *      rt_meter: dImage (device, width*height rgba32f, 16-byte aligned, alpha ignored) -> dState (device, one rt_meter_state,
+ *      16-byte aligned, owned by the caller).  Asynchronous on hipStream (NULL = the context's stream): a clear, a histogram
+ *      kernel and a one-workgroup solve kernel in stream order, no host synchronisation.  The caller zeroes the state once
+ *      (frames == 0) and passes it to every later call; a call reads only `exposure` and `frames` of the previous state and
+ *      overwrites everything else.  All arithmetic is fp32 without fused multiply-add, or integer:
+ *        Y = (0.2126f*r + 0.7152f*g) + 0.0722f*b;
+ *        Y NaN -> nNaN;  Y == +inf -> nInf;  !(Y > 0) (with -0, -inf) -> nNonPositive;  otherwise the pixel is METERED:
+ *        bin = clamp((bits(Y) >> 20) - 888, 0, 255): 8 bins per octave, linear in the top three mantissa bits, over
+ *        2^-16 <= Y < 2^16; smaller Y (denormals too) in bin 0, larger in bin 255.  minLum / maxLum: the extremes of the
+ *        metered Y, bit-exact (+inf / 0 when no pixel is metered).  sum(hist) + nNaN + nInf + nNonPositive == nPixels.
+ *      Solve, on the device behind the histogram (integer atomics only: the state is bit-identical from run to run):
+ *        n = sum(hist); lo = n*lowPermille/1000, hi = n*highPermille/1000 (64-bit floor division); hist' = hist with lo
+ *        counts removed walking the bins upward, then hi counts walking downward; nMetered = n' = n - lo - hi;
+ *        S = sum(hist'[b] * q[b]), q[b] = (b>>3)*65536 + log2q16[b&7];  meanLog2Q16 = m = S / n' (uint64 floor division):
+ *        m/65536 - 16 is the log2 of the trimmed geometric-mean luminance to within a bin;
+ *        target = clamp(key * ldexpf(pow2neg[(m>>8)&255], 16 - (m>>16)), minExposure, maxExposure): one fp32 multiply;
+ *        n' == 0: target = the stored exposure when frames != 0 and it is finite and > 0, else 1.0f;
+ *        exposure = target when frames == 0, the stored exposure is not finite and > 0, or adapt >= 1; otherwise
+ *        old + (target - old) * adapt (a subtraction, a multiplication, an addition, in that order);
+ *        frames = frames + 1, saturating at 2^32 - 1.  `hist` stays the untrimmed histogram.
+ *      rt_meter_tables: pow2neg[f] = the fp32 nearest to 2^(-f/256), log2q16[j] = round(65536*log2(1 + (j+0.5)/8)), both
+ *      evaluated in double on the host.  rt_meter_solve_host: the same solve (one source, csrc/rt_meter.h) from in->hist,
+ *      in->exposure and in->frames; the counters and minLum / maxLum are copied; out may be in.  Neither needs a GPU.
+ *      Refused with RT_ERR_INVALID_ARG: NULL context, descriptor, image or state; a pointer not 16-byte aligned; width or
+ *      height < 1; key not finite and > 0; not 0 < minExposure <= maxExposure < inf; adapt outside (0, 1]; a negative
+ *      permille or lowPermille + highPermille >= 1000; non-zero reserved words.  width*height > 2^31 - 1 (rt_meter) or
+ *      sum(hist) > 2^32 - 1 (rt_meter_solve_host): RT_ERR_TOO_LARGE. */
+typedef struct rt_meter_desc {
+    int32_t width, height;
+    float key;                         /* target mid-grey, e.g. 0.18 */
+    float minExposure, maxExposure;
+    float adapt;                       /* in (0, 1]; 1 = follow the image at once */
+    int32_t lowPermille, highPermille; /* share of the metered pixels dropped at each end */
+    int32_t reserved[4];               /* zero */
+} rt_meter_desc;
+typedef struct rt_meter_state {
+    uint32_t hist[256];
+    uint32_t nPixels, nNonPositive, nNaN, nInf;
+    float minLum, maxLum;
+    uint32_t nMetered;                 /* n' */
+    uint32_t meanLog2Q16;              /* m; 0 when n' == 0 */
+    float target, exposure;
+    uint32_t frames;
+    uint32_t reserved[5];
+} rt_meter_state;
+#define RT_METER_EXPOSURE_OFFSET 1060  /* offsetof(rt_meter_state, exposure): the device float rt_tone_desc.dExposure takes */
+int rt_meter(rt_context *ctx, const void *dImage, const rt_meter_desc *desc, void *dState, void *hipStream);
+int rt_meter_solve_host(const rt_meter_state *in, const rt_meter_desc *desc, rt_meter_state *out);
+int rt_meter_tables(float pow2neg[256], uint32_t log2q16[8]);
+
+/* ---- tone curves and a device-resident exposure in the pack.  rt_display_pack_toned / rt_present_submit_toned are
+ *      rt_display_pack / rt_present_submit (layout, flip, formats, ring, refusals; one ring serves both submits) with, per
+ *      colour channel x:
+ *        e = desc->exposure * (*dExposure): one fp32 multiply, the float read on the device in hipStream's order -- e.g.
+ *            (char *)dState + RT_METER_EXPOSURE_OFFSET behind rt_meter on the same stream; dExposure == NULL: e = desc->exposure;
+ *        y = x * e;  NaN and !(y > 0) -> 0;  otherwise t = curve(min(y, 65536.0f)), every operation rounded to fp32, IEEE division:
+ *        RT_TONE_NONE      t = y;
+ *        RT_TONE_REINHARD  invW2 = 1.0f/(white*white) (host);  a = y*invW2; b = 1+a; c = y*b; d = 1+y; t = c/d  (white maps to 1);
+ *        RT_TONE_ACES      n = y*((2.51f*y)+0.03f); d = (y*((2.43f*y)+0.59f))+0.14f; t = n/d  (Narkowicz's fit);
+ *        then rt_display_pack's rule on t: t >= 1 -> 255, else LINEAR rint(t*255) or the sRGB threshold count.
+ *      With RT_TONE_NONE and dExposure == NULL the bytes are rt_display_pack's.  Refused (RT_ERR_INVALID_ARG) beyond
+ *      rt_display_pack's refusals: NULL tone description, unknown op, REINHARD with white not finite or < 1/256, dExposure not
+ *      4-byte aligned, non-zero reserved words.  The frame loop with auto-exposure, no host round trip anywhere:
+ *          rt_frame(ctx, &p, &d, dDisplay);  rt_meter(ctx, dDisplay, &m, dState, NULL);
+ *          tone.dExposure = (char *)dState + RT_METER_EXPOSURE_OFFSET;
+ *          rt_present_submit_toned(ctx, dDisplay, &desc, &tone, NULL, &t);  if (t) rt_present_wait(ctx, t - 1, &pixels, &bytes); */
+typedef enum rt_tone_op { RT_TONE_NONE = 0, RT_TONE_REINHARD = 1, RT_TONE_ACES = 2 } rt_tone_op;
+typedef struct rt_tone_desc {
+    int32_t op;                      /* rt_tone_op */
+    float white;                     /* REINHARD: the y that maps to 1; ignored otherwise */
+    const void *dExposure;           /* device float, or NULL */
+    int32_t reserved[4];             /* zero */
+} rt_tone_desc;
+int rt_display_pack_toned(rt_context *ctx, const void *dImage, void *dOut, const rt_display_desc *desc, const rt_tone_desc *tone,
+                          void *hipStream);
+int rt_present_submit_toned(rt_context *ctx, const void *dImage, const rt_display_desc *desc, const rt_tone_desc *tone,
+                            void *hipStream, uint64_t *ticket);
+
 /* ---- multi-GPU strip helpers */
 /* Number of local rows a rank owns for interleaved strips. */
 int rt_strip_local_rows(int height, int stripRows, int stripCount, int stripIndex);
@@ -587,6 +667,12 @@ RT_SA(sizeof(rt_hit) == 32 && offsetof(rt_hit, t) == 12 && offsetof(rt_hit, norm
 RT_SA(sizeof(rt_pixel) == 8 && offsetof(rt_pixel, y) == 4, "rt_pixel layout");
 RT_SA(sizeof(rt_display_desc) == 32 && offsetof(rt_display_desc, flags) == 12 && offsetof(rt_display_desc, exposure) == 16,
       "rt_display_desc is 32 B");
+RT_SA(sizeof(rt_meter_desc) == 48 && offsetof(rt_meter_desc, adapt) == 20 && offsetof(rt_meter_desc, reserved) == 32,
+      "rt_meter_desc is 48 B");
+RT_SA(sizeof(rt_meter_state) == 1088 && offsetof(rt_meter_state, nPixels) == 1024 && offsetof(rt_meter_state, minLum) == 1040 &&
+      offsetof(rt_meter_state, nMetered) == 1048 && offsetof(rt_meter_state, exposure) == RT_METER_EXPOSURE_OFFSET &&
+      offsetof(rt_meter_state, frames) == 1064, "rt_meter_state is 1088 B");
+RT_SA(sizeof(rt_tone_desc) == 16 + 2 * sizeof(void *) && offsetof(rt_tone_desc, dExposure) == 8, "rt_tone_desc layout");
 #undef RT_SA
 #endif
 

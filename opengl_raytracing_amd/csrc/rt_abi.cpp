@@ -13,6 +13,7 @@
 
 #include "rt_device.h"
 #include "rt_mesa_math.h"
+#include "rt_meter.h"
 #include "rt_sched.h"
 
 // Last use of a context-owned scratch that post passes on any stream work in (rt_bloom's ping-pong targets, rt_ssao's depth
@@ -803,11 +804,52 @@ int rt_present_configure(rt_context *c, int slots) {
     return RT_OK;
 }
 
-int rt_present_submit(rt_context *c, const void *dImage, const rt_display_desc *d, void *hipStream, uint64_t *ticket) {
+// what the toned entry points add to a display description, validated
+struct ToneArgs {
+    int op = RT_TONE_NONE;
+    float invW2 = 0.0f;
+    const void *dExposure = nullptr;
+};
+
+static int validate_tone(rt_context *c, const rt_tone_desc *t, ToneArgs *out) {
+    if (!t) return fail(c, RT_ERR_INVALID_ARG, "tone description is NULL");
+    if (t->op != RT_TONE_NONE && t->op != RT_TONE_REINHARD && t->op != RT_TONE_ACES) return fail(c, RT_ERR_INVALID_ARG, "unknown tone operator");
+    if (t->op == RT_TONE_REINHARD && (!(t->white >= 1.0f / 256.0f) || !(t->white < HUGE_VALF)))
+        return fail(c, RT_ERR_INVALID_ARG, "Reinhard's white must be finite and >= 1/256");
+    if ((uintptr_t)t->dExposure & 3u) return fail(c, RT_ERR_INVALID_ARG, "dExposure must be 4-byte aligned");
+    if (t->reserved[0] || t->reserved[1] || t->reserved[2] || t->reserved[3]) return fail(c, RT_ERR_INVALID_ARG, "reserved words must be zero");
+    out->op = t->op;
+    out->invW2 = t->op == RT_TONE_REINHARD ? 1.0f / (t->white * t->white) : 0.0f;
+    out->dExposure = t->dExposure;
+    return RT_OK;
+}
+
+int rt_display_pack_toned(rt_context *c, const void *dImage, void *dOut, const rt_display_desc *d, const rt_tone_desc *tone, void *hipStream) {
+    if (!c) return RT_ERR_INVALID_ARG;
+    int rc = validate_display(c, dImage, d);
+    if (rc) return rc;
+    ToneArgs t;
+    if ((rc = validate_tone(c, tone, &t))) return rc;
+    if (!dOut || ((uintptr_t)dOut & 15u)) return fail(c, RT_ERR_INVALID_ARG, "the output pointer must be non-NULL and 16-byte aligned");
+    const size_t npx = (size_t)d->width * d->height;
+    const uintptr_t i0 = (uintptr_t)dImage, o0 = (uintptr_t)dOut;
+    if (i0 < o0 + npx * 4 && o0 < i0 + npx * 16) return fail(c, RT_ERR_INVALID_ARG, "rt_display_pack_toned cannot run in place: image and output overlap");
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t s = hipStream ? (hipStream_t)hipStream : c->stream;
+    HIP_TRY(c, rt_launch_display_pack_toned(dImage, dOut, d->width, d->height, d->format == RT_DISPLAY_RGBA8_SRGB,
+                                            (d->flags & RT_DISPLAY_FLIP_ROWS) != 0, d->exposure, t.op, t.invW2, t.dExposure, s));
+    return RT_OK;
+}
+
+// rt_present_submit and rt_present_submit_toned: one ring, one ticket sequence (tone == NULL: the untoned pack)
+static int present_submit(rt_context *c, const void *dImage, const rt_display_desc *d, const rt_tone_desc *tone, bool toned, void *hipStream,
+                          uint64_t *ticket) {
     if (!c) return RT_ERR_INVALID_ARG;
     if (!ticket) return fail(c, RT_ERR_INVALID_ARG, "ticket is NULL");
     int rc = validate_display(c, dImage, d);
     if (rc) return rc;
+    ToneArgs t;
+    if (toned && (rc = validate_tone(c, tone, &t))) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
     PresentRing &r = c->present;
     PresentRing::Slot &sl = r.slot[r.next % (uint64_t)r.slots];
@@ -822,8 +864,8 @@ int rt_present_submit(rt_context *c, const void *dImage, const rt_display_desc *
         HIP_TRY(c, sl.hPixels.grow(bytes));
     }
     if (sl.used) HIP_TRY(c, hipStreamWaitEvent(s, sl.done, 0));     // the copy of ticket - slots has left the staging buffer
-    HIP_TRY(c, rt_launch_display_pack(dImage, sl.dStage, d->width, d->height, d->format == RT_DISPLAY_RGBA8_SRGB,
-                                      (d->flags & RT_DISPLAY_FLIP_ROWS) != 0, d->exposure, s));
+    HIP_TRY(c, rt_launch_display_pack_toned(dImage, sl.dStage, d->width, d->height, d->format == RT_DISPLAY_RGBA8_SRGB,
+                                            (d->flags & RT_DISPLAY_FLIP_ROWS) != 0, d->exposure, t.op, t.invW2, t.dExposure, s));
     HIP_TRY(c, hipEventRecord(sl.packed, s));
     HIP_TRY(c, hipStreamWaitEvent(r.copy, sl.packed, 0));
     HIP_TRY(c, hipMemcpyAsync(sl.hPixels, sl.dStage, bytes, hipMemcpyDeviceToHost, r.copy));
@@ -833,6 +875,75 @@ int rt_present_submit(rt_context *c, const void *dImage, const rt_display_desc *
     sl.ticket = r.next;
     sl.bytes = bytes;
     *ticket = r.next++;
+    return RT_OK;
+}
+
+int rt_present_submit(rt_context *c, const void *dImage, const rt_display_desc *d, void *hipStream, uint64_t *ticket) {
+    return present_submit(c, dImage, d, nullptr, false, hipStream, ticket);
+}
+
+int rt_present_submit_toned(rt_context *c, const void *dImage, const rt_display_desc *d, const rt_tone_desc *tone, void *hipStream,
+                            uint64_t *ticket) {
+    return present_submit(c, dImage, d, tone, true, hipStream, ticket);
+}
+
+// ---- exposure metering (the header has the contract; the solve is rt_meter.h's, here and on the device)
+static int validate_meter_desc(rt_context *c, const rt_meter_desc *d) {
+    if (!d) return fail(c, RT_ERR_INVALID_ARG, "meter description is NULL");
+    if (d->width < 1 || d->height < 1) return fail(c, RT_ERR_INVALID_ARG, "width/height must be positive");
+    if (!(d->key > 0.0f) || !(d->key < HUGE_VALF)) return fail(c, RT_ERR_INVALID_ARG, "key must be finite and > 0");
+    if (!(d->minExposure > 0.0f) || !(d->maxExposure < HUGE_VALF) || !(d->minExposure <= d->maxExposure))
+        return fail(c, RT_ERR_INVALID_ARG, "exposure limits: 0 < minExposure <= maxExposure, both finite");
+    if (!(d->adapt > 0.0f) || !(d->adapt <= 1.0f)) return fail(c, RT_ERR_INVALID_ARG, "adapt must be in (0, 1]");
+    if (d->lowPermille < 0 || d->highPermille < 0 || (int64_t)d->lowPermille + d->highPermille >= 1000)
+        return fail(c, RT_ERR_INVALID_ARG, "permilles: >= 0 and lowPermille + highPermille < 1000");
+    if (d->reserved[0] || d->reserved[1] || d->reserved[2] || d->reserved[3]) return fail(c, RT_ERR_INVALID_ARG, "reserved words must be zero");
+    return RT_OK;
+}
+
+int rt_meter(rt_context *c, const void *dImage, const rt_meter_desc *d, void *dState, void *hipStream) {
+    if (!c) return RT_ERR_INVALID_ARG;
+    int rc = validate_meter_desc(c, d);
+    if (rc) return rc;
+    if (!dImage || ((uintptr_t)dImage & 15u)) return fail(c, RT_ERR_INVALID_ARG, "the image pointer must be non-NULL and 16-byte aligned");
+    if (!dState || ((uintptr_t)dState & 15u)) return fail(c, RT_ERR_INVALID_ARG, "the state pointer must be non-NULL and 16-byte aligned");
+    const uint64_t npx = (uint64_t)d->width * (uint64_t)d->height;
+    if (npx > 0x7fffffffull) return fail(c, RT_ERR_TOO_LARGE, "more than 2^31 - 1 pixels");
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t s = hipStream ? (hipStream_t)hipStream : c->stream;
+    HIP_TRY(c, rt_launch_meter(dImage, dState, (unsigned)npx, d->key, d->minExposure, d->maxExposure, d->adapt, d->lowPermille,
+                               d->highPermille, s));
+    return RT_OK;
+}
+
+int rt_meter_solve_host(const rt_meter_state *in, const rt_meter_desc *d, rt_meter_state *out) {
+    if (!in || !out) return RT_ERR_INVALID_ARG;
+    int rc = validate_meter_desc(nullptr, d);
+    if (rc) return rc;
+    uint64_t n = 0;
+    for (int b = 0; b < 256; b++) n += in->hist[b];
+    if (n > 0xffffffffull) return RT_ERR_TOO_LARGE;
+    RtMeterSolveIn si;
+    si.key = d->key; si.minExposure = d->minExposure; si.maxExposure = d->maxExposure; si.adapt = d->adapt;
+    si.lowPermille = d->lowPermille; si.highPermille = d->highPermille;
+    si.prevExposure = in->exposure;
+    si.prevFrames = in->frames;
+    const RtMeterSolved r = rt_meter_solve(in->hist, si, rt_meter_tables_ref());
+    if (out != in) *out = *in;
+    out->nMetered = r.nMetered;
+    out->meanLog2Q16 = r.meanLog2Q16;
+    out->target = r.target;
+    out->exposure = r.exposure;
+    out->frames = r.frames;
+    memset(out->reserved, 0, sizeof out->reserved);
+    return RT_OK;
+}
+
+int rt_meter_tables(float pow2neg[256], uint32_t log2q16[8]) {
+    if (!pow2neg || !log2q16) return RT_ERR_INVALID_ARG;
+    const RtMeterTables &t = rt_meter_tables_ref();
+    memcpy(pow2neg, t.pow2neg, sizeof t.pow2neg);
+    memcpy(log2q16, t.log2q16, sizeof t.log2q16);
     return RT_OK;
 }
 

@@ -102,6 +102,15 @@ hipError_t rt_launch_bloom(const void *scene, void *tmpA, void *tmpB, void *out,
 // rgba32f -> RGBA8 (rt_post.hip); `out` rows tightly packed, both pointers 16-byte aligned, W * H below 2^32 quads of 4 pixels
 hipError_t rt_launch_display_pack(const void *image, void *out, int W, int H, int srgb, int flip, float exposure, hipStream_t s);
 const float *rt_display_thresholds();      // the 256 sRGB decision thresholds ([0] = 0), built on the host on first use
+// the same pack behind a tone curve (0 none, 1 Reinhard with invW2 = 1 / white^2, 2 ACES) and, when dExposure is not NULL, with the
+// exposure multiplied by that device float; (0, NULL) is rt_launch_display_pack
+hipError_t rt_launch_display_pack_toned(const void *image, void *out, int W, int H, int srgb, int flip, float exposure, int tone,
+                                        float invW2, const void *dExposure, hipStream_t s);
+// rt_meter (rt_post.hip): clear, histogram, solve -- three operations on s; state = one rt_meter_state, nPixels <= 2^31 - 1
+hipError_t rt_launch_meter(const void *image, void *state, unsigned nPixels, float key, float minExposure, float maxExposure, float adapt,
+                           int lowPermille, int highPermille, hipStream_t s);
+struct RtMeterTables;
+const RtMeterTables &rt_meter_tables_ref();     // the solve's two tables (rt_meter.h), built on the host on first use
 hipError_t rt_launch_wire_pack(const void *dColor, const void *dPos, const void *dNormal, void *dWire, size_t nPixels,
                                hipStream_t s);
 hipError_t rt_launch_wire_unpack(const void *dWire, size_t rankStrideBytes, size_t rankPixels, const void *dRootColor,

@@ -40,6 +40,7 @@ EXPORTS = [
     "rt_mgpu_set_skybox", "rt_mgpu_set_strip_rows", "rt_mgpu_render", "rt_mgpu_sync", "rt_mgpu_get_surfaces", "rt_mgpu_readback", "rt_mgpu_last_ms",
     "rt_mgpu_last_error", "rt_trace_rays", "rt_camera_rays", "rt_pick", "rt_shade_rays", "rt_debug_device_math",
     "rt_display_pack", "rt_display_srgb_thresholds", "rt_present_configure", "rt_present_submit", "rt_present_poll", "rt_present_wait",
+    "rt_meter", "rt_meter_solve_host", "rt_meter_tables", "rt_display_pack_toned", "rt_present_submit_toned",
 ]
 
 
@@ -161,6 +162,11 @@ def load_library(build_if_missing=True):
     lib.rt_present_submit.argtypes = [vp, vp, P(L.RtDisplayDesc), vp, P(ctypes.c_uint64)]
     lib.rt_present_poll.argtypes = [vp, ctypes.c_uint64, P(ci)]
     lib.rt_present_wait.argtypes = [vp, ctypes.c_uint64, P(vp), P(ctypes.c_size_t)]
+    lib.rt_meter.argtypes = [vp, vp, P(L.RtMeterDesc), vp, vp]
+    lib.rt_meter_solve_host.argtypes = [vp, P(L.RtMeterDesc), vp]
+    lib.rt_meter_tables.argtypes = [P(cf), P(ctypes.c_uint32)]
+    lib.rt_display_pack_toned.argtypes = [vp, vp, vp, P(L.RtDisplayDesc), P(L.RtToneDesc), vp]
+    lib.rt_present_submit_toned.argtypes = [vp, vp, P(L.RtDisplayDesc), P(L.RtToneDesc), vp, P(ctypes.c_uint64)]
     for name in EXPORTS:
         if name not in ("rt_last_error", "rt_mgpu_last_error", "rt_wire_bytes"):
             getattr(lib, name).restype = ci
@@ -286,6 +292,27 @@ def display_srgb_thresholds():
     if rc:
         raise RtError(rc, "rt_display_srgb_thresholds")
     return out
+
+
+def meter_tables():
+    """(pow2neg float32[256], log2q16 uint32[8]): the two tables of rt_meter's solve (rt_meter_tables).  Needs no GPU."""
+    p, q = np.zeros(256, dtype=np.float32), np.zeros(8, dtype=np.uint32)
+    rc = load_library().rt_meter_tables(p.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), q.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)))
+    if rc:
+        raise RtError(rc, "rt_meter_tables")
+    return p, q
+
+
+def meter_solve_host(state, width, height, **desc):
+    """rt_meter's solve on the host (rt_meter_solve_host): `state` is one METER_STATE_DTYPE record (hist, exposure and frames are
+    read, the counters and extremes copied) -> the record rt_meter would leave.  `desc`: make_meter_desc's keywords.  Needs no GPU."""
+    src = np.ascontiguousarray(np.asarray(state, dtype=L.METER_STATE_DTYPE).reshape(1))
+    out = np.zeros(1, dtype=L.METER_STATE_DTYPE)
+    d = L.make_meter_desc(width, height, **desc)
+    rc = load_library().rt_meter_solve_host(_ptr(src), ctypes.byref(d), _ptr(out))
+    if rc:
+        raise RtError(rc, "rt_meter_solve_host")
+    return out[0]
 
 
 def _dev_ptr(x):
@@ -572,27 +599,54 @@ class RayTracer:
                                       strength, iterations, ctypes.c_void_p(stream) if stream else None), "rt_bloom")
 
     # ---- display packing and delivery to the host ------------------------------------------
-    def display_pack(self, d_image, d_out, width, height, format="linear", flip=False, exposure=1.0, stream=None):
+    def display_pack(self, d_image, d_out, width, height, format="linear", flip=False, exposure=1.0, stream=None,
+                     tone=None, white=1.0, d_exposure=None):
         """rgba32f surface -> RGBA8 on the device (rt_display_pack).  d_image / d_out: raw device pointers (ints) or CUDA
         tensors, 16-byte aligned, not overlapping; d_out holds height * width * 4 bytes (R, G, B, A), row 0 = bottom unless
-        `flip`.  format "linear" or "srgb".  Asynchronous on torch stream `stream` (default torch.cuda.current_stream())."""
+        `flip`.  format "linear" or "srgb".  Asynchronous on torch stream `stream` (default torch.cuda.current_stream()).
+        With `tone` ("none", "reinhard" with `white`, "aces") or `d_exposure` (the address of a device float the exposure is
+        multiplied by, e.g. a meter state's + layout.METER_EXPOSURE_OFFSET) the call is rt_display_pack_toned."""
         d = L.make_display_desc(width, height, format, flip, exposure)
-        self._on_torch_stream(stream, lambda h: self._check(self.lib.rt_display_pack(
-            self.ctx, _dev_ptr(d_image), _dev_ptr(d_out), ctypes.byref(d), ctypes.c_void_p(h)), "rt_display_pack"))
+        if tone is None and d_exposure is None:
+            self._on_torch_stream(stream, lambda h: self._check(self.lib.rt_display_pack(
+                self.ctx, _dev_ptr(d_image), _dev_ptr(d_out), ctypes.byref(d), ctypes.c_void_p(h)), "rt_display_pack"))
+            return
+        t = L.make_tone_desc(tone or "none", white, d_exposure)
+        self._on_torch_stream(stream, lambda h: self._check(self.lib.rt_display_pack_toned(
+            self.ctx, _dev_ptr(d_image), _dev_ptr(d_out), ctypes.byref(d), ctypes.byref(t), ctypes.c_void_p(h)), "rt_display_pack_toned"))
+
+    def meter(self, d_image, d_state, width, height, key=0.18, min_exposure=2.0 ** -10, max_exposure=2.0 ** 10, adapt=1.0,
+              low_permille=0, high_permille=0, stream=None):
+        """Meter the rgba32f surface d_image into the rt_meter_state at d_state (rt_meter; raw device pointers or CUDA tensors,
+        16-byte aligned; the state is 1088 bytes, zeroed once by the caller and passed to every later call): histogram of
+        log-luminance, trimmed mean, target exposure key / mean, adapted exposure.  Asynchronous on torch stream `stream`
+        (default torch.cuda.current_stream()); nothing comes back to the host -- hand the state's exposure to display_pack /
+        present_submit as d_exposure = state address + layout.METER_EXPOSURE_OFFSET, or read the state back
+        (layout.METER_STATE_DTYPE) when the host wants the figures."""
+        d = L.make_meter_desc(width, height, key, min_exposure, max_exposure, adapt, low_permille, high_permille)
+        self._on_torch_stream(stream, lambda h: self._check(self.lib.rt_meter(
+            self.ctx, _dev_ptr(d_image), ctypes.byref(d), _dev_ptr(d_state), ctypes.c_void_p(h)), "rt_meter"))
 
     def present_configure(self, slots):
         """Number of frames that can be on their way to the host at once (2..8, default 3); expires every earlier ticket and
         is refused while one is outstanding (submitted, not yet waited for or polled ready)."""
         self._check(self.lib.rt_present_configure(self.ctx, int(slots)), "rt_present_configure")
 
-    def present_submit(self, d_image, width, height, format="linear", flip=False, exposure=1.0, stream=None):
-        """Pack the rgba32f surface d_image (raw device pointer or CUDA tensor) as display_pack does and start its copy into a
-        pinned host buffer -> ticket (0, 1, 2, ...).  Ordered on torch stream `stream` (default torch.cuda.current_stream()):
-        later work on that stream may overwrite d_image at once, and the copy overlaps it.  Does not block the host."""
+    def present_submit(self, d_image, width, height, format="linear", flip=False, exposure=1.0, stream=None,
+                       tone=None, white=1.0, d_exposure=None):
+        """Pack the rgba32f surface d_image (raw device pointer or CUDA tensor) as display_pack does (`tone`, `white` and
+        `d_exposure` included: rt_present_submit_toned) and start its copy into a pinned host buffer -> ticket (0, 1, 2, ...).
+        Ordered on torch stream `stream` (default torch.cuda.current_stream()): later work on that stream may overwrite d_image
+        at once, and the copy overlaps it.  Does not block the host."""
         d = L.make_display_desc(width, height, format, flip, exposure)
         t = ctypes.c_uint64()
-        self._on_torch_stream(stream, lambda h: self._check(self.lib.rt_present_submit(
-            self.ctx, _dev_ptr(d_image), ctypes.byref(d), ctypes.c_void_p(h), ctypes.byref(t)), "rt_present_submit"))
+        if tone is None and d_exposure is None:
+            self._on_torch_stream(stream, lambda h: self._check(self.lib.rt_present_submit(
+                self.ctx, _dev_ptr(d_image), ctypes.byref(d), ctypes.c_void_p(h), ctypes.byref(t)), "rt_present_submit"))
+        else:
+            td = L.make_tone_desc(tone or "none", white, d_exposure)
+            self._on_torch_stream(stream, lambda h: self._check(self.lib.rt_present_submit_toned(
+                self.ctx, _dev_ptr(d_image), ctypes.byref(d), ctypes.byref(td), ctypes.c_void_p(h), ctypes.byref(t)), "rt_present_submit_toned"))
         self._present_shapes = getattr(self, "_present_shapes", {})
         self._present_shapes[t.value] = (int(height), int(width))
         for old in [k for k in self._present_shapes if k + 16 <= t.value]:     # (more than any ring holds)

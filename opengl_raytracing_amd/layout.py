@@ -229,3 +229,47 @@ def make_display_desc(width, height, format="linear", flip=False, exposure=1.0):
     d = RtDisplayDesc()
     d.width, d.height, d.format, d.flags, d.exposure = int(width), int(height), int(f), DISPLAY_FLIP_ROWS if flip else 0, float(exposure)
     return d
+
+
+# ---- exposure metering and tone curves (rt_meter / rt_display_pack_toned, include/rt_mi355.h) --
+TONE_NONE, TONE_REINHARD, TONE_ACES = 0, 1, 2
+METER_EXPOSURE_OFFSET = 1060
+
+
+class RtMeterDesc(ctypes.Structure):
+    """``rt_meter_desc``: surface size, key, exposure limits, adaptation rate, trimmed shares."""
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("key", ctypes.c_float), ("minExposure", ctypes.c_float),
+                ("maxExposure", ctypes.c_float), ("adapt", ctypes.c_float), ("lowPermille", ctypes.c_int32),
+                ("highPermille", ctypes.c_int32), ("reserved", ctypes.c_int32 * 4)]
+
+
+class RtToneDesc(ctypes.Structure):
+    """``rt_tone_desc``: tone operator, Reinhard's white, the device float the exposure is multiplied by (or NULL)."""
+    _fields_ = [("op", ctypes.c_int32), ("white", ctypes.c_float), ("dExposure", ctypes.c_void_p), ("reserved", ctypes.c_int32 * 4)]
+
+
+# ``rt_meter_state``: what rt_meter leaves in device memory (a zeroed one starts a sequence)
+METER_STATE_DTYPE = np.dtype({
+    "names": ["hist", "nPixels", "nNonPositive", "nNaN", "nInf", "minLum", "maxLum", "nMetered", "meanLog2Q16", "target", "exposure",
+              "frames", "reserved"],
+    "formats": [("<u4", (256,)), "<u4", "<u4", "<u4", "<u4", "<f4", "<f4", "<u4", "<u4", "<f4", "<f4", "<u4", ("<u4", (5,))],
+    "offsets": [0, 1024, 1028, 1032, 1036, 1040, 1044, 1048, 1052, 1056, 1060, 1064, 1068], "itemsize": 1088})
+
+assert ctypes.sizeof(RtMeterDesc) == 48 and ctypes.sizeof(RtToneDesc) == 32 and METER_STATE_DTYPE.itemsize == 1088
+assert METER_STATE_DTYPE.fields["exposure"][1] == METER_EXPOSURE_OFFSET
+
+
+def make_meter_desc(width, height, key=0.18, min_exposure=2.0 ** -10, max_exposure=2.0 ** 10, adapt=1.0, low_permille=0, high_permille=0):
+    d = RtMeterDesc()
+    d.width, d.height, d.key, d.minExposure, d.maxExposure = int(width), int(height), float(key), float(min_exposure), float(max_exposure)
+    d.adapt, d.lowPermille, d.highPermille = float(adapt), int(low_permille), int(high_permille)
+    return d
+
+
+def make_tone_desc(tone="none", white=1.0, d_exposure=None):
+    """d_exposure: a device address (int) or None."""
+    t = RtToneDesc()
+    t.op = int({"none": TONE_NONE, "reinhard": TONE_REINHARD, "aces": TONE_ACES}.get(tone, tone))
+    t.white = float(white)
+    t.dExposure = d_exposure or None
+    return t
