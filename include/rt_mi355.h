@@ -572,6 +572,57 @@ int rt_display_pack_toned(rt_context *ctx, const void *dImage, void *dOut, const
 int rt_present_submit_toned(rt_context *ctx, const void *dImage, const rt_display_desc *desc, const rt_tone_desc *tone,
                             void *hipStream, uint64_t *ticket);
 
+/* ---- YUV 4:2:0 video output: what a video encoder takes where a screen or an image writer takes RGBA8.
+ *      rt_display_pack_yuv: dImage (device, width*height rgba32f, as rt_display_pack) -> dOut (device, `bytes` of the layout below).
+ *      Both pointers 16-byte aligned; the two ranges must not overlap.  Asynchronous on hipStream (NULL = the context's stream).
+ *      Codes: for every pixel and colour channel, R, G, B in 0..255 are exactly the bytes rt_display_pack_toned writes for
+ *        format = desc->transfer, desc->exposure, the same tone description and *dExposure (tone == NULL: RT_TONE_NONE, no
+ *        dExposure), the NaN / <= 0 / >= 1 rules included.
+ *      Rows: output luma row j is image row j; with RT_DISPLAY_FLIP_ROWS it is image row height-1-j.  Everything below is in
+ *        OUTPUT rows, so for an odd height a flipped frame pairs other image rows into a chroma sample than an unflipped one.
+ *      Luma, per pixel:  Y = yOff + ((cYR*R + cYG*G + cYB*B + 32768) >> 16).
+ *      Chroma, one sample per 2x2 block of output pixels, sited at the block's centre: Rs, Gs, Bs = the sums of the four codes;
+ *        a block that reaches past the right or top edge of an odd-sized frame replicates the edge pixel (coordinates clamped
+ *        to width-1 / height-1);  Cb = clamp(128 + ((cBR*Rs + cBG*Gs + cBB*Bs + 131072) >> 18), 0, 255), Cr alike with cR*.
+ *        >> on the signed 32-bit sum is arithmetic (floor); every sum fits in int32.
+ *      Coefficients (rt_display_yuv_coeffs; Q16, built on the host in double, rne = round to nearest even):
+ *        BT709: Kr, Kb = 0.2126, 0.0722;  BT601: 0.299, 0.114.  LIMITED: sY = 219/255, sC = 224/255, yOff = 16;  FULL: sY = sC = 1,
+ *        yOff = 0.   cYR = rne(65536*Kr*sY), cYB = rne(65536*Kb*sY), cYG = rne(65536*sY) - cYR - cYB (white gives exactly 235 / 255);
+ *        cBB = cRR = rne(32768*sC), cBR = rne(-65536*sC*Kr/(2*(1-Kb))), cRB = rne(-65536*sC*Kb/(2*(1-Kr))), cBG = -cBB - cBR,
+ *        cRG = -cRR - cRB (each chroma row sums to 0: every grey gives exactly 128).
+ *        out[12] = {cYR, cYG, cYB, yOff, cBR, cBG, cBB, 0, cRR, cRG, cRB, 0}.  LIMITED keeps Y in 16..235 and chroma in 16..240
+ *        without the clamp; FULL reaches 256 in chroma before it.
+ *      Layout (rt_display_yuv_layout; tightly packed, cw = (width+1)/2, ch = (height+1)/2, bytes = width*height + 2*cw*ch):
+ *        RT_YUV_NV12: Y plane width x height at offset 0, then one plane of interleaved Cb, Cr, 2*cw x ch bytes, at width*height
+ *                     (offset[2] = offset[1] + 1, pitch[1] = pitch[2] = 2*cw);
+ *        RT_YUV_I420: Y, then Cb cw x ch at width*height, then Cr at width*height + cw*ch (pitch cw).
+ *      rt_present_submit_yuv: rt_present_submit with this pack.  One ring and one ticket sequence serve every submit; the slot's
+ *        buffers are sized by the frame's `bytes`; rt_present_wait returns the buffer and `bytes`, the planes are found with
+ *        rt_display_yuv_layout.  The frame loop feeding an encoder:
+ *          rt_frame(ctx, &p, &d, dDisplay);
+ *          rt_present_submit_yuv(ctx, dDisplay, &yuv, NULL, NULL, &t);  if (t) rt_present_wait(ctx, t - 1, &frame, &bytes);
+ *      Refused with RT_ERR_INVALID_ARG: NULL context, descriptor or pointers; misaligned or overlapping ranges; width or height
+ *      < 1; unknown format / matrix / range / transfer; unknown flag bits; exposure not finite and > 0; non-zero reserved words;
+ *      rt_display_pack_toned's refusals of a tone description.  RT_ERR_TOO_LARGE: more pixel blocks than one launch holds.
+ *      rt_display_yuv_coeffs and rt_display_yuv_layout need no GPU; the layout reads width, height and format only. */
+typedef enum rt_yuv_format { RT_YUV_NV12 = 0, RT_YUV_I420 = 1 } rt_yuv_format;
+typedef enum rt_yuv_matrix { RT_YUV_BT709 = 0, RT_YUV_BT601 = 1 } rt_yuv_matrix;
+typedef enum rt_yuv_range { RT_YUV_LIMITED = 0, RT_YUV_FULL = 1 } rt_yuv_range;
+typedef struct rt_yuv_desc {
+    int32_t width, height;           /* >= 1; odd sizes allowed */
+    int32_t format, matrix, range;   /* rt_yuv_format, rt_yuv_matrix, rt_yuv_range */
+    int32_t transfer;                /* rt_display_format: how the R'G'B' codes are made (LINEAR / SRGB) */
+    uint32_t flags;                  /* RT_DISPLAY_FLIP_ROWS */
+    float exposure;                  /* finite, > 0 */
+    int32_t reserved[4];             /* zero */
+} rt_yuv_desc;
+int rt_display_yuv_coeffs(int matrix, int range, int32_t out[12]);
+int rt_display_yuv_layout(const rt_yuv_desc *desc, size_t offset[3], size_t pitch[3], size_t *bytes);
+int rt_display_pack_yuv(rt_context *ctx, const void *dImage, void *dOut, const rt_yuv_desc *desc, const rt_tone_desc *tone,
+                        void *hipStream);
+int rt_present_submit_yuv(rt_context *ctx, const void *dImage, const rt_yuv_desc *desc, const rt_tone_desc *tone, void *hipStream,
+                          uint64_t *ticket);
+
 /* ---- multi-GPU strip helpers */
 /* Number of local rows a rank owns for interleaved strips. */
 int rt_strip_local_rows(int height, int stripRows, int stripCount, int stripIndex);
@@ -673,6 +724,8 @@ RT_SA(sizeof(rt_meter_state) == 1088 && offsetof(rt_meter_state, nPixels) == 102
       offsetof(rt_meter_state, nMetered) == 1048 && offsetof(rt_meter_state, exposure) == RT_METER_EXPOSURE_OFFSET &&
       offsetof(rt_meter_state, frames) == 1064, "rt_meter_state is 1088 B");
 RT_SA(sizeof(rt_tone_desc) == 16 + 2 * sizeof(void *) && offsetof(rt_tone_desc, dExposure) == 8, "rt_tone_desc layout");
+RT_SA(sizeof(rt_yuv_desc) == 48 && offsetof(rt_yuv_desc, transfer) == 20 && offsetof(rt_yuv_desc, flags) == 24 &&
+      offsetof(rt_yuv_desc, exposure) == 28 && offsetof(rt_yuv_desc, reserved) == 32, "rt_yuv_desc is 48 B");
 #undef RT_SA
 #endif
 

@@ -841,15 +841,11 @@ int rt_display_pack_toned(rt_context *c, const void *dImage, void *dOut, const r
     return RT_OK;
 }
 
-// rt_present_submit and rt_present_submit_toned: one ring, one ticket sequence (tone == NULL: the untoned pack)
-static int present_submit(rt_context *c, const void *dImage, const rt_display_desc *d, const rt_tone_desc *tone, bool toned, void *hipStream,
-                          uint64_t *ticket) {
-    if (!c) return RT_ERR_INVALID_ARG;
-    if (!ticket) return fail(c, RT_ERR_INVALID_ARG, "ticket is NULL");
-    int rc = validate_display(c, dImage, d);
-    if (rc) return rc;
-    ToneArgs t;
-    if (toned && (rc = validate_tone(c, tone, &t))) return rc;
+// Every submit's way through the ring, after its arguments were validated: the next slot, grown to `bytes` if need be, pack(stage, s)
+// into its staging buffer on the caller's stream, the copy behind it, a ticket.  One ring and one ticket sequence for every format.
+extern "C++" {
+template <class Pack>
+static int present_enqueue(rt_context *c, size_t bytes, void *hipStream, uint64_t *ticket, Pack pack) {
     HIP_TRY(c, hipSetDevice(c->device));
     PresentRing &r = c->present;
     PresentRing::Slot &sl = r.slot[r.next % (uint64_t)r.slots];
@@ -857,15 +853,13 @@ static int present_submit(rt_context *c, const void *dImage, const rt_display_de
     HIP_TRY(c, r.copy.create());
     HIP_TRY(c, sl.packed.create(hipEventDisableTiming));
     HIP_TRY(c, sl.done.create(hipEventDisableTiming));
-    const size_t bytes = (size_t)d->width * d->height * 4;
     if (!(sl.dStage.holds(bytes) && sl.hPixels.holds(bytes))) {
         if (sl.used) HIP_TRY(c, hipEventSynchronize(sl.done));      // this slot's own last copy; the other slots are untouched
         HIP_TRY(c, sl.dStage.grow(bytes));
         HIP_TRY(c, sl.hPixels.grow(bytes));
     }
     if (sl.used) HIP_TRY(c, hipStreamWaitEvent(s, sl.done, 0));     // the copy of ticket - slots has left the staging buffer
-    HIP_TRY(c, rt_launch_display_pack_toned(dImage, sl.dStage, d->width, d->height, d->format == RT_DISPLAY_RGBA8_SRGB,
-                                            (d->flags & RT_DISPLAY_FLIP_ROWS) != 0, d->exposure, t.op, t.invW2, t.dExposure, s));
+    HIP_TRY(c, pack((void *)sl.dStage.ptr, s));
     HIP_TRY(c, hipEventRecord(sl.packed, s));
     HIP_TRY(c, hipStreamWaitEvent(r.copy, sl.packed, 0));
     HIP_TRY(c, hipMemcpyAsync(sl.hPixels, sl.dStage, bytes, hipMemcpyDeviceToHost, r.copy));
@@ -877,6 +871,22 @@ static int present_submit(rt_context *c, const void *dImage, const rt_display_de
     *ticket = r.next++;
     return RT_OK;
 }
+}  // extern "C++"
+
+// rt_present_submit and rt_present_submit_toned (tone == NULL: the untoned pack)
+static int present_submit(rt_context *c, const void *dImage, const rt_display_desc *d, const rt_tone_desc *tone, bool toned, void *hipStream,
+                          uint64_t *ticket) {
+    if (!c) return RT_ERR_INVALID_ARG;
+    if (!ticket) return fail(c, RT_ERR_INVALID_ARG, "ticket is NULL");
+    int rc = validate_display(c, dImage, d);
+    if (rc) return rc;
+    ToneArgs t;
+    if (toned && (rc = validate_tone(c, tone, &t))) return rc;
+    return present_enqueue(c, (size_t)d->width * d->height * 4, hipStream, ticket, [&](void *stage, hipStream_t s) {
+        return rt_launch_display_pack_toned(dImage, stage, d->width, d->height, d->format == RT_DISPLAY_RGBA8_SRGB,
+                                            (d->flags & RT_DISPLAY_FLIP_ROWS) != 0, d->exposure, t.op, t.invW2, t.dExposure, s);
+    });
+}
 
 int rt_present_submit(rt_context *c, const void *dImage, const rt_display_desc *d, void *hipStream, uint64_t *ticket) {
     return present_submit(c, dImage, d, nullptr, false, hipStream, ticket);
@@ -885,6 +895,92 @@ int rt_present_submit(rt_context *c, const void *dImage, const rt_display_desc *
 int rt_present_submit_toned(rt_context *c, const void *dImage, const rt_display_desc *d, const rt_tone_desc *tone, void *hipStream,
                             uint64_t *ticket) {
     return present_submit(c, dImage, d, tone, true, hipStream, ticket);
+}
+
+// ---- YUV 4:2:0 output (the header has the contract)
+int rt_display_yuv_coeffs(int matrix, int range, int32_t out[12]) {
+    if (!out || (matrix != RT_YUV_BT709 && matrix != RT_YUV_BT601) || (range != RT_YUV_LIMITED && range != RT_YUV_FULL)) return RT_ERR_INVALID_ARG;
+    const double Kr = matrix == RT_YUV_BT709 ? 0.2126 : 0.299, Kb = matrix == RT_YUV_BT709 ? 0.0722 : 0.114;
+    const double sY = range == RT_YUV_LIMITED ? 219.0 / 255.0 : 1.0, sC = range == RT_YUV_LIMITED ? 224.0 / 255.0 : 1.0;
+    auto rne = [](double x) { return (int32_t)nearbyint(x); };       // (the default rounding mode: to nearest, ties to even)
+    const int32_t cYR = rne(65536.0 * Kr * sY), cYB = rne(65536.0 * Kb * sY), cYG = rne(65536.0 * sY) - cYR - cYB;
+    const int32_t cC = rne(32768.0 * sC);
+    const int32_t cBR = rne(-65536.0 * sC * Kr / (2.0 * (1.0 - Kb))), cRB = rne(-65536.0 * sC * Kb / (2.0 * (1.0 - Kr)));
+    const int32_t t[12] = {cYR, cYG, cYB, range == RT_YUV_LIMITED ? 16 : 0, cBR, -cC - cBR, cC, 0, cC, -cC - cRB, cRB, 0};
+    memcpy(out, t, sizeof t);
+    return RT_OK;
+}
+
+int rt_display_yuv_layout(const rt_yuv_desc *d, size_t offset[3], size_t pitch[3], size_t *bytes) {
+    if (!d || !offset || !pitch) return RT_ERR_INVALID_ARG;
+    if (d->width < 1 || d->height < 1 || (d->format != RT_YUV_NV12 && d->format != RT_YUV_I420)) return RT_ERR_INVALID_ARG;
+    const size_t W = (size_t)d->width, H = (size_t)d->height, cw = (W + 1) / 2, ch = (H + 1) / 2;
+    offset[0] = 0;
+    offset[1] = W * H;
+    pitch[0] = W;
+    if (d->format == RT_YUV_NV12) {
+        offset[2] = offset[1] + 1;
+        pitch[1] = pitch[2] = 2 * cw;
+    } else {
+        offset[2] = offset[1] + cw * ch;
+        pitch[1] = pitch[2] = cw;
+    }
+    if (bytes) *bytes = W * H + 2 * cw * ch;
+    return RT_OK;
+}
+
+// a validated rt_yuv_desc with its optional tone description: what the launch takes
+struct YuvArgs {
+    ToneArgs tone;
+    int32_t coef[12];
+    size_t bytes = 0;
+};
+
+static int validate_yuv(rt_context *c, const void *dImage, const rt_yuv_desc *d, const rt_tone_desc *tone, YuvArgs *out) {
+    if (!d) return fail(c, RT_ERR_INVALID_ARG, "YUV description is NULL");
+    if (d->width < 1 || d->height < 1) return fail(c, RT_ERR_INVALID_ARG, "width/height must be positive");
+    if (d->format != RT_YUV_NV12 && d->format != RT_YUV_I420) return fail(c, RT_ERR_INVALID_ARG, "unknown YUV format");
+    if (rt_display_yuv_coeffs(d->matrix, d->range, out->coef) != RT_OK) return fail(c, RT_ERR_INVALID_ARG, "unknown YUV matrix or range");
+    if (d->transfer != RT_DISPLAY_RGBA8_LINEAR && d->transfer != RT_DISPLAY_RGBA8_SRGB) return fail(c, RT_ERR_INVALID_ARG, "unknown transfer");
+    if (d->flags & ~RT_DISPLAY_FLIP_ROWS) return fail(c, RT_ERR_INVALID_ARG, "unknown display flag bits");
+    if (!(d->exposure > 0.0f) || !(d->exposure < HUGE_VALF)) return fail(c, RT_ERR_INVALID_ARG, "exposure must be finite and > 0");
+    if (d->reserved[0] || d->reserved[1] || d->reserved[2] || d->reserved[3]) return fail(c, RT_ERR_INVALID_ARG, "reserved words must be zero");
+    if (!dImage || ((uintptr_t)dImage & 15u)) return fail(c, RT_ERR_INVALID_ARG, "the image pointer must be non-NULL and 16-byte aligned");
+    int rc;
+    if (tone && (rc = validate_tone(c, tone, &out->tone))) return rc;
+    if (rt_display_yuv_blocks(d->width, d->height) > 0xffffff00ull) return fail(c, RT_ERR_TOO_LARGE, "frame too large for one pack launch");
+    size_t offset[3], pitch[3];
+    (void)rt_display_yuv_layout(d, offset, pitch, &out->bytes);
+    return RT_OK;
+}
+
+static hipError_t launch_yuv(const void *dImage, void *dOut, const rt_yuv_desc *d, const YuvArgs &a, hipStream_t s) {
+    return rt_launch_display_pack_yuv(dImage, dOut, d->width, d->height, d->format == RT_YUV_I420, d->transfer == RT_DISPLAY_RGBA8_SRGB,
+                                      (d->flags & RT_DISPLAY_FLIP_ROWS) != 0, d->exposure, a.tone.op, a.tone.invW2, a.tone.dExposure, a.coef, s);
+}
+
+int rt_display_pack_yuv(rt_context *c, const void *dImage, void *dOut, const rt_yuv_desc *d, const rt_tone_desc *tone, void *hipStream) {
+    if (!c) return RT_ERR_INVALID_ARG;
+    YuvArgs a;
+    int rc = validate_yuv(c, dImage, d, tone, &a);
+    if (rc) return rc;
+    if (!dOut || ((uintptr_t)dOut & 15u)) return fail(c, RT_ERR_INVALID_ARG, "the output pointer must be non-NULL and 16-byte aligned");
+    const size_t npx = (size_t)d->width * d->height;
+    const uintptr_t i0 = (uintptr_t)dImage, o0 = (uintptr_t)dOut;
+    if (i0 < o0 + a.bytes && o0 < i0 + npx * 16) return fail(c, RT_ERR_INVALID_ARG, "rt_display_pack_yuv cannot run in place: image and output overlap");
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t s = hipStream ? (hipStream_t)hipStream : c->stream;
+    HIP_TRY(c, launch_yuv(dImage, dOut, d, a, s));
+    return RT_OK;
+}
+
+int rt_present_submit_yuv(rt_context *c, const void *dImage, const rt_yuv_desc *d, const rt_tone_desc *tone, void *hipStream, uint64_t *ticket) {
+    if (!c) return RT_ERR_INVALID_ARG;
+    if (!ticket) return fail(c, RT_ERR_INVALID_ARG, "ticket is NULL");
+    YuvArgs a;
+    int rc = validate_yuv(c, dImage, d, tone, &a);
+    if (rc) return rc;
+    return present_enqueue(c, a.bytes, hipStream, ticket, [&](void *stage, hipStream_t s) { return launch_yuv(dImage, stage, d, a, s); });
 }
 
 // ---- exposure metering (the header has the contract; the solve is rt_meter.h's, here and on the device)

@@ -106,6 +106,12 @@ const float *rt_display_thresholds();      // the 256 sRGB decision thresholds (
 // exposure multiplied by that device float; (0, NULL) is rt_launch_display_pack
 hipError_t rt_launch_display_pack_toned(const void *image, void *out, int W, int H, int srgb, int flip, float exposure, int tone,
                                         float invW2, const void *dExposure, hipStream_t s);
+// rgba32f -> NV12 (i420 = 0) or I420 (rt_post.hip): the toned pack's codes behind the integer matrix coef[12] of
+// rt_display_yuv_coeffs; `out` holds W * H + 2 * ((W + 1) / 2) * ((H + 1) / 2) bytes, both pointers 16-byte aligned.
+// rt_display_yuv_blocks: the lanes such a launch needs; above 0xffffff00 the frame is refused
+hipError_t rt_launch_display_pack_yuv(const void *image, void *out, int W, int H, int i420, int srgb, int flip, float exposure, int tone,
+                                      float invW2, const void *dExposure, const int *coef, hipStream_t s);
+unsigned long long rt_display_yuv_blocks(int W, int H);
 // rt_meter (rt_post.hip): clear, histogram, solve -- three operations on s; state = one rt_meter_state, nPixels <= 2^31 - 1
 hipError_t rt_launch_meter(const void *image, void *state, unsigned nPixels, float key, float minExposure, float maxExposure, float adapt,
                            int lowPermille, int highPermille, hipStream_t s);

@@ -1021,6 +1021,166 @@ hipError_t rt_launch_display_pack_toned(const void *image, void *out, int W, int
 }
 
 // =========================================================================================
+// YUV 4:2:0 packing (rt_display_pack_yuv, include/rt_mi355.h): the same rgba32f surface -> the NV12 / I420 frame a video encoder
+// takes.  The R'G'B' codes are the pack's own (display_code and tone_curve above, the sRGB tree staged in LDS the same way); behind
+// them an integer matrix with Q16 coefficients that arrive as kernel arguments (wave-uniform).  Bandwidth-bound like the pack: 16 B
+// read, 1.5 B written per pixel.  A lane owns a block of RT_YUV_BW x 2 OUTPUT pixels -- one row pair, so every chroma sample's four
+// pixels sit in one lane and no lane talks to another -- and consecutive lanes own consecutive blocks of the row pair: a wave reads
+// two contiguous runs of 64 * RT_YUV_BW * 16 B.
+// FAST (W % 8 == 0 and H even): every block is whole and every segment a lane stores is naturally aligned (the planes start at
+// multiples of 8, I420's chroma rows at multiples of 4): 2 x RT_YUV_BW 16-B loads, two RT_YUV_BW-byte luma stores, one
+// RT_YUV_BW-byte NV12 chroma store or two half as wide for I420, no edge predicate.  Otherwise the loads go to coordinates clamped
+// into the image (the edge replication of the definition) and every byte is stored on its own under its predicate.
+// Each output byte is written by exactly one lane, once.
+// =========================================================================================
+#ifndef RT_YUV_BW
+#define RT_YUV_BW 4               // block width in pixels: 4 or 8 (DESIGN.md 16 has both measured: 8 costs occupancy and time)
+#endif
+static_assert(RT_YUV_BW == 8 || RT_YUV_BW == 4, "a block is 8 or 4 pixels wide");
+struct RtYuvCoef { int v[12]; };  // rt_display_yuv_coeffs' order: cYR cYG cYB yOff | cBR cBG cBB 0 | cRR cRG cRB 0
+
+namespace {
+template <int N> struct yuv_seg;                              // N bytes stored at once
+template <> struct yuv_seg<8> { typedef uint2 type; };
+template <> struct yuv_seg<4> { typedef unsigned type; };
+template <> struct yuv_seg<2> { typedef unsigned short type; };
+// bytes b[0..N-1] (each 0..255) to p, N-byte aligned, as one store
+template <int N>
+__device__ __forceinline__ void yuv_store(unsigned char *p, const unsigned (&b)[N]) {
+    if constexpr (N == 2) {
+        *(unsigned short *)p = (unsigned short)(b[0] | (b[1] << 8));
+    } else {
+        unsigned w[N / 4];
+#pragma unroll
+        for (int k = 0; k < N / 4; k++) w[k] = b[4 * k] | (b[4 * k + 1] << 8) | (b[4 * k + 2] << 16) | (b[4 * k + 3] << 24);
+        if constexpr (N == 8) *(uint2 *)p = make_uint2(w[0], w[1]);
+        else *(unsigned *)p = w[0];
+    }
+}
+}  // namespace
+
+template <bool SRGB, int TONE, bool I420, bool FAST>
+__global__ __launch_bounds__(256) void rt_display_pack_yuv_kernel(const float4 *__restrict__ in, unsigned char *__restrict__ out, int W, int H,
+                                                                  unsigned blocksPerRow, unsigned nBlocks, int flip, float exposure,
+                                                                  const float *__restrict__ dExposure, float invW2, const RtYuvCoef cf,
+                                                                  const RtDisplayTree tree) {
+    constexpr int BW = RT_YUV_BW;
+    __shared__ float lds[SRGB ? 256 : 1];
+    const float e = dExposure ? exposure * *dExposure : exposure;      // (wave-uniform: one scalar load, one multiply)
+    const unsigned g = blockIdx.x * 256u + threadIdx.x;
+    const bool valid = g < nBlocks;                           // (no early return: the sRGB form has a barrier below)
+    const unsigned jp = g / blocksPerRow, bq = g - jp * blocksPerRow;
+    const int x0 = (int)bq * BW, j0 = (int)jp * 2;            // the block's first output column and row
+    const int j1 = FAST ? j0 + 1 : min(j0 + 1, H - 1);        // its second output row, replicated at the top of an odd frame
+    const int jr[2] = {flip ? H - 1 - j0 : j0, flip ? H - 1 - j1 : j1};       // the image rows behind the two output rows
+    float4 p[2][BW];
+#pragma unroll
+    for (int r = 0; r < 2; r++) {
+        const float4 *src = in + (size_t)jr[r] * W;
+#pragma unroll
+        for (int k = 0; k < BW; k++) {
+            const int x = FAST ? x0 + k : min(x0 + k, W - 1); // the right edge replicated
+            p[r][k] = valid ? src[x] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        }
+    }
+    if constexpr (SRGB) {                                     // the table goes to LDS while the pixels are on their way
+        lds[threadIdx.x] = tree.node[threadIdx.x];
+        __syncthreads();
+    }
+    if (!valid) return;
+    const float ce = TONE == TONE_NONE ? e : 1.0f;            // as display_pack_body: code(x * e), or code(curve(x * e) * 1)
+    auto code = [&](float x) -> int { return (int)display_code<SRGB>(tone_curve<TONE>(x, e, invW2), ce, lds); };
+    unsigned yb[2][BW], cb[BW / 2], cr[BW / 2];
+#pragma unroll
+    for (int c = 0; c < BW / 2; c++) {                        // one chroma sample: columns 2c, 2c + 1 of both rows
+        int Rs = 0, Gs = 0, Bs = 0;
+#pragma unroll
+        for (int r = 0; r < 2; r++) {
+#pragma unroll
+            for (int d = 0; d < 2; d++) {
+                const float4 q = p[r][2 * c + d];
+                const int R = code(q.x), G = code(q.y), B = code(q.z);
+                Rs += R; Gs += G; Bs += B;
+                yb[r][2 * c + d] = (unsigned)(cf.v[3] + ((cf.v[0] * R + cf.v[1] * G + cf.v[2] * B + 32768) >> 16));
+            }
+        }
+        const int u = 128 + ((cf.v[4] * Rs + cf.v[5] * Gs + cf.v[6] * Bs + 131072) >> 18);
+        const int v = 128 + ((cf.v[8] * Rs + cf.v[9] * Gs + cf.v[10] * Bs + 131072) >> 18);
+        cb[c] = (unsigned)min(max(u, 0), 255);
+        cr[c] = (unsigned)min(max(v, 0), 255);
+    }
+    const int cw = (W + 1) >> 1, ch = (H + 1) >> 1;
+    const size_t lumaBytes = (size_t)W * H;
+    unsigned char *y0 = out + (size_t)j0 * W + x0, *y1 = out + (size_t)(j0 + 1) * W + x0;
+    unsigned char *c0 = out + lumaBytes + (I420 ? (size_t)jp * cw + (x0 >> 1) : (size_t)jp * 2 * cw + x0);     // Cb, or the Cb,Cr pairs
+    unsigned char *c1 = c0 + (size_t)cw * ch;                                                                  // I420's Cr
+    if constexpr (FAST) {
+        yuv_store<BW>(y0, yb[0]);
+        yuv_store<BW>(y1, yb[1]);
+        if constexpr (I420) {
+            yuv_store<BW / 2>(c0, cb);
+            yuv_store<BW / 2>(c1, cr);
+        } else {
+            unsigned uv[BW];
+#pragma unroll
+            for (int c = 0; c < BW / 2; c++) { uv[2 * c] = cb[c]; uv[2 * c + 1] = cr[c]; }
+            yuv_store<BW>(c0, uv);
+        }
+    } else {
+        const bool row1 = j0 + 1 < H;
+#pragma unroll
+        for (int k = 0; k < BW; k++) {
+            if (x0 + k < W) {
+                y0[k] = (unsigned char)yb[0][k];
+                if (row1) y1[k] = (unsigned char)yb[1][k];
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < BW / 2; c++) {
+            if ((x0 >> 1) + c < cw) {
+                if constexpr (I420) { c0[c] = (unsigned char)cb[c]; c1[c] = (unsigned char)cr[c]; }
+                else { c0[2 * c] = (unsigned char)cb[c]; c0[2 * c + 1] = (unsigned char)cr[c]; }
+            }
+        }
+    }
+}
+
+unsigned long long rt_display_yuv_blocks(int W, int H) {
+    return (unsigned long long)(((unsigned)W + RT_YUV_BW - 1u) / RT_YUV_BW) * (((unsigned)H + 1u) / 2u);
+}
+
+// srgb / tone / dExposure / invW2 as rt_launch_display_pack_toned; i420: 0 NV12, 1 I420; coef: rt_display_yuv_coeffs' twelve words
+hipError_t rt_launch_display_pack_yuv(const void *image, void *out, int W, int H, int i420, int srgb, int flip, float exposure, int tone,
+                                      float invW2, const void *dExposure, const int *coef, hipStream_t s) {
+    const unsigned blocksPerRow = ((unsigned)W + RT_YUV_BW - 1u) / RT_YUV_BW;
+    const unsigned long long nBlocks = rt_display_yuv_blocks(W, H);
+    if (nBlocks > 0xffffff00ull || tone < TONE_NONE || tone > TONE_ACES) return hipErrorInvalidValue;   // (callers refuse such frames first)
+    const dim3 grid((unsigned)((nBlocks + 255) / 256));
+    const RtDisplayTree &tree = display_tables().tree;
+    RtYuvCoef cf;
+    memcpy(cf.v, coef, sizeof cf.v);
+    auto go = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, (const float4 *)image, (unsigned char *)out, W, H, blocksPerRow, (unsigned)nBlocks,
+                           flip, exposure, (const float *)dExposure, invW2, cf, tree);
+    };
+    const bool fast = (W & 7) == 0 && (H & 1) == 0;
+    auto pick = [&](auto toneC, auto srgbC) {
+        constexpr int T = decltype(toneC)::value;
+        constexpr bool S = decltype(srgbC)::value;
+        if (i420) fast ? go(rt_display_pack_yuv_kernel<S, T, true, true>) : go(rt_display_pack_yuv_kernel<S, T, true, false>);
+        else fast ? go(rt_display_pack_yuv_kernel<S, T, false, true>) : go(rt_display_pack_yuv_kernel<S, T, false, false>);
+    };
+    auto pickTone = [&](auto srgbC) {
+        if (tone == TONE_NONE) pick(std::integral_constant<int, TONE_NONE>{}, srgbC);
+        else if (tone == TONE_REINHARD) pick(std::integral_constant<int, TONE_REINHARD>{}, srgbC);
+        else pick(std::integral_constant<int, TONE_ACES>{}, srgbC);
+    };
+    if (srgb) pickTone(std::true_type{});
+    else pickTone(std::false_type{});
+    return hipGetLastError();
+}
+
+// =========================================================================================
 // Exposure metering (rt_meter, include/rt_mi355.h): a 256-bin histogram of log-luminance over any rgba32f surface, then the solve
 // of rt_meter.h as a launch of its own behind it.  Bandwidth-bound like the pack (16 B read per pixel, nothing written but the
 // 1 KiB state), and the code base's one device-wide reduction: integer atomics only, so the state is bit-identical from run to run.

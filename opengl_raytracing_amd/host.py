@@ -41,6 +41,7 @@ EXPORTS = [
     "rt_mgpu_last_error", "rt_trace_rays", "rt_camera_rays", "rt_pick", "rt_shade_rays", "rt_debug_device_math",
     "rt_display_pack", "rt_display_srgb_thresholds", "rt_present_configure", "rt_present_submit", "rt_present_poll", "rt_present_wait",
     "rt_meter", "rt_meter_solve_host", "rt_meter_tables", "rt_display_pack_toned", "rt_present_submit_toned",
+    "rt_display_yuv_coeffs", "rt_display_yuv_layout", "rt_display_pack_yuv", "rt_present_submit_yuv",
 ]
 
 
@@ -167,6 +168,10 @@ def load_library(build_if_missing=True):
     lib.rt_meter_tables.argtypes = [P(cf), P(ctypes.c_uint32)]
     lib.rt_display_pack_toned.argtypes = [vp, vp, vp, P(L.RtDisplayDesc), P(L.RtToneDesc), vp]
     lib.rt_present_submit_toned.argtypes = [vp, vp, P(L.RtDisplayDesc), P(L.RtToneDesc), vp, P(ctypes.c_uint64)]
+    lib.rt_display_yuv_coeffs.argtypes = [ci, ci, P(ctypes.c_int32)]
+    lib.rt_display_yuv_layout.argtypes = [P(L.RtYuvDesc), P(ctypes.c_size_t), P(ctypes.c_size_t), P(ctypes.c_size_t)]
+    lib.rt_display_pack_yuv.argtypes = [vp, vp, vp, P(L.RtYuvDesc), P(L.RtToneDesc), vp]
+    lib.rt_present_submit_yuv.argtypes = [vp, vp, P(L.RtYuvDesc), P(L.RtToneDesc), vp, P(ctypes.c_uint64)]
     for name in EXPORTS:
         if name not in ("rt_last_error", "rt_mgpu_last_error", "rt_wire_bytes"):
             getattr(lib, name).restype = ci
@@ -313,6 +318,46 @@ def meter_solve_host(state, width, height, **desc):
     if rc:
         raise RtError(rc, "rt_meter_solve_host")
     return out[0]
+
+
+YuvLayout = collections.namedtuple("YuvLayout", "offset pitch bytes")
+YuvLayout.__doc__ = """rt_display_yuv_layout's answer: byte offsets and row pitches of the Y, Cb and Cr planes (NV12: Cb and Cr interleaved,
+offset[2] = offset[1] + 1), and the size of the whole frame."""
+
+
+def yuv_coeffs(matrix="bt709", range="limited"):
+    """The twelve Q16 words of the YUV matrix (rt_display_yuv_coeffs): int32 [cYR, cYG, cYB, yOff, cBR, cBG, cBB, 0, cRR, cRG, cRB, 0].
+    Needs no GPU."""
+    d = L.make_yuv_desc(1, 1, matrix=matrix, range=range)
+    out = np.zeros(12, dtype=np.int32)
+    rc = load_library().rt_display_yuv_coeffs(d.matrix, d.range, out.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)))
+    if rc:
+        raise RtError(rc, "rt_display_yuv_coeffs")
+    return out
+
+
+def yuv_layout(width, height, format="nv12"):
+    """Where the planes of a width x height NV12 / I420 frame lie (rt_display_yuv_layout) -> YuvLayout.  Needs no GPU."""
+    d = L.make_yuv_desc(width, height, format=format)
+    off, pitch, n = (ctypes.c_size_t * 3)(), (ctypes.c_size_t * 3)(), ctypes.c_size_t(0)
+    rc = load_library().rt_display_yuv_layout(ctypes.byref(d), off, pitch, ctypes.byref(n))
+    if rc:
+        raise RtError(rc, "rt_display_yuv_layout")
+    return YuvLayout(tuple(off), tuple(pitch), n.value)
+
+
+def yuv_planes(frame, width, height, format="nv12"):
+    """Views of the planes of one frame (uint8, yuv_layout(...).bytes long): (y[H, W], uv[ch, cw, 2]) for NV12,
+    (y[H, W], cb[ch, cw], cr[ch, cw]) for I420."""
+    w, h = int(width), int(height)
+    cw, ch = (w + 1) // 2, (h + 1) // 2
+    lay = yuv_layout(w, h, format)
+    frame = np.asarray(frame).reshape(-1)
+    assert frame.dtype == np.uint8 and frame.size == lay.bytes
+    y = frame[: w * h].reshape(h, w)
+    if L.make_yuv_desc(w, h, format=format).format == L.YUV_NV12:
+        return y, frame[lay.offset[1]:].reshape(ch, cw, 2)
+    return y, frame[lay.offset[1]: lay.offset[2]].reshape(ch, cw), frame[lay.offset[2]:].reshape(ch, cw)
 
 
 def _dev_ptr(x):
@@ -664,6 +709,8 @@ class RayTracer:
         view of the ring's pinned slot instead: valid until the present_submit that returns ticket + slots (or
         present_configure, or close()), after which its memory is rewritten or gone -- copy what must outlive that."""
         p, n = ctypes.c_void_p(), ctypes.c_size_t(0)
+        if int(ticket) in getattr(self, "_present_yuv", {}):
+            raise ValueError(f"ticket {int(ticket)} is a YUV frame (present_submit_yuv): wait for it with present_wait_yuv")
         self._check(self.lib.rt_present_wait(self.ctx, int(ticket), ctypes.byref(p), ctypes.byref(n)), "rt_present_wait")
         h, w = self._present_shapes[int(ticket)]
         assert n.value == h * w * 4
@@ -672,6 +719,52 @@ class RayTracer:
             return view.copy()
         view.flags.writeable = False
         return view
+
+    # ---- YUV 4:2:0 output: the frame a video encoder takes ------------------------------------
+    def display_pack_yuv(self, d_image, d_out, width, height, format="nv12", matrix="bt709", range="limited", transfer="srgb",
+                         flip=False, exposure=1.0, tone=None, white=1.0, d_exposure=None, stream=None):
+        """rgba32f surface -> NV12 or I420 on the device (rt_display_pack_yuv).  d_image / d_out: raw device pointers or CUDA
+        tensors, 16-byte aligned, not overlapping; d_out holds yuv_layout(width, height, format).bytes.  The R'G'B' codes are
+        display_pack's for format=`transfer` with the same `exposure`, `tone`, `white` and `d_exposure`; matrix "bt709" / "bt601",
+        range "limited" / "full"; `flip` makes output row 0 the top image row.  Asynchronous on torch stream `stream`."""
+        d = L.make_yuv_desc(width, height, format, matrix, range, transfer, flip, exposure)
+        t = None if tone is None and d_exposure is None else L.make_tone_desc(tone or "none", white, d_exposure)
+        self._on_torch_stream(stream, lambda h: self._check(self.lib.rt_display_pack_yuv(
+            self.ctx, _dev_ptr(d_image), _dev_ptr(d_out), ctypes.byref(d), ctypes.byref(t) if t is not None else None, ctypes.c_void_p(h)),
+            "rt_display_pack_yuv"))
+
+    def present_submit_yuv(self, d_image, width, height, format="nv12", matrix="bt709", range="limited", transfer="srgb",
+                           flip=False, exposure=1.0, tone=None, white=1.0, d_exposure=None, stream=None):
+        """present_submit with display_pack_yuv's frame: same ring, same ticket sequence.  Wait for the ticket with present_wait_yuv."""
+        d = L.make_yuv_desc(width, height, format, matrix, range, transfer, flip, exposure)
+        td = None if tone is None and d_exposure is None else L.make_tone_desc(tone or "none", white, d_exposure)
+        t = ctypes.c_uint64()
+        self._on_torch_stream(stream, lambda h: self._check(self.lib.rt_present_submit_yuv(
+            self.ctx, _dev_ptr(d_image), ctypes.byref(d), ctypes.byref(td) if td is not None else None, ctypes.c_void_p(h), ctypes.byref(t)),
+            "rt_present_submit_yuv"))
+        self._present_yuv = getattr(self, "_present_yuv", {})
+        self._present_yuv[t.value] = (int(width), int(height), d.format)
+        for old in [k for k in self._present_yuv if k + 16 <= t.value]:         # (more than any ring holds)
+            del self._present_yuv[old]
+        getattr(self, "_present_shapes", {}).pop(t.value, None)
+        return t.value
+
+    def present_wait_yuv(self, ticket, copy=True):
+        """Block until the YUV frame of `ticket` is in host memory -> (y[H, W], uv[ch, cw, 2]) for NV12, (y[H, W], cb[ch, cw],
+        cr[ch, cw]) for I420, uint8.  copy=False returns read-only views of the ring's pinned slot (present_wait's rules)."""
+        if int(ticket) not in getattr(self, "_present_yuv", {}):
+            raise ValueError(f"ticket {int(ticket)} is not a live YUV frame of present_submit_yuv (RGBA8 tickets: present_wait)")
+        p, n = ctypes.c_void_p(), ctypes.c_size_t(0)
+        self._check(self.lib.rt_present_wait(self.ctx, int(ticket), ctypes.byref(p), ctypes.byref(n)), "rt_present_wait")
+        w, h, fmt = self._present_yuv[int(ticket)]
+        if n.value != yuv_layout(w, h, fmt).bytes:
+            raise RtError(-1, f"ticket {int(ticket)} holds {n.value} bytes, not a {w}x{h} YUV frame")
+        frame = np.frombuffer((ctypes.c_uint8 * n.value).from_address(p.value), dtype=np.uint8)
+        if copy:
+            frame = frame.copy()
+        else:
+            frame.flags.writeable = False
+        return yuv_planes(frame, w, h, fmt)
 
     def tile_costs(self):
         """(costs[tilesY, tilesX] uint32, cycles/64 per tile) of the last feedback-scheduled launch."""

@@ -273,3 +273,30 @@ def make_tone_desc(tone="none", white=1.0, d_exposure=None):
     t.white = float(white)
     t.dExposure = d_exposure or None
     return t
+
+
+# ---- YUV 4:2:0 video output (rt_display_pack_yuv / rt_present_submit_yuv, include/rt_mi355.h) --
+YUV_NV12, YUV_I420 = 0, 1
+YUV_BT709, YUV_BT601 = 0, 1
+YUV_LIMITED, YUV_FULL = 0, 1
+
+
+class RtYuvDesc(ctypes.Structure):
+    """``rt_yuv_desc``: size of the rgba32f surface, plane format, matrix, range, transfer of the R'G'B' codes, flags, exposure."""
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("format", ctypes.c_int32), ("matrix", ctypes.c_int32),
+                ("range", ctypes.c_int32), ("transfer", ctypes.c_int32), ("flags", ctypes.c_uint32), ("exposure", ctypes.c_float),
+                ("reserved", ctypes.c_int32 * 4)]
+
+
+assert ctypes.sizeof(RtYuvDesc) == 48
+
+
+def make_yuv_desc(width, height, format="nv12", matrix="bt709", range="limited", transfer="srgb", flip=False, exposure=1.0):
+    d = RtYuvDesc()
+    d.width, d.height = int(width), int(height)
+    d.format = int({"nv12": YUV_NV12, "i420": YUV_I420}.get(format, format))
+    d.matrix = int({"bt709": YUV_BT709, "bt601": YUV_BT601}.get(matrix, matrix))
+    d.range = int({"limited": YUV_LIMITED, "full": YUV_FULL}.get(range, range))
+    d.transfer = int({"linear": DISPLAY_RGBA8_LINEAR, "srgb": DISPLAY_RGBA8_SRGB}.get(transfer, transfer))
+    d.flags, d.exposure = DISPLAY_FLIP_ROWS if flip else 0, float(exposure)
+    return d
