@@ -15,8 +15,10 @@ LIB_PATH = os.path.join(PKG_DIR, "librt_mi355.so")
 ORACLE_DIR = os.path.join(REPO, "oracle")
 ORACLE_LIB = os.path.join(ORACLE_DIR, "liboracle_rt.so")
 
-SOURCES = ["rt_kernels.hip", "rt_post.hip", "rt_abi.cpp", "rt_sched.cpp", "rt_host.cpp", "rt_mgpu.cpp"]
-HEADERS = [os.path.join(CSRC, "rt_device.h"), os.path.join(CSRC, "rt_sched.h"), os.path.join(CSRC, "rt_devbuf.h"), os.path.join(CSRC, "rt_packet.inc"), os.path.join(CSRC, "rt_shadowtab.inc"), os.path.join(CSRC, "rt_query.inc"), os.path.join(CSRC, "rt_shade.inc"), os.path.join(CSRC, "rt_mesa_math.h"), os.path.join(CSRC, "rt_fastmath.h"), os.path.join(CSRC, "rt_meter.h"), os.path.join(REPO, "include", "rt_mi355.h")]
+SOURCES = ["rt_kernels.hip", "rt_post.hip", "rt_display.hip", "rt_abi.cpp", "rt_display.cpp", "rt_present.cpp", "rt_sched.cpp", "rt_host.cpp",
+           "rt_mgpu.cpp"]
+# every header and include file of csrc/ plus the public header: nothing to keep by hand, so no stale build from a forgotten one
+HEADERS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".inc"))) + [os.path.join(REPO, "include", "rt_mi355.h")]
 
 # -ffp-contract=off: the reference's GL never fuses a*b+c; IEEE divide and
 # sqrt are hipcc's default (-fhip-fp32-correctly-rounded-divide-sqrt).

@@ -8,134 +8,11 @@
 #include <string.h>
 
 #include <new>
-#include <string>
-#include <vector>
 
-#include "rt_device.h"
+#include "rt_context.h"
 #include "rt_mesa_math.h"
-#include "rt_meter.h"
-#include "rt_sched.h"
-
-// Last use of a context-owned scratch that post passes on any stream work in (rt_bloom's ping-pong targets, rt_ssao's depth
-// plane).  The scratch is one per context, so its users run one after another: a pass orders its stream behind the previous
-// use (acquire), launches, and records its own (release).  Every use waits for the one before it, so the event of the last
-// one stands for all of them: the host waits on it alone before the scratch is freed (drain).  Nothing here blocks the host
-// in steady state; behind a use on the same stream the wait is already met by stream order.
-struct ScratchUse {
-    DevEvent ev;
-    bool used = false;
-    hipError_t create() { return ev.create(hipEventDisableTiming); }
-    hipError_t acquire(hipStream_t s) { return used ? hipStreamWaitEvent(s, ev, 0) : hipSuccess; }
-    hipError_t release(hipStream_t s) {
-        used = true;
-        return hipEventRecord(ev, s);
-    }
-    hipError_t drain() { return used ? hipEventSynchronize(ev) : hipSuccess; }
-};
-
-// The ring rt_present_submit delivers packed frames through.  Ticket t lives in slot t % slots: the pack kernel writes the
-// slot's device staging buffer on the caller's stream, the copy stream moves it to the slot's pinned buffer behind `packed`
-// and records `done`.  The next user of the slot orders its pack behind `done` on the device; the host waits on `done` only
-// for the ticket it asks for, before the slot's buffers grow, and (the copy stream as a whole) before the ring goes.
-struct PresentRing {
-    static constexpr int kMaxSlots = 8;
-    struct Slot {
-        DevBuf<uint8_t> dStage;
-        PinnedBuf<uint8_t> hPixels;
-        DevEvent packed, done;
-        bool used = false;               // `done` has been recorded at least once
-        bool seen = false;               // the host has seen the slot's current ticket complete (wait, or a ready poll)
-        uint64_t ticket = 0;
-        size_t bytes = 0;
-    };
-    DevStream copy;                      // created by the first submit: a context that never presents opens no second stream
-    Slot slot[kMaxSlots];
-    int slots = 3;
-    uint64_t next = 0;                   // the ticket the next submit returns
-    uint64_t base = 0;                   // tickets below it were expired by rt_present_configure
-    bool live(uint64_t t) const { return t < next && t >= base && next - t <= (uint64_t)slots; }
-};
-
-// Everything the context allocates is held by an owner (rt_devbuf.h): after rt_destroy has drained the streams, `delete`
-// releases it all.  The stream comes first so that it goes last.
-struct rt_context {
-    int device = 0;
-    DevStream stream;
-    DevEvent evStart, evStop, evScene;
-    bool timed = false;
-    // raw SSBO bytes + compiled scene
-    DevBuf<uint8_t> dObjects, dLights;
-    DevBuf<float4> dCompiled;
-    int nObj = 0, nLt = 0;
-    bool anyPcss = false;               // some light of the current scene has shadowType 2 (selects the kernel instantiation)
-    // double-buffered pinned staging so rt_set_scene never blocks on the GPU and the caller's
-    // bytes are consumed before it returns (glBufferData semantics)
-    PinnedBuf<uint8_t> hStage[2];
-    DevEvent evStage[2];
-    bool stageUsed[2] = {false, false};
-    unsigned stageSeq = 0;
-    // textures
-    DevBuf<uint8_t> dNoise;
-    int noiseW = 0, noiseH = 0;
-    DevBuf<uint16_t> dSky;
-    int skySize = 0;
-    // context-owned output surfaces
-    DevBuf<float4> dColor, dPos;
-    DevBuf<uint2> dNormal;
-    int surfW = 0, surfH = 0;
-    DevBuf<unsigned long long> dRayCounter;
-    int variant = 1;   // 1 = wavefront-packet kernel (default), 0 = exhaustive per-lane loop
-    unsigned long long lastStats[32] = {};   // rt_count_rays diagnostics (rt_debug_stats)
-    RtTileScheduler sched;                     // tile order of the packet kernel's frames; the record of every stream launches go to
-    DevBuf<uint2> dBloom[2];                   // rgba16f ping-pong targets of rt_bloom
-    DevBuf<float> dSsaoDepth;                  // gPosition.z plane of rt_ssao
-    ScratchUse bloomUse, ssaoUse;              // who ran last in dBloom / dSsaoDepth, on whichever stream
-    // rt_frame: AO result (raw, blurred), TAA history ping-pong, bloom-combined image when the caller passes none
-    DevBuf<float> dFrameAO[2];
-    DevBuf<float4> dHistory[2];
-    DevBuf<float4> dFrameDisplay;
-    int frameW = 0, frameH = 0, lastHistory = -1;
-    bool frameAOValid = false;
-    // shadow tables of the current scene (rt_shadowtab.inc)
-    DevBuf<unsigned> dShadowTab;
-    bool shadowTabValid = false;
-    bool shadowTabBlocker = false;             // the buffer also holds the blocker-ray tables of the scene's PCSS lights
-    std::vector<uint8_t> lastScene;            // the bytes of the current scene (objects, then lights): an identical re-upload is a no-op
-    bool stOnePhase = false;                   // RT_ST_BUILD=full: the one-phase builder (every object in every cell; comparison builds only)
-    RtShadowTabGeom stGeomSmall = {48, 96, 32}, stGeomLarge = {32, 64, 32};      // <= 32 objects / more (RT_ST_GEOM overrides both); measured: DESIGN.md
-    unsigned sceneGen = 0, texGen = 0;         // bumped by rt_set_scene / rt_set_noise / rt_set_skybox / rt_equirect_to_cubemap
-    // rt_pick: the hit record on the device and its pinned host copy
-    DevBuf<float4> dPick;
-    PinnedBuf<rt_hit> hPick;
-    PresentRing present;                       // rt_present_*: staging, pinned buffers and events of the frames on their way to the host
-    std::string err;
-};
 
 namespace {
-
-int fail(rt_context *c, int code, const char *what, hipError_t e = hipSuccess) {
-    if (c) {
-        c->err = what;
-        if (e != hipSuccess) {
-            c->err += ": ";
-            c->err += hipGetErrorString(e);
-        }
-    }
-    return code;
-}
-
-#define HIP_TRY(c, call)                                        \
-    do {                                                        \
-        hipError_t e_ = (call);                                 \
-        if (e_ != hipSuccess) return fail(c, RT_ERR_HIP, #call, e_); \
-    } while (0)
-
-// a call of the scheduler's: the error string names the HIP call that failed inside it
-#define SCHED_TRY(c, call)                                      \
-    do {                                                        \
-        hipError_t e_ = (c)->sched.call;                        \
-        if (e_ != hipSuccess) return fail(c, RT_ERR_HIP, (c)->sched.failedCall, e_); \
-    } while (0)
 
 // haltonSequence (/root/reference/shader/raytracingCs.glsl:278-288), host copy for the
 // per-depth bounce sample.
@@ -236,7 +113,7 @@ int launch(rt_context *c, const rt_params *p, float4 *dColor, float4 *dPos, uint
 // A launch on the caller's stream (null = the context's own) that reads the device scene: a foreign stream first orders
 // itself behind the last scene upload (evScene).
 int caller_stream(rt_context *c, void *hipStream, hipStream_t *out) {
-    hipStream_t s = hipStream ? (hipStream_t)hipStream : c->stream.s;
+    hipStream_t s = stream_or_own(c, hipStream);
     if (s != c->stream) HIP_TRY(c, hipStreamWaitEvent(s, c->evScene, 0));
     *out = s;
     return RT_OK;
@@ -280,6 +157,7 @@ int rt_create(rt_context **out, int deviceId) {
         return RT_ERR_HIP;
     }
     c->sched.init(c->stream);
+    c->present.init(deviceId);
     *out = c;
     return RT_OK;
 }
@@ -290,7 +168,7 @@ int rt_destroy(rt_context *c) {
     (void)c->sched.drain();            // the context's stream, the phase stream, every stream's last launch
     (void)c->bloomUse.drain();         // post passes on caller streams: the scratch they work in goes with the context
     (void)c->ssaoUse.drain();
-    if (c->present.copy) (void)hipStreamSynchronize(c->present.copy);   // frames on their way to the pinned buffers (and, before them, their packs)
+    (void)c->present.drain();          // frames on their way to the pinned buffers (and, before them, their packs)
     delete c;
     return RT_OK;
 }
@@ -304,22 +182,20 @@ int rt_set_scene(rt_context *c, const void *objects, int nObj, const void *light
     // The reference re-specifies both SSBOs every frame whether or not anything moved (ImGUIManager.cpp:202, :338).  Identical
     // bytes leave the device scene, its compiled form and its shadow tables as they are (and the scheduler's view of "the same
     // frame as before" intact).
-    {
-        const size_t ob = (size_t)nObj * RT_OBJECT_STRIDE, lb = (size_t)nLt * RT_LIGHT_STRIDE;
-        if (c->dCompiled && c->nObj == nObj && c->nLt == nLt && c->lastScene.size() == ob + lb &&
-            (ob == 0 || memcmp(c->lastScene.data(), objects, ob) == 0) && (lb == 0 || memcmp(c->lastScene.data() + ob, lights, lb) == 0))
-            return RT_OK;
-        c->lastScene.clear();              // (refilled at the end: a failed update must not look like the current scene)
-        c->sceneGen++;
-    }
-    HIP_TRY(c, c->dObjects.grow((size_t)nObj * RT_OBJECT_STRIDE));
-    HIP_TRY(c, c->dLights.grow((size_t)nLt * RT_LIGHT_STRIDE));
+    const size_t objBytes = (size_t)nObj * RT_OBJECT_STRIDE, ltBytes = (size_t)nLt * RT_LIGHT_STRIDE;
+    if (c->dCompiled && c->nObj == nObj && c->nLt == nLt && c->lastScene.size() == objBytes + ltBytes &&
+        (objBytes == 0 || memcmp(c->lastScene.data(), objects, objBytes) == 0) &&
+        (ltBytes == 0 || memcmp(c->lastScene.data() + objBytes, lights, ltBytes) == 0))
+        return RT_OK;
+    c->lastScene.clear();                  // (refilled at the end: a failed update must not look like the current scene)
+    c->sceneGen++;
+    HIP_TRY(c, c->dObjects.grow(objBytes));
+    HIP_TRY(c, c->dLights.grow(ltBytes));
     HIP_TRY(c, c->dCompiled.grow(rt_compiled_total_f4(nObj, nLt)));
     // The scene buffers are about to be rewritten on the context's stream: order that behind the last launch of
     // EVERY stream frames have been issued on (one event per stream; a single shared event would only cover the
     // most recent one -- ADVICE r1).  The reference re-uploads its SSBOs every frame, so this is the common path.
     SCHED_TRY(c, waitForLaunches(c->stream));
-    const size_t objBytes = (size_t)nObj * RT_OBJECT_STRIDE, ltBytes = (size_t)nLt * RT_LIGHT_STRIDE;
     const int k = (int)(c->stageSeq++ & 1u);
     if (c->stageUsed[k]) HIP_TRY(c, hipEventSynchronize(c->evStage[k]));
     if (objBytes + ltBytes > c->hStage[k].cap) HIP_TRY(c, c->hStage[k].grow(objBytes + ltBytes < 65536 ? 65536 : objBytes + ltBytes));
@@ -558,29 +434,21 @@ static int count_rays_impl(rt_context *c, const rt_params *p, uint64_t *rays, in
     int rc = validate_params(c, p);
     if (rc) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
-    size_t npx = (size_t)p->regionW * p->regionH;
-    float4 *col = nullptr, *pos = nullptr;
-    uint2 *nrm = nullptr;
-    size_t n = npx ? npx : 1;
-    HIP_TRY(c, hipMalloc((void **)&col, n * sizeof(float4)));
-    hipError_t e1 = hipMalloc((void **)&pos, n * sizeof(float4));
-    hipError_t e2 = hipMalloc((void **)&nrm, n * sizeof(uint2));
-    if (e1 == hipSuccess && e2 == hipSuccess) {
-        rc = RT_OK;
-        if (hipMemsetAsync(c->dRayCounter, 0, 32 * sizeof(unsigned long long), c->stream) != hipSuccess) rc = RT_ERR_HIP;
-        if (!rc) rc = launch(c, p, col, pos, nrm, c->dRayCounter, c->stream, false, countMode);
-        unsigned long long v[32] = {};
-        if (!rc && (hipStreamSynchronize(c->stream) != hipSuccess ||
-                    hipMemcpy(v, c->dRayCounter, sizeof v, hipMemcpyDeviceToHost) != hipSuccess))
-            rc = fail(c, RT_ERR_HIP, "ray counter readback");
-        *rays = v[0];
-        for (int k = 0; k < 32; k++) c->lastStats[k] = v[k];
-    } else {
-        rc = fail(c, RT_ERR_HIP, "hipMalloc (ray count scratch)", e1 != hipSuccess ? e1 : e2);
-    }
-    (void)hipFree(col);
-    if (pos) (void)hipFree(pos);
-    if (nrm) (void)hipFree(nrm);
+    const size_t npx = (size_t)p->regionW * p->regionH;
+    DevBuf<float4> col, pos;
+    DevBuf<uint2> nrm;
+    hipError_t e = col.grow(npx);
+    if (e == hipSuccess) e = pos.grow(npx);
+    if (e == hipSuccess) e = nrm.grow(npx);
+    if (e != hipSuccess) return fail(c, RT_ERR_HIP, "hipMalloc (ray count scratch)", e);
+    if (hipMemsetAsync(c->dRayCounter, 0, 32 * sizeof(unsigned long long), c->stream) != hipSuccess) rc = RT_ERR_HIP;
+    if (!rc) rc = launch(c, p, col, pos, nrm, c->dRayCounter, c->stream, false, countMode);
+    unsigned long long v[32] = {};
+    if (!rc && (hipStreamSynchronize(c->stream) != hipSuccess ||
+                hipMemcpy(v, c->dRayCounter, sizeof v, hipMemcpyDeviceToHost) != hipSuccess))
+        rc = fail(c, RT_ERR_HIP, "ray counter readback");
+    *rays = v[0];
+    for (int k = 0; k < 32; k++) c->lastStats[k] = v[k];
     return rc;
 }
 
@@ -641,7 +509,7 @@ int rt_taa_resolve(rt_context *c, const void *dCurrent, const void *dHistory, co
         return fail(c, RT_ERR_INVALID_ARG, "bad rt_taa_resolve arguments");
     if (dOut == dCurrent || dOut == dHistory) return fail(c, RT_ERR_INVALID_ARG, "rt_taa_resolve cannot run in place");
     HIP_TRY(c, hipSetDevice(c->device));
-    hipStream_t s = hipStream ? (hipStream_t)hipStream : c->stream;
+    hipStream_t s = stream_or_own(c, hipStream);
     HIP_TRY(c, rt_launch_taa_resolve(dCurrent, dHistory, dNormal, dOut, width, height, blendFactor, jitterX, jitterY, s));
     return RT_OK;
 }
@@ -652,7 +520,7 @@ int rt_bloom(rt_context *c, const void *dScene, void *dOut, int width, int heigh
     if (!dScene || !dOut || width <= 0 || height <= 0 || iterations < 0) return fail(c, RT_ERR_INVALID_ARG, "bad rt_bloom arguments");
     if (dOut == dScene) return fail(c, RT_ERR_INVALID_ARG, "rt_bloom cannot run in place");     // the fused passes read neighbouring tiles' scene texels
     HIP_TRY(c, hipSetDevice(c->device));
-    hipStream_t s = hipStream ? (hipStream_t)hipStream : c->stream;
+    hipStream_t s = stream_or_own(c, hipStream);
     const size_t npx = (size_t)width * height;
     if (!(c->dBloom[0].holds(npx) && c->dBloom[1].holds(npx))) {
         HIP_TRY(c, c->bloomUse.drain());       // the last pass in the old targets, on whichever stream it ran
@@ -688,7 +556,7 @@ int rt_debug_device_math(rt_context *c, int op, const void *dIn, void *dOut, siz
     if (((uintptr_t)dIn | (uintptr_t)dOut) & 15u) return fail(c, RT_ERR_INVALID_ARG, "input and output pointers must be 16-byte aligned");
     if (n > ((size_t)0x7fffffff) * 256) return fail(c, RT_ERR_TOO_LARGE, "too many records in one call");
     HIP_TRY(c, hipSetDevice(c->device));
-    hipStream_t s = hipStream ? (hipStream_t)hipStream : c->stream;
+    hipStream_t s = stream_or_own(c, hipStream);
     HIP_TRY(c, rt_launch_device_math(op, (const uint4 *)dIn, (uint4 *)dOut, n, s));
     return RT_OK;
 }
@@ -729,7 +597,7 @@ int rt_ssao(rt_context *c, const void *dPosition, const void *dNormal, void *dOu
     if (noiseW <= 0 || noiseH <= 0 || noiseW * noiseH > 16) return fail(c, RT_ERR_TOO_LARGE, "rotation texture larger than 16 texels");
     if (dOut == dPosition || dOut == dNormal) return fail(c, RT_ERR_INVALID_ARG, "rt_ssao cannot run in place");   // samples read other pixels' G-buffer
     HIP_TRY(c, hipSetDevice(c->device));
-    hipStream_t s = hipStream ? (hipStream_t)hipStream : c->stream;
+    hipStream_t s = stream_or_own(c, hipStream);
     const size_t npx = (size_t)width * height;
     if (!c->dSsaoDepth.holds(npx)) {
         HIP_TRY(c, c->ssaoUse.drain());        // the last pass that read the old plane, on whichever stream it ran
@@ -747,342 +615,8 @@ int rt_ssao_blur(rt_context *c, const void *dIn, void *dOut, int width, int heig
     if (!dIn || !dOut || width <= 0 || height <= 0) return fail(c, RT_ERR_INVALID_ARG, "bad rt_ssao_blur arguments");
     if (dIn == dOut) return fail(c, RT_ERR_INVALID_ARG, "rt_ssao_blur cannot run in place");
     HIP_TRY(c, hipSetDevice(c->device));
-    hipStream_t s = hipStream ? (hipStream_t)hipStream : c->stream;
+    hipStream_t s = stream_or_own(c, hipStream);
     HIP_TRY(c, rt_launch_ssao_blur(dIn, dOut, width, height, horizontal, s));
-    return RT_OK;
-}
-
-// ---- display packing and delivery (the header has the contract)
-static int validate_display(rt_context *c, const void *dImage, const rt_display_desc *d) {
-    if (!d) return fail(c, RT_ERR_INVALID_ARG, "display description is NULL");
-    if (d->width <= 0 || d->height <= 0) return fail(c, RT_ERR_INVALID_ARG, "width/height must be positive");
-    if (d->format != RT_DISPLAY_RGBA8_LINEAR && d->format != RT_DISPLAY_RGBA8_SRGB) return fail(c, RT_ERR_INVALID_ARG, "unknown display format");
-    if (d->flags & ~RT_DISPLAY_FLIP_ROWS) return fail(c, RT_ERR_INVALID_ARG, "unknown display flag bits");
-    if (!(d->exposure > 0.0f) || !(d->exposure < HUGE_VALF)) return fail(c, RT_ERR_INVALID_ARG, "exposure must be finite and > 0");
-    if (d->reserved[0] || d->reserved[1] || d->reserved[2]) return fail(c, RT_ERR_INVALID_ARG, "reserved words must be zero");
-    if (!dImage || ((uintptr_t)dImage & 15u)) return fail(c, RT_ERR_INVALID_ARG, "the image pointer must be non-NULL and 16-byte aligned");
-    if ((((uint64_t)d->width + 3) / 4) * (uint64_t)d->height > 0xffffff00ull) return fail(c, RT_ERR_TOO_LARGE, "frame too large for one pack launch");
-    return RT_OK;
-}
-
-int rt_display_srgb_thresholds(float out[256]) {
-    if (!out) return RT_ERR_INVALID_ARG;
-    memcpy(out, rt_display_thresholds(), 256 * sizeof(float));
-    return RT_OK;
-}
-
-int rt_display_pack(rt_context *c, const void *dImage, void *dOut, const rt_display_desc *d, void *hipStream) {
-    if (!c) return RT_ERR_INVALID_ARG;
-    int rc = validate_display(c, dImage, d);
-    if (rc) return rc;
-    if (!dOut || ((uintptr_t)dOut & 15u)) return fail(c, RT_ERR_INVALID_ARG, "the output pointer must be non-NULL and 16-byte aligned");
-    const size_t npx = (size_t)d->width * d->height;
-    const uintptr_t i0 = (uintptr_t)dImage, o0 = (uintptr_t)dOut;
-    if (i0 < o0 + npx * 4 && o0 < i0 + npx * 16) return fail(c, RT_ERR_INVALID_ARG, "rt_display_pack cannot run in place: image and output overlap");
-    HIP_TRY(c, hipSetDevice(c->device));
-    hipStream_t s = hipStream ? (hipStream_t)hipStream : c->stream;
-    HIP_TRY(c, rt_launch_display_pack(dImage, dOut, d->width, d->height, d->format == RT_DISPLAY_RGBA8_SRGB,
-                                      (d->flags & RT_DISPLAY_FLIP_ROWS) != 0, d->exposure, s));
-    return RT_OK;
-}
-
-int rt_present_configure(rt_context *c, int slots) {
-    if (!c) return RT_ERR_INVALID_ARG;
-    PresentRing &r = c->present;
-    if (slots < 2 || slots > PresentRing::kMaxSlots) return fail(c, RT_ERR_INVALID_ARG, "rt_present_configure: 2..8 slots");
-    for (int k = 0; k < r.slots; k++)
-        if (r.slot[k].used && r.live(r.slot[k].ticket) && !r.slot[k].seen)
-            return fail(c, RT_ERR_INVALID_ARG, "rt_present_configure: a ticket is outstanding (wait for it first)");
-    // every live ticket's copy has been seen complete, older ones finished before them (one copy stream): nothing reads the buffers
-    HIP_TRY(c, hipSetDevice(c->device));
-    for (int k = slots; k < PresentRing::kMaxSlots; k++) {
-        HIP_TRY(c, r.slot[k].dStage.release());
-        HIP_TRY(c, r.slot[k].hPixels.release());
-    }
-    r.slots = slots;
-    r.base = r.next;
-    return RT_OK;
-}
-
-// what the toned entry points add to a display description, validated
-struct ToneArgs {
-    int op = RT_TONE_NONE;
-    float invW2 = 0.0f;
-    const void *dExposure = nullptr;
-};
-
-static int validate_tone(rt_context *c, const rt_tone_desc *t, ToneArgs *out) {
-    if (!t) return fail(c, RT_ERR_INVALID_ARG, "tone description is NULL");
-    if (t->op != RT_TONE_NONE && t->op != RT_TONE_REINHARD && t->op != RT_TONE_ACES) return fail(c, RT_ERR_INVALID_ARG, "unknown tone operator");
-    if (t->op == RT_TONE_REINHARD && (!(t->white >= 1.0f / 256.0f) || !(t->white < HUGE_VALF)))
-        return fail(c, RT_ERR_INVALID_ARG, "Reinhard's white must be finite and >= 1/256");
-    if ((uintptr_t)t->dExposure & 3u) return fail(c, RT_ERR_INVALID_ARG, "dExposure must be 4-byte aligned");
-    if (t->reserved[0] || t->reserved[1] || t->reserved[2] || t->reserved[3]) return fail(c, RT_ERR_INVALID_ARG, "reserved words must be zero");
-    out->op = t->op;
-    out->invW2 = t->op == RT_TONE_REINHARD ? 1.0f / (t->white * t->white) : 0.0f;
-    out->dExposure = t->dExposure;
-    return RT_OK;
-}
-
-int rt_display_pack_toned(rt_context *c, const void *dImage, void *dOut, const rt_display_desc *d, const rt_tone_desc *tone, void *hipStream) {
-    if (!c) return RT_ERR_INVALID_ARG;
-    int rc = validate_display(c, dImage, d);
-    if (rc) return rc;
-    ToneArgs t;
-    if ((rc = validate_tone(c, tone, &t))) return rc;
-    if (!dOut || ((uintptr_t)dOut & 15u)) return fail(c, RT_ERR_INVALID_ARG, "the output pointer must be non-NULL and 16-byte aligned");
-    const size_t npx = (size_t)d->width * d->height;
-    const uintptr_t i0 = (uintptr_t)dImage, o0 = (uintptr_t)dOut;
-    if (i0 < o0 + npx * 4 && o0 < i0 + npx * 16) return fail(c, RT_ERR_INVALID_ARG, "rt_display_pack_toned cannot run in place: image and output overlap");
-    HIP_TRY(c, hipSetDevice(c->device));
-    hipStream_t s = hipStream ? (hipStream_t)hipStream : c->stream;
-    HIP_TRY(c, rt_launch_display_pack_toned(dImage, dOut, d->width, d->height, d->format == RT_DISPLAY_RGBA8_SRGB,
-                                            (d->flags & RT_DISPLAY_FLIP_ROWS) != 0, d->exposure, t.op, t.invW2, t.dExposure, s));
-    return RT_OK;
-}
-
-// Every submit's way through the ring, after its arguments were validated: the next slot, grown to `bytes` if need be, pack(stage, s)
-// into its staging buffer on the caller's stream, the copy behind it, a ticket.  One ring and one ticket sequence for every format.
-extern "C++" {
-template <class Pack>
-static int present_enqueue(rt_context *c, size_t bytes, void *hipStream, uint64_t *ticket, Pack pack) {
-    HIP_TRY(c, hipSetDevice(c->device));
-    PresentRing &r = c->present;
-    PresentRing::Slot &sl = r.slot[r.next % (uint64_t)r.slots];
-    hipStream_t s = hipStream ? (hipStream_t)hipStream : c->stream;
-    HIP_TRY(c, r.copy.create());
-    HIP_TRY(c, sl.packed.create(hipEventDisableTiming));
-    HIP_TRY(c, sl.done.create(hipEventDisableTiming));
-    if (!(sl.dStage.holds(bytes) && sl.hPixels.holds(bytes))) {
-        if (sl.used) HIP_TRY(c, hipEventSynchronize(sl.done));      // this slot's own last copy; the other slots are untouched
-        HIP_TRY(c, sl.dStage.grow(bytes));
-        HIP_TRY(c, sl.hPixels.grow(bytes));
-    }
-    if (sl.used) HIP_TRY(c, hipStreamWaitEvent(s, sl.done, 0));     // the copy of ticket - slots has left the staging buffer
-    HIP_TRY(c, pack((void *)sl.dStage.ptr, s));
-    HIP_TRY(c, hipEventRecord(sl.packed, s));
-    HIP_TRY(c, hipStreamWaitEvent(r.copy, sl.packed, 0));
-    HIP_TRY(c, hipMemcpyAsync(sl.hPixels, sl.dStage, bytes, hipMemcpyDeviceToHost, r.copy));
-    HIP_TRY(c, hipEventRecord(sl.done, r.copy));
-    sl.used = true;
-    sl.seen = false;
-    sl.ticket = r.next;
-    sl.bytes = bytes;
-    *ticket = r.next++;
-    return RT_OK;
-}
-}  // extern "C++"
-
-// rt_present_submit and rt_present_submit_toned (tone == NULL: the untoned pack)
-static int present_submit(rt_context *c, const void *dImage, const rt_display_desc *d, const rt_tone_desc *tone, bool toned, void *hipStream,
-                          uint64_t *ticket) {
-    if (!c) return RT_ERR_INVALID_ARG;
-    if (!ticket) return fail(c, RT_ERR_INVALID_ARG, "ticket is NULL");
-    int rc = validate_display(c, dImage, d);
-    if (rc) return rc;
-    ToneArgs t;
-    if (toned && (rc = validate_tone(c, tone, &t))) return rc;
-    return present_enqueue(c, (size_t)d->width * d->height * 4, hipStream, ticket, [&](void *stage, hipStream_t s) {
-        return rt_launch_display_pack_toned(dImage, stage, d->width, d->height, d->format == RT_DISPLAY_RGBA8_SRGB,
-                                            (d->flags & RT_DISPLAY_FLIP_ROWS) != 0, d->exposure, t.op, t.invW2, t.dExposure, s);
-    });
-}
-
-int rt_present_submit(rt_context *c, const void *dImage, const rt_display_desc *d, void *hipStream, uint64_t *ticket) {
-    return present_submit(c, dImage, d, nullptr, false, hipStream, ticket);
-}
-
-int rt_present_submit_toned(rt_context *c, const void *dImage, const rt_display_desc *d, const rt_tone_desc *tone, void *hipStream,
-                            uint64_t *ticket) {
-    return present_submit(c, dImage, d, tone, true, hipStream, ticket);
-}
-
-// ---- YUV 4:2:0 output (the header has the contract)
-int rt_display_yuv_coeffs(int matrix, int range, int32_t out[12]) {
-    if (!out || (matrix != RT_YUV_BT709 && matrix != RT_YUV_BT601) || (range != RT_YUV_LIMITED && range != RT_YUV_FULL)) return RT_ERR_INVALID_ARG;
-    const double Kr = matrix == RT_YUV_BT709 ? 0.2126 : 0.299, Kb = matrix == RT_YUV_BT709 ? 0.0722 : 0.114;
-    const double sY = range == RT_YUV_LIMITED ? 219.0 / 255.0 : 1.0, sC = range == RT_YUV_LIMITED ? 224.0 / 255.0 : 1.0;
-    auto rne = [](double x) { return (int32_t)nearbyint(x); };       // (the default rounding mode: to nearest, ties to even)
-    const int32_t cYR = rne(65536.0 * Kr * sY), cYB = rne(65536.0 * Kb * sY), cYG = rne(65536.0 * sY) - cYR - cYB;
-    const int32_t cC = rne(32768.0 * sC);
-    const int32_t cBR = rne(-65536.0 * sC * Kr / (2.0 * (1.0 - Kb))), cRB = rne(-65536.0 * sC * Kb / (2.0 * (1.0 - Kr)));
-    const int32_t t[12] = {cYR, cYG, cYB, range == RT_YUV_LIMITED ? 16 : 0, cBR, -cC - cBR, cC, 0, cC, -cC - cRB, cRB, 0};
-    memcpy(out, t, sizeof t);
-    return RT_OK;
-}
-
-int rt_display_yuv_layout(const rt_yuv_desc *d, size_t offset[3], size_t pitch[3], size_t *bytes) {
-    if (!d || !offset || !pitch) return RT_ERR_INVALID_ARG;
-    if (d->width < 1 || d->height < 1 || (d->format != RT_YUV_NV12 && d->format != RT_YUV_I420)) return RT_ERR_INVALID_ARG;
-    const size_t W = (size_t)d->width, H = (size_t)d->height, cw = (W + 1) / 2, ch = (H + 1) / 2;
-    offset[0] = 0;
-    offset[1] = W * H;
-    pitch[0] = W;
-    if (d->format == RT_YUV_NV12) {
-        offset[2] = offset[1] + 1;
-        pitch[1] = pitch[2] = 2 * cw;
-    } else {
-        offset[2] = offset[1] + cw * ch;
-        pitch[1] = pitch[2] = cw;
-    }
-    if (bytes) *bytes = W * H + 2 * cw * ch;
-    return RT_OK;
-}
-
-// a validated rt_yuv_desc with its optional tone description: what the launch takes
-struct YuvArgs {
-    ToneArgs tone;
-    int32_t coef[12];
-    size_t bytes = 0;
-};
-
-static int validate_yuv(rt_context *c, const void *dImage, const rt_yuv_desc *d, const rt_tone_desc *tone, YuvArgs *out) {
-    if (!d) return fail(c, RT_ERR_INVALID_ARG, "YUV description is NULL");
-    if (d->width < 1 || d->height < 1) return fail(c, RT_ERR_INVALID_ARG, "width/height must be positive");
-    if (d->format != RT_YUV_NV12 && d->format != RT_YUV_I420) return fail(c, RT_ERR_INVALID_ARG, "unknown YUV format");
-    if (rt_display_yuv_coeffs(d->matrix, d->range, out->coef) != RT_OK) return fail(c, RT_ERR_INVALID_ARG, "unknown YUV matrix or range");
-    if (d->transfer != RT_DISPLAY_RGBA8_LINEAR && d->transfer != RT_DISPLAY_RGBA8_SRGB) return fail(c, RT_ERR_INVALID_ARG, "unknown transfer");
-    if (d->flags & ~RT_DISPLAY_FLIP_ROWS) return fail(c, RT_ERR_INVALID_ARG, "unknown display flag bits");
-    if (!(d->exposure > 0.0f) || !(d->exposure < HUGE_VALF)) return fail(c, RT_ERR_INVALID_ARG, "exposure must be finite and > 0");
-    if (d->reserved[0] || d->reserved[1] || d->reserved[2] || d->reserved[3]) return fail(c, RT_ERR_INVALID_ARG, "reserved words must be zero");
-    if (!dImage || ((uintptr_t)dImage & 15u)) return fail(c, RT_ERR_INVALID_ARG, "the image pointer must be non-NULL and 16-byte aligned");
-    int rc;
-    if (tone && (rc = validate_tone(c, tone, &out->tone))) return rc;
-    if (rt_display_yuv_blocks(d->width, d->height) > 0xffffff00ull) return fail(c, RT_ERR_TOO_LARGE, "frame too large for one pack launch");
-    size_t offset[3], pitch[3];
-    (void)rt_display_yuv_layout(d, offset, pitch, &out->bytes);
-    return RT_OK;
-}
-
-static hipError_t launch_yuv(const void *dImage, void *dOut, const rt_yuv_desc *d, const YuvArgs &a, hipStream_t s) {
-    return rt_launch_display_pack_yuv(dImage, dOut, d->width, d->height, d->format == RT_YUV_I420, d->transfer == RT_DISPLAY_RGBA8_SRGB,
-                                      (d->flags & RT_DISPLAY_FLIP_ROWS) != 0, d->exposure, a.tone.op, a.tone.invW2, a.tone.dExposure, a.coef, s);
-}
-
-int rt_display_pack_yuv(rt_context *c, const void *dImage, void *dOut, const rt_yuv_desc *d, const rt_tone_desc *tone, void *hipStream) {
-    if (!c) return RT_ERR_INVALID_ARG;
-    YuvArgs a;
-    int rc = validate_yuv(c, dImage, d, tone, &a);
-    if (rc) return rc;
-    if (!dOut || ((uintptr_t)dOut & 15u)) return fail(c, RT_ERR_INVALID_ARG, "the output pointer must be non-NULL and 16-byte aligned");
-    const size_t npx = (size_t)d->width * d->height;
-    const uintptr_t i0 = (uintptr_t)dImage, o0 = (uintptr_t)dOut;
-    if (i0 < o0 + a.bytes && o0 < i0 + npx * 16) return fail(c, RT_ERR_INVALID_ARG, "rt_display_pack_yuv cannot run in place: image and output overlap");
-    HIP_TRY(c, hipSetDevice(c->device));
-    hipStream_t s = hipStream ? (hipStream_t)hipStream : c->stream;
-    HIP_TRY(c, launch_yuv(dImage, dOut, d, a, s));
-    return RT_OK;
-}
-
-int rt_present_submit_yuv(rt_context *c, const void *dImage, const rt_yuv_desc *d, const rt_tone_desc *tone, void *hipStream, uint64_t *ticket) {
-    if (!c) return RT_ERR_INVALID_ARG;
-    if (!ticket) return fail(c, RT_ERR_INVALID_ARG, "ticket is NULL");
-    YuvArgs a;
-    int rc = validate_yuv(c, dImage, d, tone, &a);
-    if (rc) return rc;
-    return present_enqueue(c, a.bytes, hipStream, ticket, [&](void *stage, hipStream_t s) { return launch_yuv(dImage, stage, d, a, s); });
-}
-
-// ---- exposure metering (the header has the contract; the solve is rt_meter.h's, here and on the device)
-static int validate_meter_desc(rt_context *c, const rt_meter_desc *d) {
-    if (!d) return fail(c, RT_ERR_INVALID_ARG, "meter description is NULL");
-    if (d->width < 1 || d->height < 1) return fail(c, RT_ERR_INVALID_ARG, "width/height must be positive");
-    if (!(d->key > 0.0f) || !(d->key < HUGE_VALF)) return fail(c, RT_ERR_INVALID_ARG, "key must be finite and > 0");
-    if (!(d->minExposure > 0.0f) || !(d->maxExposure < HUGE_VALF) || !(d->minExposure <= d->maxExposure))
-        return fail(c, RT_ERR_INVALID_ARG, "exposure limits: 0 < minExposure <= maxExposure, both finite");
-    if (!(d->adapt > 0.0f) || !(d->adapt <= 1.0f)) return fail(c, RT_ERR_INVALID_ARG, "adapt must be in (0, 1]");
-    if (d->lowPermille < 0 || d->highPermille < 0 || (int64_t)d->lowPermille + d->highPermille >= 1000)
-        return fail(c, RT_ERR_INVALID_ARG, "permilles: >= 0 and lowPermille + highPermille < 1000");
-    if (d->reserved[0] || d->reserved[1] || d->reserved[2] || d->reserved[3]) return fail(c, RT_ERR_INVALID_ARG, "reserved words must be zero");
-    return RT_OK;
-}
-
-int rt_meter(rt_context *c, const void *dImage, const rt_meter_desc *d, void *dState, void *hipStream) {
-    if (!c) return RT_ERR_INVALID_ARG;
-    int rc = validate_meter_desc(c, d);
-    if (rc) return rc;
-    if (!dImage || ((uintptr_t)dImage & 15u)) return fail(c, RT_ERR_INVALID_ARG, "the image pointer must be non-NULL and 16-byte aligned");
-    if (!dState || ((uintptr_t)dState & 15u)) return fail(c, RT_ERR_INVALID_ARG, "the state pointer must be non-NULL and 16-byte aligned");
-    const uint64_t npx = (uint64_t)d->width * (uint64_t)d->height;
-    if (npx > 0x7fffffffull) return fail(c, RT_ERR_TOO_LARGE, "more than 2^31 - 1 pixels");
-    HIP_TRY(c, hipSetDevice(c->device));
-    hipStream_t s = hipStream ? (hipStream_t)hipStream : c->stream;
-    HIP_TRY(c, rt_launch_meter(dImage, dState, (unsigned)npx, d->key, d->minExposure, d->maxExposure, d->adapt, d->lowPermille,
-                               d->highPermille, s));
-    return RT_OK;
-}
-
-int rt_meter_solve_host(const rt_meter_state *in, const rt_meter_desc *d, rt_meter_state *out) {
-    if (!in || !out) return RT_ERR_INVALID_ARG;
-    int rc = validate_meter_desc(nullptr, d);
-    if (rc) return rc;
-    uint64_t n = 0;
-    for (int b = 0; b < 256; b++) n += in->hist[b];
-    if (n > 0xffffffffull) return RT_ERR_TOO_LARGE;
-    RtMeterSolveIn si;
-    si.key = d->key; si.minExposure = d->minExposure; si.maxExposure = d->maxExposure; si.adapt = d->adapt;
-    si.lowPermille = d->lowPermille; si.highPermille = d->highPermille;
-    si.prevExposure = in->exposure;
-    si.prevFrames = in->frames;
-    const RtMeterSolved r = rt_meter_solve(in->hist, si, rt_meter_tables_ref());
-    if (out != in) *out = *in;
-    out->nMetered = r.nMetered;
-    out->meanLog2Q16 = r.meanLog2Q16;
-    out->target = r.target;
-    out->exposure = r.exposure;
-    out->frames = r.frames;
-    memset(out->reserved, 0, sizeof out->reserved);
-    return RT_OK;
-}
-
-int rt_meter_tables(float pow2neg[256], uint32_t log2q16[8]) {
-    if (!pow2neg || !log2q16) return RT_ERR_INVALID_ARG;
-    const RtMeterTables &t = rt_meter_tables_ref();
-    memcpy(pow2neg, t.pow2neg, sizeof t.pow2neg);
-    memcpy(log2q16, t.log2q16, sizeof t.log2q16);
-    return RT_OK;
-}
-
-static int present_slot(rt_context *c, uint64_t ticket, PresentRing::Slot **out) {
-    PresentRing &r = c->present;
-    if (ticket >= r.next) return fail(c, RT_ERR_INVALID_ARG, "ticket has not been issued");
-    if (!r.live(ticket)) return fail(c, RT_ERR_INVALID_ARG, "ticket has expired (its slot was reused or the ring reconfigured)");
-    *out = &r.slot[ticket % (uint64_t)r.slots];
-    return RT_OK;
-}
-
-int rt_present_poll(rt_context *c, uint64_t ticket, int *ready) {
-    if (!c) return RT_ERR_INVALID_ARG;
-    if (!ready) return fail(c, RT_ERR_INVALID_ARG, "ready is NULL");
-    *ready = 0;
-    PresentRing::Slot *sl;
-    int rc = present_slot(c, ticket, &sl);
-    if (rc) return rc;
-    HIP_TRY(c, hipSetDevice(c->device));
-    const hipError_t e = hipEventQuery(sl->done);
-    if (e == hipErrorNotReady) {
-        (void)hipGetLastError();           // not an error: keep it out of the next launch's hipGetLastError()
-        return RT_OK;
-    }
-    if (e != hipSuccess) return fail(c, RT_ERR_HIP, "hipEventQuery(done)", e);
-    sl->seen = true;
-    *ready = 1;
-    return RT_OK;
-}
-
-int rt_present_wait(rt_context *c, uint64_t ticket, const void **hostPixels, size_t *bytes) {
-    if (!c) return RT_ERR_INVALID_ARG;
-    if (!hostPixels) return fail(c, RT_ERR_INVALID_ARG, "hostPixels is NULL");
-    *hostPixels = nullptr;
-    if (bytes) *bytes = 0;
-    PresentRing::Slot *sl;
-    int rc = present_slot(c, ticket, &sl);
-    if (rc) return rc;
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipEventSynchronize(sl->done));
-    sl->seen = true;
-    *hostPixels = sl->hPixels.ptr;
-    if (bytes) *bytes = sl->bytes;
     return RT_OK;
 }
 
@@ -1173,7 +707,7 @@ int rt_deinterleave(rt_context *c, const void *src, void *dst, int width, int he
     if (((size_t)width * bytesPerPixel) % 4 != 0 || rankStrideBytes % 4 != 0)
         return fail(c, RT_ERR_INVALID_ARG, "row bytes and rank stride must be multiples of 4");
     HIP_TRY(c, hipSetDevice(c->device));
-    hipStream_t s = hipStream ? (hipStream_t)hipStream : c->stream;
+    hipStream_t s = stream_or_own(c, hipStream);
     HIP_TRY(c, rt_launch_deinterleave(src, dst, width, height, bytesPerPixel, stripRows, stripCount, rankStrideBytes, s));
     return RT_OK;
 }
@@ -1185,7 +719,7 @@ int rt_wire_pack(rt_context *c, const void *dColor, const void *dPosition, const
     if (!c) return RT_ERR_INVALID_ARG;
     if (!dColor || !dPosition || !dNormal || !dWire) return fail(c, RT_ERR_INVALID_ARG, "bad wire_pack arguments");
     HIP_TRY(c, hipSetDevice(c->device));
-    hipStream_t s = hipStream ? (hipStream_t)hipStream : c->stream;
+    hipStream_t s = stream_or_own(c, hipStream);
     HIP_TRY(c, rt_launch_wire_pack(dColor, dPosition, dNormal, dWire, nPixels, s));
     return RT_OK;
 }
@@ -1208,7 +742,7 @@ int rt_wire_unpack(rt_context *c, const void *dWire, size_t rankStrideBytes, siz
     if (rankPixels < needPixels || rankStrideBytes % 4 != 0 || rankStrideBytes < rankPixels * 30)
         return fail(c, RT_ERR_INVALID_ARG, "rank buffers too small or misaligned for this strip plan");
     HIP_TRY(c, hipSetDevice(c->device));
-    hipStream_t s = hipStream ? (hipStream_t)hipStream : c->stream;
+    hipStream_t s = stream_or_own(c, hipStream);
     HIP_TRY(c, rt_launch_wire_unpack(dWire, rankStrideBytes, rankPixels, dRootColor, dRootPosition, dRootNormal,
                                      rootStrips * stripRows, dColor, dPosition, dNormal, width, height, stripRows, stripCount, s));
     return RT_OK;

@@ -1,0 +1,99 @@
+// rt_context.h -- what the files that implement context entry points share (rt_abi.cpp, rt_display.cpp): the context itself,
+// the way an entry point reports a failure, and the stream an entry point works on.  Nothing else knows the context's layout
+// (rt_mgpu.cpp drives contexts through the public ABI).  Not part of the public ABI.
+#pragma once
+#include <string>
+#include <vector>
+
+#include "rt_device.h"
+#include "rt_present.h"
+#include "rt_sched.h"
+
+// Everything the context allocates is held by an owner (rt_devbuf.h): after rt_destroy has drained the streams, `delete`
+// releases it all.  The stream comes first so that it goes last.
+struct rt_context {
+    int device = 0;
+    DevStream stream;
+    DevEvent evStart, evStop, evScene;
+    bool timed = false;
+    // raw SSBO bytes + compiled scene
+    DevBuf<uint8_t> dObjects, dLights;
+    DevBuf<float4> dCompiled;
+    int nObj = 0, nLt = 0;
+    bool anyPcss = false;               // some light of the current scene has shadowType 2 (selects the kernel instantiation)
+    // double-buffered pinned staging so rt_set_scene never blocks on the GPU and the caller's
+    // bytes are consumed before it returns (glBufferData semantics)
+    PinnedBuf<uint8_t> hStage[2];
+    DevEvent evStage[2];
+    bool stageUsed[2] = {false, false};
+    unsigned stageSeq = 0;
+    // textures
+    DevBuf<uint8_t> dNoise;
+    int noiseW = 0, noiseH = 0;
+    DevBuf<uint16_t> dSky;
+    int skySize = 0;
+    // context-owned output surfaces
+    DevBuf<float4> dColor, dPos;
+    DevBuf<uint2> dNormal;
+    int surfW = 0, surfH = 0;
+    DevBuf<unsigned long long> dRayCounter;
+    int variant = 1;   // 1 = wavefront-packet kernel (default), 0 = exhaustive per-lane loop
+    unsigned long long lastStats[32] = {};   // rt_count_rays diagnostics (rt_debug_stats)
+    RtTileScheduler sched;                     // tile order of the packet kernel's frames; the record of every stream launches go to
+    DevBuf<uint2> dBloom[2];                   // rgba16f ping-pong targets of rt_bloom
+    DevBuf<float> dSsaoDepth;                  // gPosition.z plane of rt_ssao
+    ScratchUse bloomUse, ssaoUse;              // who ran last in dBloom / dSsaoDepth, on whichever stream
+    // rt_frame: AO result (raw, blurred), TAA history ping-pong, bloom-combined image when the caller passes none
+    DevBuf<float> dFrameAO[2];
+    DevBuf<float4> dHistory[2];
+    DevBuf<float4> dFrameDisplay;
+    int frameW = 0, frameH = 0, lastHistory = -1;
+    bool frameAOValid = false;
+    // shadow tables of the current scene (rt_shadowtab.inc)
+    DevBuf<unsigned> dShadowTab;
+    bool shadowTabValid = false;
+    bool shadowTabBlocker = false;             // the buffer also holds the blocker-ray tables of the scene's PCSS lights
+    std::vector<uint8_t> lastScene;            // the bytes of the current scene (objects, then lights): an identical re-upload is a no-op
+    bool stOnePhase = false;                   // RT_ST_BUILD=full: the one-phase builder (every object in every cell; comparison builds only)
+    RtShadowTabGeom stGeomSmall = {48, 96, 32}, stGeomLarge = {32, 64, 32};      // <= 32 objects / more (RT_ST_GEOM overrides both); measured: DESIGN.md
+    unsigned sceneGen = 0, texGen = 0;         // bumped by rt_set_scene / rt_set_noise / rt_set_skybox / rt_equirect_to_cubemap
+    // rt_pick: the hit record on the device and its pinned host copy
+    DevBuf<float4> dPick;
+    PinnedBuf<rt_hit> hPick;
+    PresentRing present;                       // rt_present_*: the frames on their way to the host (rt_present.h)
+    std::string err;
+};
+
+inline int fail(rt_context *c, int code, const char *what, hipError_t e = hipSuccess) {
+    if (c) {
+        c->err = what;
+        if (e != hipSuccess) {
+            c->err += ": ";
+            c->err += hipGetErrorString(e);
+        }
+    }
+    return code;
+}
+
+#define HIP_TRY(c, call)                                        \
+    do {                                                        \
+        hipError_t e_ = (call);                                 \
+        if (e_ != hipSuccess) return fail(c, RT_ERR_HIP, #call, e_); \
+    } while (0)
+
+// a call of the scheduler's: the error string names the HIP call that failed inside it
+#define SCHED_TRY(c, call)                                      \
+    do {                                                        \
+        hipError_t e_ = (c)->sched.call;                        \
+        if (e_ != hipSuccess) return fail(c, RT_ERR_HIP, (c)->sched.failedCall, e_); \
+    } while (0)
+
+// a call of the present ring's: the ring says what was refused, or which HIP call failed inside it
+#define PRESENT_TRY(c, call)                                    \
+    do {                                                        \
+        int rc_ = (c)->present.call;                            \
+        if (rc_) return fail(c, rc_, (c)->present.failed, (c)->present.failedHip); \
+    } while (0)
+
+// the ABI's `void *hipStream`: the caller's stream, or the context's own when it is NULL
+inline hipStream_t stream_or_own(const rt_context *c, void *hipStream) { return hipStream ? (hipStream_t)hipStream : c->stream.s; }

@@ -62,3 +62,20 @@ struct DevStream {
     operator hipStream_t() const { return s; }
     hipError_t create() { return s ? hipSuccess : hipStreamCreateWithFlags(&s, hipStreamNonBlocking); }
 };
+
+// Last use of a context-owned scratch that post passes on any stream work in (rt_bloom's ping-pong targets, rt_ssao's depth
+// plane).  The scratch is one per context, so its users run one after another: a pass orders its stream behind the previous
+// use (acquire), launches, and records its own (release).  Every use waits for the one before it, so the event of the last
+// one stands for all of them: the host waits on it alone before the scratch is freed (drain).  Nothing here blocks the host
+// in steady state; behind a use on the same stream the wait is already met by stream order.
+struct ScratchUse {
+    DevEvent ev;
+    bool used = false;
+    hipError_t create() { return ev.create(hipEventDisableTiming); }
+    hipError_t acquire(hipStream_t s) { return used ? hipStreamWaitEvent(s, ev, 0) : hipSuccess; }
+    hipError_t release(hipStream_t s) {
+        used = true;
+        return hipEventRecord(ev, s);
+    }
+    hipError_t drain() { return used ? hipEventSynchronize(ev) : hipSuccess; }
+};

@@ -1,5 +1,5 @@
-// rt_device.h -- shared declarations between the HIP kernels (rt_kernels.hip) and the
-// C-ABI implementation (rt_abi.cpp).  Not part of the public ABI.
+// rt_device.h -- shared declarations between the HIP kernels (rt_kernels.hip, rt_post.hip) and the
+// C-ABI implementation (rt_abi.cpp).  The display path's are in rt_display.h.  Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -78,7 +78,7 @@ static inline size_t rt_compiled_f4(int nObj, int nLt) {
     return (size_t)nObj * (RT_HOT_F4 + RT_MAT_F4) + (size_t)nLt * RT_LGT_F4 + 2 * (RT_HALTON_N / 4);
 }
 
-// Launch wrappers implemented in rt_kernels.hip
+// Launch wrappers implemented in rt_kernels.hip (the post passes': rt_post.hip)
 hipError_t rt_launch_compile_scene(const uint8_t *dObjects, int nObj, const uint8_t *dLights, int nLt,
                                    float4 *dCompiled, hipStream_t s);
 hipError_t rt_launch_render(const RtFrame &f, const RtDeviceScene &sc, float4 *dColor, float4 *dPos,
@@ -99,24 +99,6 @@ hipError_t rt_launch_ssao_blur(const void *in, void *out, int W, int H, int hori
 hipError_t rt_launch_equirect_to_cubemap(const float *dRgb, void *dTex, int W, int H, int S, void *dFaces, hipStream_t s);
 hipError_t rt_launch_bloom(const void *scene, void *tmpA, void *tmpB, void *out, int W, int H, float threshold, float strength,
                            int iterations, hipStream_t s);
-// rgba32f -> RGBA8 (rt_post.hip); `out` rows tightly packed, both pointers 16-byte aligned, W * H below 2^32 quads of 4 pixels
-hipError_t rt_launch_display_pack(const void *image, void *out, int W, int H, int srgb, int flip, float exposure, hipStream_t s);
-const float *rt_display_thresholds();      // the 256 sRGB decision thresholds ([0] = 0), built on the host on first use
-// the same pack behind a tone curve (0 none, 1 Reinhard with invW2 = 1 / white^2, 2 ACES) and, when dExposure is not NULL, with the
-// exposure multiplied by that device float; (0, NULL) is rt_launch_display_pack
-hipError_t rt_launch_display_pack_toned(const void *image, void *out, int W, int H, int srgb, int flip, float exposure, int tone,
-                                        float invW2, const void *dExposure, hipStream_t s);
-// rgba32f -> NV12 (i420 = 0) or I420 (rt_post.hip): the toned pack's codes behind the integer matrix coef[12] of
-// rt_display_yuv_coeffs; `out` holds W * H + 2 * ((W + 1) / 2) * ((H + 1) / 2) bytes, both pointers 16-byte aligned.
-// rt_display_yuv_blocks: the lanes such a launch needs; above 0xffffff00 the frame is refused
-hipError_t rt_launch_display_pack_yuv(const void *image, void *out, int W, int H, int i420, int srgb, int flip, float exposure, int tone,
-                                      float invW2, const void *dExposure, const int *coef, hipStream_t s);
-unsigned long long rt_display_yuv_blocks(int W, int H);
-// rt_meter (rt_post.hip): clear, histogram, solve -- three operations on s; state = one rt_meter_state, nPixels <= 2^31 - 1
-hipError_t rt_launch_meter(const void *image, void *state, unsigned nPixels, float key, float minExposure, float maxExposure, float adapt,
-                           int lowPermille, int highPermille, hipStream_t s);
-struct RtMeterTables;
-const RtMeterTables &rt_meter_tables_ref();     // the solve's two tables (rt_meter.h), built on the host on first use
 hipError_t rt_launch_wire_pack(const void *dColor, const void *dPos, const void *dNormal, void *dWire, size_t nPixels,
                                hipStream_t s);
 hipError_t rt_launch_wire_unpack(const void *dWire, size_t rankStrideBytes, size_t rankPixels, const void *dRootColor,

@@ -1,7 +1,7 @@
 // rt_meter.h -- the solve of rt_meter (include/rt_mi355.h has the definition): histogram of log-luminance bins ->
 // trimmed mean -> target exposure -> adapted exposure.  Written once for host and device, in the style of
-// rt_mesa_math.h: the device runs its pieces as rt_meter_solve_kernel behind the histogram kernel (rt_post.hip), the
-// host runs them as rt_meter_solve_host (rt_abi.cpp), which tests/test_meter_host.py pins to a numpy / Python-int
+// rt_mesa_math.h: the device runs its pieces as rt_meter_solve_kernel behind the histogram kernel (rt_display.hip), the
+// host runs them as rt_meter_solve_host (rt_display.cpp), which tests/test_meter_host.py pins to a numpy / Python-int
 // restatement and tests/test_meter.py compares the device with.  Integer arithmetic and single fp32 operations only
 // (-ffp-contract=off on both sides): no transcendental runs on the device, the two tables come from the host.
 #pragma once

@@ -1,4 +1,4 @@
-// rt_sched.h -- the packet kernel's tile scheduler, held by value in rt_context (rt_abi.cpp).  It keeps the record of every
+// rt_sched.h -- the packet kernel's tile scheduler, held by value in rt_context (rt_context.h).  It keeps the record of every
 // stream a launch has been issued on (the stream protocol that renders, queries, shading and the scene / texture setters share)
 // and decides the tile order of each frame: begin() before rt_launch_render, end() after it.  Not part of the public ABI.
 #pragma once

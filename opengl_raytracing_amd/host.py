@@ -382,6 +382,10 @@ def _query_mode(mode):
 
 
 # ---- the device context ---------------------------------------------------------------------
+# what the Python side remembers of a present_submit* ticket: "rgba8" or "yuv", the frame's size, the description's format
+_PresentTicket = collections.namedtuple("_PresentTicket", "kind width height format")
+
+
 class RayTracer:
     def __init__(self, device=0):
         self.lib = load_library()
@@ -391,6 +395,7 @@ class RayTracer:
             self.ctx = None
             raise RtError(rc, "rt_create (is a HIP device present?)")
         self._region = None
+        self._present_tickets = {}                    # ticket -> _PresentTicket, for present_wait / present_wait_yuv
         v = int(os.environ.get("RT_VARIANT", "-1"))   # A/B switch for measurements and tests
         if v >= 0:
             self.set_variant(v)
@@ -692,10 +697,7 @@ class RayTracer:
             td = L.make_tone_desc(tone or "none", white, d_exposure)
             self._on_torch_stream(stream, lambda h: self._check(self.lib.rt_present_submit_toned(
                 self.ctx, _dev_ptr(d_image), ctypes.byref(d), ctypes.byref(td), ctypes.c_void_p(h), ctypes.byref(t)), "rt_present_submit_toned"))
-        self._present_shapes = getattr(self, "_present_shapes", {})
-        self._present_shapes[t.value] = (int(height), int(width))
-        for old in [k for k in self._present_shapes if k + 16 <= t.value]:     # (more than any ring holds)
-            del self._present_shapes[old]
+        self._present_issued(t.value, "rgba8", width, height, d.format)
         return t.value
 
     def present_poll(self, ticket):
@@ -708,13 +710,25 @@ class RayTracer:
         """Block until the frame of `ticket` is in host memory -> uint8 [height, width, 4].  copy=False returns a read-only
         view of the ring's pinned slot instead: valid until the present_submit that returns ticket + slots (or
         present_configure, or close()), after which its memory is rewritten or gone -- copy what must outlive that."""
-        p, n = ctypes.c_void_p(), ctypes.c_size_t(0)
-        if int(ticket) in getattr(self, "_present_yuv", {}):
+        rec = self._present_tickets.get(int(ticket))
+        if rec is not None and rec.kind == "yuv":
             raise ValueError(f"ticket {int(ticket)} is a YUV frame (present_submit_yuv): wait for it with present_wait_yuv")
+        view = self._present_pinned(ticket, copy)
+        rec = self._present_tickets[int(ticket)]
+        assert view.size == rec.height * rec.width * 4
+        return view.reshape(rec.height, rec.width, 4)
+
+    def _present_issued(self, ticket, kind, width, height, format):
+        """Remember what `ticket` holds; forget the tickets no ring can still hold (one rule: 16 back, twice the largest ring)."""
+        self._present_tickets[ticket] = _PresentTicket(kind, int(width), int(height), format)
+        for old in [k for k in self._present_tickets if k + 16 <= ticket]:
+            del self._present_tickets[old]
+
+    def _present_pinned(self, ticket, copy):
+        """rt_present_wait -> the ticket's bytes, uint8 [n]: a copy, or a read-only view of the ring's pinned slot."""
+        p, n = ctypes.c_void_p(), ctypes.c_size_t(0)
         self._check(self.lib.rt_present_wait(self.ctx, int(ticket), ctypes.byref(p), ctypes.byref(n)), "rt_present_wait")
-        h, w = self._present_shapes[int(ticket)]
-        assert n.value == h * w * 4
-        view = np.frombuffer((ctypes.c_uint8 * n.value).from_address(p.value), dtype=np.uint8).reshape(h, w, 4)
+        view = np.frombuffer((ctypes.c_uint8 * n.value).from_address(p.value), dtype=np.uint8)
         if copy:
             return view.copy()
         view.flags.writeable = False
@@ -742,29 +756,19 @@ class RayTracer:
         self._on_torch_stream(stream, lambda h: self._check(self.lib.rt_present_submit_yuv(
             self.ctx, _dev_ptr(d_image), ctypes.byref(d), ctypes.byref(td) if td is not None else None, ctypes.c_void_p(h), ctypes.byref(t)),
             "rt_present_submit_yuv"))
-        self._present_yuv = getattr(self, "_present_yuv", {})
-        self._present_yuv[t.value] = (int(width), int(height), d.format)
-        for old in [k for k in self._present_yuv if k + 16 <= t.value]:         # (more than any ring holds)
-            del self._present_yuv[old]
-        getattr(self, "_present_shapes", {}).pop(t.value, None)
+        self._present_issued(t.value, "yuv", width, height, d.format)
         return t.value
 
     def present_wait_yuv(self, ticket, copy=True):
         """Block until the YUV frame of `ticket` is in host memory -> (y[H, W], uv[ch, cw, 2]) for NV12, (y[H, W], cb[ch, cw],
         cr[ch, cw]) for I420, uint8.  copy=False returns read-only views of the ring's pinned slot (present_wait's rules)."""
-        if int(ticket) not in getattr(self, "_present_yuv", {}):
+        rec = self._present_tickets.get(int(ticket))
+        if rec is None or rec.kind != "yuv":
             raise ValueError(f"ticket {int(ticket)} is not a live YUV frame of present_submit_yuv (RGBA8 tickets: present_wait)")
-        p, n = ctypes.c_void_p(), ctypes.c_size_t(0)
-        self._check(self.lib.rt_present_wait(self.ctx, int(ticket), ctypes.byref(p), ctypes.byref(n)), "rt_present_wait")
-        w, h, fmt = self._present_yuv[int(ticket)]
-        if n.value != yuv_layout(w, h, fmt).bytes:
-            raise RtError(-1, f"ticket {int(ticket)} holds {n.value} bytes, not a {w}x{h} YUV frame")
-        frame = np.frombuffer((ctypes.c_uint8 * n.value).from_address(p.value), dtype=np.uint8)
-        if copy:
-            frame = frame.copy()
-        else:
-            frame.flags.writeable = False
-        return yuv_planes(frame, w, h, fmt)
+        frame = self._present_pinned(ticket, copy)
+        if frame.size != yuv_layout(rec.width, rec.height, rec.format).bytes:
+            raise RtError(-1, f"ticket {int(ticket)} holds {frame.size} bytes, not a {rec.width}x{rec.height} YUV frame")
+        return yuv_planes(frame, rec.width, rec.height, rec.format)
 
     def tile_costs(self):
         """(costs[tilesY, tilesX] uint32, cycles/64 per tile) of the last feedback-scheduled launch."""

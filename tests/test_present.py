@@ -352,3 +352,32 @@ def test_refusals_leave_the_context_usable(ring, table):
     assert lib.rt_present_wait(ctx, 0, None, ctypes.byref(nb)) == INVALID
     assert (ring.present_wait(t) == want).all()
     still_works()
+
+
+# ---- 10. the ring drains itself ----------------------------------------------------------------------------------------------------------
+def test_close_with_frames_in_flight(host, table):
+    """Three frames submitted on a side stream to a fresh 3-slot ring -- two 67x9 RGBA8 (ragged quads, odd height), one 16x4 NV12 --
+    and none waited for: close() has to drain the copy stream before the ring's buffers go.  The next context starts over at
+    ticket 0 and delivers the right bytes."""
+    import torch
+    rng = np.random.default_rng(10)
+    w, h = 67, 9
+    frames = [hdr_image(rng, w, h), hdr_image(rng, w, h), hdr_image(rng, 16, 4)]
+    d = [up(f) for f in frames]
+    first = host.RayTracer(0)
+    try:
+        first.present_configure(3)
+        s = torch.cuda.Stream()
+        assert first.present_submit(d[0], w, h, format="srgb", flip=True, stream=s) == 0
+        assert first.present_submit(d[1], w, h, format="linear", exposure=0.37, stream=s) == 1
+        assert first.present_submit_yuv(d[2], 16, 4, format="nv12", stream=s) == 2
+    finally:
+        first.close()
+    second = host.RayTracer(0)
+    try:
+        t = second.present_submit(d[1], w, h, format="srgb", exposure=2.5, stream=s)
+        assert t == 0
+        assert (second.present_wait(t) == pack_oracle(frames[1], "srgb", False, 2.5, table)).all()
+    finally:
+        second.close()
+    s.synchronize()
