@@ -91,18 +91,15 @@ struct SceneLds {
     const float *halton3;  // RT_HALTON_N
     unsigned long long *stats = nullptr;   // diagnostic counters (instrumented build only)
     const float4 *global = nullptr;        // the same records in global memory (scalar-load path)
-    float *park = nullptr;                 // per-thread LDS parking area, RT_PARK_FLOATS floats x BLOCK_THREADS (packet kernel)
+    float *park = nullptr;                 // per-thread LDS parking area, PK_PARK_FLOATS floats x 64 lanes (packet kernel)
     int tileX = 0, tileY = 0;              // this workgroup's tile (packet kernel; wave-uniform)
     int lgtF4Base = 0, haltonFloatBase = 0;   // offsets of the light / Halton sections (float4 / float units)
-    // Compact staging (packet kernel, scenes too large to keep whole in LDS at full occupancy): LDS holds only
-    // the two bounds float4 of every object (stride 2); shape / material records read per lane by hit index come
-    // from the global copy.  hotStride = float4 stride of `hot`, matF4Base = material section in `global`.
-    bool compact = false;
+    // Packet kernel: LDS holds at most the two bounds float4 of every object (hotStride 2); shape / material records read
+    // per lane by hit index come from the global copy.  hotStride = float4 stride of `hot`, matF4Base = material section in `global`.
+    bool compact = false;       // shape / material records by hit index come from the global copy (pk_lane_hot / pk_lane_mat)
     bool boundsLds = true;      // packet kernel profile: the cull passes' per-lane AABB reads come from LDS (else from the global copy)
-    bool wedge = false;         // packet kernel profile: convergent-packet cull of point / area light shadow rays
     int straight = 0;           // packet kernel profile: which candidate loops use the predicate-algebra tests (rt_packet.inc RT_PK_STRAIGHT)
-    bool split = false;         // packet kernel profile: octant-split culling of sign-straddling packets
-    bool keepAabb = true;       // packet kernel profile: chunk 0's AABB lives in the lane's VGPRs (else re-read from LDS per cull pass)
+    bool split = false;         // packet kernel profile: octant-split culling of sign-straddling light packets
     int hotStride = RT_HOT_F4, matF4Base = 0;
     int pcfTabF4 = -1;          // float4 index in `global` of the directional lights' PCF ray tables, -1 = not usable (noise bound)
     const unsigned *stab = nullptr;        // shadow tables (rt_shadowtab.inc): per-light headers, then the cells
@@ -740,37 +737,27 @@ __global__ RT_V0_BOUNDS void rt_render_kernel(const RtFrame f, const RtDeviceSce
 //                                                     C2       C3      C4      C5
 //   round 1 shapes (whole scene in LDS, 4 waves/SIMD)  0.459    5.27    8.25    48.4   (after the fast 1/x, sqrt paths)
 //   LIGHT / HEAVY profiles                             0.404    4.84    8.15    43.2
-#ifndef RT_PK_WAVES_SMALL
-#define RT_PK_WAVES_SMALL 5
-#endif
-#ifndef RT_PK_LIGHT_SCENE
-#define RT_PK_LIGHT_SCENE 32    // objects: at or below, the LIGHT profile
-#endif
+// BT and COMPACT are 64 and true in every instantiation; the parameters stay because the kernels' names carry them.
 template <int COUNT, int BT, bool COMPACT, typename PROFILE>
 __global__ __launch_bounds__(BT, PROFILE::waves)
 void rt_render_packet_kernel(const RtFrame f, const RtDeviceScene dsc, float4 *__restrict__ gColor,
                              float4 *__restrict__ gPosition, uint2 *__restrict__ gNormal,
                              unsigned long long *rayCounter) {
+    static_assert(BT == 64 && COMPACT, "one-wave workgroups, only the AABBs staged in LDS");
     extern __shared__ float4 lds[];
     const int nAll = f.nObj * (RT_HOT_F4 + RT_MAT_F4) + f.nLt * RT_LGT_F4 + 2 * (RT_HALTON_N / 4);
-    const int nF4 = !PROFILE::boundsLds ? 0 : (COMPACT ? f.nObj * 2 : nAll);          // float4 staged in LDS
-    if (COMPACT) {
-        for (int i = threadIdx.x; i < nF4; i += BT) lds[i] = dsc.compiled[(i >> 1) * RT_HOT_F4 + (i & 1)];
-    } else {
-        for (int i = threadIdx.x; i < nF4; i += BT) lds[i] = dsc.compiled[i];
-    }
+    const int nF4 = PROFILE::boundsLds ? f.nObj * 2 : 0;          // float4 staged in LDS: the objects' two bounds float4
+    for (int i = threadIdx.x; i < nF4; i += BT) lds[i] = dsc.compiled[(i >> 1) * RT_HOT_F4 + (i & 1)];
     __syncthreads();
     SceneLds sc;
-    sc.compact = COMPACT;
-    sc.keepAabb = PROFILE::keepAabb;
+    sc.compact = true;
     sc.boundsLds = PROFILE::boundsLds;
     sc.straight = PROFILE::straight;
     sc.split = PROFILE::split;
-    sc.wedge = PROFILE::wedge;
-    sc.hotStride = COMPACT ? 2 : RT_HOT_F4;
+    sc.hotStride = 2;
     sc.matF4Base = f.nObj * RT_HOT_F4;
     sc.hot = lds;
-    sc.mat = sc.hot + f.nObj * RT_HOT_F4;                  // (not staged, never read through LDS, when COMPACT)
+    sc.mat = sc.hot + f.nObj * RT_HOT_F4;                  // (not staged, never read through LDS)
     sc.lgt = sc.mat + f.nObj * RT_MAT_F4;
     sc.halton2 = (const float *)(sc.lgt + f.nLt * RT_LGT_F4);
     sc.halton3 = sc.halton2 + RT_HALTON_N;
@@ -783,8 +770,7 @@ void rt_render_packet_kernel(const RtFrame f, const RtDeviceScene dsc, float4 *_
     sc.stab = dsc.shadowTab;
 
     // tile of this workgroup: longest-first order from the previous frame's measured costs, if any
-    constexpr int TILE_ = (BT == 256) ? 16 : 8;
-    const int tilesX = (f.p.regionW + TILE_ - 1) / TILE_;
+    const int tilesX = (f.p.regionW + 7) / 8;
     const unsigned tile = dsc.tileOrder ? dsc.tileOrder[blockIdx.x] : blockIdx.x;
     // an order buffer is a permutation of [0, gridDim.x) by construction (identity-initialised, rewritten only by
     // rt_lpt_sort_kernel); the guard keeps a corrupted entry from turning into out-of-bounds tileCost / surface writes
@@ -1087,26 +1073,26 @@ hipError_t rt_launch_render(const RtFrame &f, const RtDeviceScene &sc, float4 *d
         const bool light = bt == 64 && f.nObj <= RT_PK_LIGHT_SCENE && !(f.nObj > 0 && f.nLt > 0 && !sc.shadowTab);
         // LDS: the AABBs (2 float4 per object) + the 16-byte counter slot + the profile's parking area
         const size_t ldsBytes = ((size_t)((light || PkHeavy::boundsLds) ? f.nObj * 2 : 0) + 1) * sizeof(float4) +
-                                (size_t)(light ? PkLight::parkFloats : PkHeavy::parkFloats) * bt * sizeof(float);
-#define RT_LAUNCH_PK(BT_, PROFILE_)                                                                                                   \
+                                (size_t)PK_PARK_FLOATS * bt * sizeof(float);
+#define RT_LAUNCH_PK(PROFILE_)                                                                                                        \
         do {                                                                                                                          \
-            if (dRayCounter && countMode == 2) hipLaunchKernelGGL((rt_render_packet_kernel<2, BT_, true, PROFILE_>), grid, dim3(BT_), ldsBytes, s, f, sc, dColor, dPos, dNormal, dRayCounter); \
-            else if (dRayCounter) hipLaunchKernelGGL((rt_render_packet_kernel<1, BT_, true, PROFILE_>), grid, dim3(BT_), ldsBytes, s, f, sc, dColor, dPos, dNormal, dRayCounter);            \
-            else hipLaunchKernelGGL((rt_render_packet_kernel<0, BT_, true, PROFILE_>), grid, dim3(BT_), ldsBytes, s, f, sc, dColor, dPos, dNormal, dRayCounter);                             \
+            if (dRayCounter && countMode == 2) hipLaunchKernelGGL((rt_render_packet_kernel<2, 64, true, PROFILE_>), grid, dim3(64), ldsBytes, s, f, sc, dColor, dPos, dNormal, dRayCounter); \
+            else if (dRayCounter) hipLaunchKernelGGL((rt_render_packet_kernel<1, 64, true, PROFILE_>), grid, dim3(64), ldsBytes, s, f, sc, dColor, dPos, dNormal, dRayCounter);            \
+            else hipLaunchKernelGGL((rt_render_packet_kernel<0, 64, true, PROFILE_>), grid, dim3(64), ldsBytes, s, f, sc, dColor, dPos, dNormal, dRayCounter);                             \
         } while (0)
         // scenes without shadow tables (more than RT_ST_MAX_OBJECTS objects or RT_ST_MAX_LIGHTS lights: rt_set_scene builds none)
         // run the profile that finds the lights' candidates per packet
         const bool noTab = PkLight::tabWords > 0 && f.nObj > 0 && f.nLt > 0 && (!sc.shadowTab || f.nObj > RT_ST_MAX_OBJECTS);
         if (f.anyPcss) {
-            if (noTab) RT_LAUNCH_PK(64, PkHugeS);
-            else if (light) RT_LAUNCH_PK(64, PkLightS);
-            else if (f.nObj <= 64) RT_LAUNCH_PK(64, PkHeavy1S);
-            else RT_LAUNCH_PK(64, PkHeavyS);
+            if (noTab) RT_LAUNCH_PK(PkHugeS);
+            else if (light) RT_LAUNCH_PK(PkLightS);
+            else if (f.nObj <= 64) RT_LAUNCH_PK(PkHeavy1S);
+            else RT_LAUNCH_PK(PkHeavyS);
         } else {
-            if (noTab) RT_LAUNCH_PK(64, PkHuge);
-            else if (light) RT_LAUNCH_PK(64, PkLight);
-            else if (f.nObj <= 64) RT_LAUNCH_PK(64, PkHeavy1);
-            else RT_LAUNCH_PK(64, PkHeavy);
+            if (noTab) RT_LAUNCH_PK(PkHuge);
+            else if (light) RT_LAUNCH_PK(PkLight);
+            else if (f.nObj <= 64) RT_LAUNCH_PK(PkHeavy1);
+            else RT_LAUNCH_PK(PkHeavy);
         }
 #undef RT_LAUNCH_PK
     } else {

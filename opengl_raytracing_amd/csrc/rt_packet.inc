@@ -18,29 +18,24 @@
 //      intersectAABB could pass, so results are bit-identical to the exhaustive loop.
 //      Packets with NaNs, non-finite bounds or mixed-sign / zero direction components on an
 //      axis simply lose that axis' constraint (or all culling).
-//   3. Each lane keeps "its" object's AABB in registers for the first 64 objects (the common
-//      case: one cull pass = ~66 VALU instructions, no memory access); larger scenes stream
-//      further 64-object chunks from LDS.
-
-// PCF samples per group (a profile constant, see below): GROUPN rays are set up together and every candidate record is fetched
-// once for the group (more ILP, fewer scalar loads, +~25 VGPRs per extra ray); 4 costs too many registers.
+//   3. NO OBJECT DATA LIVES IN REGISTERS ACROSS THE KERNEL.  Every cull pass reads the lane's object's AABB again (pk_bounds: from
+//      LDS in the LIGHT profile, from the global copy -- L1 / L2 hits -- in the others), 64 objects per pass.  Round 1 kept the
+//      first chunk's AABB in 8 VGPRs per lane; the registers were worth more as occupancy (DESIGN.md section 4).
+//
 // Kernel PROFILES (template constants, chosen per scene size by the launcher; measured in DESIGN.md section 4).  The kernel is
-// latency-bound, so what a profile really trades is VGPRs (= resident waves) against re-reads and LDS per wave.  Both profiles
-// run 5 waves/SIMD at 96 VGPRs with the shading point (P, N, V, material) parked in LDS while a light's shadow rays are traced
-// (23 floats/lane) and the lane's own AABB re-read per cull pass instead of living in 8 VGPRs:
-//   LIGHT (<= RT_PK_LIGHT_SCENE objects): AABBs staged in LDS (<= 1 KB), PCF rays one at a time -- no scratch at all;
+// latency-bound, so what a profile really trades is VGPRs (= resident waves) against re-reads and LDS per wave.  Every profile
+// keeps the path state a bounce only touches at its ends and the shading point (P, N, V, material) in a per-lane LDS parking
+// area (PK_PARK_FLOATS floats / lane) while a light's shadow rays are traced:
+//   LIGHT (<= RT_PK_LIGHT_SCENE objects): AABBs staged in LDS (<= 1 KB), PCF rays four at a time -- no scratch at all;
 //   HEAVY (more objects): PCF rays in pairs (each candidate record fetched once per pair: with 15-50 candidates per packet
 //         that beats one at a time by 8-14 %), the cull passes read the AABBs from the GLOBAL copy (L1 / L2 hits) -- a per-wave
-//         LDS copy of 256 objects' AABBs (8 KB) capped occupancy at 2.5 waves/SIMD -- and sign-straddling packets are culled
-//         per direction octant (pk_ray_mask).
-#ifndef RT_PK_RESIDENT
-#define RT_PK_RESIDENT 1    // (profile constant `resident`) the path state a bounce only touches at its ends -- finalColor, throughput, the last hit's P and N -- LIVES in
-                            // the parking area (read-modify-write where it changes) instead of travelling between registers and LDS: it is
-                            // no longer live across the closest-hit traversal and the loop's back edge, which is where the compiler spilled
-                            // (6 scratch stores per bounce at the loop header: two thirds of C2's scratch traffic).  Measured, bit-identical:
-                            // scratch 96 -> 0 B/lane in LIGHT (C2 0.360 -> 0.353 ms), 156 -> 60 in HEAVY1 (C4 unchanged), 164 -> 68 in
-                            // HEAVY (C5 25.5 -> 26.0 ms: +2 % for 2.4x less scratch traffic, which the paired subsurface probes it makes
-                            // room for win back: 25.4 ms)
+//         LDS copy of 256 objects' AABBs (8 KB) capped occupancy at 2.5 waves/SIMD.  A light's candidates come from its shadow
+//         table (rt_shadowtab.inc); scenes beyond the tables (HUGE) use the packet-level masks and the per-lane shape level.
+//
+// ---- tunables: one macro each, re-tryable with -D (which side wins has flipped with the compiler's behaviour before: DESIGN.md
+// section 4 item 36).  Alternatives that were structurally dead or superseded are gone (DESIGN.md section 18).
+#ifndef RT_PK_LIGHT_SCENE
+#define RT_PK_LIGHT_SCENE 32    // objects: at or below, the LIGHT profile (rt_launch_render)
 #endif
 #ifndef RT_PK_STRAIGHT
 #define RT_PK_STRAIGHT 12   // (profile constant `straight` of the LIGHT profile; bits: 1 closest-hit, 2 any-hit, 4 PCF pair loop, 8 PCF
@@ -52,18 +47,6 @@
                             // in the few-object profile's PCF loops: C2 0.3465 -> 0.3218 ms with bits 4 / 12, 0.3236 with all four
                             // (the closest-hit and any-hit traversals gain nothing).  PCSS (C3 +0.7 % with 15) and the many-object
                             // profiles (all four: C4 +1.1 %, C5 +1.9 %; closest-hit only: +-0) keep the nested form.
-#ifndef RT_LIGHTS_STRAIGHT
-#define RT_LIGHTS_STRAIGHT 0
-#endif
-#ifndef RT_HEAVY_STRAIGHT
-#define RT_HEAVY_STRAIGHT 0
-#endif
-#ifndef RT_HEAVY_BLOCKER_TAB
-#define RT_HEAVY_BLOCKER_TAB 1   // ... and the many-object PCSS profiles (2 / 8 dwords per cell)
-#endif
-#ifndef RT_PK_BLOCKER_TAB
-#define RT_PK_BLOCKER_TAB 1      // PkLightS: pcssShadow's blocker rays take their candidates from the lights' blocker tables (rt_shadowtab.inc)
-#endif
 #ifndef RT_LIGHT_FAST_PBR
 #define RT_LIGHT_FAST_PBR 1     // computePBR's nine divisions through rt_fastmath.h's shared-reciprocal quotients (compute_pbr, rt_kernels.hip).
 #endif                          // With the SLP vectorizer on it was a loss in LIGHT (C2 0.347 -> 0.367 ms, C3 3.39 -> 3.44) and a gain in HEAVY
@@ -71,39 +54,17 @@
 #ifndef RT_HEAVY_FAST_PBR
 #define RT_HEAVY_FAST_PBR 1
 #endif
-#ifndef RT_PK_HIT_BATCH
-#define RT_PK_HIT_BATCH 1               // the hit object's records requested as one batch of gathers (render_packet)
+#ifndef RT_LIGHT_GROUPN
+#define RT_LIGHT_GROUPN 4       // PCF samples per traversal in the LIGHT profile: GROUPN rays are set up together and every candidate record is
+                                // fetched once for the group (more ILP, fewer scalar loads, +~25 VGPRs per extra ray).  C2: 0.402 ms one at a
+                                // time, 0.383 in pairs (92 B/lane of cold scratch; 0.4065 at 4 waves/SIMD without any), 0.449 in fours; round 2's
+                                // first attempt at pairs was 8 % SLOWER -- where the allocator puts the spills decides, and that moved with the
+                                // surrounding code.  Built without the SLP vectorizer fours fit 96 VGPRs without scratch: C2 0.298 -> 0.294 ms
+                                // on top of the probes in fours
 #endif
-#ifndef RT_PK_REACH
-#define RT_PK_REACH 1                   // per-lane second cull level for a light's PCF rays (pk_pcf_shadow): 0 the AABB interval test from 8
-                                        // samples on, 1 spheres on their shape from 3 samples on, 2 the same + non-spheres on their AABB
+#ifndef RT_HEAVY_GROUPN
+#define RT_HEAVY_GROUPN 2       // ... in the HEAVY profiles: pairs (4 costs too many registers there)
 #endif
-#ifndef RT_HEAVY_WAVES
-#define RT_HEAVY_WAVES 6        // the multi-chunk HEAVY profile is compiled for 6 waves/SIMD (80 VGPRs): after the shape level the loops are short and
-#endif                          // latency-bound again, a sixth wave buys C5 36.0 -> 34.5 ms (for 56 B/lane more cold scratch); LIGHT and HEAVY1 stay at 5
-#ifndef RT_HEAVY_HIT_BATCH
-#define RT_HEAVY_HIT_BATCH 0    // HEAVY: the hit records one after the other again.  With the per-lane shape level in place (RT_PK_REACH) the batch
-#endif                          // form and the octant split lost their edge: C4 6.40 -> 6.26 ms, C5 36.9 -> 35.8 ms and 32-36 B/lane less scratch without both
-#ifndef RT_HEAVY_RELOAD
-#define RT_HEAVY_RELOAD 0
-#endif
-#ifndef RT_LIGHT_REACH
-#define RT_LIGHT_REACH 0                // ... in the LIGHT profile: C2 0.385 ms without, 0.447 with (3 candidates per packet: nothing to prune)
-#endif
-#ifndef RT_PK_REACH_MIN_SAMPLES
-#define RT_PK_REACH_MIN_SAMPLES 3
-#endif
-#ifndef RT_PK_CONE_MIN_SAMPLES
-#define RT_PK_CONE_MIN_SAMPLES 8        // non-spheres: interval slab test of the AABB per lane, from this many samples on
-#endif
-#ifndef RT_PK_WAVES_SMALL
-#define RT_PK_WAVES_SMALL 5     // resident waves per SIMD the packet kernels are compiled for (96 VGPRs)
-#endif
-// reloadLight (profile constant): fetch the light's colour / intensity again after its shadow rays instead of carrying 8 SGPRs across
-// them.  Scalar pressure decides these kernels -- 55-110 SGPRs are spilled to VGPR lanes, and a loop that has to v_readlane its
-// operands back every trip is what a slow build looks like (tools/isa_loops.py) -- but which build the allocator produces is not
-// monotone in the pressure, so the switch is set per instantiation by measurement: C4 (PkHeavy1) 8.20 -> 7.76 ms, C3 (PkLightS)
-// 3.52 -> 3.49, C2 (PkLight) unchanged, C5 (PkHeavy) 39.1 -> 43.9 (off there).
 #ifndef RT_LIGHT_SSS_GROUP
 #define RT_LIGHT_SSS_GROUP 4    // subsurface probe rays per traversal (pk_trace_closest_group): 1, 2 or 4.  Round 2 (registers full): C2 0.385 / 0.403 / 0.453 ms;
                                 // with the path state resident in LDS (round 3) pairs won: C2 0.352 -> 0.347 ms; built without the SLP vectorizer
@@ -112,92 +73,131 @@
 #ifndef RT_HEAVY_SSS_GROUP
 #define RT_HEAVY_SSS_GROUP 2    // (round 3, path state resident in LDS: C5 26.1 -> 25.4 ms, C4 unchanged)
 #endif
-#ifndef RT_LIGHT_GROUPN
-#define RT_LIGHT_GROUPN 4       // PCF samples per traversal in the LIGHT profile.  C2: 0.402 ms one at a time, 0.383 in pairs (92 B/lane of
-                                // cold scratch; 0.4065 at 4 waves/SIMD without any), 0.449 in fours; round 2's first attempt at pairs was 8 %
-                                // SLOWER -- where the allocator puts the spills decides, and that moved with the surrounding code.  Built
-                                // without the SLP vectorizer fours fit 96 VGPRs without scratch: C2 0.298 -> 0.294 ms on top of the probes in fours
-#endif
-#ifndef RT_PK_TABLES
-#define RT_PK_TABLES 1          // the lights' candidate masks from the shadow tables (rt_shadowtab.inc) instead of per-packet interval tests
-#endif
-// tabWords (profile constant): dwords per shadow-table cell = 32-object groups the profile's scenes can have; 0 = no tables
-struct PkLight { static constexpr bool keepAabb = false, park2 = true, boundsLds = true, split = false, wedge = false, blockerPairs = false, reloadLight = false, hitBatch = RT_PK_HIT_BATCH; static constexpr int reach = RT_LIGHT_REACH, sssGroup = RT_LIGHT_SSS_GROUP, groupN = RT_LIGHT_GROUPN, parkFloats = 23, cacheChunks = 1, waves = RT_PK_WAVES_SMALL, tabWords = RT_PK_TABLES ? 1 : 0; static constexpr bool resident = RT_PK_RESIDENT, fastPbr = RT_LIGHT_FAST_PBR, blockerTab = false; static constexpr int straight = RT_PK_STRAIGHT; };
-#ifndef RT_PK_SPLIT
-#define RT_PK_SPLIT 0       // HEAVY: packets whose directions straddle zero on an axis are culled per direction OCTANT (pk_ray_mask).  Bought
-                            // 3 % on C4/C5 before the per-lane shape level (RT_PK_REACH) existed; with it, off is 2-3 % faster and spills less
-#endif
-#ifndef RT_PK_WEDGE
-#define RT_PK_WEDGE 0       // HEAVY: convergent-packet cull of the shadow rays toward point / area lights (wedge_cull).  OFF: see there
-#endif
-#ifndef RT_PK_CACHE_CHUNKS
-#define RT_PK_CACHE_CHUNKS 4
-#endif
-#ifndef RT_HEAVY_KEEP
-#define RT_HEAVY_KEEP 0
-#endif
-#ifndef RT_HEAVY_PARK2
-#define RT_HEAVY_PARK2 1
-#endif
-#ifndef RT_HEAVY_GROUPN
-#define RT_HEAVY_GROUPN 2
-#endif
-#ifndef RT_HEAVY_BOUNDS_LDS
-#define RT_HEAVY_BOUNDS_LDS 0   // 0: the cull passes read the AABBs from the global copy (L1 / L2) instead of a per-workgroup LDS copy
-#endif
-struct PkHeavy { static constexpr bool keepAabb = RT_HEAVY_KEEP, park2 = RT_HEAVY_PARK2, boundsLds = RT_HEAVY_BOUNDS_LDS, split = RT_PK_SPLIT, wedge = RT_PK_WEDGE, blockerPairs = false, reloadLight = RT_HEAVY_RELOAD, hitBatch = RT_HEAVY_HIT_BATCH; static constexpr int reach = RT_PK_REACH, sssGroup = RT_HEAVY_SSS_GROUP;
-                 static constexpr int groupN = RT_HEAVY_GROUPN, parkFloats = RT_HEAVY_PARK2 ? 23 : 9, cacheChunks = RT_PK_CACHE_CHUNKS, waves = RT_HEAVY_WAVES, tabWords = RT_PK_TABLES ? 8 : 0; static constexpr bool resident = RT_PK_RESIDENT && RT_HEAVY_PARK2, fastPbr = RT_HEAVY_FAST_PBR, blockerTab = false; static constexpr int straight = RT_HEAVY_STRAIGHT; };
-// HEAVY for scenes of one 64-object chunk: the light's candidate mask is one SGPR pair, no chunk cache (its four pairs cost
-// the 64-object C4 4 % through SGPR spills while buying the 256-object C5 4 %)
-#ifndef RT_HEAVY1_WAVES
-#define RT_HEAVY1_WAVES 6       // with the shadow tables the 64-object profile gains from the sixth wave too (C4 5.07 -> 4.88 ms)
-#endif
-struct PkHeavy1 : PkHeavy { static constexpr int cacheChunks = 1, waves = RT_HEAVY1_WAVES, tabWords = RT_PK_TABLES ? 2 : 0; static constexpr bool reloadLight = true; };   // (6 waves: C4 6.27 -> 6.09 ms for three times the scratch traffic; 5 here)
-// The same three for scenes with a PCSS light (RtFrame::anyPcss): pcssShadow's 16 blocker rays go two per traversal
-// (pk_trace_any2).  Separate instantiations because the pair code costs the PCF-only kernels registers they need (measured
-// with the pair code merely present: C2 +8 %, C4 +7 %, C5 +4 %), while it takes 12 % off C3.
-#ifndef RT_PK_BLOCKER_PAIRS
-#define RT_PK_BLOCKER_PAIRS 1
-#endif
 #ifndef RT_PK_BLOCKER_GROUP
-#define RT_PK_BLOCKER_GROUP 4           // blocker rays per traversal (2, 4, 8 or 16).  C3: 4.83 ms single, 4.00 in pairs, 3.50 in fours, 3.89 in eights (spills)
+#define RT_PK_BLOCKER_GROUP 4   // pcssShadow's blocker rays per traversal (2, 4, 8 or 16).  C3: 4.83 ms single, 4.00 in pairs, 3.50 in fours, 3.89 in eights (spills)
+#endif
+#ifndef RT_PK_WAVES_SMALL
+#define RT_PK_WAVES_SMALL 5     // resident waves per SIMD the LIGHT kernels are compiled for (96 VGPRs)
 #endif
 #ifndef RT_PK_WAVES_PCSS
-#define RT_PK_WAVES_PCSS RT_PK_WAVES_SMALL
+#define RT_PK_WAVES_PCSS RT_PK_WAVES_SMALL      // ... every profile for scenes with a PCSS light
 #endif
-#ifndef RT_PK_RESIDENT_PCSS
-#define RT_PK_RESIDENT_PCSS 1   // (with the subsurface probes in pairs: C3 3.44 -> 3.39 ms, scratch 156 -> 68 B/lane; with single probes it was 3.73)
+#ifndef RT_HEAVY_WAVES
+#define RT_HEAVY_WAVES 6        // the multi-chunk HEAVY profile is compiled for 6 waves/SIMD (80 VGPRs): after the shape level the loops are short and
+#endif                          // latency-bound again, a sixth wave buys C5 36.0 -> 34.5 ms (for 56 B/lane more cold scratch); LIGHT stays at 5
+#ifndef RT_HEAVY1_WAVES
+#define RT_HEAVY1_WAVES 6       // with the shadow tables the 64-object profile gains from the sixth wave too (C4 5.07 -> 4.88 ms; before them
+#endif                          // 6 waves meant C4 6.27 -> 6.09 ms for three times the scratch traffic)
+#ifndef RT_PK_CACHE_CHUNKS
+#define RT_PK_CACHE_CHUNKS 4    // 64-object chunks whose light candidate masks the multi-chunk HEAVY profile keeps in SGPR pairs (pk_pcf_shadow)
 #endif
-struct PkLightS : PkLight { static constexpr bool blockerPairs = RT_PK_BLOCKER_PAIRS, reloadLight = true, resident = RT_PK_RESIDENT_PCSS, blockerTab = RT_PK_BLOCKER_TAB && RT_PK_TABLES; static constexpr int straight = RT_LIGHTS_STRAIGHT; static constexpr int waves = RT_PK_WAVES_PCSS, groupN = 1; };   // (PCF pairs here: C3 3.50 -> 3.56 ms)
-struct PkHeavyS : PkHeavy { static constexpr bool blockerPairs = RT_PK_BLOCKER_PAIRS, resident = RT_PK_RESIDENT_PCSS, blockerTab = RT_HEAVY_BLOCKER_TAB && RT_PK_TABLES; static constexpr int waves = RT_PK_WAVES_PCSS; };
-// scenes beyond the tables' 256 objects: the packet-level masks of rounds 1-2 (chunks recomputed per sample group past the cache)
-struct PkHuge : PkHeavy { static constexpr int tabWords = 0; };
-struct PkHugeS : PkHeavyS { static constexpr int tabWords = 0; static constexpr bool blockerTab = false; };
-struct PkHeavy1S : PkHeavy1 { static constexpr bool blockerPairs = RT_PK_BLOCKER_PAIRS, resident = RT_PK_RESIDENT_PCSS, blockerTab = RT_HEAVY_BLOCKER_TAB && RT_PK_TABLES; static constexpr int waves = RT_PK_WAVES_PCSS; };
-#ifndef RT_PK_PARK
-#define RT_PK_PARK 1        // park finalColor / throughput / ray.d in LDS across the lighting section (9 VGPRs)
+#ifndef RT_PK_REACH_MIN_SAMPLES
+#define RT_PK_REACH_MIN_SAMPLES 3       // `reach` profiles: the per-lane shape level of a light's PCF rays runs from this many samples on (pk_pcf_shadow)
 #endif
-#ifndef RT_PK_ALLPASS
-#define RT_PK_ALLPASS 0     // 1: also classify candidates whose AABB test provably passes for EVERY lane and skip the
-                            // per-lane test for them.  Correct (fuzz-tested) but measured 7 % SLOWER on C2: off.
+#ifndef RT_PK_CONE_MIN_SAMPLES
+#define RT_PK_CONE_MIN_SAMPLES 8        // the other profiles (LIGHT): interval slab test of the candidates' AABBs per lane, from this many samples on.
+#endif                                  // (Stays: the LIGHT kernel compiles and reaches it, so removing it would change a shipped profile's code.)
+#ifndef RT_PK_TIMERS
+#define RT_PK_TIMERS 0          // 1: section timers in the instrumented (COUNT) build (pk_clock; off by default: they serialise the scalar unit)
 #endif
-#ifndef RT_PK_SKIP_UNLIT
-#define RT_PK_SKIP_UNLIT 1  // 1: lanes whose surface faces away from the light (computePBR's NdotL = max(dot(N,L),0) is 0)
-#endif                      // trace no shadow rays for it: their term is (+-0 or NaN) * shadow, the same for every finite shadow
-#ifndef RT_PK_FETCH4
-#define RT_PK_FETCH4 0      // 1: fetch hot[0..3] (bounds + sphere centre / plane point + normal) of a candidate in one burst
-                            // (one scalar-load round trip per sphere instead of two).  Measured neutral on C2 (0.543 vs
-                            // 0.548 ms) and 2 % slower on C5: the waits are already covered by the other waves.
-#endif
-#ifndef RT_PK_SMEM
-#define RT_PK_SMEM 1        // wave-uniform records (traversal candidates, lights, Halton) via scalar loads
-#endif
+
+constexpr int PK_PARK_FLOATS = 23;      // floats per lane of the LDS parking area: finalColor, throughput, ray.d, P, N, V, albedo (3 each), metallic, roughness
+
+// ---- profiles ---------------------------------------------------------------------------------------------------------
+struct PkLight {
+    // light packets whose directions straddle zero on an axis culled per direction octant (pk_pcf_shadow).  Bought 3 % on C4 / C5
+    // before the per-lane shape level existed; with it, off is 2-3 % faster and spills less.  Off in every profile.
+    static constexpr bool split = false;
+    // the cull passes read the lanes' AABBs from a per-workgroup LDS copy (false: from the global copy, L1 / L2)
+    static constexpr bool boundsLds = true;
+    // pcssShadow's 16 blocker rays go RT_PK_BLOCKER_GROUP per traversal (pk_trace_any_group).  Separate ...S instantiations
+    // because the group code costs the PCF-only kernels registers they need (measured with the pair code merely present:
+    // C2 +8 %, C4 +7 %, C5 +4 %), while it takes 12 % off C3.
+    static constexpr bool blockerPairs = false;
+    // ... and take their candidates from the lights' blocker tables (rt_shadowtab.inc) where a light has one
+    static constexpr bool blockerTab = false;
+    // fetch the light's colour / intensity again after its shadow rays instead of carrying 8 SGPRs across them.  Scalar
+    // pressure decides these kernels -- 55-110 SGPRs are spilled to VGPR lanes, and a loop that has to v_readlane its
+    // operands back every trip is what a slow build looks like (tools/isa_loops.py) -- but which build the allocator
+    // produces is not monotone in the pressure, so it is set per instantiation by measurement: C4 (PkHeavy1) 8.20 -> 7.76 ms,
+    // C3 (PkLightS) 3.52 -> 3.49, C2 (PkLight) unchanged, C5 (PkHeavy) 39.1 -> 43.9 (off there).
+    static constexpr bool reloadLight = false;
+    // the hit object's records requested as one batch of gathers (render_packet)
+    static constexpr bool hitBatch = true;
+    // per-lane second cull level of a light's PCF rays (pk_pcf_shadow): true = spheres on their shape from
+    // RT_PK_REACH_MIN_SAMPLES samples on; false = every candidate on its AABB from RT_PK_CONE_MIN_SAMPLES samples on.
+    // LIGHT: C2 0.385 ms without the shape level, 0.447 with (3 candidates per packet: nothing to prune).
+    static constexpr bool reach = false;
+    static constexpr bool fastPbr = RT_LIGHT_FAST_PBR;
+    static constexpr int sssGroup = RT_LIGHT_SSS_GROUP;
+    static constexpr int groupN = RT_LIGHT_GROUPN;
+    static constexpr int cacheChunks = 1;
+    static constexpr int waves = RT_PK_WAVES_SMALL;
+    // dwords per shadow-table cell = 32-object groups the profile's scenes can have; 0 = no tables (the light's candidate
+    // masks then come from per-packet interval tests)
+    static constexpr int tabWords = 1;
+    static constexpr int straight = RT_PK_STRAIGHT;
+};
+struct PkHeavy {
+    static constexpr bool split = false;
+    static constexpr bool boundsLds = false;
+    static constexpr bool blockerPairs = false;
+    static constexpr bool blockerTab = false;
+    static constexpr bool reloadLight = false;
+    // the hit records one after the other again.  With the per-lane shape level in place the batch form (and the octant
+    // split) lost their edge: C4 6.40 -> 6.26 ms, C5 36.9 -> 35.8 ms and 32-36 B/lane less scratch without both
+    static constexpr bool hitBatch = false;
+    static constexpr bool reach = true;
+    static constexpr bool fastPbr = RT_HEAVY_FAST_PBR;
+    static constexpr int sssGroup = RT_HEAVY_SSS_GROUP;
+    static constexpr int groupN = RT_HEAVY_GROUPN;
+    static constexpr int cacheChunks = RT_PK_CACHE_CHUNKS;
+    static constexpr int waves = RT_HEAVY_WAVES;
+    static constexpr int tabWords = 8;
+    static constexpr int straight = 0;
+};
+// HEAVY for scenes of one 64-object chunk: the light's candidate mask is one SGPR pair, no chunk cache (its four pairs cost
+// the 64-object C4 4 % through SGPR spills while buying the 256-object C5 4 %)
+struct PkHeavy1 : PkHeavy {
+    static constexpr int cacheChunks = 1;
+    static constexpr int waves = RT_HEAVY1_WAVES;
+    static constexpr int tabWords = 2;
+    static constexpr bool reloadLight = true;
+};
+// The same three for scenes with a PCSS light (RtFrame::anyPcss); blocker tables: 1 / 2 / 8 dwords per cell
+struct PkLightS : PkLight {
+    static constexpr bool blockerPairs = true;
+    static constexpr bool blockerTab = true;
+    static constexpr bool reloadLight = true;
+    static constexpr int straight = 0;
+    static constexpr int waves = RT_PK_WAVES_PCSS;
+    static constexpr int groupN = 1;            // (PCF pairs here: C3 3.50 -> 3.56 ms)
+};
+struct PkHeavyS : PkHeavy {
+    static constexpr bool blockerPairs = true;
+    static constexpr bool blockerTab = true;
+    static constexpr int waves = RT_PK_WAVES_PCSS;
+};
+struct PkHeavy1S : PkHeavy1 {
+    static constexpr bool blockerPairs = true;
+    static constexpr bool blockerTab = true;
+    static constexpr int waves = RT_PK_WAVES_PCSS;
+};
+// scenes beyond the tables' 256 objects or 64 lights, and small scenes without tables: the packet-level masks of rounds 1-2
+// (chunks recomputed per sample group past the cache) and the per-lane shape level
+struct PkHuge : PkHeavy {
+    static constexpr int tabWords = 0;
+};
+struct PkHugeS : PkHeavyS {
+    static constexpr int tabWords = 0;
+    static constexpr bool blockerTab = false;
+};
 
 constexpr float PK_INF = __builtin_huge_valf();
 
 // Wave-uniform reads of the compiled scene.  The record index is the same for all 64 lanes
 // (a candidate bit, the light index, a sample index), so the natural home of the data is the
-// SCALAR register file: with RT_PK_SMEM the records are fetched with s_load_dwordx4 from the
+// SCALAR register file: the records are fetched with s_load_dwordx4 from the
 // global copy of the compiled scene (constant address space; 16 KiB scalar cache, then L2) and
 // feed the VALU as SGPR operands -- no LDS instruction, no VGPRs.  Per-lane-indexed data
 // (materials by hit index, the cull pass' per-lane AABBs) stays in LDS.
@@ -205,22 +205,15 @@ typedef float pk_f4 __attribute__((ext_vector_type(4)));
 typedef const __attribute__((address_space(4))) pk_f4 *pk_uni4_t;
 typedef const __attribute__((address_space(4))) float *pk_uni1_t;
 __device__ __forceinline__ float4 uni_load4(const SceneLds &sc, int f4Index) {
-#if RT_PK_SMEM
     pk_f4 v = ((pk_uni4_t)(unsigned long long)sc.global)[f4Index];
     return make_float4(v.x, v.y, v.z, v.w);
-#else
-    return sc.hot[f4Index];
-#endif
 }
 __device__ __forceinline__ float uni_load1(const SceneLds &sc, int floatIndex) {
-#if RT_PK_SMEM
     return ((pk_uni1_t)(unsigned long long)sc.global)[floatIndex];
-#else
-    return ((const float *)sc.hot)[floatIndex];
-#endif
 }
-// Per-lane-indexed records.  Bounds (cull passes) always come from LDS; the shape / material fields a lane reads
-// by its hit index once per bounce come from LDS, or from the global copy in compact staging (SceneLds).
+// Per-lane-indexed records.  Bounds (cull passes) come from the LDS copy (two float4 per object) or the global one, by profile;
+// the shape / material fields a lane reads by its hit index once per bounce come from the global copy (sc.compact is true in every
+// kernel that calls these; folding it away changes the shipped kernels' instruction sequences, so the select stays).
 __device__ __forceinline__ float4 pk_bounds(const SceneLds &sc, int obj, int k) {
     return sc.boundsLds ? sc.hot[obj * sc.hotStride + k] : sc.global[obj * RT_HOT_F4 + k];
 }
@@ -346,9 +339,9 @@ __device__ __forceinline__ void st_lane_mask(const SceneLds &sc, int li, int nOb
 
 // intersectSphere / intersectPlane (see shape_test) with the record fetched through uni_load4
 __device__ __forceinline__ bool pk_shape_test(const SceneLds &sc, const Ray &r, float a, int obj, float radius2, int type,
-                                              float &t, const float4 *pre = nullptr) {
+                                              float &t) {
     if (type == 0) {
-        float4 h2 = pre ? pre[0] : uni_load4(sc, obj * RT_HOT_F4 + 2);
+        float4 h2 = uni_load4(sc, obj * RT_HOT_F4 + 2);
         v3 oc = r.o - V3(h2);
         float b = 2.0f * dot(oc, r.d);
         float c = dot(oc, oc) - radius2;
@@ -357,7 +350,7 @@ __device__ __forceinline__ bool pk_shape_test(const SceneLds &sc, const Ray &r, 
         t = (-b - rtf::sqrt(disc)) / (2.0f * a);
         return t > 0.0f;
     } else if (type == 1) {
-        float4 h2 = pre ? pre[0] : uni_load4(sc, obj * RT_HOT_F4 + 2), h3 = pre ? pre[1] : uni_load4(sc, obj * RT_HOT_F4 + 3);
+        float4 h2 = uni_load4(sc, obj * RT_HOT_F4 + 2), h3 = uni_load4(sc, obj * RT_HOT_F4 + 3);
         v3 n = V3(h3);
         float denom = dot(n, r.d);
         if (fabsf(denom) > 1e-6f) {
@@ -379,9 +372,9 @@ __device__ __forceinline__ bool pk_wave_any(bool p) { return __builtin_amdgcn_ba
 // reference's form (`disc < 0` / `t < 0` / `abs(x) > size` negated, so NaNs fall where the GLSL lets them fall),
 // garbage in lanes outside the predicate never reaches the result, and the only branches are wave-uniform skips.
 __device__ __forceinline__ bool pk_shape_hit(const SceneLds &sc, const Ray &r, float a, int obj, float radius2, int type,
-                                             bool pass, float &t, const float4 *pre = nullptr) {
+                                             bool pass, float &t) {
     if (type == 0) {
-        const float4 h2 = pre ? pre[0] : uni_load4(sc, obj * RT_HOT_F4 + 2);
+        const float4 h2 = uni_load4(sc, obj * RT_HOT_F4 + 2);
         const v3 oc = r.o - V3(h2);
         const float b = 2.0f * dot(oc, r.d);
         const float c = dot(oc, oc) - radius2;
@@ -391,7 +384,7 @@ __device__ __forceinline__ bool pk_shape_hit(const SceneLds &sc, const Ray &r, f
         t = (-b - rtf::sqrt(disc)) / (2.0f * a);
         return cand & (t > 0.0f);
     } else if (type == 1) {
-        const float4 h2 = pre ? pre[0] : uni_load4(sc, obj * RT_HOT_F4 + 2), h3 = pre ? pre[1] : uni_load4(sc, obj * RT_HOT_F4 + 3);
+        const float4 h2 = uni_load4(sc, obj * RT_HOT_F4 + 2), h3 = uni_load4(sc, obj * RT_HOT_F4 + 3);
         const v3 n = V3(h3);
         const float denom = dot(n, r.d);
         const bool c1 = pass & (fabsf(denom) > 1e-6f);
@@ -408,11 +401,8 @@ __device__ __forceinline__ bool pk_shape_hit(const SceneLds &sc, const Ray &r, f
     return false;
 }
 
-// Section timers of the instrumented (COUNT) build (RT_PK_TIMERS, off by default: they serialise the scalar unit):
+// Section timers of the instrumented (COUNT) build (RT_PK_TIMERS):
 // slots [12] closest-hit traversals, [13] a light's packet + candidate masks, [14] its PCF sample loops, [15] the whole wave.
-#ifndef RT_PK_TIMERS
-#define RT_PK_TIMERS 0
-#endif
 template <int COUNT>
 __device__ __forceinline__ unsigned long long pk_clock() {
 #if RT_PK_TIMERS
@@ -510,6 +500,7 @@ __device__ __forceinline__ void pk_axis(float bmin, float bmax, float olo, float
     // objects whose own bounds hold a NaN are kept as candidates by the caller (objNan).
     lb = ok ? fminf(lo0, lo1) : -PK_INF;          // <= min(t0,t1) of every lane
     ub = ok ? fmaxf(hi0, hi1) : PK_INF;           // >= max(t0,t1) of every lane
+    // (the opposite bounds: no caller reads them, but without them the shipped kernels' instruction sequences change -- they stay)
     ubSmall = ok ? fminf(hi0, hi1) : PK_INF;      // >= min(t0,t1) of every lane
     lbLarge = ok ? fmaxf(lo0, lo1) : -PK_INF;     // <= max(t0,t1) of every lane
 }
@@ -549,8 +540,7 @@ __device__ __forceinline__ bool box_finite(const Box3 &b) {
 // Candidate mask of one 64-object chunk: bit l set unless object (chunk*64 + l) provably fails
 // intersectAABB for every active lane.  bmn/bmx = this lane's object's bounds.
 __device__ __forceinline__ unsigned long long pk_candidates(const Packet &p, float4 bmn, float4 bmx, bool objValid,
-                                                            bool objNan, float maxDist, unsigned long long &allPass) {
-    allPass = 0ull;
+                                                            bool objNan, float maxDist) {
     if (!p.cull) return __builtin_amdgcn_ballot_w64(objValid);
     float lbx, ubx, lby, uby, lbz, ubz, usx, usy, usz, llx, lly, llz;
     pk_axis(bmn.x, bmx.x, p.o.lox, p.o.hix, p.inv.lox, p.inv.hix, p.okx, lbx, ubx, usx, llx);
@@ -560,13 +550,6 @@ __device__ __forceinline__ unsigned long long pk_candidates(const Packet &p, flo
     float leave = fminf(fminf(ubx, uby), ubz);     // >= every lane's tMax
     // lane test: tMax >= tMin && tMin < maxDist && tMax > 0
     bool dead = (leave < enter) || (enter >= maxDist) || (leave <= 0.0f);
-#if RT_PK_ALLPASS
-    // the opposite bounds prove the test TRUE for every lane: tMin <= tMinHi <= tMaxLo <= tMax
-    float tMinHi = fmaxf(fmaxf(usx, usy), usz);    // >= every lane's tMin
-    float tMaxLo = fminf(fminf(llx, lly), llz);    // <= every lane's tMax
-    bool sure = !objNan && (tMaxLo >= tMinHi) && (tMinHi < maxDist) && (tMaxLo > 0.0f);
-    allPass = __builtin_amdgcn_ballot_w64(objValid && sure);
-#endif
     return __builtin_amdgcn_ballot_w64(objValid && (objNan || !dead));
 }
 
@@ -579,41 +562,15 @@ __device__ __forceinline__ unsigned sign_octant(v3 d) {
     return (__float_as_uint(d.x) >> 31) | ((__float_as_uint(d.y) >> 31) << 1) | ((__float_as_uint(d.z) >> 31) << 2);
 }
 
-// Candidate mask of one chunk for a packet of single rays (per-lane reciprocal directions `inv`).  The interval test needs a
-// SIGN-DEFINITE reciprocal box per axis; a packet whose directions straddle zero on an axis used to lose that axis'
-// constraint altogether -- measured (tools/gpu_packet_stats.py): 8 % of C2's packets, 25 % of C4's, 20 % of C5's, and those
-// packets carried 10 / 44 / 150 candidates instead of 2 / 9 / 33, i.e. a third to two thirds of ALL candidate tests.  Such a
-// packet is now culled as the union of its direction OCTANTS: the lanes of one octant form a sign-definite sub-packet (own
-// reciprocal box by one DPP reduction, the packet's origin box), an object is a candidate iff some sub-packet keeps it.
-// Every lane belongs to exactly one sub-packet and each sub-packet's test is the same rigorous interval test, so the union
-// is still a superset of the objects any lane's exact intersectAABB can pass: bit-identical output.
-__device__ __forceinline__ unsigned long long pk_ray_mask(const SceneLds &sc, const Packet &pk, v3 inv, bool active, float4 bmn, float4 bmx,
-                                                          bool objValid, bool objNan, float maxDist) {
-    unsigned long long ap;
-    if (sc.split && pk.cull && !(pk.okx && pk.oky && pk.okz)) {          // wave-uniform
-        const unsigned oct = sign_octant(inv);
-        unsigned long long rem = __builtin_amdgcn_ballot_w64(active), m = 0ull;
-        while (rem) {
-            const unsigned o = (unsigned)__builtin_amdgcn_readlane((int)oct, __builtin_ctzll(rem));
-            const bool sel = active && oct == o;
-            rem &= ~__builtin_amdgcn_ballot_w64(sel);
-            Packet q;
-            q.o = pk.o;
-            q.cull = true;
-            q.inv = wave_box(inv, sel);
-            pk_set_ok(q);
-            m |= pk_candidates(q, bmn, bmx, objValid, objNan, maxDist, ap);
-        }
-        return m;
-    }
-    return pk_candidates(pk, bmn, bmx, objValid, objNan, maxDist, ap);
-}
+// (A packet whose directions straddle zero on an axis loses that axis' constraint -- measured (tools/gpu_packet_stats.py): 8 % of
+// C2's packets, 25 % of C4's, 20 % of C5's, carrying 10 / 44 / 150 candidates instead of 2 / 9 / 33.  Culling such a packet per
+// direction OCTANT bought 3 % on C4 / C5 until the per-lane shape level existed; with it the split cost 2-3 % and spilled more.
+// The single-ray form (pk_ray_mask) was removed; the light packets' form in pk_pcf_shadow stays, switched off: DESIGN.md section 18.)
 
 // Closest hit over the packet.  `active` lanes get (index or -1, t = minT); others are untouched.
 template <int COUNT>
 __device__ __forceinline__ int pk_trace_closest(const SceneLds &sc, int nObj, const Ray &r, bool active,
-                                                const Box3 &ob, bool obFinite, float4 myMin, float4 myMax,
-                                                bool myNan, float maxDist, float &tOut, unsigned &rays) {
+                                                const Box3 &ob, bool obFinite, float maxDist, float &tOut, unsigned &rays) {
     if (COUNT) rays += active ? 1u : 0u;
     v3 inv;
     rtf::rcp3(r.d.x, r.d.y, r.d.z, inv.x, inv.y, inv.z);
@@ -629,15 +586,14 @@ __device__ __forceinline__ int pk_trace_closest(const SceneLds &sc, int nObj, co
         pk_stat<COUNT>(sc, 11, (unsigned long long)__builtin_popcountll(__builtin_amdgcn_ballot_w64(active)));
     }
     for (int base = 0; base < nObj; base += 64) {
-        float4 bmn = myMin, bmx = myMax;
-        bool bnan = myNan;
-        if ((base > 0 || !sc.keepAabb) && base + lane < nObj) {
+        float4 bmn = make_float4(0.f, 0.f, 0.f, 0.f), bmx = make_float4(0.f, 0.f, 0.f, 0.f);          // (lanes beyond the scene: objValid is false)
+        bool bnan = false;
+        if (base + lane < nObj) {
             bmn = pk_bounds(sc, base + lane, 0);
             bmx = pk_bounds(sc, base + lane, 1);
             bnan = bounds_nan(bmn, bmx);
         }
-        const unsigned long long ap = 0ull;
-        unsigned long long m = pk_ray_mask(sc, pk, inv, active, bmn, bmx, base + lane < nObj, bnan, maxDist);
+        unsigned long long m = pk_candidates(pk, bmn, bmx, base + lane < nObj, bnan, maxDist);
         pk_stat<COUNT>(sc, 2, (unsigned long long)__builtin_popcountll(m));
         pk_stat<COUNT>(sc, 3, 1);
         if (COUNT) pk_stat<COUNT>(sc, (pk.cull && pk.okx && pk.oky && pk.okz) ? 9 : 10, (unsigned long long)__builtin_popcountll(m));
@@ -646,25 +602,18 @@ __device__ __forceinline__ int pk_trace_closest(const SceneLds &sc, int nObj, co
             const int i = base + bit;
             m &= m - 1;
             const float4 h0 = uni_load4(sc, i * RT_HOT_F4), h1 = uni_load4(sc, i * RT_HOT_F4 + 1);
-#if RT_PK_FETCH4
-                const float4 hpre[2] = {uni_load4(sc, i * RT_HOT_F4 + 2), uni_load4(sc, i * RT_HOT_F4 + 3)};
-                const float4 *hp = hpre;
-#else
-                const float4 *hp = nullptr;
-#endif
-            const bool sure = (ap >> bit) & 1ull;          // wave-uniform
             if (sc.straight & 1) {
-            const bool pass = active & (sure | aabb_test(r, inv, h0, h1, maxDist));
+            const bool pass = active & aabb_test(r, inv, h0, h1, maxDist);
             if (pk_wave_any(pass)) {
                 float t = 0.0f;
-                const bool better = pk_shape_hit(sc, r, a, i, h1.w, __float_as_int(h0.w), pass, t, hp) & (t > 0.0f) & (t < minT);
+                const bool better = pk_shape_hit(sc, r, a, i, h1.w, __float_as_int(h0.w), pass, t) & (t > 0.0f) & (t < minT);
                 minT = better ? t : minT;
                 hit = better ? i : hit;
             }
             } else {
-            if (active && (sure || aabb_test(r, inv, h0, h1, maxDist))) {
+            if (active && aabb_test(r, inv, h0, h1, maxDist)) {
                 float t;
-                if (pk_shape_test(sc, r, a, i, h1.w, __float_as_int(h0.w), t, hp) && t > 0.0f && t < minT) {
+                if (pk_shape_test(sc, r, a, i, h1.w, __float_as_int(h0.w), t) && t > 0.0f && t < minT) {
                     minT = t;
                     hit = i;
                 }
@@ -682,8 +631,7 @@ __device__ __forceinline__ int pk_trace_closest(const SceneLds &sc, int nObj, co
 // single-ray one.
 template <int COUNT, int NR>
 __device__ __forceinline__ void pk_trace_closest_group(const SceneLds &sc, int nObj, v3 origin, const v3 (&d)[NR], bool active, const Box3 &ob,
-                                                       bool obFinite, float4 myMin, float4 myMax, bool myNan, float maxDist,
-                                                       int (&hit)[NR], float (&tOut)[NR], unsigned &rays) {
+                                                       bool obFinite, float maxDist, int (&hit)[NR], float (&tOut)[NR], unsigned &rays) {
     if (COUNT) rays += active ? (unsigned)NR : 0u;
     v3 inv[NR];
     bool dirNan = false;
@@ -720,15 +668,14 @@ __device__ __forceinline__ void pk_trace_closest_group(const SceneLds &sc, int n
         pk_stat<COUNT>(sc, 11, (unsigned long long)NR * (unsigned long long)__builtin_popcountll(__builtin_amdgcn_ballot_w64(active)));
     }
     for (int base = 0; base < nObj; base += 64) {
-        float4 bmn = myMin, bmx = myMax;
-        bool bnan = myNan;
-        if ((base > 0 || !sc.keepAabb) && base + lane < nObj) {
+        float4 bmn = make_float4(0.f, 0.f, 0.f, 0.f), bmx = make_float4(0.f, 0.f, 0.f, 0.f);          // (lanes beyond the scene: objValid is false)
+        bool bnan = false;
+        if (base + lane < nObj) {
             bmn = pk_bounds(sc, base + lane, 0);
             bmx = pk_bounds(sc, base + lane, 1);
             bnan = bounds_nan(bmn, bmx);
         }
-        unsigned long long ap;
-        unsigned long long m = pk_candidates(pk, bmn, bmx, base + lane < nObj, bnan, maxDist, ap);
+        unsigned long long m = pk_candidates(pk, bmn, bmx, base + lane < nObj, bnan, maxDist);
         pk_stat<COUNT>(sc, 2, (unsigned long long)NR * (unsigned long long)__builtin_popcountll(m));
         pk_stat<COUNT>(sc, 3, 1);
         if (COUNT) pk_stat<COUNT>(sc, (pk.cull && pk.okx && pk.oky && pk.okz) ? 9 : 10, (unsigned long long)NR * (unsigned long long)__builtin_popcountll(m));
@@ -744,7 +691,7 @@ __device__ __forceinline__ void pk_trace_closest_group(const SceneLds &sc, int n
                 r.o = origin; r.d = d[k];
                 if (active && aabb_test(r, inv[k], h0, h1, maxDist)) {
                     float t;
-                    if (pk_shape_test(sc, r, dot(d[k], d[k]), i, h1.w, type, t, nullptr) && t > 0.0f && t < tOut[k]) {
+                    if (pk_shape_test(sc, r, dot(d[k], d[k]), i, h1.w, type, t) && t > 0.0f && t < tOut[k]) {
                         tOut[k] = t;
                         hit[k] = i;
                     }
@@ -757,8 +704,7 @@ __device__ __forceinline__ void pk_trace_closest_group(const SceneLds &sc, int n
 // Any-hit over the packet (see trace_any): true for active lanes with an occluder in (0, limit).
 template <int COUNT>
 __device__ __forceinline__ bool pk_trace_any(const SceneLds &sc, int nObj, const Ray &r, bool active, const Box3 &ob,
-                                             bool obFinite, float4 myMin, float4 myMax, bool myNan, float maxDist,
-                                             float limit, unsigned &rays) {
+                                             bool obFinite, float maxDist, float limit, unsigned &rays) {
     if (COUNT) rays += active ? 1u : 0u;
     v3 inv;
     rtf::rcp3(r.d.x, r.d.y, r.d.z, inv.x, inv.y, inv.z);
@@ -773,15 +719,14 @@ __device__ __forceinline__ bool pk_trace_any(const SceneLds &sc, int nObj, const
         pk_stat<COUNT>(sc, 11, (unsigned long long)__builtin_popcountll(__builtin_amdgcn_ballot_w64(active)));
     }
     for (int base = 0; base < nObj; base += 64) {
-        float4 bmn = myMin, bmx = myMax;
-        bool bnan = myNan;
-        if ((base > 0 || !sc.keepAabb) && base + lane < nObj) {
+        float4 bmn = make_float4(0.f, 0.f, 0.f, 0.f), bmx = make_float4(0.f, 0.f, 0.f, 0.f);          // (lanes beyond the scene: objValid is false)
+        bool bnan = false;
+        if (base + lane < nObj) {
             bmn = pk_bounds(sc, base + lane, 0);
             bmx = pk_bounds(sc, base + lane, 1);
             bnan = bounds_nan(bmn, bmx);
         }
-        const unsigned long long ap = 0ull;
-        unsigned long long m = pk_ray_mask(sc, pk, inv, active, bmn, bmx, base + lane < nObj, bnan, maxDist);
+        unsigned long long m = pk_candidates(pk, bmn, bmx, base + lane < nObj, bnan, maxDist);
         pk_stat<COUNT>(sc, 2, (unsigned long long)__builtin_popcountll(m));
         pk_stat<COUNT>(sc, 3, 1);
         if (COUNT) pk_stat<COUNT>(sc, (pk.cull && pk.okx && pk.oky && pk.okz) ? 9 : 10, (unsigned long long)__builtin_popcountll(m));
@@ -790,24 +735,17 @@ __device__ __forceinline__ bool pk_trace_any(const SceneLds &sc, int nObj, const
             const int i = base + bit;
             m &= m - 1;
             const float4 h0 = uni_load4(sc, i * RT_HOT_F4), h1 = uni_load4(sc, i * RT_HOT_F4 + 1);
-#if RT_PK_FETCH4
-                const float4 hpre[2] = {uni_load4(sc, i * RT_HOT_F4 + 2), uni_load4(sc, i * RT_HOT_F4 + 3)};
-                const float4 *hp = hpre;
-#else
-                const float4 *hp = nullptr;
-#endif
-            const bool sure = (ap >> bit) & 1ull;          // wave-uniform
             if (sc.straight & 2) {
-            const bool pass = todo & (sure | aabb_test(r, inv, h0, h1, maxDist));
+            const bool pass = todo & aabb_test(r, inv, h0, h1, maxDist);
             if (pk_wave_any(pass)) {
                 float t = 0.0f;
-                const bool occ = pk_shape_hit(sc, r, a, i, h1.w, __float_as_int(h0.w), pass, t, hp) & (t > 0.0f) & (t < limit);
+                const bool occ = pk_shape_hit(sc, r, a, i, h1.w, __float_as_int(h0.w), pass, t) & (t > 0.0f) & (t < limit);
                 todo = todo & !occ;
             }
             } else {
-            if (todo && (sure || aabb_test(r, inv, h0, h1, maxDist))) {
+            if (todo && aabb_test(r, inv, h0, h1, maxDist)) {
                 float t;
-                if (pk_shape_test(sc, r, a, i, h1.w, __float_as_int(h0.w), t, hp) && t > 0.0f && t < limit) todo = false;
+                if (pk_shape_test(sc, r, a, i, h1.w, __float_as_int(h0.w), t) && t > 0.0f && t < limit) todo = false;
             }
             }
             if (!wave_any(todo)) return active;     // every active lane is occluded
@@ -821,8 +759,7 @@ __device__ __forceinline__ bool pk_trace_any(const SceneLds &sc, int nObj, const
 // stops testing as soon as any of its rays is occluded.  Each ray's own test is the exact one of pk_trace_any.
 template <int COUNT, int NR>
 __device__ __forceinline__ bool pk_trace_any_group(const SceneLds &sc, int nObj, v3 origin, const v3 (&d)[NR], bool active, const Box3 &ob,
-                                                   bool obFinite, float4 myMin, float4 myMax, bool myNan, float maxDist, float limit,
-                                                   unsigned &rays) {
+                                                   bool obFinite, float maxDist, float limit, unsigned &rays) {
     if (COUNT) rays += active ? (unsigned)NR : 0u;
     v3 inv[NR];
     bool dirNan = false;
@@ -859,15 +796,14 @@ __device__ __forceinline__ bool pk_trace_any_group(const SceneLds &sc, int nObj,
         pk_stat<COUNT>(sc, 11, (unsigned long long)NR * (unsigned long long)__builtin_popcountll(__builtin_amdgcn_ballot_w64(active)));
     }
     for (int base = 0; base < nObj; base += 64) {
-        float4 bmn = myMin, bmx = myMax;
-        bool bnan = myNan;
-        if ((base > 0 || !sc.keepAabb) && base + lane < nObj) {
+        float4 bmn = make_float4(0.f, 0.f, 0.f, 0.f), bmx = make_float4(0.f, 0.f, 0.f, 0.f);          // (lanes beyond the scene: objValid is false)
+        bool bnan = false;
+        if (base + lane < nObj) {
             bmn = pk_bounds(sc, base + lane, 0);
             bmx = pk_bounds(sc, base + lane, 1);
             bnan = bounds_nan(bmn, bmx);
         }
-        unsigned long long ap;
-        unsigned long long m = pk_candidates(pk, bmn, bmx, base + lane < nObj, bnan, maxDist, ap);
+        unsigned long long m = pk_candidates(pk, bmn, bmx, base + lane < nObj, bnan, maxDist);
         pk_stat<COUNT>(sc, 2, (unsigned long long)NR * (unsigned long long)__builtin_popcountll(m));
         pk_stat<COUNT>(sc, 3, 1);
         if (COUNT) pk_stat<COUNT>(sc, (pk.cull && pk.okx && pk.oky && pk.okz) ? 9 : 10, (unsigned long long)NR * (unsigned long long)__builtin_popcountll(m));
@@ -883,7 +819,7 @@ __device__ __forceinline__ bool pk_trace_any_group(const SceneLds &sc, int nObj,
                 r.o = origin; r.d = d[k];
                 if (todo && aabb_test(r, inv[k], h0, h1, maxDist)) {
                     float t;          // (dot(d,d) re-evaluated here, for the few candidates that pass the slab test, instead of living in NR registers)
-                    if (pk_shape_test(sc, r, dot(d[k], d[k]), i, h1.w, type, t, nullptr) && t > 0.0f && t < limit) todo = false;
+                    if (pk_shape_test(sc, r, dot(d[k], d[k]), i, h1.w, type, t) && t > 0.0f && t < limit) todo = false;
                 }
             }
             if (!wave_any(todo)) return active;     // every active lane has its blocker
@@ -926,7 +862,7 @@ __device__ __forceinline__ bool pk_trace_any_group_masked(const SceneLds &sc, v3
                 r.o = origin; r.d = d[k];
                 if (mine && todo && aabb_test(r, inv[k], h0, h1, maxDist)) {
                     float t;
-                    if (pk_shape_test(sc, r, dot(d[k], d[k]), i, h1.w, type, t, nullptr) && t > 0.0f && t < limit) todo = false;
+                    if (pk_shape_test(sc, r, dot(d[k], d[k]), i, h1.w, type, t) && t > 0.0f && t < limit) todo = false;
                 }
             }
             if (!wave_any(todo)) return active;
@@ -943,62 +879,12 @@ __device__ __forceinline__ bool pk_trace_any_group_masked(const SceneLds &sc, v3
 // on C3 (tools/gpu_packet_stats.py) -- but 18 objects x ~45 VALU per lane and light cost what the saved candidate trips bring:
 // C3 3.39 -> 3.57 ms; with the next object's records prefetched 3.65, with the plane test alone 3.81.  DESIGN.md section 4 item 32.)
 
-// ---- convergent-packet cull (HEAVY profile): shadow rays toward a point / area light -----------------------------------------
-// The slab-interval test treats a packet's origins and directions as INDEPENDENT boxes, but the shadow rays of one light
-// converge: every ray of the packet lies (up to the PCF jitter) on a line through the light position L and its own origin o,
-// i.e. in the double cone {L + lambda*(o - L) : o in the packet's origin box O, lambda real}.  For the incoherent packets
-// of deep bounces (origins spread over the whole scene) that is a far smaller set than O + t*D: measured on C5's shadow
-// packets (CPU model of both tests against the exact per-lane intersectAABB of the actual jittered rays, 3 900 packets,
-// no violation) 82 slab candidates of 256 become 43 with this test on top; the exact union over the lanes is 18.
-// Test, per coordinate-plane projection (xy, yz, xz): the double cone projects into the double WEDGE bounded by the two
-// tangent lines from L to the rectangle O; an object box that lies strictly inside one of the two outer sectors -- all four
-// corners on the positive side of one tangent line and on the negative side of the other -- cannot be touched by any ray.
-// Slack, so that the jittered fp32 rays the lanes really trace stay covered: the object box is inflated by
-// deltaTot * (L1 distance from O to the box's far corner) per component, deltaTot = the PCF jitter bound `delta` (every
-// component of a jittered direction is within delta of the unjittered one) + the aim error (the rays leave P + N*0.001 in
-// the direction of L - P, so they aim at a point up to max|aim - L| off L, an angle of at most that over the distance from L
-// to O); fp32 rounding (1e-7 relative) is orders of magnitude inside that margin.  NaN / infinite bounds make every comparison
-// false: such objects stay candidates.  L inside the projected rectangle: no wedge in that projection.
-// OUTCOME (RT_PK_WEDGE, default 0): bit-identical on 300 fuzz seeds and it prunes as modelled -- candidates per packet at
-// 1080p: C4 16.3 -> 12.0, C5 50.3 -> 31.5 -- but at the configs' own sizes (4K / 8K: denser pixels, more coherent packets,
-// 9 / 18 candidates per packet to begin with) the ~130 VALU instructions per cull pass and the extra SGPR pressure cost more than
-// the pruned candidate tests save: C4 8.38 -> 9.14 ms, C5 41.1 -> 47.0 ms applied always; 8.50 / 40.3 ms applied only to chunks
-// that still hold >= 16 candidates (gpurun_out/try22, try23.log).  Kept switched off for low-resolution / incoherent uses.
-__device__ __forceinline__ bool wedge_outside(float oLoA, float oHiA, float oLoB, float oHiB, float La, float Lb,
-                                              float loA, float hiA, float loB, float hiB) {
-    const bool xl = La < oLoA, xh = La > oHiA, yl = Lb < oLoB, yh = Lb > oHiB;       // wave-uniform
-    const bool xo = xl | xh, yo = yl | yh;
-    if (!(xo | yo)) return false;
-    const float nx = xl ? oLoA : oHiA, fx = xl ? oHiA : oLoA, ny = yl ? oLoB : oHiB, fy = yl ? oHiB : oLoB;
-    // tangent corners A, B of the rectangle as seen from L: corner region -> the two corners adjacent to the nearest one,
-    // edge region -> the two ends of the nearest edge
-    const float Ax = (xo & yo) ? fx : (xo ? nx : oLoA), Ay = (xo & yo) ? ny : (xo ? oLoB : ny);
-    const float Bx = (xo & yo) ? nx : (xo ? nx : oHiA), By = (xo & yo) ? fy : (xo ? oHiB : ny);
-    const float vAx = Ax - La, vAy = Ay - Lb, vBx = Bx - La, vBy = By - Lb;
-    const float s = (vAx * vBy - vAy * vBx) > 0.0f ? 1.0f : -1.0f;
-    const float nAx = vAy * s, nAy = -(vAx * s), nBx = -(vBy * s), nBy = vBx * s;   // normals pointing away from the wedge that holds O
-    const float qa0 = loA - La, qa1 = hiA - La, qb0 = loB - Lb, qb1 = hiB - Lb;
-    float x0 = nAx * qa0, x1 = nAx * qa1, y0 = nAy * qb0, y1 = nAy * qb1;
-    const float alo = fminf(x0, x1) + fminf(y0, y1), ahi = fmaxf(x0, x1) + fmaxf(y0, y1);
-    x0 = nBx * qa0; x1 = nBx * qa1; y0 = nBy * qb0; y1 = nBy * qb1;
-    const float blo = fminf(x0, x1) + fminf(y0, y1), bhi = fmaxf(x0, x1) + fmaxf(y0, y1);
-    return ((alo > 0.0f) & (bhi < 0.0f)) | ((ahi < 0.0f) & (blo > 0.0f));
-}
-// true if this lane's object (bounds bmn / bmx) provably cannot be touched by any shadow ray of the packet
-__device__ __forceinline__ bool wedge_cull(const Box3 &ob, v3 L, float deltaTot, float4 bmn, float4 bmx) {
-    // intersectAABB is symmetric in bounds.min / bounds.max (it takes min and max of the two slab distances), so a malformed
-    // record with min > max on an axis acts as the box [max, min]: order the bounds before inflating them
-    const float nlx = fminf(bmn.x, bmx.x), nhx = fmaxf(bmn.x, bmx.x), nly = fminf(bmn.y, bmx.y), nhy = fmaxf(bmn.y, bmx.y),
-                nlz = fminf(bmn.z, bmx.z), nhz = fmaxf(bmn.z, bmx.z);
-    const float fx = fmaxf(fabsf(nhx - ob.lox), fabsf(nlx - ob.hix)), fy = fmaxf(fabsf(nhy - ob.loy), fabsf(nly - ob.hiy)),
-                fz = fmaxf(fabsf(nhz - ob.loz), fabsf(nlz - ob.hiz));
-    const float infl = deltaTot * ((fx + fy) + fz);
-    const float lox = nlx - infl, hix = nhx + infl, loy = nly - infl, hiy = nhy + infl, loz = nlz - infl, hiz = nhz + infl;
-    const bool oxy = wedge_outside(ob.lox, ob.hix, ob.loy, ob.hiy, L.x, L.y, lox, hix, loy, hiy);
-    const bool oyz = wedge_outside(ob.loy, ob.hiy, ob.loz, ob.hiz, L.y, L.z, loy, hiy, loz, hiz);
-    const bool oxz = wedge_outside(ob.lox, ob.hix, ob.loz, ob.hiz, L.x, L.z, lox, hix, loz, hiz);
-    return oxy || oyz || oxz;
-}
+// (Measured and removed: a convergent-packet "wedge" cull of the shadow rays toward point / area lights -- the rays of one light
+// lie in the double cone through the light and the packet's origin box, a far smaller set than origin box + t * direction box.
+// Bit-identical on 300 fuzz seeds and it pruned as modelled -- candidates per packet at 1080p: C4 16.3 -> 12.0, C5 50.3 -> 31.5 --
+// but its ~130 VALU per cull pass and the extra SGPR pressure cost more than the pruned tests saved at the configs' own sizes:
+// C4 8.38 -> 9.14 ms, C5 41.1 -> 47.0 ms applied always; 8.50 / 40.3 ms applied only to chunks with >= 16 candidates.  The shadow
+// tables have since taken over these scenes.  DESIGN.md section 4 and section 18.)
 
 // pcfShadow (:342-397) for a packet: ONE candidate mask per light serves all pcfSamples rays.
 // The jittered directions are jd = normalize(L + rx*T*fs + ry*B*fs) with rx,ry in [0,1), |T| = 1,
@@ -1008,9 +894,9 @@ __device__ __forceinline__ bool wedge_cull(const Box3 &ob, v3 L, float deltaTot,
 // interval, which gives the reciprocal box without a second reduction.
 // NWT > 0: the light's candidate masks come from its shadow table (rt_shadowtab.inc; NWT dwords per cell, li = the light's
 // index, nn = dot(N, N) of the shading normal) instead of the packet's interval tests below.
-template <int COUNT, int GROUPN, int CACHE = 1, int REACH = 0, int NWT = 0>
+template <int COUNT, int GROUPN, int CACHE = 1, bool REACH = false, int NWT = 0>
 __device__ __forceinline__ float pk_pcf_shadow(const SceneLds &sc, int nObj, v3 origin, bool need, const Box3 &ob,
-                                               bool obFinite, float4 myMin, float4 myMax, bool myNan, int ltype,
+                                               bool obFinite, int ltype,
                                                int pcfSamples, float filterSize, v3 lightDir, float limit, float nz,
                                                float maxDist, unsigned &rays, int tabF4 = -1, v3 lightPos = V3(0.f, 0.f, 0.f),
                                                float lightDist = 0.0f, int li = 0, float nn = 0.0f) {
@@ -1031,7 +917,7 @@ __device__ __forceinline__ float pk_pcf_shadow(const SceneLds &sc, int nObj, v3 
             v3 jd = (lightDir + (tangent * rx) * filterSize) + (bitangent * ry) * filterSize;
             if (ltype != 1) jd = normalize(jd);
             Ray sr; sr.o = origin; sr.d = jd;
-            bool occ = pk_trace_any<COUNT>(sc, nObj, sr, need, ob, obFinite, myMin, myMax, myNan, maxDist, limit, rays);
+            bool occ = pk_trace_any<COUNT>(sc, nObj, sr, need, ob, obFinite, maxDist, limit, rays);
             shadow += occ ? 0.0f : 1.0f;
         }
         return shadow / (float)pcfSamples;
@@ -1063,18 +949,9 @@ __device__ __forceinline__ float pk_pcf_shadow(const SceneLds &sc, int nObj, v3 
     // The reciprocal box only has to CONTAIN the reciprocals (it feeds the conservative cull, never a pixel), so the
     // six wave-uniform divisions need not be IEEE: v_rcp_f32 (1 ulp) widened outward by 3e-7 relative is rigorous
     // and a third of the instructions.  The 1 % slack of the jitter bound likewise absorbs the approximate division.
-#ifndef RT_PK_FAST_RCPBOX
-#define RT_PK_FAST_RCPBOX 1
-#endif
-#if RT_PK_FAST_RCPBOX
     const float delta = (4.0f * fsA * __builtin_amdgcn_rcpf(1.0f - 2.0f * fsA)) * 1.01f + 2e-5f;
     auto rcp_lo = [](float x) { const float r = __builtin_amdgcn_rcpf(x); return r - fabsf(r) * 3e-7f; };
     auto rcp_hi = [](float x) { const float r = __builtin_amdgcn_rcpf(x); return r + fabsf(r) * 3e-7f; };
-#else
-    const float delta = (4.0f * fsA / (1.0f - 2.0f * fsA)) * 1.01f + 2e-5f;
-    auto rcp_lo = [](float x) { return 1.0f / x; };
-    auto rcp_hi = [](float x) { return 1.0f / x; };
-#endif
     // reciprocal-direction box of the jittered rays from the box of the lanes' light directions
     auto inv_box = [&](const Box3 &b, Packet &p) {
         float dlo = b.lox - delta, dhi = b.hix + delta;
@@ -1088,41 +965,16 @@ __device__ __forceinline__ float pk_pcf_shadow(const SceneLds &sc, int nObj, v3 
         p.okz = (dlo > 0.0f || dhi < 0.0f) && finite_f(p.inv.loz) && finite_f(p.inv.hiz);
     };
     if constexpr (NWT == 0) inv_box(lb, pk);
-    // Candidate mask of one chunk for this light's rays.  Like pk_ray_mask: when the lanes' light directions straddle zero on
-    // an axis (a light roughly above the tile: x and z change sign across it), the packet is culled per OCTANT of the light
+    // Candidate mask of one chunk for this light's rays.  `split` (false in every profile): when the lanes' light directions straddle
+    // zero on an axis (a light roughly above the tile: x and z change sign across it), the packet is culled per OCTANT of the light
     // direction -- each sub-packet's direction box is its lanes' light-direction box widened by the jitter bound, so it still
     // contains every jittered ray of its lanes (a component within `delta` of zero simply keeps straddling and loses the axis).
+    // (Stays although no profile switches it on: without this branch the table-less kernels compile 2.5 % slower, DESIGN.md section 18.)
     const bool splitLight = NWT == 0 && sc.split && ltype != 1 && pk.cull && !(pk.okx && pk.oky && pk.okz);       // wave-uniform
-    // convergent-packet cull (see wedge_cull): point / area lights only
-    bool wedgeOn = false;
-    float deltaTot = 0.0f;
-    v3 Lw = V3(0.0f, 0.0f, 0.0f);
-    if (NWT == 0 && sc.wedge && ltype != 1 && pk.cull) {
-        Lw = V3(__int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(lightPos.x))),
-                __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(lightPos.y))),
-                __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(lightPos.z))));
-        const v3 aimErr = (origin + lightDir * lightDist) - Lw;       // the rays aim at origin + lightDir*|L - P|, not exactly at L
-        const Box3 eb = wave_box(aimErr, need);
-        const float epsA = fmaxf(fmaxf(fmaxf(fabsf(eb.lox), fabsf(eb.hix)), fmaxf(fabsf(eb.loy), fabsf(eb.hiy))), fmaxf(fabsf(eb.loz), fabsf(eb.hiz)));
-        const float gx = fmaxf(fmaxf(ob.lox - Lw.x, Lw.x - ob.hix), 0.0f), gy = fmaxf(fmaxf(ob.loy - Lw.y, Lw.y - ob.hiy), 0.0f),
-                    gz = fmaxf(fmaxf(ob.loz - Lw.z, Lw.z - ob.hiz), 0.0f);
-        const float dmin2 = (gz * gz + gy * gy) + gx * gx;            // squared distance from L to the origin box
-        deltaTot = delta + 1.8f * epsA * __builtin_amdgcn_rsqf(dmin2) * 1.001f;      // (rsq(0) = inf: no culling)
-        wedgeOn = finite_f(Lw.x) && finite_f(Lw.y) && finite_f(Lw.z) && (epsA == epsA);
-    }
-#ifndef RT_PK_WEDGE_MIN
-#define RT_PK_WEDGE_MIN 16      // run the wedge test on a chunk only if the slab test left at least this many candidates in it
-#endif
-    auto wedge_prune = [&](unsigned long long m, float4 bmn, float4 bmx, bool objNan) -> unsigned long long {
-        if (wedgeOn && __builtin_popcountll(m) >= RT_PK_WEDGE_MIN)           // wave-uniform
-            m &= __builtin_amdgcn_ballot_w64(objNan || !wedge_cull(ob, Lw, deltaTot, bmn, bmx));
-        return m;
-    };
-    auto light_mask = [&](float4 bmn, float4 bmx, bool objValid, bool objNan, unsigned long long &ap) -> unsigned long long {
+    auto light_mask = [&](float4 bmn, float4 bmx, bool objValid, bool objNan) -> unsigned long long {
         if (splitLight) {
-            ap = 0ull;
             const unsigned oct = sign_octant(lightDir);
-            unsigned long long rem = __builtin_amdgcn_ballot_w64(need), m = 0ull, apq;
+            unsigned long long rem = __builtin_amdgcn_ballot_w64(need), m = 0ull;
             while (rem) {
                 const unsigned o = (unsigned)__builtin_amdgcn_readlane((int)oct, __builtin_ctzll(rem));
                 const bool sel = need && oct == o;
@@ -1131,11 +983,11 @@ __device__ __forceinline__ float pk_pcf_shadow(const SceneLds &sc, int nObj, v3 
                 q.o = pk.o;
                 q.cull = true;
                 inv_box(wave_box(lightDir, sel), q);
-                m |= pk_candidates(q, bmn, bmx, objValid, objNan, maxDist, apq);
+                m |= pk_candidates(q, bmn, bmx, objValid, objNan, maxDist);
             }
-            return wedge_prune(m, bmn, bmx, objNan);
+            return m;
         }
-        return wedge_prune(pk_candidates(pk, bmn, bmx, objValid, objNan, maxDist, ap), bmn, bmx, objNan);
+        return pk_candidates(pk, bmn, bmx, objValid, objNan, maxDist);
     };
     // ---- table path: every lane gathers its cell, the wave ORs the masks (NWT dwords = up to CACHE 64-object chunks)
     unsigned long long tm[CACHE];
@@ -1183,11 +1035,10 @@ __device__ __forceinline__ float pk_pcf_shadow(const SceneLds &sc, int nObj, v3 
         cm[c] = tm[c];
         if (NWT == 0 && cached && c < nChunks) {
             const int base = c * 64;
-            float4 b0 = myMin, b1 = myMax;
-            bool bn = myNan;
-            if ((c > 0 || !sc.keepAabb) && base + lane < nObj) { b0 = pk_bounds(sc, base + lane, 0); b1 = pk_bounds(sc, base + lane, 1); bn = bounds_nan(b0, b1); }
-            unsigned long long apc;
-            cm[c] = light_mask(b0, b1, base + lane < nObj, bn, apc);
+            float4 b0 = make_float4(0.f, 0.f, 0.f, 0.f), b1 = make_float4(0.f, 0.f, 0.f, 0.f);
+            bool bn = false;
+            if (base + lane < nObj) { b0 = pk_bounds(sc, base + lane, 0); b1 = pk_bounds(sc, base + lane, 1); bn = bounds_nan(b0, b1); }
+            cm[c] = light_mask(b0, b1, base + lane < nObj, bn);
             if (c == 0) pk_stat<COUNT>(sc, 1, (unsigned long long)pcfSamples);
             pk_stat<COUNT>(sc, 2, (unsigned long long)__builtin_popcountll(cm[c]) * (unsigned long long)pcfSamples);
             pk_stat<COUNT>(sc, (pk.cull && pk.okx && pk.oky && pk.okz) ? 9 : 10, (unsigned long long)__builtin_popcountll(cm[c]) * (unsigned long long)pcfSamples);
@@ -1212,29 +1063,12 @@ __device__ __forceinline__ float pk_pcf_shadow(const SceneLds &sc, int nObj, v3 
     //                  or  p + |r| + s*eta' < 0                               (wholly behind the origin: t > 0 fails)
     //                  or  p - |r| - s*eta' > limit   (point / area lights)   (wholly beyond the light: t < limit fails)
     // with eta' = eta + 1e-4.  NaN / infinite operands make the comparisons false (the candidate stays) except s^2 = inf, where
-    // the exact test cannot report a hit either (its discriminant is -inf or NaN); planes and unknown types always stay.
+    // the exact test cannot report a hit either (its discriminant is -inf or NaN); planes and unknown types always stay (testing
+    // them on their AABB here as well was measured and removed: DESIGN.md section 4 item 16).
     // ~28 VALU per candidate against two exact slab tests per candidate and PAIR of samples: pays from 3 samples per light on.
-    if constexpr (REACH > 0) {
+    if constexpr (REACH) {
     if (cached && pk.cull && pcfSamples >= RT_PK_REACH_MIN_SAMPLES) {          // wave-uniform
         const float etaP = fsA * 1.41563f + 1.02e-4f;
-        // Planes (and anything that is not a sphere) are tested on their AABB instead, from RT_PK_CONE_MIN_SAMPLES samples on (the test
-        // is dearer and their boxes are large): one interval slab test per (lane, candidate) -- exact origin, reciprocal-direction
-        // interval of lightDir +- delta per component -- bounds all of the lane's samples the same rigorous way the packet test does
-        // (monotone rounding; an axis whose direction interval touches zero, or a NaN direction, drops out; NaN bounds stay).
-        const bool boxLevel = REACH > 1 && pcfSamples >= RT_PK_CONE_MIN_SAMPLES;          // (REACH 1: spheres only)
-        v3 ilo = V3(0.0f, 0.0f, 0.0f), ihi = ilo;
-        bool okx = false, oky = false, okz = false;
-        if (boxLevel) {
-            float dlo = lightDir.x - delta, dhi = lightDir.x + delta;
-            ilo.x = rcp_lo(dhi); ihi.x = rcp_hi(dlo);
-            okx = (dlo > 0.0f || dhi < 0.0f) && finite_f(ilo.x) && finite_f(ihi.x);
-            dlo = lightDir.y - delta; dhi = lightDir.y + delta;
-            ilo.y = rcp_lo(dhi); ihi.y = rcp_hi(dlo);
-            oky = (dlo > 0.0f || dhi < 0.0f) && finite_f(ilo.y) && finite_f(ihi.y);
-            dlo = lightDir.z - delta; dhi = lightDir.z + delta;
-            ilo.z = rcp_lo(dhi); ihi.z = rcp_hi(dlo);
-            okz = (dlo > 0.0f || dhi < 0.0f) && finite_f(ilo.z) && finite_f(ihi.z);
-        }
 #pragma unroll
         for (int c = 0; c < CACHE; c++) {
             unsigned long long m = cm[c], keep = 0ull;
@@ -1254,15 +1088,6 @@ __device__ __forceinline__ float pk_pcf_shadow(const SceneLds &sc, int nObj, v3 
                     const bool behind = p + rr < 0.0f;
                     const bool beyond = (ltype != 1) && (p - rr > limit);
                     reach = need && !(beside || behind || beyond);
-                } else if (boxLevel) {
-                    const float4 h1 = uni_load4(sc, i * RT_HOT_F4 + 1);
-                    float lbx, ubx, lby, uby, lbz, ubz, u0, u1;
-                    pk_axis(h0.x, h1.x, origin.x, origin.x, ilo.x, ihi.x, okx, lbx, ubx, u0, u1);
-                    pk_axis(h0.y, h1.y, origin.y, origin.y, ilo.y, ihi.y, oky, lby, uby, u0, u1);
-                    pk_axis(h0.z, h1.z, origin.z, origin.z, ilo.z, ihi.z, okz, lbz, ubz, u0, u1);
-                    const float enter = fmaxf(fmaxf(lbx, lby), lbz), leave = fminf(fminf(ubx, uby), ubz);
-                    const bool dead = (leave < enter) || (enter >= maxDist) || (leave <= 0.0f);
-                    reach = need && (bounds_nan(h0, h1) || !dead);
                 }
                 if (wave_any(reach)) keep |= 1ull << bit;
             }
@@ -1344,18 +1169,18 @@ __device__ __forceinline__ float pk_pcf_shadow(const SceneLds &sc, int nObj, v3 
         }
         for (int base = 0; base < nObj; base += 64) {
             const int ci = base >> 6;
-            unsigned long long m = 0ull, ap = 0ull;
+            unsigned long long m = 0ull;
 #pragma unroll
             for (int c = 0; c < CACHE; c++) m = (ci == c) ? cm[c] : m;        // wave-uniform select, no dynamic SGPR index
             if (NWT == 0 && !cached) {
-                float4 bmn = myMin, bmx = myMax;
-                bool bnan = myNan;
-                if ((base > 0 || !sc.keepAabb) && base + lane < nObj) {
+                float4 bmn = make_float4(0.f, 0.f, 0.f, 0.f), bmx = make_float4(0.f, 0.f, 0.f, 0.f);          // (lanes beyond the scene: objValid is false)
+                bool bnan = false;
+                if (base + lane < nObj) {
                     bmn = pk_bounds(sc, base + lane, 0);
                     bmx = pk_bounds(sc, base + lane, 1);
                     bnan = bounds_nan(bmn, bmx);
                 }
-                m = light_mask(bmn, bmx, base + lane < nObj, bnan, ap);
+                m = light_mask(bmn, bmx, base + lane < nObj, bnan);
                 const int ns = pcfSamples - s0 < GROUPN ? pcfSamples - s0 : GROUPN;
                 if (base == 0) pk_stat<COUNT>(sc, 1, (unsigned long long)ns);
                 pk_stat<COUNT>(sc, 2, (unsigned long long)__builtin_popcountll(m) * (unsigned long long)ns);
@@ -1371,20 +1196,13 @@ __device__ __forceinline__ float pk_pcf_shadow(const SceneLds &sc, int nObj, v3 
                 const int i = base + bit;
                 m &= m - 1;
                 const float4 h0 = uni_load4(sc, i * RT_HOT_F4), h1 = uni_load4(sc, i * RT_HOT_F4 + 1);
-#if RT_PK_FETCH4
-                const float4 hpre[2] = {uni_load4(sc, i * RT_HOT_F4 + 2), uni_load4(sc, i * RT_HOT_F4 + 3)};
-                const float4 *hp = hpre;
-#else
-                const float4 *hp = nullptr;
-#endif
                 const int type = __float_as_int(h0.w);
-                const bool sure = (ap >> bit) & 1ull;      // wave-uniform
 #if RT_PK_TIMERS
                 pk_stat<COUNT>(sc, 22, 1);                                       // [22] candidate trips of the sample loops
                 {
                     bool anyPass = false;
 #pragma unroll
-                    for (int k = 0; k < GROUPN; k++) anyPass |= todo[k] && (sure || aabb_test(sr[k], inv[k], h0, h1, maxDist));
+                    for (int k = 0; k < GROUPN; k++) anyPass |= todo[k] && aabb_test(sr[k], inv[k], h0, h1, maxDist);
                     if (wave_any(anyPass)) pk_stat<COUNT>(sc, 23, 1);            // [23] ... in which some lane passes the slab test
                     pk_stat<COUNT>(sc, 24, (unsigned long long)__builtin_popcountll(__builtin_amdgcn_ballot_w64(anyPass)));   // [24] lanes passing
                 }
@@ -1392,16 +1210,16 @@ __device__ __forceinline__ float pk_pcf_shadow(const SceneLds &sc, int nObj, v3 
 #pragma unroll
                 for (int k = 0; k < GROUPN; k++) {
                     if (sc.straight & 4) {
-                    const bool pass = todo[k] & (sure | aabb_test(sr[k], inv[k], h0, h1, maxDist));
+                    const bool pass = todo[k] & aabb_test(sr[k], inv[k], h0, h1, maxDist);
                     if (pk_wave_any(pass)) {
                         float t = 0.0f;
-                        const bool occ = pk_shape_hit(sc, sr[k], a[k], i, h1.w, type, pass, t, hp) & (t > 0.0f) & (t < limit);
+                        const bool occ = pk_shape_hit(sc, sr[k], a[k], i, h1.w, type, pass, t) & (t > 0.0f) & (t < limit);
                         todo[k] = todo[k] & !occ;
                     }
                     } else {
-                    if (todo[k] && (sure || aabb_test(sr[k], inv[k], h0, h1, maxDist))) {
+                    if (todo[k] && aabb_test(sr[k], inv[k], h0, h1, maxDist)) {
                         float t;
-                        if (pk_shape_test(sc, sr[k], a[k], i, h1.w, type, t, hp) && t > 0.0f && t < limit) todo[k] = false;
+                        if (pk_shape_test(sc, sr[k], a[k], i, h1.w, type, t) && t > 0.0f && t < limit) todo[k] = false;
                     }
                     }
                 }
@@ -1419,20 +1237,19 @@ __device__ __forceinline__ float pk_pcf_shadow(const SceneLds &sc, int nObj, v3 
     const unsigned long long tMasks = pk_clock<COUNT>();
     pk_stat<COUNT>(sc, 13, tMasks - tEnter);
     for (int base = 0; base < nObj; base += 64) {
-        float4 bmn = myMin, bmx = myMax;
-        bool bnan = myNan;
-        if (NWT == 0 && (base > 0 || !sc.keepAabb) && base + lane < nObj) {
+        float4 bmn = make_float4(0.f, 0.f, 0.f, 0.f), bmx = make_float4(0.f, 0.f, 0.f, 0.f);          // (lanes beyond the scene: objValid is false)
+        bool bnan = false;
+        if (NWT == 0 && base + lane < nObj) {
             bmn = pk_bounds(sc, base + lane, 0);
             bmx = pk_bounds(sc, base + lane, 1);
             bnan = bounds_nan(bmn, bmx);
         }
-        unsigned long long ap = 0ull;
         unsigned long long mask = 0ull;
         if constexpr (NWT > 0) {
 #pragma unroll
             for (int c = 0; c < CACHE; c++) mask = ((base >> 6) == c) ? tm[c] : mask;
         } else {
-            mask = light_mask(bmn, bmx, base + lane < nObj, bnan, ap);
+            mask = light_mask(bmn, bmx, base + lane < nObj, bnan);
         }
         if (NWT == 0)
         pk_stat<COUNT>(sc, 2, (unsigned long long)__builtin_popcountll(mask) * (unsigned long long)pcfSamples);
@@ -1463,24 +1280,17 @@ __device__ __forceinline__ float pk_pcf_shadow(const SceneLds &sc, int nObj, v3 
                 const int i = base + bit;
                 m &= m - 1;
                 const float4 h0 = uni_load4(sc, i * RT_HOT_F4), h1 = uni_load4(sc, i * RT_HOT_F4 + 1);
-#if RT_PK_FETCH4
-                const float4 hpre[2] = {uni_load4(sc, i * RT_HOT_F4 + 2), uni_load4(sc, i * RT_HOT_F4 + 3)};
-                const float4 *hp = hpre;
-#else
-                const float4 *hp = nullptr;
-#endif
-                const bool sure = (ap >> bit) & 1ull;      // wave-uniform
                 if (sc.straight & 8) {
-                const bool pass = todo & (sure | aabb_test(sr, inv, h0, h1, maxDist));
+                const bool pass = todo & aabb_test(sr, inv, h0, h1, maxDist);
                 if (pk_wave_any(pass)) {
                     float t = 0.0f;
-                    const bool occ = pk_shape_hit(sc, sr, a, i, h1.w, __float_as_int(h0.w), pass, t, hp) & (t > 0.0f) & (t < limit);
+                    const bool occ = pk_shape_hit(sc, sr, a, i, h1.w, __float_as_int(h0.w), pass, t) & (t > 0.0f) & (t < limit);
                     todo = todo & !occ;
                 }
                 } else {
-                if (todo && (sure || aabb_test(sr, inv, h0, h1, maxDist))) {
+                if (todo && aabb_test(sr, inv, h0, h1, maxDist)) {
                     float t;
-                    if (pk_shape_test(sc, sr, a, i, h1.w, __float_as_int(h0.w), t, hp) && t > 0.0f && t < limit) todo = false;
+                    if (pk_shape_test(sc, sr, a, i, h1.w, __float_as_int(h0.w), t) && t > 0.0f && t < limit) todo = false;
                 }
                 }
                 if (!wave_any(todo)) break;
@@ -1500,26 +1310,19 @@ template <int COUNT, int BT, typename PROFILE>
 __device__ __forceinline__ void render_packet(const RtFrame &f, const RtDeviceScene &dsc, const SceneLds &sc,
                                               float4 *gColor,
                                               float4 *gPosition, uint2 *gNormal, unsigned &rays) {
+    static_assert(BT == 64, "one-wave workgroups: the 8x8 tile and the parking area's stride assume it");
     constexpr int GROUPN = PROFILE::groupN;
-    constexpr bool PARK2 = PROFILE::park2;
-    const int lane = threadIdx.x & 63;
-    (void)lane;
     const int nObj = f.nObj;
     const float maxDist = f.p.maxRayDistance;
     pk_timers_begin<COUNT>();
     const unsigned long long tWave = pk_clock<COUNT>();
-    // this lane's object (first 64-object chunk) stays in registers for every cull pass
-    float4 myMin = make_float4(0.f, 0.f, 0.f, 0.f), myMax = myMin;          // (placeholders when the profile re-reads chunk 0 from LDS)
-    if (PROFILE::keepAabb && lane < nObj) { myMin = pk_bounds(sc, lane, 0); myMax = pk_bounds(sc, lane, 1); }
-    const bool myNan = PROFILE::keepAabb ? bounds_nan(myMin, myMax) : false;
 
     // lane -> pixel (wave w owns the 8x8 tile (w&1, w>>1) of the 16x16 workgroup tile).  The ids are
     // recomputed at their three points of use instead of staying live across the bounce loop.
     auto pixel = [&](int &gxI, int &gyI, size_t &outIdx) -> bool {
         const int wave = threadIdx.x >> 6, ln = threadIdx.x & 63;
-        constexpr int TILE_ = (BT == 256) ? 16 : 8;
-        const int i = sc.tileX * TILE_ + (wave & 1) * 8 + (ln & 7);
-        const int j = sc.tileY * TILE_ + (wave >> 1) * 8 + (ln >> 3);
+        const int i = sc.tileX * 8 + (wave & 1) * 8 + (ln & 7);
+        const int j = sc.tileY * 8 + (wave >> 1) * 8 + (ln >> 3);
         gxI = f.p.x0 + i;
         const int ly = f.p.y0 + j;
         gyI = (ly / f.p.stripRows) * f.p.stripCycleRows + f.p.stripOffsetRows + ly % f.p.stripRows;
@@ -1550,11 +1353,15 @@ __device__ __forceinline__ void render_packet(const RtFrame &f, const RtDeviceSc
         ray.o = V3(f.p.camPos[0], f.p.camPos[1], f.p.camPos[2]);
         ray.d = normalize((cd + cr * ux) + cu * uy);
     }
-    v3 finalColor = V3(0.0f, 0.0f, 0.0f), throughput = V3(1.0f, 1.0f, 1.0f);
+    // The path state a bounce only touches at its ends -- finalColor, throughput, the last hit's P and N -- LIVES in the parking
+    // area (SoA, one column per thread; read-modify-write where it changes) instead of travelling between registers and LDS: it
+    // is not live across the closest-hit traversal and the loop's back edge, which is where the compiler spilled (6 scratch
+    // stores per bounce at the loop header: two thirds of C2's scratch traffic).  Measured, bit-identical: scratch 96 -> 0 B/lane
+    // in LIGHT (C2 0.360 -> 0.353 ms), 156 -> 60 in HEAVY1 (C4 unchanged), 164 -> 68 in HEAVY (C5 25.5 -> 26.0 ms: +2 % for 2.4x
+    // less scratch traffic, which the paired subsurface probes it makes room for win back: 25.4 ms); PCSS profiles, with the
+    // subsurface probes in pairs: C3 3.44 -> 3.39 ms, scratch 156 -> 68 B/lane (with single probes it was 3.73).
     v3 P = V3(0.0f, 0.0f, 0.0f), N = V3(0.0f, 0.0f, 0.0f);
-    constexpr bool RESIDENT = PROFILE::resident;
-    if constexpr (RESIDENT) {
-        static_assert(!RESIDENT || PARK2, "the resident path state uses the parking area's shading-point slots");
+    {
         float *pk_ = sc.park + threadIdx.x;
         pk_[0 * BT] = 0.0f; pk_[1 * BT] = 0.0f; pk_[2 * BT] = 0.0f;            // finalColor
         pk_[3 * BT] = 1.0f; pk_[4 * BT] = 1.0f; pk_[5 * BT] = 1.0f;            // throughput
@@ -1573,20 +1380,16 @@ __device__ __forceinline__ void render_packet(const RtFrame &f, const RtDeviceSc
         if (!wave_any(alive)) break;
         float t;
         const unsigned long long tTrace = pk_clock<COUNT>();
-        int idx = pk_trace_closest<COUNT>(sc, nObj, ray, alive, rayBox, rayBoxFinite, myMin, myMax, myNan, maxDist, t, rays);
+        int idx = pk_trace_closest<COUNT>(sc, nObj, ray, alive, rayBox, rayBoxFinite, maxDist, t, rays);
         const unsigned long long tHit = pk_clock<COUNT>();
         pk_stat<COUNT>(sc, 12, tHit - tTrace);
         const bool missed = alive && idx < 0;
         if (wave_any(missed && f.p.useSkybox && dsc.sky != nullptr)) {
-            if constexpr (RESIDENT) {
             if (missed && f.p.useSkybox && dsc.sky) {
                 float *pk_ = sc.park + threadIdx.x;
                 const v3 fc = V3(pk_[0 * BT], pk_[1 * BT], pk_[2 * BT]), thr = V3(pk_[3 * BT], pk_[4 * BT], pk_[5 * BT]);
                 const v3 nf = fc + thr * sample_cube(dsc.sky, f.skySize, ray.d);
                 pk_[0 * BT] = nf.x; pk_[1 * BT] = nf.y; pk_[2 * BT] = nf.z;
-            }
-            } else {
-            if (missed && f.p.useSkybox && dsc.sky) finalColor = finalColor + throughput * sample_cube(dsc.sky, f.skySize, ray.d);
             }
         }
         alive = alive && idx >= 0;          // a miss ends the path (:533)
@@ -1602,53 +1405,34 @@ __device__ __forceinline__ void render_packet(const RtFrame &f, const RtDeviceSc
             // load (sphere centre or plane normal) used to wait for the first, two memory round trips per bounce
             const float4 hb = pk_bounds(sc, ii, 0), h2 = pk_lane_hot(sc, ii, 2), h3 = pk_lane_hot(sc, ii, 3);
             const float4 m0 = pk_lane_mat(sc, ii, 0), m1 = pk_lane_mat(sc, ii, 1);
-            if (RESIDENT || alive) {      // (resident path state: P, N are this bounce's temporaries, written to LDS for the lanes that hit)
-                P = ray.o + ray.d * t;
-                const v3 Ns = normalize(P - V3(h2));
-                N = (__float_as_int(hb.w) == 0) ? Ns : V3(h3);
-            }
+            // (P, N are this bounce's temporaries, written to the parking area for the lanes that hit)
+            P = ray.o + ray.d * t;
+            const v3 Ns = normalize(P - V3(h2));
+            N = (__float_as_int(hb.w) == 0) ? Ns : V3(h3);
             albedo = V3(m0); metallic = m0.w; roughness = m1.x;
             } else {
-            if (RESIDENT || alive) {
-                if (__float_as_int(pk_bounds(sc, ii, 0).w) == 0) N = normalize((ray.o + ray.d * t) - V3(pk_lane_hot(sc, ii, 2)));
-                else N = V3(pk_lane_hot(sc, ii, 3));
-                P = ray.o + ray.d * t;
-            }
+            if (__float_as_int(pk_bounds(sc, ii, 0).w) == 0) N = normalize((ray.o + ray.d * t) - V3(pk_lane_hot(sc, ii, 2)));
+            else N = V3(pk_lane_hot(sc, ii, 3));
+            P = ray.o + ray.d * t;
             const float4 m0 = pk_lane_mat(sc, ii, 0), m1 = pk_lane_mat(sc, ii, 1);
             albedo = V3(m0); metallic = m0.w; roughness = m1.x;
             }
         }
-        Mat m;   // view for compute_pbr (unused fields are never read there)
-        m.albedo = albedo; m.metallic = metallic; m.roughness = roughness;
         v3 V = normalize(-ray.d);
         const v3 shadowOrigin = P + N * 0.001f;
         // one origin box per bounce serves every shadow / SSS ray leaving these shading points
         const Box3 shBox = wave_box(shadowOrigin, alive);
         const bool shBoxFinite = box_finite(shBox);
 
-        if constexpr (RESIDENT) {   // the ray's direction waits in LDS for the next-direction step; the hit's P and N replace the last hit's for the lanes that hit
+        {   // the ray's direction waits in LDS for the next-direction step; the hit's P and N replace the last hit's for the lanes that hit
             float *pk_ = sc.park + threadIdx.x;
             pk_[6 * BT] = ray.d.x; pk_[7 * BT] = ray.d.y; pk_[8 * BT] = ray.d.z;
             if (alive) {
                 pk_[9 * BT] = P.x; pk_[10 * BT] = P.y; pk_[11 * BT] = P.z;
                 pk_[12 * BT] = N.x; pk_[13 * BT] = N.y; pk_[14 * BT] = N.z;
             }
-            pk_[15 * BT] = V.x; pk_[16 * BT] = V.y; pk_[17 * BT] = V.z;
-            pk_[18 * BT] = albedo.x; pk_[19 * BT] = albedo.y; pk_[20 * BT] = albedo.z;
-            pk_[21 * BT] = metallic; pk_[22 * BT] = roughness;
-        } else {
-        // park the state the lighting section does not touch in LDS (SoA, one column per thread)
-            float *pk_ = sc.park + threadIdx.x;
-            pk_[0 * BT] = finalColor.x; pk_[1 * BT] = finalColor.y; pk_[2 * BT] = finalColor.z;
-            pk_[3 * BT] = throughput.x; pk_[4 * BT] = throughput.y; pk_[5 * BT] = throughput.z;
-            pk_[6 * BT] = ray.d.x; pk_[7 * BT] = ray.d.y; pk_[8 * BT] = ray.d.z;
-        }
-        // ... and the shading point itself: constant over the light loop, needed only before (P, N: light vector, lit
-        // test) and after (N, V, material: computePBR) a light's shadow rays -- not while they are traced
-        if constexpr (PARK2 && !RESIDENT) {
-            float *pk_ = sc.park + threadIdx.x;
-            pk_[9 * BT] = P.x; pk_[10 * BT] = P.y; pk_[11 * BT] = P.z;
-            pk_[12 * BT] = N.x; pk_[13 * BT] = N.y; pk_[14 * BT] = N.z;
+            // ... and the rest of the shading point: constant over the light loop, needed only before (P, N: light vector, lit
+            // test) and after (N, V, material: computePBR) a light's shadow rays -- not while they are traced
             pk_[15 * BT] = V.x; pk_[16 * BT] = V.y; pk_[17 * BT] = V.z;
             pk_[18 * BT] = albedo.x; pk_[19 * BT] = albedo.y; pk_[20 * BT] = albedo.z;
             pk_[21 * BT] = metallic; pk_[22 * BT] = roughness;
@@ -1661,8 +1445,8 @@ __device__ __forceinline__ void render_packet(const RtFrame &f, const RtDeviceSc
             const int lb4 = sc.lgtF4Base + li * RT_LGT_F4;
             const float4 l0 = uni_load4(sc, lb4), l1 = uni_load4(sc, lb4 + 1), l2 = uni_load4(sc, lb4 + 2), l3 = uni_load4(sc, lb4 + 3);
             const int ltype = __builtin_amdgcn_readfirstlane(__float_as_int(l0.w));
-            v3 Pl = P, Nl0 = N;     // this light's view of the shading point (re-read from the parking area when parked)
-            if constexpr (PARK2) {
+            v3 Pl, Nl0;             // this light's view of the shading point, re-read from the parking area
+            {
                 asm volatile("" ::: "memory");
                 const float *pk_ = sc.park + threadIdx.x;
                 Pl = V3(pk_[9 * BT], pk_[10 * BT], pk_[11 * BT]);
@@ -1701,7 +1485,6 @@ __device__ __forceinline__ void render_packet(const RtFrame &f, const RtDeviceSc
                 // zero samples is 0/0, :396); the instrumented build traces everything so that its ray count stays
                 // the reference's.
                 bool lit = alive;
-#if RT_PK_SKIP_UNLIT
                 if (COUNT != 1 && pcfSamples >= 1) {
                     // ... and the same holds where the light's radiance (color * attenuation) * intensity (:493) is +-0
                     // or NaN in all three channels (an area light facing away from the point, :487-489; a black light)
@@ -1710,7 +1493,6 @@ __device__ __forceinline__ void render_packet(const RtFrame &f, const RtDeviceSc
                                         ((rad.z != 0.0f) & (rad.z == rad.z));
                     lit = alive && shines && (fmaxf(dot(Nl0, normalize(lightDir)), 0.0f) > 0.0f);
                 }
-#endif
                 bool needPcf = lit;
                 if (shadowType == 2) {          // pcssShadow (:400-440): 16 blocker rays, then PCF if any
                     const float searchSize = l3.z;
@@ -1750,8 +1532,7 @@ __device__ __forceinline__ void render_packet(const RtFrame &f, const RtDeviceSc
                             const float rr = pk_halton(sc, 1, s + k, 3) * 2.0f - 1.0f;
                             bd[k] = normalize((lightDir + splat(rr * searchSize)) + splat(rr * searchSize));
                         }
-                        anyBlocker |= pk_trace_any_group<COUNT, NB>(sc, nObj, shadowOrigin, bd, search, shBox, shBoxFinite, myMin, myMax, myNan,
-                                                                    maxDist, limit, rays);
+                        anyBlocker |= pk_trace_any_group<COUNT, NB>(sc, nObj, shadowOrigin, bd, search, shBox, shBoxFinite, maxDist, limit, rays);
                     }
                     } else {
                     for (int s = 0; s < 16; s++) {
@@ -1760,15 +1541,15 @@ __device__ __forceinline__ void render_packet(const RtFrame &f, const RtDeviceSc
                         float rr = pk_halton(sc, 1, s, 3) * 2.0f - 1.0f;
                         v3 sd = (lightDir + splat(rr * searchSize)) + splat(rr * searchSize);
                         Ray sr; sr.o = shadowOrigin; sr.d = normalize(sd);
-                        anyBlocker |= pk_trace_any<COUNT>(sc, nObj, sr, search, shBox, shBoxFinite, myMin, myMax, myNan, maxDist, limit, rays);
+                        anyBlocker |= pk_trace_any<COUNT>(sc, nObj, sr, search, shBox, shBoxFinite, maxDist, limit, rays);
                     }
                     }
                     needPcf = lit && anyBlocker;
                     pk_stat<COUNT>(sc, 28, pk_clock<COUNT>() - tBlk);            // [28] PCSS blocker search
                 }
                 if (wave_any(needPcf)) {        // pcfShadow (:342-397)
-                    float shadow = pk_pcf_shadow<COUNT, GROUPN, PROFILE::cacheChunks, PROFILE::reach, PROFILE::tabWords>(sc, nObj, shadowOrigin, needPcf, shBox, shBoxFinite, myMin, myMax,
-                                                        myNan, ltype, pcfSamples, filterSize, lightDir, limit, nz, maxDist, rays,
+                    float shadow = pk_pcf_shadow<COUNT, GROUPN, PROFILE::cacheChunks, PROFILE::reach, PROFILE::tabWords>(sc, nObj, shadowOrigin, needPcf, shBox, shBoxFinite,
+                                                        ltype, pcfSamples, filterSize, lightDir, limit, nz, maxDist, rays,
                                                         (ltype == 1 && sc.pcfTabF4 >= 0) ? sc.pcfTabF4 + li * (RT_PCF_TAB_N * 2) : -1,
                                                         V3(l0), lightDistance, li, dot(Nl0, Nl0));
                     if (needPcf) shadowFactor = shadow;
@@ -1776,9 +1557,9 @@ __device__ __forceinline__ void render_packet(const RtFrame &f, const RtDeviceSc
             } else if (shadowType != 0) {
                 shadowFactor = 0.0f;            // calculateShadow's fall-through (:445)
             }
-            v3 Nl = Nl0, Vl = V;
-            Mat ml = m;
-            if constexpr (PARK2) {
+            v3 Nl, Vl;
+            Mat ml;   // view for compute_pbr (unused fields are never read there)
+            {
                 asm volatile("" ::: "memory");      // keep these reads AFTER the shadow rays: that is the whole point
                 const float *pk_ = sc.park + threadIdx.x;
                 Nl = V3(pk_[12 * BT], pk_[13 * BT], pk_[14 * BT]);
@@ -1813,8 +1594,8 @@ __device__ __forceinline__ void render_packet(const RtFrame &f, const RtDeviceSc
             if constexpr (PROFILE::sssGroup > 1) {       // the four probes PROFILE::sssGroup per traversal
                 constexpr int NS = PROFILE::sssGroup;
                 for (int s0 = 0; s0 < 4; s0 += NS) {
-                    v3 Ns = N;
-                    if constexpr (PARK2) {
+                    v3 Ns;
+                    {
                         asm volatile("" ::: "memory");
                         const float *pkn_ = sc.park + threadIdx.x;
                         Ns = V3(pkn_[12 * BT], pkn_[13 * BT], pkn_[14 * BT]);
@@ -1824,7 +1605,7 @@ __device__ __forceinline__ void render_packet(const RtFrame &f, const RtDeviceSc
                     for (int s = 0; s < NS; s++) pd[s] = hemisphere_dir(V3(f.sssHemi[s0 + s][0], f.sssHemi[s0 + s][1], f.sssHemi[s0 + s][2]), Ns);
                     int sid[NS];
                     float tsd[NS];
-                    pk_trace_closest_group<COUNT, NS>(sc, nObj, shadowOrigin, pd, needSss, shBox, shBoxFinite, myMin, myMax, myNan, maxDist, sid, tsd, rays);
+                    pk_trace_closest_group<COUNT, NS>(sc, nObj, shadowOrigin, pd, needSss, shBox, shBoxFinite, maxDist, sid, tsd, rays);
 #pragma unroll
                     for (int s = 0; s < NS; s++) {
                         if (needSss && sid[s] >= 0) {
@@ -1837,15 +1618,15 @@ __device__ __forceinline__ void render_packet(const RtFrame &f, const RtDeviceSc
             for (int s = 0; s < 4; s++) {
                 Ray r;
                 r.o = shadowOrigin;
-                v3 Ns = N;
-                if constexpr (PARK2) {      // the normal stays parked around the traversal
+                v3 Ns;
+                {      // the normal stays parked around the traversal
                     asm volatile("" ::: "memory");
                     const float *pkn_ = sc.park + threadIdx.x;
                     Ns = V3(pkn_[12 * BT], pkn_[13 * BT], pkn_[14 * BT]);
                 }
                 r.d = hemisphere_dir(V3(f.sssHemi[s][0], f.sssHemi[s][1], f.sssHemi[s][2]), Ns);
                 float ts;
-                int si = pk_trace_closest<COUNT>(sc, nObj, r, needSss, shBox, shBoxFinite, myMin, myMax, myNan, maxDist, ts, rays);
+                int si = pk_trace_closest<COUNT>(sc, nObj, r, needSss, shBox, shBoxFinite, maxDist, ts, rays);
                 if (needSss && si >= 0) {
                     float att = det_expf(-ts / scatterDistance);
                     sss = sss + V3(pk_lane_mat(sc, si, 0)) * att;
@@ -1855,7 +1636,6 @@ __device__ __forceinline__ void render_packet(const RtFrame &f, const RtDeviceSc
         }
         const unsigned long long tAfter = pk_clock<COUNT>();
         pk_stat<COUNT>(sc, 27, tAfter - tSss);                                   // [27] subsurface section
-        if constexpr (RESIDENT) {
         if (alive) {        // finalColor += throughput * Lo, in place
             asm volatile("" ::: "memory");
             float *pk_ = sc.park + threadIdx.x;
@@ -1913,64 +1693,6 @@ __device__ __forceinline__ void render_packet(const RtFrame &f, const RtDeviceSc
             ray.d = nd; ray.o = no;
             if (alive) { pk_[3 * BT] = thr.x; pk_[4 * BT] = thr.y; pk_[5 * BT] = thr.z; }
         }
-        } else {
-        {
-            asm volatile("" ::: "memory");
-            const float *pk_ = sc.park + threadIdx.x;
-            finalColor = V3(pk_[0 * BT], pk_[1 * BT], pk_[2 * BT]);
-            throughput = V3(pk_[3 * BT], pk_[4 * BT], pk_[5 * BT]);
-            ray.d = V3(pk_[6 * BT], pk_[7 * BT], pk_[8 * BT]);
-        }
-        if (alive) finalColor = finalColor + throughput * Lo;
-        if constexpr (PARK2) {   // the bounce-level copies come back for the roulette, the next direction and the final stores
-            const float *pk_ = sc.park + threadIdx.x;
-            P = V3(pk_[9 * BT], pk_[10 * BT], pk_[11 * BT]);
-            N = V3(pk_[12 * BT], pk_[13 * BT], pk_[14 * BT]);
-            V = V3(pk_[15 * BT], pk_[16 * BT], pk_[17 * BT]);
-            m.albedo = V3(pk_[18 * BT], pk_[19 * BT], pk_[20 * BT]);
-            m.roughness = pk_[22 * BT];
-        }
-
-        // After the last iteration nothing reads `alive`, `throughput` or the ray again (the stores below take
-        // finalColor and the last hit's P / N), so its Russian roulette and bounce set-up are dead (SURVEY.md
-        // A.1#17: at MAX_RAY_DEPTH = 4 the roulette can never change the output).
-        if (depth + 1 >= f.p.maxRayDepth) break;
-        const float4 mb = pk_lane_mat(sc, ii, 1);             // (roughness, diffuseStrength, ior, transparency)
-        const float diffuseStrength = mb.y, ior = mb.z, transparency = mb.w;
-        if (depth > 2) {   // Russian roulette (:544-549)
-            float dw = length(m.albedo) * diffuseStrength;
-            float cp = fminf(fmaxf(throughput.x, fmaxf(throughput.y, throughput.z)) * 0.95f + dw, 0.99f);
-            bool stop = false;
-            if (alive) {
-                int rx_, ry_; size_t ro_;
-                pixel(rx_, ry_, ro_);
-                float rnd = random2((float)((unsigned)rx_ + (unsigned)depth), (float)((unsigned)ry_ + (unsigned)depth));
-                stop = rnd > cp;
-            }
-            if (alive && !stop) throughput = div3(throughput, cp);
-            alive = alive && !stop;
-        }
-        // ---- next direction (:552-576)
-        if (alive) {
-            float F = fresnel_schlick(fmaxf(dot(V, N), 0.0f), ior);
-            if (diffuseStrength > 0.0f) {
-                const int dd = depth < RT_MAX_DEPTH ? depth : RT_MAX_DEPTH - 1;
-                v3 sd = reflect(ray.d, N);
-                v3 hd = hemisphere_dir(V3(f.hemi[dd][0], f.hemi[dd][1], f.hemi[dd][2]), N);
-                ray.d = normalize(mix_fast(sd, hd, m.roughness));
-                ray.o = P + N * 0.001f;
-                throughput = throughput * (m.albedo * diffuseStrength);
-            } else if (transparency > 0.0f) {
-                ray.d = calc_refraction(ray, N, ior);
-                ray.o = P - N * 0.001f;
-                throughput = throughput * ((m.albedo * (1.0f - F)) * transparency);
-            } else {
-                ray.d = reflect(ray.d, N);
-                ray.o = P + N * 0.001f;
-                throughput = throughput * (m.albedo * F);
-            }
-        }
-        }   // (register form of the path state)
         rayBox = wave_box(ray.o, alive);
         rayBoxFinite = box_finite(rayBox);
         pk_stat<COUNT>(sc, 30, pk_clock<COUNT>() - tAfter);                      // [30] roulette + next direction
@@ -1983,7 +1705,8 @@ __device__ __forceinline__ void render_packet(const RtFrame &f, const RtDeviceSc
     const bool inWindow = pixel(sx_, sy_, so_);
     const bool inImageS = inWindow && sx_ < f.p.width && sy_ < f.p.height;
     const size_t outIdxS = so_;
-    if constexpr (RESIDENT) {
+    v3 finalColor;
+    {
         asm volatile("" ::: "memory");
         const float *pk_ = sc.park + threadIdx.x;
         finalColor = V3(pk_[0 * BT], pk_[1 * BT], pk_[2 * BT]);

@@ -20,7 +20,9 @@ Frames are 48 x 32: 24 one-wave tiles.
    lanes which need the IEEE redo with lanes which do not);
 3. mixed magnitudes within one scene;
 4. rt_camera_rays / rt_trace_rays / rt_shade_rays on a subset of the same scenes;
-5. the shadow tables of scaled scenes against brute-force fp64 rays (soundness only).
+5. the shadow tables of scaled scenes against brute-force fp64 rays (soundness only);
+6. (not a matter of magnitudes, but this file has the table-less base scene) the packet-level light culls and the per-lane shape
+   level of scenes WITHOUT shadow tables: huge300 under PCSS lights and with 2 / 3 / 7 / 8 / 16 PCF samples per light.
 """
 import dataclasses
 import functools
@@ -254,9 +256,30 @@ def _mixed_cases():
     return out
 
 
+# ---- scenes without shadow tables: the packet-level light culls and the per-lane shape level ----------------------------------
+REACH_SAMPLES = (2, 3, 7, 8, 16)                  # below, at and above RT_PK_REACH_MIN_SAMPLES = 3, and across 8
+REACH_NAMES = ("huge300_pcss",) + tuple(f"huge300/pcf={n}" for n in REACH_SAMPLES)
+
+
+def _reach_cases():
+    """Scenes with shadow tables (<= 256 objects, <= 64 lights) take their light candidates from the tables, so the packet-level
+    light culls and the per-lane shape level of pk_pcf_shadow run in the table-less profiles only: huge300 (302 objects) under
+    PCSS lights is PkHugeS's one deterministic case, and huge300 with 2 / 3 / 7 / 8 / 16 PCF samples per light walks PkHuge
+    across the shape level's sample threshold."""
+    base = _bases()["huge300"]
+    floors = dict(finite=True, nonzero_min=0.15, hit_min=0.20)
+    out = [Case("huge300_pcss", _own(base, "huge300_pcss", lights=scenes._lights3(L.SHADOW_PCSS)), "reach", **floors)]
+    for n in REACH_SAMPLES:
+        sc = _own(base, f"huge300-pcf{n}")
+        sc.lights["pcfSamples"] = n
+        out.append(Case(f"huge300/pcf={n}", sc, "reach", **floors))
+    assert tuple(c.name for c in out) == REACH_NAMES
+    return out
+
+
 @functools.lru_cache(maxsize=None)
 def all_cases():
-    cases = _scale_cases() + _field_cases() + _mixed_cases()
+    cases = _scale_cases() + _field_cases() + _mixed_cases() + _reach_cases()
     assert len({c.name for c in cases}) == len(cases)
     return tuple(cases)
 
@@ -353,6 +376,13 @@ def test_material_and_light_magnitudes(tracer, oracle, base, field):
 @pytest.mark.parametrize("group", ["mixed-radii", "mixed-far", "mixed-fov"])
 def test_mixed_magnitudes_in_one_scene(tracer, oracle, group):
     check_cases(tracer, oracle, cases_of(group))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", REACH_NAMES)
+def test_light_culls_of_scenes_without_shadow_tables(tracer, oracle, name):
+    """One 48 x 32 frame per case of _reach_cases, in both kernel variants: surfaces bit for bit, equal ray counts."""
+    check_cases(tracer, oracle, [case(name)])
 
 
 # ---- 4. the query and shade kernels on the same scenes -----------------------------------------------------------------------------

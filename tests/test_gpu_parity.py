@@ -248,9 +248,11 @@ def test_pcf_sample_counts_and_shadow_types(tracer, host, oracle):
 @pytest.mark.parametrize("cfg,samples", [(4, 3), (4, 8), (4, 16), (5, 3), (5, 9), (5, 16)])
 def test_many_pcf_samples_in_many_object_scenes(tracer, host, oracle, cfg, samples):
     """From RT_PK_REACH_MIN_SAMPLES = 3 samples per light on, the many-object kernel profiles refine each light's candidate mask
-    per LANE on the spheres themselves before the sample loops (rt_packet.inc, RT_PK_REACH): C4's / C5's scenes at the threshold
-    (3), at 8 / 9 and at the UI's maximum of 16 PCF samples, and with a softness near the bound where the jitter interval swallows
-    whole direction components (filterSize 0.15 of the 0.2 limit)."""
+    per LANE on the spheres themselves before the sample loops (rt_packet.inc, the profiles' `reach`): C4's / C5's scenes at the
+    threshold (3), at 8 / 9 and at the UI's maximum of 16 PCF samples, and with a softness near the bound where the jitter interval
+    swallows whole direction components (filterSize 0.15 of the 0.2 limit).  Both scenes have shadow tables (PkHeavy1 / PkHeavy), so
+    what this reaches is the shape level applied to the TABLES' masks; the packet-level light culls and the shape level on their
+    masks run only in scenes without tables (PkHuge / PkHugeS): tests/test_exponent_range.py's huge300 cases pin those."""
     sc = scenes.make_scene(cfg, host.generate_aabb)
     sc.lights["pcfSamples"] = samples
     p = sc.params(width=80, height=48)
@@ -743,7 +745,7 @@ def _grazing_scene(kind, scale, offset, samples, softness, ltype, seed):
 
 @pytest.mark.parametrize("kind", ["tiny", "mixed", "huge", "axis"])
 def test_grazing_shadow_rays_far_from_the_origin(tracer, host, oracle, kind):
-    """ADVICE r2 / VERDICT r2 #4b: the per-lane sphere level (RT_PK_REACH) and the shadow tables drop candidates on margin
+    """ADVICE r2 / VERDICT r2 #4b: the per-lane sphere level (the profiles' `reach`) and the shadow tables drop candidates on margin
     arguments; this aims rays at sphere limbs -- shadow edges of tiny, huge and on-axis spheres, at scales 1 and 1e3 and offsets
     up to 1e5 from the origin, 3 / 4 / 16 samples, softness 0 to the 0.2 filter bound, point / area / directional lights (41
     objects: the many-object profile, per-lane level on from 3 samples) -- against the oracle, bit for bit."""
