@@ -623,6 +623,50 @@ int rt_display_pack_yuv(rt_context *ctx, const void *dImage, void *dOut, const r
 int rt_present_submit_yuv(rt_context *ctx, const void *dImage, const rt_yuv_desc *desc, const rt_tone_desc *tone, void *hipStream,
                           uint64_t *ticket);
 
+/* ---- resampling in linear light, in front of rt_meter / rt_display_pack* / rt_present_submit*: render at one size, deliver
+ *      another (4K -> 1080p is 4x supersampling; a fraction of the output size scaled up keeps a heavy scene at display rate).
+ *      rt_display_resample: dSrc (device, srcWidth*srcHeight rgba32f) -> dDst (device, dstWidth*dstHeight rgba32f), any ratio,
+ *      the axes independent.  Both pointers 16-byte aligned; the two ranges must not overlap.  Asynchronous on hipStream (NULL =
+ *      the context's stream).  Separable, horizontal first, every channel (alpha included) alike, in fp32 with separate
+ *      multiplies and adds (never fused), the accumulator starting as the first product and the taps in table order:
+ *        h[r][i] = (((wx[i][0]*s[r][X(i,0)]) + wx[i][1]*s[r][X(i,1)]) + ...)    X(i,k) = clamp(firstx[i]+k, 0, srcWidth-1)
+ *        d[j][i] = (((wy[j][0]*h[Y(j,0)][i]) + wy[j][1]*h[Y(j,1)][i]) + ...)    Y(j,k) = clamp(firsty[j]+k, 0, srcHeight-1)
+ *      Edge pixels are replicated (the clamps).  Zero-weight padding taps are multiplied and added like any other, so by IEEE
+ *      rules a NaN or infinite texel poisons every output whose window holds it (0 * inf = NaN), padding included.  With
+ *      src size == dst size, AREA and TRIANGLE have one tap of weight 1: the call is a bit-exact copy.
+ *      rt_resample_taps (host only, needs no GPU) returns the tables of one axis the kernel uses, source size S -> destination
+ *      size D: *nTaps = n, the taps per destination index (the same for every index of the axis); first[D], the first source
+ *      index of each window (it may be negative or reach past S-1); weights[D*n], weights[i*n+k].  first == weights == NULL
+ *      asks for n only; otherwise capWeights is the capacity of `weights` in floats (below D*n: RT_ERR_TOO_LARGE) and `first`
+ *      holds D entries.  Windows are decided in integers, weights evaluated in double and rounded to fp32 once:
+ *        AREA (exact coverage): j0 = (i*S) div D, j1 = ((i+1)*S + D - 1) div D - 1,
+ *          w_j = (min((i+1)*S, (j+1)*D) - max(i*S, j*D)) / S.
+ *        TRIANGLE: f(x) = max(0, 1-|x|), R = 1.  LANCZOS3: f(x) = sinc(x)*sinc(x/3) for |x| < 3, R = 3, sinc exactly 1 at 0 and
+ *          exactly 0 at every other x that is an integer in double.  fs = max(1, S/D), c = ((2i+1)*S - D) / (2*D); the window is
+ *          the source pixels strictly inside c +- R*fs; w_j = f(x_j) / sum f, x_j = (j-c)/fs evaluated as the one quotient
+ *          (2*D*j - (2i+1)*S + D) / (2*max(S,D)), the sum taken in window order.
+ *        n is the largest window of the axis; a shorter window starts at its own j0 and is padded with zero weights at the end.
+ *      n > RT_RESAMPLE_MAX_TAPS: RT_ERR_TOO_LARGE (LANCZOS3 reaches about 1/10 scale, AREA 1/64).
+ *      The context keeps device copies of the two axis tables, keyed by (S, D, filter) per axis: a frame loop of one shape
+ *      builds them once; a new shape waits for the last launch that read the old tables, then rebuilds and uploads.
+ *      Refused with RT_ERR_INVALID_ARG: NULL context, descriptor or pointers (rt_resample_taps: NULL nTaps, or exactly one of
+ *      first / weights NULL); misaligned or overlapping ranges; a size < 1; an unknown filter; non-zero flags or reserved words.
+ *      RT_ERR_TOO_LARGE: an axis over the tap cap or longer than 2^20 pixels; more than 2^31 - 1 tiles of 64 x 16 destination
+ *      pixels (fewer rows per tile at large ratios).  The context stays usable after a refusal.  The 1080p loop off a 4K render:
+ *          rt_render(ctx, &p4k);  rt_get_surfaces(ctx, &dColor, NULL, NULL);
+ *          rt_display_resample(ctx, dColor, dSmall, &rs, NULL);  rt_meter(ctx, dSmall, &m, dState, NULL);
+ *          rt_present_submit_toned(ctx, dSmall, &disp1080, &tone, NULL, &t); */
+typedef enum rt_resample_filter { RT_RESAMPLE_AREA = 0, RT_RESAMPLE_TRIANGLE = 1, RT_RESAMPLE_LANCZOS3 = 2 } rt_resample_filter;
+typedef struct rt_resample_desc {
+    int32_t srcWidth, srcHeight, dstWidth, dstHeight;   /* >= 1, any ratio, the axes independent */
+    int32_t filter;                                      /* rt_resample_filter */
+    uint32_t flags;                                      /* zero */
+    int32_t reserved[2];                                 /* zero */
+} rt_resample_desc;
+#define RT_RESAMPLE_MAX_TAPS 64
+int rt_resample_taps(int srcSize, int dstSize, int filter, int *nTaps, int32_t *first, float *weights, size_t capWeights);
+int rt_display_resample(rt_context *ctx, const void *dSrc, void *dDst, const rt_resample_desc *desc, void *hipStream);
+
 /* ---- multi-GPU strip helpers */
 /* Number of local rows a rank owns for interleaved strips. */
 int rt_strip_local_rows(int height, int stripRows, int stripCount, int stripIndex);
@@ -726,6 +770,8 @@ RT_SA(sizeof(rt_meter_state) == 1088 && offsetof(rt_meter_state, nPixels) == 102
 RT_SA(sizeof(rt_tone_desc) == 16 + 2 * sizeof(void *) && offsetof(rt_tone_desc, dExposure) == 8, "rt_tone_desc layout");
 RT_SA(sizeof(rt_yuv_desc) == 48 && offsetof(rt_yuv_desc, transfer) == 20 && offsetof(rt_yuv_desc, flags) == 24 &&
       offsetof(rt_yuv_desc, exposure) == 28 && offsetof(rt_yuv_desc, reserved) == 32, "rt_yuv_desc is 48 B");
+RT_SA(sizeof(rt_resample_desc) == 32 && offsetof(rt_resample_desc, filter) == 16 && offsetof(rt_resample_desc, flags) == 20 &&
+      offsetof(rt_resample_desc, reserved) == 24, "rt_resample_desc is 32 B");
 #undef RT_SA
 #endif
 

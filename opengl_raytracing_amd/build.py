@@ -15,7 +15,7 @@ LIB_PATH = os.path.join(PKG_DIR, "librt_mi355.so")
 ORACLE_DIR = os.path.join(REPO, "oracle")
 ORACLE_LIB = os.path.join(ORACLE_DIR, "liboracle_rt.so")
 
-SOURCES = ["rt_kernels.hip", "rt_post.hip", "rt_display.hip", "rt_abi.cpp", "rt_display.cpp", "rt_present.cpp", "rt_sched.cpp", "rt_host.cpp",
+SOURCES = ["rt_kernels.hip", "rt_post.hip", "rt_display.hip", "rt_abi.cpp", "rt_display.cpp", "rt_present.cpp", "rt_resample.hip", "rt_resample.cpp", "rt_sched.cpp", "rt_host.cpp",
            "rt_mgpu.cpp"]
 # every header and include file of csrc/ plus the public header: nothing to keep by hand, so no stale build from a forgotten one
 HEADERS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".inc"))) + [os.path.join(REPO, "include", "rt_mi355.h")]

@@ -152,7 +152,7 @@ int rt_create(rt_context **out, int deviceId) {
     }
     if (c->stream.create() != hipSuccess || c->evStart.create(hipEventDefault) != hipSuccess ||
         c->evStop.create(hipEventDefault) != hipSuccess || c->evScene.create(hipEventDisableTiming) != hipSuccess ||
-        c->bloomUse.create() != hipSuccess || c->ssaoUse.create() != hipSuccess || c->dRayCounter.grow(32) != hipSuccess) {
+        c->bloomUse.create() != hipSuccess || c->ssaoUse.create() != hipSuccess || c->resample.create() != hipSuccess || c->dRayCounter.grow(32) != hipSuccess) {
         rt_destroy(c);
         return RT_ERR_HIP;
     }
@@ -168,6 +168,7 @@ int rt_destroy(rt_context *c) {
     (void)c->sched.drain();            // the context's stream, the phase stream, every stream's last launch
     (void)c->bloomUse.drain();         // post passes on caller streams: the scratch they work in goes with the context
     (void)c->ssaoUse.drain();
+    (void)c->resample.drain();         // the last launch that read the resampler's tables
     (void)c->present.drain();          // frames on their way to the pinned buffers (and, before them, their packs)
     delete c;
     return RT_OK;

@@ -1,4 +1,4 @@
-// rt_context.h -- what the files that implement context entry points share (rt_abi.cpp, rt_display.cpp): the context itself,
+// rt_context.h -- what the files that implement context entry points share (rt_abi.cpp, rt_display.cpp, rt_resample.cpp): the context itself,
 // the way an entry point reports a failure, and the stream an entry point works on.  Nothing else knows the context's layout
 // (rt_mgpu.cpp drives contexts through the public ABI).  Not part of the public ABI.
 #pragma once
@@ -7,6 +7,7 @@
 
 #include "rt_device.h"
 #include "rt_present.h"
+#include "rt_resample.h"
 #include "rt_sched.h"
 
 // Everything the context allocates is held by an owner (rt_devbuf.h): after rt_destroy has drained the streams, `delete`
@@ -61,6 +62,7 @@ struct rt_context {
     DevBuf<float4> dPick;
     PinnedBuf<rt_hit> hPick;
     PresentRing present;                       // rt_present_*: the frames on their way to the host (rt_present.h)
+    ResampleTables resample;                   // rt_display_resample: the device copies of the two axis tables (rt_resample.h)
     std::string err;
 };
 

@@ -42,6 +42,7 @@ EXPORTS = [
     "rt_display_pack", "rt_display_srgb_thresholds", "rt_present_configure", "rt_present_submit", "rt_present_poll", "rt_present_wait",
     "rt_meter", "rt_meter_solve_host", "rt_meter_tables", "rt_display_pack_toned", "rt_present_submit_toned",
     "rt_display_yuv_coeffs", "rt_display_yuv_layout", "rt_display_pack_yuv", "rt_present_submit_yuv",
+    "rt_resample_taps", "rt_display_resample",
 ]
 
 
@@ -172,6 +173,8 @@ def load_library(build_if_missing=True):
     lib.rt_display_yuv_layout.argtypes = [P(L.RtYuvDesc), P(ctypes.c_size_t), P(ctypes.c_size_t), P(ctypes.c_size_t)]
     lib.rt_display_pack_yuv.argtypes = [vp, vp, vp, P(L.RtYuvDesc), P(L.RtToneDesc), vp]
     lib.rt_present_submit_yuv.argtypes = [vp, vp, P(L.RtYuvDesc), P(L.RtToneDesc), vp, P(ctypes.c_uint64)]
+    lib.rt_resample_taps.argtypes = [ci, ci, ci, P(ci), P(ctypes.c_int32), P(cf), ctypes.c_size_t]
+    lib.rt_display_resample.argtypes = [vp, vp, vp, P(L.RtResampleDesc), vp]
     for name in EXPORTS:
         if name not in ("rt_last_error", "rt_mgpu_last_error", "rt_wire_bytes"):
             getattr(lib, name).restype = ci
@@ -358,6 +361,24 @@ def yuv_planes(frame, width, height, format="nv12"):
     if L.make_yuv_desc(w, h, format=format).format == L.YUV_NV12:
         return y, frame[lay.offset[1]:].reshape(ch, cw, 2)
     return y, frame[lay.offset[1]: lay.offset[2]].reshape(ch, cw), frame[lay.offset[2]:].reshape(ch, cw)
+
+
+def resample_taps(src, dst, filter="lanczos3"):
+    """The tap table of one axis of rt_display_resample, source size `src` -> destination size `dst` (rt_resample_taps):
+    (n, first int32[dst], weights float32[dst, n]) -- destination index i reads source pixels clamp(first[i] + k, 0, src - 1),
+    k = 0..n-1, with weights[i, k] (zero padding behind a shorter window).  filter "area", "triangle" or "lanczos3".  Needs no GPU."""
+    lib = load_library()
+    f = int(L.RESAMPLE_FILTERS.get(filter, filter))
+    n = ctypes.c_int(0)
+    rc = lib.rt_resample_taps(int(src), int(dst), f, ctypes.byref(n), None, None, 0)
+    if rc:
+        raise RtError(rc, "rt_resample_taps")
+    first, weights = np.zeros(int(dst), dtype=np.int32), np.zeros((int(dst), n.value), dtype=np.float32)
+    rc = lib.rt_resample_taps(int(src), int(dst), f, ctypes.byref(n), first.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                              weights.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), weights.size)
+    if rc:
+        raise RtError(rc, "rt_resample_taps")
+    return n.value, first, weights
 
 
 def _dev_ptr(x):
@@ -664,6 +685,15 @@ class RayTracer:
         t = L.make_tone_desc(tone or "none", white, d_exposure)
         self._on_torch_stream(stream, lambda h: self._check(self.lib.rt_display_pack_toned(
             self.ctx, _dev_ptr(d_image), _dev_ptr(d_out), ctypes.byref(d), ctypes.byref(t), ctypes.c_void_p(h)), "rt_display_pack_toned"))
+
+    def resample(self, d_src, d_dst, src_w, src_h, dst_w, dst_h, filter="lanczos3", stream=None):
+        """rgba32f surface src_w x src_h -> rgba32f surface dst_w x dst_h on the device, in linear light, in front of meter /
+        display_pack / present_submit (rt_display_resample).  d_src / d_dst: raw device pointers (ints) or CUDA tensors, 16-byte
+        aligned, not overlapping.  filter "area" (exact coverage), "triangle" or "lanczos3"; the taps are resample_taps'.
+        Asynchronous on torch stream `stream` (default torch.cuda.current_stream())."""
+        d = L.make_resample_desc(src_w, src_h, dst_w, dst_h, filter)
+        self._on_torch_stream(stream, lambda h: self._check(self.lib.rt_display_resample(
+            self.ctx, _dev_ptr(d_src), _dev_ptr(d_dst), ctypes.byref(d), ctypes.c_void_p(h)), "rt_display_resample"))
 
     def meter(self, d_image, d_state, width, height, key=0.18, min_exposure=2.0 ** -10, max_exposure=2.0 ** 10, adapt=1.0,
               low_permille=0, high_permille=0, stream=None):

@@ -300,3 +300,25 @@ def make_yuv_desc(width, height, format="nv12", matrix="bt709", range="limited",
     d.transfer = int({"linear": DISPLAY_RGBA8_LINEAR, "srgb": DISPLAY_RGBA8_SRGB}.get(transfer, transfer))
     d.flags, d.exposure = DISPLAY_FLIP_ROWS if flip else 0, float(exposure)
     return d
+
+
+# ---- resampling in front of the display path (rt_display_resample / rt_resample_taps, include/rt_mi355.h) --
+RESAMPLE_AREA, RESAMPLE_TRIANGLE, RESAMPLE_LANCZOS3 = 0, 1, 2
+RESAMPLE_MAX_TAPS = 64
+RESAMPLE_FILTERS = {"area": RESAMPLE_AREA, "triangle": RESAMPLE_TRIANGLE, "lanczos3": RESAMPLE_LANCZOS3}
+
+
+class RtResampleDesc(ctypes.Structure):
+    """``rt_resample_desc``: source and destination sizes of the rgba32f surfaces, filter, flags (zero)."""
+    _fields_ = [("srcWidth", ctypes.c_int32), ("srcHeight", ctypes.c_int32), ("dstWidth", ctypes.c_int32), ("dstHeight", ctypes.c_int32),
+                ("filter", ctypes.c_int32), ("flags", ctypes.c_uint32), ("reserved", ctypes.c_int32 * 2)]
+
+
+assert ctypes.sizeof(RtResampleDesc) == 32
+
+
+def make_resample_desc(src_w, src_h, dst_w, dst_h, filter="lanczos3"):
+    d = RtResampleDesc()
+    d.srcWidth, d.srcHeight, d.dstWidth, d.dstHeight = int(src_w), int(src_h), int(dst_w), int(dst_h)
+    d.filter = int(RESAMPLE_FILTERS.get(filter, filter))
+    return d
