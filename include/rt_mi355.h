@@ -667,6 +667,69 @@ typedef struct rt_resample_desc {
 int rt_resample_taps(int srcSize, int dstSize, int filter, int *nTaps, int32_t *first, float *weights, size_t capWeights);
 int rt_display_resample(rt_context *ctx, const void *dSrc, void *dDst, const rt_resample_desc *desc, void *hipStream);
 
+/* ---- progressive accumulation: the running mean of many one-sample frames, and a convergence report that stays on the device.
+ *      The accumulator (device, caller-owned, 16-byte aligned, all-zero = empty; rt_accum_layout gives offset[2] = {0,
+ *      width*height*16} and bytes = width*height*32) is two planes of width*height float4:
+ *        plane 0: the running MEAN rgba32f -- as it stands a valid input of rt_meter, rt_display_resample, every pack and every
+ *                 present submit; there is no resolve pass;
+ *        plane 1: {mY, M2, count (the bits of a uint32), 0}: Welford's moments of the sample luminance.
+ *      The state (device, one rt_accum_state of 1 KiB, 16-byte aligned, caller-owned, zeroed once -- or by rt_accum_reset).
+ *      rt_accum_add: dImage (device, width*height rgba32f, 16-byte aligned) is one more sample of every pixel.  Asynchronous on
+ *      hipStream (NULL = the context's stream), no host synchronisation: a clear of the state except `frames`, the accumulate
+ *      kernel, a one-workgroup solve, in stream order.  Per pixel, in fp32, never fused, IEEE division, in exactly this order:
+ *        Y = (0.2126f*r + 0.7152f*g) + 0.0722f*b of the sample (rt_meter's formula).
+ *        The sample is ACCEPTED when all four channels are finite with |x| <= 2^48 and count < 2^24; otherwise the pixel's 32
+ *        bytes are left untouched and nRejected counts it.  With this bound and the floor's, no value the accumulator ever holds
+ *        is NaN or infinite: |mean|, |mY| <= 2^48, every term of M2 is at most 2^49 * 2^49, so M2 <= 2^24 * 2^98 = 2^122 < 2^128;
+ *        and m*m >= 2^-80 below is a normal number.
+ *        Accepted:  n = count+1; nf = (float)n;  per channel d = x - mean; mean = mean + d/nf;
+ *                   dY = Y - mY; mY' = mY + dY/nf; M2 = M2 + dY*(Y - mY');  mY = mY'; count = n.
+ *        Afterwards, for EVERY pixel, on the state it now holds:
+ *          count < 2: nUnsampled counts it.  Otherwise  nf = (float)count; q = M2/(nf*(nf-1.0f)); m = fmaxf(mY, lumFloor);
+ *          r2 = q/(m*m) -- the squared relative standard error of the mean luminance -- and the pixel is BINNED:
+ *          bin = !(r2 > 0) ? 0 : clamp((bits(r2) >> 21) - 396, 0, 127): four bins per octave over 2^-28 <= r2 < 2^4; hist[bin]++.
+ *          It is CONVERGED (nConverged) when count >= minSamples && r2 <= thr2, thr2 = relError*relError (one fp32 multiply
+ *          on the host).  minCount / maxCount run over all pixels, maxR2Bits = max bits(r2) over the binned ones (0: none).
+ *          sum(hist) + nUnsampled == nPixels.
+ *        Solve: with n = sum(hist), medianBin / p95Bin = the smallest bin whose cumulative count reaches ceil(n*500/1000) /
+ *          ceil(n*950/1000) (64-bit integers; 0 when n == 0); done = nConverged*1000 >= (uint64)nPixels*donePermille;
+ *          frames = frames+1, saturating at 2^32-1.  rt_accum_solve_host runs the same solve (one source for host and device)
+ *          from in->hist, nUnsampled, nConverged, nPixels and frames without a GPU and copies the other words.
+ *      Every reduction is an integer atomic: the state is bit-identical from run to run.
+ *      rt_accum_view: dAccum -> dOut (device, width*height rgba32f (v,v,v,1), 16-byte aligned, not overlapping the accumulator):
+ *        RT_ACCUM_VIEW_RELERR: v = sqrtf(r2), +inf where count < 2 (packs to white);  RT_ACCUM_VIEW_COUNT: v = (float)count;
+ *        RT_ACCUM_VIEW_CONVERGED: v = 1 or 0.  The heat maps of where the noise is.
+ *      rt_accum_reset: two asynchronous memsets; the accumulator is empty and the state zero (`frames` too) behind it.
+ *      Refused before anything is enqueued, with RT_ERR_INVALID_ARG: NULL context, descriptor or pointer; a pointer not 16-byte
+ *      aligned; dImage, dOut or dState overlapping the accumulator; width or height < 1; relError not finite and > 0; lumFloor
+ *      not finite or < 2^-40; minSamples < 2; donePermille outside 1..1000; an unknown view mode; non-zero reserved words.
+ *      RT_ERR_TOO_LARGE: width*height > 2^31 - 1; in rt_accum_solve_host, sum(hist) + nUnsampled above 2^32 - 1.  The context
+ *      stays usable after a refusal and keeps no state of this feature.  The loop:
+ *          rt_render(ctx, &p);  rt_get_surfaces(ctx, &dColor, NULL, NULL);  rt_accum_add(ctx, dColor, dAccum, &a, dState, NULL);
+ *          every k frames a 4-byte read of dState + offsetof(rt_accum_state, done);
+ *          rt_present_submit_toned(ctx, dAccum, &disp, &tone, NULL, &t);          (plane 0 is the image) */
+typedef enum rt_accum_view_mode { RT_ACCUM_VIEW_RELERR = 0, RT_ACCUM_VIEW_COUNT = 1, RT_ACCUM_VIEW_CONVERGED = 2 } rt_accum_view_mode;
+typedef struct rt_accum_desc {
+    int32_t width, height;           /* >= 1 */
+    float relError;                  /* target relative standard error of a pixel's mean luminance: finite, > 0 (e.g. 0.02f) */
+    float lumFloor;                  /* finite, >= 2^-40: a mean luminance below it is judged against the floor instead */
+    int32_t minSamples;              /* >= 2: a pixel with fewer accepted samples is never converged */
+    int32_t donePermille;            /* 1..1000: the share of all pixels that must be converged for state.done */
+    int32_t reserved[4];             /* zero */
+} rt_accum_desc;
+typedef struct rt_accum_state {
+    uint32_t hist[128];              /* pixels per bin of r2, four bins per octave */
+    uint32_t nPixels, nUnsampled, nConverged, nRejected;
+    uint32_t minCount, maxCount, maxR2Bits;
+    uint32_t medianBin, p95Bin, done, frames;
+    uint32_t reserved[117];          /* zero */
+} rt_accum_state;
+int rt_accum_layout(int width, int height, size_t offset[2], size_t *bytes);
+int rt_accum_reset(rt_context *ctx, void *dAccum, void *dState, int width, int height, void *hipStream);
+int rt_accum_add(rt_context *ctx, const void *dImage, void *dAccum, const rt_accum_desc *desc, void *dState, void *hipStream);
+int rt_accum_solve_host(const rt_accum_state *in, const rt_accum_desc *desc, rt_accum_state *out);
+int rt_accum_view(rt_context *ctx, const void *dAccum, void *dOut, const rt_accum_desc *desc, int mode, void *hipStream);
+
 /* ---- multi-GPU strip helpers */
 /* Number of local rows a rank owns for interleaved strips. */
 int rt_strip_local_rows(int height, int stripRows, int stripCount, int stripIndex);
@@ -772,6 +835,11 @@ RT_SA(sizeof(rt_yuv_desc) == 48 && offsetof(rt_yuv_desc, transfer) == 20 && offs
       offsetof(rt_yuv_desc, exposure) == 28 && offsetof(rt_yuv_desc, reserved) == 32, "rt_yuv_desc is 48 B");
 RT_SA(sizeof(rt_resample_desc) == 32 && offsetof(rt_resample_desc, filter) == 16 && offsetof(rt_resample_desc, flags) == 20 &&
       offsetof(rt_resample_desc, reserved) == 24, "rt_resample_desc is 32 B");
+RT_SA(sizeof(rt_accum_desc) == 40 && offsetof(rt_accum_desc, relError) == 8 && offsetof(rt_accum_desc, minSamples) == 16 &&
+      offsetof(rt_accum_desc, reserved) == 24, "rt_accum_desc is 40 B");
+RT_SA(sizeof(rt_accum_state) == 1024 && offsetof(rt_accum_state, nPixels) == 512 && offsetof(rt_accum_state, minCount) == 528 &&
+      offsetof(rt_accum_state, medianBin) == 540 && offsetof(rt_accum_state, done) == 548 && offsetof(rt_accum_state, frames) == 552 &&
+      offsetof(rt_accum_state, reserved) == 556, "rt_accum_state is 1 KiB");
 #undef RT_SA
 #endif
 

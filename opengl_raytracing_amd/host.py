@@ -43,6 +43,7 @@ EXPORTS = [
     "rt_meter", "rt_meter_solve_host", "rt_meter_tables", "rt_display_pack_toned", "rt_present_submit_toned",
     "rt_display_yuv_coeffs", "rt_display_yuv_layout", "rt_display_pack_yuv", "rt_present_submit_yuv",
     "rt_resample_taps", "rt_display_resample",
+    "rt_accum_layout", "rt_accum_reset", "rt_accum_add", "rt_accum_solve_host", "rt_accum_view",
 ]
 
 
@@ -54,6 +55,8 @@ class RtFrameDesc(ctypes.Structure):
                 ("aoSamples", ctypes.POINTER(ctypes.c_float)), ("aoNoise", ctypes.POINTER(ctypes.c_float)),
                 ("reserved", ctypes.c_float * 2)]
 
+
+RtAccumDesc, RtAccumState = L.RtAccumDesc, L.RtAccumState      # rt_accum_desc / rt_accum_state (layout.py has every record)
 
 RT_OK = 0
 STATUS_NAMES = {0: "RT_OK", -1: "RT_ERR_INVALID_ARG", -2: "RT_ERR_NO_DEVICE", -3: "RT_ERR_HIP",
@@ -175,6 +178,11 @@ def load_library(build_if_missing=True):
     lib.rt_present_submit_yuv.argtypes = [vp, vp, P(L.RtYuvDesc), P(L.RtToneDesc), vp, P(ctypes.c_uint64)]
     lib.rt_resample_taps.argtypes = [ci, ci, ci, P(ci), P(ctypes.c_int32), P(cf), ctypes.c_size_t]
     lib.rt_display_resample.argtypes = [vp, vp, vp, P(L.RtResampleDesc), vp]
+    lib.rt_accum_layout.argtypes = [ci, ci, P(ctypes.c_size_t), P(ctypes.c_size_t)]
+    lib.rt_accum_reset.argtypes = [vp, vp, vp, ci, ci, vp]
+    lib.rt_accum_add.argtypes = [vp, vp, vp, P(L.RtAccumDesc), vp, vp]
+    lib.rt_accum_solve_host.argtypes = [vp, P(L.RtAccumDesc), vp]
+    lib.rt_accum_view.argtypes = [vp, vp, vp, P(L.RtAccumDesc), ci, vp]
     for name in EXPORTS:
         if name not in ("rt_last_error", "rt_mgpu_last_error", "rt_wire_bytes"):
             getattr(lib, name).restype = ci
@@ -379,6 +387,32 @@ def resample_taps(src, dst, filter="lanczos3"):
     if rc:
         raise RtError(rc, "rt_resample_taps")
     return n.value, first, weights
+
+
+AccumLayout = collections.namedtuple("AccumLayout", "offset bytes")
+AccumLayout.__doc__ = """rt_accum_layout's answer: byte offsets of the accumulator's two planes (the mean, the moments) and its size."""
+
+
+def accum_layout(width, height):
+    """Where the two planes of a width x height accumulator lie (rt_accum_layout) -> AccumLayout.  Needs no GPU."""
+    off, n = (ctypes.c_size_t * 2)(), ctypes.c_size_t(0)
+    rc = load_library().rt_accum_layout(int(width), int(height), off, ctypes.byref(n))
+    if rc:
+        raise RtError(rc, "rt_accum_layout")
+    return AccumLayout(tuple(off), n.value)
+
+
+def accum_solve_host(state, width, height, **desc):
+    """rt_accum_add's solve on the host (rt_accum_solve_host): `state` is one ACCUM_STATE_DTYPE record (hist, nUnsampled,
+    nConverged, nPixels and frames are read, the other words copied) -> the record rt_accum_add would leave.  `desc`:
+    make_accum_desc's keywords.  Needs no GPU."""
+    src = np.ascontiguousarray(np.asarray(state, dtype=L.ACCUM_STATE_DTYPE).reshape(1))
+    out = np.zeros(1, dtype=L.ACCUM_STATE_DTYPE)
+    d = L.make_accum_desc(width, height, **desc)
+    rc = load_library().rt_accum_solve_host(_ptr(src), ctypes.byref(d), _ptr(out))
+    if rc:
+        raise RtError(rc, "rt_accum_solve_host")
+    return out[0]
 
 
 def _dev_ptr(x):
@@ -706,6 +740,51 @@ class RayTracer:
         d = L.make_meter_desc(width, height, key, min_exposure, max_exposure, adapt, low_permille, high_permille)
         self._on_torch_stream(stream, lambda h: self._check(self.lib.rt_meter(
             self.ctx, _dev_ptr(d_image), ctypes.byref(d), _dev_ptr(d_state), ctypes.c_void_p(h)), "rt_meter"))
+
+    # ---- progressive accumulation ----------------------------------------------------------
+    def accum_alloc(self, width, height):
+        """(d_accum, d_state): a zeroed accumulator (torch uint8, accum_layout(width, height).bytes: the mean plane, then the
+        moments) and a zeroed rt_accum_state (torch uint8, 1024 bytes) on the current device -- empty, ready for accum_add."""
+        import torch
+        return (torch.zeros(accum_layout(width, height).bytes, dtype=torch.uint8, device="cuda"),
+                torch.zeros(L.ACCUM_STATE_BYTES, dtype=torch.uint8, device="cuda"))
+
+    def accum_reset(self, d_accum, d_state, width, height, stream=None):
+        """Empty the accumulator and zero the state, `frames` included (rt_accum_reset): two asynchronous memsets on torch
+        stream `stream` (default torch.cuda.current_stream())."""
+        self._on_torch_stream(stream, lambda h: self._check(self.lib.rt_accum_reset(
+            self.ctx, _dev_ptr(d_accum), _dev_ptr(d_state), int(width), int(height), ctypes.c_void_p(h)), "rt_accum_reset"))
+
+    def accum_add(self, d_image, d_accum, d_state, width, height, rel_error=0.02, lum_floor=2.0 ** -10, min_samples=16,
+                  done_permille=950, stream=None):
+        """One more sample of every pixel (rt_accum_add): the rgba32f surface d_image into the running mean and the luminance
+        moments of d_accum, the convergence report of the whole image into d_state (raw device pointers or CUDA tensors, 16-byte
+        aligned).  A pixel is converged when it has min_samples samples and the relative standard error of its mean luminance
+        (judged against lum_floor where the mean is darker) is at most rel_error; state.done says that done_permille / 1000 of all
+        pixels are.  Asynchronous on torch stream `stream` (default torch.cuda.current_stream()); nothing comes back to the host:
+        read the 4 bytes at state address + layout.ACCUM_DONE_OFFSET every few frames, or the whole state
+        (layout.ACCUM_STATE_DTYPE) when the host wants the figures."""
+        d = L.make_accum_desc(width, height, rel_error, lum_floor, min_samples, done_permille)
+        self._on_torch_stream(stream, lambda h: self._check(self.lib.rt_accum_add(
+            self.ctx, _dev_ptr(d_image), _dev_ptr(d_accum), ctypes.byref(d), _dev_ptr(d_state), ctypes.c_void_p(h)), "rt_accum_add"))
+
+    def accum_view(self, d_accum, d_out, width, height, mode="relerr", rel_error=0.02, lum_floor=2.0 ** -10, min_samples=16,
+                   done_permille=950, stream=None):
+        """A heat map of the accumulator as an rgba32f surface (v, v, v, 1) at d_out (rt_accum_view): mode "relerr" (the relative
+        standard error, +inf where a pixel has fewer than 2 samples), "count" (samples) or "converged" (1 or 0, by accum_add's
+        rule for the same keywords).  Asynchronous on torch stream `stream`."""
+        d = L.make_accum_desc(width, height, rel_error, lum_floor, min_samples, done_permille)
+        m = int(L.ACCUM_VIEWS.get(mode, mode))
+        self._on_torch_stream(stream, lambda h: self._check(self.lib.rt_accum_view(
+            self.ctx, _dev_ptr(d_accum), _dev_ptr(d_out), ctypes.byref(d), m, ctypes.c_void_p(h)), "rt_accum_view"))
+
+    @staticmethod
+    def accum_mean(d_accum, width, height):
+        """Plane 0 of an accum_alloc accumulator, the running mean, as a float32 [height, width, 4] tensor that shares its
+        memory: what meter, resample, display_pack* and present_submit* take as it stands."""
+        import torch
+        n = int(width) * int(height) * 16
+        return d_accum[:n].view(torch.float32).view(int(height), int(width), 4)
 
     def present_configure(self, slots):
         """Number of frames that can be on their way to the host at once (2..8, default 3); expires every earlier ticket and

@@ -322,3 +322,43 @@ def make_resample_desc(src_w, src_h, dst_w, dst_h, filter="lanczos3"):
     d.srcWidth, d.srcHeight, d.dstWidth, d.dstHeight = int(src_w), int(src_h), int(dst_w), int(dst_h)
     d.filter = int(RESAMPLE_FILTERS.get(filter, filter))
     return d
+
+
+# ---- progressive accumulation (rt_accum_*, include/rt_mi355.h) ---------------------------------------------
+ACCUM_VIEW_RELERR, ACCUM_VIEW_COUNT, ACCUM_VIEW_CONVERGED = 0, 1, 2
+ACCUM_VIEWS = {"relerr": ACCUM_VIEW_RELERR, "count": ACCUM_VIEW_COUNT, "converged": ACCUM_VIEW_CONVERGED}
+ACCUM_BINS = 128
+ACCUM_STATE_BYTES = 1024
+
+
+class RtAccumDesc(ctypes.Structure):
+    """``rt_accum_desc``: surface size, target relative error, luminance floor, least sample count, share of converged pixels."""
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("relError", ctypes.c_float), ("lumFloor", ctypes.c_float),
+                ("minSamples", ctypes.c_int32), ("donePermille", ctypes.c_int32), ("reserved", ctypes.c_int32 * 4)]
+
+
+class RtAccumState(ctypes.Structure):
+    """``rt_accum_state``: the 1 KiB convergence report rt_accum_add leaves on the device."""
+    _fields_ = [("hist", ctypes.c_uint32 * 128), ("nPixels", ctypes.c_uint32), ("nUnsampled", ctypes.c_uint32),
+                ("nConverged", ctypes.c_uint32), ("nRejected", ctypes.c_uint32), ("minCount", ctypes.c_uint32),
+                ("maxCount", ctypes.c_uint32), ("maxR2Bits", ctypes.c_uint32), ("medianBin", ctypes.c_uint32),
+                ("p95Bin", ctypes.c_uint32), ("done", ctypes.c_uint32), ("frames", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 117)]
+
+
+# the same record as a numpy dtype (what a read-back of the state is viewed as)
+ACCUM_STATE_DTYPE = np.dtype({
+    "names": ["hist", "nPixels", "nUnsampled", "nConverged", "nRejected", "minCount", "maxCount", "maxR2Bits", "medianBin", "p95Bin",
+              "done", "frames", "reserved"],
+    "formats": [("<u4", (128,))] + ["<u4"] * 11 + [("<u4", (117,))],
+    "offsets": [0] + [512 + 4 * k for k in range(12)], "itemsize": 1024})
+ACCUM_DONE_OFFSET = 548        # offsetof(rt_accum_state, done): the 4 bytes a frame loop reads every k frames
+
+assert ctypes.sizeof(RtAccumDesc) == 40 and ctypes.sizeof(RtAccumState) == ACCUM_STATE_BYTES == ACCUM_STATE_DTYPE.itemsize
+assert ACCUM_STATE_DTYPE.fields["done"][1] == ACCUM_DONE_OFFSET == RtAccumState.done.offset
+
+
+def make_accum_desc(width, height, rel_error=0.02, lum_floor=2.0 ** -10, min_samples=16, done_permille=950):
+    d = RtAccumDesc()
+    d.width, d.height, d.relError, d.lumFloor = int(width), int(height), float(rel_error), float(lum_floor)
+    d.minSamples, d.donePermille = int(min_samples), int(done_permille)
+    return d

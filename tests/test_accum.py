@@ -1,0 +1,447 @@
+"""Progressive accumulation on the GPU (include/rt_mi355.h): both planes of the accumulator, the whole rt_accum_state and the three views,
+bit for bit, against the numpy restatement of tests/accum_oracle.py -- after every frame of sequences of 1, 2, 3 and 17 frames over
+ragged shapes with every special value planted, on accumulators the test writes itself (constant pixels, pixels at the convergence
+threshold and on both sides of minSamples, counts at the saturation rule, r2 at both clamps of the histogram, a negative mean), run to
+run, on a caller's stream feeding rt_meter and rt_display_pack_toned with no host synchronisation in between, behind rt_accum_reset,
+behind rt_render; then every refusal.  Every comparison is exact equality; guard bytes around every buffer stay untouched."""
+import ctypes
+
+import numpy as np
+import pytest
+
+import accum_oracle as AO
+import meter_oracle as MO
+from opengl_raytracing_amd import layout as L
+from test_present import pack_oracle
+
+pytestmark = pytest.mark.gpu
+
+GUARD = 64
+SENTINEL = 0xA5
+INVALID, TOO_LARGE = -1, -4
+F = np.float32
+DESC = dict(rel_error=0.15, lum_floor=2.0 ** -6, min_samples=3, done_permille=400)      # a mix of converged and unconverged pixels at 17 frames
+
+
+@pytest.fixture(scope="module")
+def rt(host):
+    t = host.RayTracer(0)
+    yield t
+    t.close()
+
+
+def up(a):
+    import torch
+    t = torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    torch.cuda.synchronize()
+    return t
+
+
+class Guarded:
+    """`nbytes` zeroed device bytes between two runs of GUARD sentinel bytes; .t is the tensor of the bytes in between."""
+
+    def __init__(self, nbytes, init=None):
+        import torch
+        self.n = nbytes
+        self.raw = torch.full((nbytes + 2 * GUARD,), SENTINEL, dtype=torch.uint8, device="cuda")
+        self.t = self.raw[GUARD: GUARD + nbytes]
+        if init is None:
+            self.t.zero_()
+        else:
+            self.t.copy_(torch.from_numpy(np.ascontiguousarray(init).view(np.uint8).reshape(-1)))
+        torch.cuda.synchronize()
+        assert self.t.data_ptr() % 16 == 0
+
+    def read(self):
+        import torch
+        torch.cuda.synchronize()
+        raw = self.raw.cpu().numpy()
+        assert (raw[:GUARD] == SENTINEL).all(), "bytes in front of the buffer were written"
+        assert (raw[GUARD + self.n:] == SENTINEL).all(), "bytes behind the buffer were written"
+        return raw[GUARD: GUARD + self.n].copy()
+
+
+class Device:
+    """A guarded accumulator, state and view output of one shape."""
+
+    def __init__(self, w, h, acc=None):
+        self.w, self.h = w, h
+        self.accum = Guarded(w * h * 32, acc)
+        self.state = Guarded(1024)
+        self.out = Guarded(w * h * 16)
+
+    def read_accum(self):
+        return self.accum.read().view(np.float32).reshape(2, self.h, self.w, 4)
+
+    def read_state(self):
+        return self.state.read().view(L.ACCUM_STATE_DTYPE)[0]
+
+    def add(self, rt, img, **desc):
+        rt.accum_add(up(img), self.accum.t, self.state.t, self.w, self.h, **desc)
+        return self.read_accum(), self.read_state()
+
+    def view(self, rt, mode, **desc):
+        rt.accum_view(self.accum.t, self.out.t, self.w, self.h, mode=mode, **desc)
+        return self.out.read().view(np.float32).reshape(self.h, self.w, 4)
+
+
+def same_bits(a, b):
+    return np.ascontiguousarray(a).tobytes() == np.ascontiguousarray(b).tobytes()
+
+
+def check_state(got, want, what=""):
+    assert same_bits(AO.state_bytes(got), AO.state_bytes(want)), (what, AO.describe_difference(got, want))
+    assert int(got["hist"].sum()) + int(got["nUnsampled"]) == int(got["nPixels"])
+
+
+def check_accum(got, want, what=""):
+    if not same_bits(got, want):
+        bad = np.argwhere((got.view(np.uint32) != want.view(np.uint32)).any(axis=(0, 3)))
+        y, x = bad[0]
+        raise AssertionError((what, f"{len(bad)} pixels differ; first ({x}, {y}): got {got[:, y, x]!r} want {want[:, y, x]!r}"))
+
+
+def check_views(rt, dev, acc, what="", **desc):
+    for mode in ("relerr", "count", "converged"):
+        assert same_bits(dev.view(rt, mode, **desc), AO.view(acc, mode, **desc)), (what, mode)
+
+
+def run_sequence(rt, dev, frames, acc, prev_frames=0, **desc):
+    """Add the frames one by one, the device and the oracle side by side, comparing everything after every frame."""
+    for k, img in enumerate(frames):
+        acc, want = AO.accumulate(acc, img, prev_frames + k, **desc)
+        got_acc, got_state = dev.add(rt, img, **desc)
+        check_accum(got_acc, acc, f"frame {k}")
+        check_state(got_state, want, f"frame {k}")
+    return acc, want
+
+
+# ---- 1. parity over shapes and sequence lengths -----------------------------------------------------------------------------------
+@pytest.mark.parametrize("n", [1, 2, 3, 17])
+@pytest.mark.parametrize("w,h", AO.SHAPES, ids=[f"{w}x{h}" for w, h in AO.SHAPES])
+def test_sequence_matches_numpy(rt, w, h, n):
+    rng = np.random.default_rng(3000 * w + 17 * h + n)
+    frames = AO.noisy_frames(rng, AO.base_image(rng, w, h), n)
+    dev = Device(w, h)
+    acc, state = run_sequence(rt, dev, frames, AO.empty(w, h), **DESC)
+    check_views(rt, dev, acc, **DESC)
+    assert state["frames"] == n and state["nPixels"] == w * h and state["maxCount"] <= n
+    if w * h >= 600:                                           # every special value in every frame: the counts diverge
+        assert state["nRejected"] >= AO.N_REJECTED_SPECIALS - 3 and state["minCount"] < n == state["maxCount"]
+    if (w, h, n) == (640, 360, 17):
+        assert 0 < state["nConverged"] < w * h and state["nUnsampled"] == 0 and (state["hist"] != 0).sum() > 8
+        assert state["medianBin"] < state["p95Bin"]
+
+
+def test_more_chunks_than_workgroups(rt):
+    """1031 x 599 pixels are 604 chunks of 1024 for a grid of two workgroups per CU (512 on an MI355X): the grid-stride loop takes a
+    second turn in some workgroups and not in others, and the last chunk is ragged."""
+    rng = np.random.default_rng(31)
+    w, h = 1031, 599
+    frames = AO.noisy_frames(rng, AO.base_image(rng, w, h), 2)
+    dev = Device(w, h)
+    acc, state = run_sequence(rt, dev, frames, AO.empty(w, h), **DESC)
+    check_views(rt, dev, acc, **DESC)
+    assert state["nPixels"] == w * h and state["maxCount"] == 2 and 0 < state["nUnsampled"] < 64
+
+
+def test_default_description_and_done(rt):
+    """Low-noise frames under the default description: every pixel converges at minSamples = 16 and `done` rises in that frame."""
+    rng = np.random.default_rng(5)
+    w, h = 67, 9
+    base = AO.base_image(rng, w, h) + F(0.5)
+    frames = [(base * rng.uniform(0.99, 1.01, base.shape)).astype(np.float32) for _ in range(17)]
+    dev = Device(w, h)
+    acc = AO.empty(w, h)
+    done = []
+    for k, img in enumerate(frames):
+        acc, want = AO.accumulate(acc, img, k)
+        got_acc, got_state = dev.add(rt, img)
+        check_accum(got_acc, acc, f"frame {k}")
+        check_state(got_state, want, f"frame {k}")
+        done.append(int(got_state["done"]))
+    assert done == [0] * 15 + [1, 1] and got_state["nConverged"] == w * h
+    check_views(rt, dev, acc)
+
+
+# ---- 2. planted accumulators --------------------------------------------------------------------------------------------------------
+def _planted():
+    """An accumulator of 67 x 9 written by hand, and the frame added to it.  Row 0..5 take the sample (1, 1, 1, 1), whose luminance Yc
+    the planted mY equals: dY = 0, so mY and M2 stay and the count alone moves."""
+    w, h = 67, 9
+    rng = np.random.default_rng(9)
+    one = np.ones((1, 1, 4), dtype=np.float32)
+    Yc = AO.luminance(one)[0, 0]
+    desc = dict(rel_error=0.05, lum_floor=2.0 ** -40, min_samples=101, done_permille=500)
+    thr2 = F(0.05) * F(0.05)
+    acc = AO.empty(w, h)
+    acc[0] = 1.0
+    acc[1, ..., 0] = Yc
+    AO.set_counts(acc, np.ones((h, w), dtype=bool), 100)
+    img = np.ones((h, w, 4), dtype=np.float32)
+
+    def m2_for(r2, n):                                          # M2 that gives about r2 at count n and mean Yc (float64, rounded once)
+        return F(np.float64(r2) * n * (n - 1) * np.float64(Yc) ** 2)
+
+    # row 0: M2 = 0 -- constant over time: bin 0, converged
+    # row 1: 67 consecutive floats of M2 around the one that puts r2 at thr2 for count 101: both sides of the threshold
+    centre = m2_for(thr2, 101)
+    acc[1, 1, :, 1] = (centre.view(np.int32) + np.arange(-33, 34, dtype=np.int32)).view(np.float32)
+    # row 2: half that M2, count 99 -> 100: below minSamples = 101, never converged whatever r2 says
+    acc[1, 2, :, 1] = acc[1, 1, :, 1] * F(0.5)
+    AO.set_counts(acc, np.arange(h)[:, None].repeat(w, 1) == 2, 99)
+    # row 3: r2 around both clamps of the histogram: below 2^-28 (bin 0, r2 > 0), at 2^-28, at bin 1's lower edge 1.25 * 2^-28, just
+    # below and above 2^4, far above, infinite
+    r2s = [2.0 ** -40, 2.0 ** -29, 2.0 ** -28 * (1 - 1e-6), 2.0 ** -28 * (1 + 1e-6), 2.0 ** -28 * 1.25 * (1 + 1e-6), 15.9, 16.1, 2.0 ** 30]
+    for x, r2 in enumerate(r2s):
+        acc[1, 3, x, 1] = m2_for(r2, 101)
+    acc[1, 3, 8, 1] = 2.0 ** 120                                # with the floor as m below: r2 overflows to +inf
+    acc[1, 3, 8, 0] = -1.0
+    acc[0, 3, 8] = -1.0
+    # row 4: counts at the saturation rule: 2^24 - 2 and 2^24 - 1 still take the sample, 2^24 refuses it
+    AO.set_counts(acc, np.arange(h)[:, None].repeat(w, 1) == 4, np.resize([2 ** 24 - 2, 2 ** 24 - 1, 2 ** 24], w))
+    acc[1, 4, :, 1] = rng.uniform(0, 2.0 ** 40, w).astype(np.float32)
+    acc[1, 4, ::5, 3] = 7.0                                     # a foreign fourth word: kept by a refused sample, zeroed by an accepted one
+    # row 5: negative and tiny mean luminance: the floor is the yardstick
+    acc[1, 5, :, 0] = np.resize(np.array([-3.0, -0.0, 0.0, 1e-40, 2.0 ** -40, 2.0 ** -41, -2.0 ** 40], dtype=np.float32), w)
+    acc[0, 5] = acc[1, 5, :, 0:1]
+    acc[1, 5, :, 1] = rng.uniform(0, 4.0, w).astype(np.float32)
+    img[5] = acc[0, 5]                                          # the sample is the mean again (Y rounds: dY is tiny, not zero)
+    # rows 6..8: empty pixels, and pixels with one sample, taking noisy samples with the special values
+    AO.set_counts(acc, np.arange(h)[:, None].repeat(w, 1) >= 6, np.resize([0, 1], 3 * w))
+    acc[0, 6:] = 0.0
+    acc[1, 6:, :, :2] = 0.0
+    img[6:] = AO.noisy_frames(rng, AO.base_image(rng, w, 3), 1)[0]
+    ones = (AO.counts(acc) == 1) & (np.arange(h)[:, None] >= 6)
+    acc[0][ones] = 2.0
+    acc[1, ..., 0][ones] = AO.luminance(np.full((1, 4), 2.0, dtype=np.float32))[0]
+    return w, h, acc, img, desc, thr2
+
+
+def test_planted_accumulator(rt):
+    w, h, acc0, img, desc, thr2 = _planted()
+    dev = Device(w, h, acc0)
+    acc, want = AO.accumulate(acc0, img, 0, **desc)
+    got_acc, got_state = dev.add(rt, img, **desc)
+    check_accum(got_acc, acc)
+    check_state(got_state, want)
+    check_views(rt, dev, acc, **desc)
+    # the planted cases are the cases they claim to be
+    j = AO.judge(acc, **desc)
+    c = j["count"]
+    assert (acc[1, 0, :, 1] == 0).all() and (j["bin"][0] == 0).all() and j["converged"][0].all() and (c[0] == 101).all()
+    assert (c[1] == 101).all() and (j["r2"][1] <= thr2).any() and (j["r2"][1] > thr2).any()
+    assert (j["converged"][1] == (j["r2"][1] <= thr2)).all() and 0 < j["converged"][1].sum() < w
+    assert np.abs(j["r2"][1] / thr2 - 1).max() < 1e-5
+    assert (c[2] == 100).all() and not j["converged"][2].any() and (j["r2"][2] <= thr2).any()
+    assert j["bin"][3, :9].tolist() == [0, 0, 0, 0, 1, 127, 127, 127, 127] and (j["r2"][3, :4] > 0).all() and np.isposinf(j["r2"][3, 8])
+    assert j["r2"][3, 2] < F(2.0 ** -28) <= j["r2"][3, 3] and j["r2"][3, 5] < 16 <= j["r2"][3, 6]
+    assert c[4, :3].tolist() == [2 ** 24 - 1, 2 ** 24, 2 ** 24] and same_bits(acc[:, 4, 2::3], acc0[:, 4, 2::3])
+    assert acc[1, 4, 5, 3] == 7.0 and acc[1, 4, 0, 3] == 0.0 and acc0[1, 4, 0, 3] == 7.0      # x = 5: count 2^24, refused; x = 0: accepted
+    assert got_state["maxCount"] == 2 ** 24 and got_state["minCount"] == 0 and got_state["maxR2Bits"] == 0x7f800000
+    assert (acc[1, 5, :, 0] < 0).any() and np.isfinite(j["r2"][5]).all()
+    assert got_state["nRejected"] >= len(range(2, w, 3))
+    assert got_state["nUnsampled"] > 0 and (c[6:] == 2).any() and (c[6:] == 0).any()
+    assert np.isposinf(AO.view(acc, "relerr", **desc)[6:, :, 0]).any()
+
+
+def test_rejected_samples_leave_the_pixel_untouched(rt):
+    """A frame of nothing but refused samples over a used accumulator: all 32 bytes of every pixel stay, and the state still reports."""
+    rng = np.random.default_rng(12)
+    w, h = 257, 3
+    dev = Device(w, h)
+    acc, _ = run_sequence(rt, dev, AO.noisy_frames(rng, AO.base_image(rng, w, h), 3, planted=False), AO.empty(w, h), **DESC)
+    bad = np.ones((h, w, 4), dtype=np.float32)
+    refused = AO.SPECIALS[[0, 1, 2, 5, 6, 13]]
+    bad.reshape(-1, 4)[np.arange(w * h), rng.integers(0, 4, w * h)] = np.resize(refused, w * h)          # one bad channel each, alpha too
+    acc2, want = AO.accumulate(acc, bad, 3, **DESC)
+    assert same_bits(acc2, acc) and want["nRejected"] == w * h
+    got_acc, got_state = dev.add(rt, bad, **DESC)
+    check_accum(got_acc, acc)
+    check_state(got_state, want)
+    assert got_state["frames"] == 4 and got_state["minCount"] == got_state["maxCount"] == 3
+
+
+# ---- 3. determinism ---------------------------------------------------------------------------------------------------------------
+def test_same_sequence_same_bytes(rt):
+    rng = np.random.default_rng(44)
+    w, h = 640, 360
+    frames = [up(f) for f in AO.noisy_frames(rng, AO.base_image(rng, w, h), 3)]
+    runs = []
+    for _ in range(3):
+        dev = Device(w, h)
+        states = []
+        for f in frames:
+            rt.accum_add(f, dev.accum.t, dev.state.t, w, h, **DESC)
+            states.append(dev.state.read().tobytes())
+        runs.append((dev.accum.read().tobytes(), states))
+    assert all(r == runs[0] for r in runs[1:])
+
+
+# ---- 4. streams ---------------------------------------------------------------------------------------------------------------------
+def test_accum_feeds_meter_and_toned_pack_on_a_side_stream(rt, host):
+    """Upload, two accum_adds, meter on plane 0 and display_pack(d_exposure = the meter's) on one side stream, the host running ahead:
+    the only wait is the one before the read-back.  Every result equals the chain of oracles."""
+    import torch
+    w, h = 900, 400
+    rng = np.random.default_rng(66)
+    frames = AO.noisy_frames(rng, AO.base_image(rng, w, h), 2)
+    table, tables = host.display_srgb_thresholds(), host.meter_tables()
+    mdesc = dict(key=0.3, low_permille=5, high_permille=5)
+    dev = Device(w, h)
+    d_meter = Guarded(1088)
+    d_packed = Guarded(w * h * 4)
+    pinned = [torch.from_numpy(f).pin_memory() for f in frames]
+    d_img = [torch.zeros((h, w, 4), dtype=torch.float32, device="cuda") for _ in frames]
+    torch.cuda.synchronize()
+    s = torch.cuda.Stream()
+    with torch.cuda.stream(s):
+        for k in range(2):
+            d_img[k].copy_(pinned[k], non_blocking=True)
+            rt.accum_add(d_img[k], dev.accum.t, dev.state.t, w, h, stream=s, **DESC)
+        mean = rt.accum_mean(dev.accum.t, w, h)
+        rt.meter(mean, d_meter.t, w, h, stream=s, **mdesc)
+        rt.display_pack(mean, d_packed.t, w, h, format="srgb", flip=True, exposure=0.75, stream=s, tone="aces",
+                        d_exposure=d_meter.t.data_ptr() + L.METER_EXPOSURE_OFFSET)
+    s.synchronize()
+    acc = AO.empty(w, h)
+    for k in range(2):
+        acc, want = AO.accumulate(acc, frames[k], k, **DESC)
+    check_accum(dev.read_accum(), acc)
+    check_state(dev.read_state(), want)
+    assert mean.shape == (h, w, 4) and mean.data_ptr() == dev.accum.t.data_ptr() and same_bits(mean.cpu().numpy(), acc[0])
+    want_meter = MO.meter(acc[0], np.zeros(1, dtype=L.METER_STATE_DTYPE)[0], tables, **mdesc)
+    got_meter = d_meter.read().view(L.METER_STATE_DTYPE)[0]
+    assert same_bits(MO.state_bytes(got_meter), MO.state_bytes(want_meter)), MO.describe_difference(got_meter, want_meter)
+    got = d_packed.read().reshape(h, w, 4)
+    assert (got == MO.pack_toned(acc[0], "srgb", True, 0.75, table, "aces", dev_exposure=want_meter["exposure"])).all()
+    assert len(np.unique(got[..., :3])) > 64
+
+
+def test_relerr_view_packs_unsampled_pixels_to_white(rt, host):
+    rng = np.random.default_rng(70)
+    w, h = 67, 9
+    frames = AO.noisy_frames(rng, AO.base_image(rng, w, h), 2)
+    dev = Device(w, h)
+    acc, state = run_sequence(rt, dev, frames, AO.empty(w, h), **DESC)
+    assert 0 < state["nUnsampled"] < w * h
+    d_packed = Guarded(w * h * 4)
+    dev.view(rt, "relerr", **DESC)
+    rt.display_pack(dev.out.t, d_packed.t, w, h, format="linear")
+    got = d_packed.read().reshape(h, w, 4)
+    want = pack_oracle(AO.view(acc, "relerr", **DESC), "linear", False, 1.0, host.display_srgb_thresholds())
+    assert (got == want).all()
+    assert (got[AO.counts(acc) < 2][:, :3] == 255).all()
+
+
+# ---- 5. reset -----------------------------------------------------------------------------------------------------------------------
+def test_reset_returns_to_the_empty_state(rt):
+    rng = np.random.default_rng(80)
+    w, h = 67, 9
+    frames = AO.noisy_frames(rng, AO.base_image(rng, w, h), 4)
+    dev = Device(w, h)
+    run_sequence(rt, dev, frames[:3], AO.empty(w, h), **DESC)
+    assert dev.accum.read().any() and dev.read_state()["frames"] == 3
+    rt.accum_reset(dev.accum.t, dev.state.t, w, h)
+    assert not dev.accum.read().any() and not dev.state.read().any()
+    acc, state = run_sequence(rt, dev, frames[3:], AO.empty(w, h), **DESC)
+    assert state["frames"] == 1
+
+
+# ---- 6. end to end ------------------------------------------------------------------------------------------------------------------
+def test_render_then_accumulate(rt, host):
+    """A noise-textured scene at 96 x 54, frameCount 0..7: rt_render, then rt_accum_add on the context's colour surface, both on the
+    context's stream.  The accumulator equals the oracle fed with the read-back of each frame."""
+    from opengl_raytracing_amd import scenes
+    sc = scenes.make_scene(3, host.generate_aabb)
+    w, h = 96, 54
+    rt.load(sc)
+    dev = Device(w, h)
+    acc = AO.empty(w, h)
+    lib, vp = rt.lib, ctypes.c_void_p
+    d = L.make_accum_desc(w, h, **DESC)
+    colours = []
+    for k in range(8):
+        sc.frame_count = k
+        rt.render(sc.params(width=w, height=h))
+        d_color = rt.get_surfaces()[0]
+        assert lib.rt_accum_add(rt.ctx, vp(d_color), vp(dev.accum.t.data_ptr()), ctypes.byref(d), vp(dev.state.t.data_ptr()), None) == 0
+        colour = rt.readback()[0]                               # (rt_readback waits for the context's stream)
+        colours.append(colour)
+        acc, want = AO.accumulate(acc, colour, k, **DESC)
+        check_accum(dev.read_accum(), acc, f"frame {k}")
+        got = dev.read_state()
+        check_state(got, want, f"frame {k}")
+    assert got["minCount"] == got["maxCount"] == 8 and got["frames"] == 8 and got["nRejected"] == 0 and got["nUnsampled"] == 0
+    assert int(got["hist"].sum()) == w * h
+    assert any(not same_bits(colours[0], c) for c in colours[1:]), "frameCount did not move the samples"
+    assert np.abs(acc[0][..., :3] - np.mean(np.stack(colours).astype(np.float64), axis=0)[..., :3]).max() < 1e-4 * max(1.0, float(np.max(colours)))
+
+
+# ---- 7. refusals --------------------------------------------------------------------------------------------------------------------
+def test_refusals_leave_the_context_usable(rt):
+    import torch
+    rng = np.random.default_rng(77)
+    w, h = 8, 4
+    frames = AO.noisy_frames(rng, AO.base_image(rng, w, h), 2, planted=False)
+    dev = Device(w, h)
+    d_img = up(frames[0])
+    lib, ctx, vp = rt.lib, rt.ctx, ctypes.c_void_p
+    acc1, want = AO.accumulate(AO.empty(w, h), frames[0], 0, **DESC)
+
+    def desc(**kw):
+        d = L.make_accum_desc(w, h, **DESC)
+        for k, v in kw.items():
+            if k == "reserved":
+                d.reserved[v] = 1
+            else:
+                setattr(d, k, v)
+        return d
+
+    def ref(d):
+        return ctypes.byref(d) if d is not None else None
+
+    def add(image, accum, d, state, c=ctx):
+        return lib.rt_accum_add(c, vp(image), vp(accum), ref(d), vp(state), None)
+
+    def view(accum, out, d, mode, c=ctx):
+        return lib.rt_accum_view(c, vp(accum), vp(out), ref(d), mode, None)
+
+    def reset(accum, state, rw, rh, c=ctx):
+        return lib.rt_accum_reset(c, vp(accum), vp(state), rw, rh, None)
+
+    i, a, s, o = d_img.data_ptr(), dev.accum.t.data_ptr(), dev.state.t.data_ptr(), dev.out.t.data_ptr()
+
+    def still_works():
+        assert reset(a, s, w, h) == 0
+        assert add(i, a, desc(), s) == 0
+        rt.sync()
+        check_accum(dev.read_accum(), acc1)
+        check_state(dev.read_state(), want)
+        assert view(a, o, desc(), L.ACCUM_VIEW_RELERR) == 0
+        rt.sync()
+        assert same_bits(dev.out.read().view(np.float32).reshape(h, w, 4), AO.view(acc1, "relerr", **DESC))
+
+    nan, inf = float("nan"), float("inf")
+    bad = [desc(width=0), desc(width=-2), desc(height=0), desc(height=-1), desc(relError=0.0), desc(relError=-1.0), desc(relError=nan),
+           desc(relError=inf), desc(lumFloor=0.0), desc(lumFloor=2.0 ** -41), desc(lumFloor=nan), desc(lumFloor=inf), desc(minSamples=1),
+           desc(minSamples=-1), desc(donePermille=0), desc(donePermille=1001), desc(reserved=0), desc(reserved=1), desc(reserved=2),
+           desc(reserved=3), None]
+    for k, d in enumerate(bad):
+        assert add(i, a, d, s) == INVALID, k
+        assert view(a, o, d, L.ACCUM_VIEW_COUNT) == INVALID, k
+    still_works()
+    for image, accum, state in [(None, a, s), (i, None, s), (i, a, None), (i + 4, a, s), (i + 8, a, s), (i, a + 8, s), (i, a, s + 4),
+                                (a, a, s), (a + w * h * 16, a, s), (a + w * h * 32 - 16, a, s), (i, a, a + 16)]:
+        assert add(image, accum, desc(), state) == INVALID, (image, accum, state)
+    still_works()
+    for accum, out, mode in [(None, o, 0), (a, None, 0), (a + 4, o, 0), (a, o + 8, 0), (a, a, 0), (a, a + w * h * 16, 1), (a, o, 3), (a, o, -1)]:
+        assert view(accum, out, desc(), mode) == INVALID, (accum, out, mode)
+    for accum, state, rw, rh in [(None, s, w, h), (a, None, w, h), (a + 4, s, w, h), (a, s + 8, w, h), (a, s, 0, h), (a, s, w, -1), (a, a + 32, w, h)]:
+        assert reset(accum, state, rw, rh) == INVALID, (accum, state, rw, rh)
+    still_works()
+    assert add(i, a, desc(), s, c=None) == INVALID and view(a, o, desc(), 0, c=None) == INVALID and reset(a, s, w, h, c=None) == INVALID
+    huge = desc(width=65536, height=32768)                      # 2^31 pixels
+    assert add(i, a, huge, s) == TOO_LARGE and view(a, o, huge, 0) == TOO_LARGE and reset(a, s, 65536, 32768) == TOO_LARGE
+    still_works()
+    torch.cuda.synchronize()
