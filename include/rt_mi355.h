@@ -730,6 +730,76 @@ int rt_accum_add(rt_context *ctx, const void *dImage, void *dAccum, const rt_acc
 int rt_accum_solve_host(const rt_accum_state *in, const rt_accum_desc *desc, rt_accum_state *out);
 int rt_accum_view(rt_context *ctx, const void *dAccum, void *dOut, const rt_accum_desc *desc, int mode, void *hipStream);
 
+/* ---- denoising: the spatial half of SVGF -- a variance-guided 5x5 B3-spline a-trous wavelet filter, steered by first-hit records.
+ *      It makes the first frames of a still view presentable while the accumulator converges.  Three device planes of
+ *      width*height 16-byte records go in, one comes out, all caller-owned and 16-byte aligned:
+ *        dImage:   rgba32f -- the accumulator's plane 0, or one raw frame;
+ *        dMoments: the accumulator's plane 1 {mY, M2, count (the bits of a uint32), 0}, or NULL (every count reads as 1);
+ *        dGuide:   rt_denoise_guide_rec records {n[3], object}, made once per still view by rt_denoise_guide from the rt_hit
+ *                  records of rt_camera_rays -> rt_trace_rays(RT_QUERY_CLOSEST).  The render's own gPosition / gNormal are the
+ *                  path's LAST hit and change with frameCount; the first hit is exact and still.  The plane is dense on purpose:
+ *                  a tap gathered from the upper half of 32-byte rt_hit records would touch twice the cache lines;
+ *        dScratch: two planes A, B of width*height float4 (rt_denoise_layout: offset[2] = {0, width*height*16}, bytes =
+ *                  width*height*32), holding (r, g, b, var);
+ *        dOut:     rgba32f -- as it stands a valid input of rt_meter, rt_display_resample, every pack and every present submit.
+ *      Asynchronous on hipStream (NULL = the context's stream), no host synchronisation, and the context keeps no state of the
+ *      feature: rt_denoise_guide is one launch, rt_denoise is 1 + iterations launches in stream order.  All arithmetic is fp32,
+ *      never fused, with IEEE divide and sqrt; exp_ is rtm::exp_ of csrc/rt_mesa_math.h (one source for host and device).  Every
+ *      sum below starts at +0 and adds the kept terms one by one in row-major order of the window (dy outer, dx inner); max0(x)
+ *      is x > 0 ? x : 0 and min1(x) is x < 1 ? x : 1 (fmaxf / fminf that give +0 for -0 and drop a NaN).
+ *      Y(r, g, b) = (0.2126f*r + 0.7152f*g) + 0.0722f*b, rt_meter's and the accumulator's luminance.
+ *      GUIDE.  s = (nx*nx + ny*ny) + nz*nz of the hit's normal;  s > 0: n^ = n / sqrtf(s) per component, otherwise n^ = 0; object
+ *        is copied.  A plane's raw, unnormalised normal becomes the unit normal; a miss (object -1, normal 0) stays 0.  The
+ *        hits' normals are finite, as rt_trace_rays' are; a normal too short or too long for s to be a normal number loses its
+ *        direction (s == 0 or s == inf both give n^ = 0, and such a pixel passes through the filter unchanged).
+ *      PREPARE (dImage, dMoments, dGuide -> plane A).  A pixel is USABLE when r, g and b are finite with |x| <= 2^48; otherwise it
+ *        is SKIPPED everywhere below: it is never a tap of another pixel, and is itself filled from its neighbours.  The mark of a
+ *        skipped pixel is the sign bit of var: it stores (r, g, b, -0.0f), as it does in every later plane; a usable pixel's var is
+ *        never negative (M2 is the accumulator's: >= +0).  For a usable pixel, count = the moments' count (1 without moments):
+ *          count >= minCount:  nf = (float)count;  var = M2 / (nf*(nf - 1.0f));
+ *          otherwise the spatial estimate: over the k usable pixels of the 5x5 window (stride 1) that lie inside the image and have
+ *          the centre's object (the centre is one of them):  m1 = sum(Y)/kf;  m2 = sum(Y*Y)/kf;  var = max0(m2 - m1*m1) /
+ *          (float)max(count, 1).
+ *        With the bound, as in the accumulator, every sum stays finite: |Y| <= 2^49, Y*Y <= 2^98, M2 <= 2^122, var <= 2^121, a
+ *        weight is at most about 1, so 25 terms of w*rgb stay below 2^53 and 25 of (w*w)*var below 2^126.
+ *      ITERATION i = 0 .. iterations-1, step d = 1 << i, reads one plane and writes the other (0: A -> B, 1: B -> A, ...); the
+ *        last one writes dOut.  For the centre p with its record (rgb_p, var_p), guide (n^p, object_p) and Yp = Y(rgb_p):
+ *          gv = sum(g*var_q) / sum(g) over the 3x3 window at stride 1 with g = gk[dx]*gk[dy], gk = {1/4, 1/2, 1/4}, taps outside the
+ *            image, skipped or of another object dropped -- the variance of a neighbouring object must not reach across the edge
+ *            either -- (sum(g) == 0: gv = 0);   sl = sigmaLum*sqrtf(gv) + lumEps;
+ *          the 25 taps q = p + d*(dx, dy), dx, dy = -2..2, h = {1/16, 1/4, 3/8, 1/4, 1/16}: a tap is DROPPED when it lies outside the
+ *            image (no clamping), when it is skipped, or when object_q != object_p.  For the others
+ *              c = min1(max0((n^p.x*n^q.x + n^p.y*n^q.y) + n^p.z*n^q.z));   wn = c squared normalLog2Power times (c = c*c), or 1
+ *              when object_p < 0 (sky filters with sky);   wl = fabsf(Yp - Yq) / sl, or 0 when p is skipped;
+ *              w = ((h[dx]*h[dy]) * wn) * exp_(-wl);
+ *          sw = sum(w);  rgb' = sum(w*rgb_q) / sw per channel;  var' = sum((w*w)*var_q) / (sw*sw);
+ *          sw == 0 (p skipped without a usable neighbour of its object, or n^p = 0): rgb' = rgb_p, var' = 0.
+ *          A skipped p stores var' = -0.0f whatever the sums say.  The last iteration stores dImage's alpha of the pixel instead
+ *          of var'.
+ *      Refused before anything is enqueued, with RT_ERR_INVALID_ARG: NULL context, descriptor or pointer (except dMoments); a
+ *      pointer not 16-byte aligned; dOut or dScratch overlapping an input or each other, dGuide overlapping dHits; width or height
+ *      < 1; iterations outside 1..5; normalLog2Power outside 0..7; sigmaLum not finite and > 0; lumEps not finite or < 2^-40;
+ *      minCount < 2; non-zero reserved words.  RT_ERR_TOO_LARGE: width*height > 2^31 - 1.  The context stays usable.  The loop:
+ *          once per still view:  rt_camera_rays(ctx, &p, dRays, s);  rt_trace_rays(ctx, dRays, n, RT_QUERY_CLOSEST, dHits, s);
+ *                                rt_denoise_guide(ctx, dHits, dGuide, w, h, s);
+ *          at display cadence:   rt_render;  rt_accum_add(ctx, dColor, dAccum, &a, dState, s);
+ *                                rt_denoise(ctx, dAccum, dAccum + w*h*16, dGuide, dScratch, dOut, &dn, s);
+ *                                rt_present_submit_toned(ctx, dOut, &disp, &tone, s, &t); */
+typedef struct rt_denoise_guide_rec { float n[3]; int32_t object; } rt_denoise_guide_rec;   /* one pixel of the guide plane */
+typedef struct rt_denoise_desc {
+    int32_t width, height;           /* >= 1 */
+    int32_t iterations;              /* 1..5: steps 1, 2, 4, 8, 16 */
+    int32_t normalLog2Power;         /* 0..7: the normal weight is the clamped cosine to the power 2^normalLog2Power */
+    float sigmaLum;                  /* finite, > 0: luminance differences are measured in sigmaLum standard deviations */
+    float lumEps;                    /* finite, >= 2^-40: added to that scale */
+    int32_t minCount;                /* >= 2: a pixel with fewer samples takes the spatial variance estimate */
+    int32_t reserved[5];             /* zero */
+} rt_denoise_desc;
+int rt_denoise_guide(rt_context *ctx, const void *dHits, void *dGuide, int width, int height, void *hipStream);
+int rt_denoise_layout(int width, int height, size_t offset[2], size_t *bytes);
+int rt_denoise(rt_context *ctx, const void *dImage, const void *dMoments, const void *dGuide, void *dScratch, void *dOut,
+               const rt_denoise_desc *desc, void *hipStream);
+
 /* ---- multi-GPU strip helpers */
 /* Number of local rows a rank owns for interleaved strips. */
 int rt_strip_local_rows(int height, int stripRows, int stripCount, int stripIndex);
@@ -840,6 +910,9 @@ RT_SA(sizeof(rt_accum_desc) == 40 && offsetof(rt_accum_desc, relError) == 8 && o
 RT_SA(sizeof(rt_accum_state) == 1024 && offsetof(rt_accum_state, nPixels) == 512 && offsetof(rt_accum_state, minCount) == 528 &&
       offsetof(rt_accum_state, medianBin) == 540 && offsetof(rt_accum_state, done) == 548 && offsetof(rt_accum_state, frames) == 552 &&
       offsetof(rt_accum_state, reserved) == 556, "rt_accum_state is 1 KiB");
+RT_SA(sizeof(rt_denoise_guide_rec) == 16 && offsetof(rt_denoise_guide_rec, object) == 12, "rt_denoise_guide_rec is the upper half of rt_hit");
+RT_SA(sizeof(rt_denoise_desc) == 48 && offsetof(rt_denoise_desc, iterations) == 8 && offsetof(rt_denoise_desc, sigmaLum) == 16 &&
+      offsetof(rt_denoise_desc, minCount) == 24 && offsetof(rt_denoise_desc, reserved) == 28, "rt_denoise_desc is 48 B");
 #undef RT_SA
 #endif
 

@@ -44,6 +44,7 @@ EXPORTS = [
     "rt_display_yuv_coeffs", "rt_display_yuv_layout", "rt_display_pack_yuv", "rt_present_submit_yuv",
     "rt_resample_taps", "rt_display_resample",
     "rt_accum_layout", "rt_accum_reset", "rt_accum_add", "rt_accum_solve_host", "rt_accum_view",
+    "rt_denoise_guide", "rt_denoise_layout", "rt_denoise",
 ]
 
 
@@ -183,6 +184,9 @@ def load_library(build_if_missing=True):
     lib.rt_accum_add.argtypes = [vp, vp, vp, P(L.RtAccumDesc), vp, vp]
     lib.rt_accum_solve_host.argtypes = [vp, P(L.RtAccumDesc), vp]
     lib.rt_accum_view.argtypes = [vp, vp, vp, P(L.RtAccumDesc), ci, vp]
+    lib.rt_denoise_guide.argtypes = [vp, vp, vp, ci, ci, vp]
+    lib.rt_denoise_layout.argtypes = [ci, ci, P(ctypes.c_size_t), P(ctypes.c_size_t)]
+    lib.rt_denoise.argtypes = [vp, vp, vp, vp, vp, vp, P(L.RtDenoiseDesc), vp]
     for name in EXPORTS:
         if name not in ("rt_last_error", "rt_mgpu_last_error", "rt_wire_bytes"):
             getattr(lib, name).restype = ci
@@ -413,6 +417,19 @@ def accum_solve_host(state, width, height, **desc):
     if rc:
         raise RtError(rc, "rt_accum_solve_host")
     return out[0]
+
+
+DenoiseLayout = collections.namedtuple("DenoiseLayout", "offset bytes")
+DenoiseLayout.__doc__ = """rt_denoise_layout's answer: byte offsets of the two scratch planes of rt_denoise and the size of both."""
+
+
+def denoise_layout(width, height):
+    """Where the two scratch planes of a width x height rt_denoise lie (rt_denoise_layout) -> DenoiseLayout.  Needs no GPU."""
+    off, n = (ctypes.c_size_t * 2)(), ctypes.c_size_t(0)
+    rc = load_library().rt_denoise_layout(int(width), int(height), off, ctypes.byref(n))
+    if rc:
+        raise RtError(rc, "rt_denoise_layout")
+    return DenoiseLayout(tuple(off), n.value)
 
 
 def _dev_ptr(x):
@@ -777,6 +794,46 @@ class RayTracer:
         m = int(L.ACCUM_VIEWS.get(mode, mode))
         self._on_torch_stream(stream, lambda h: self._check(self.lib.rt_accum_view(
             self.ctx, _dev_ptr(d_accum), _dev_ptr(d_out), ctypes.byref(d), m, ctypes.c_void_p(h)), "rt_accum_view"))
+
+    # ---- denoising ------------------------------------------------------------------------
+    def denoise_guide(self, d_hits, width, height, out=None, stream=None):
+        """The guide plane of rt_denoise from first-hit records (rt_denoise_guide): d_hits is trace_rays(camera_rays(params))'s
+        CUDA tensor (or a raw device pointer) of width * height rt_hit -> a CUDA uint8 tensor of width * height
+        layout.DENOISE_GUIDE_DTYPE records (`out` may supply it), asynchronous on torch stream `stream` (default
+        torch.cuda.current_stream()).  Made once per still view."""
+        import torch
+        if out is None:
+            out = torch.empty(int(width) * int(height) * 16, dtype=torch.uint8, device="cuda")
+        self._on_torch_stream(stream, lambda h: self._check(self.lib.rt_denoise_guide(
+            self.ctx, _dev_ptr(d_hits), _dev_ptr(out), int(width), int(height), ctypes.c_void_p(h)), "rt_denoise_guide"))
+        return out
+
+    def denoise_alloc(self, width, height):
+        """(d_scratch, d_out): the two scratch planes of denoise (torch uint8, denoise_layout(width, height).bytes) and an rgba32f
+        output surface (torch float32 [height, width, 4]) on the current device."""
+        import torch
+        return (torch.empty(denoise_layout(width, height).bytes, dtype=torch.uint8, device="cuda"),
+                torch.empty((int(height), int(width), 4), dtype=torch.float32, device="cuda"))
+
+    def denoise(self, d_image, d_moments, d_guide, d_scratch, d_out, width, height, iterations=4, normal_log2_power=5, sigma_lum=4.0,
+                lum_eps=2.0 ** -10, min_count=4, stream=None):
+        """The variance-guided a-trous filter (rt_denoise): the rgba32f surface d_image -- the accumulator's plane 0, or one raw
+        frame -- with the accumulator's plane 1 as d_moments (None: the variance is estimated spatially) and denoise_guide's plane
+        as d_guide, through the scratch planes d_scratch into the rgba32f surface d_out, which rt_meter, rt_display_resample, every
+        pack and every present submit take as it stands.  Raw device pointers or CUDA tensors, 16-byte aligned; asynchronous on
+        torch stream `stream` (default torch.cuda.current_stream()): 1 + iterations launches, no host synchronisation."""
+        d = L.make_denoise_desc(width, height, iterations, normal_log2_power, sigma_lum, lum_eps, min_count)
+        mom = _dev_ptr(d_moments) if d_moments is not None else None
+        self._on_torch_stream(stream, lambda h: self._check(self.lib.rt_denoise(
+            self.ctx, _dev_ptr(d_image), mom, _dev_ptr(d_guide), _dev_ptr(d_scratch), _dev_ptr(d_out), ctypes.byref(d),
+            ctypes.c_void_p(h)), "rt_denoise"))
+
+    @staticmethod
+    def accum_moments(d_accum, width, height):
+        """Plane 1 of an accum_alloc accumulator, the luminance moments, as a uint8 tensor that shares its memory: denoise's
+        d_moments."""
+        n = int(width) * int(height) * 16
+        return d_accum[n: 2 * n]
 
     @staticmethod
     def accum_mean(d_accum, width, height):

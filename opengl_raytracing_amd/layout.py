@@ -362,3 +362,27 @@ def make_accum_desc(width, height, rel_error=0.02, lum_floor=2.0 ** -10, min_sam
     d.width, d.height, d.relError, d.lumFloor = int(width), int(height), float(rel_error), float(lum_floor)
     d.minSamples, d.donePermille = int(min_samples), int(done_permille)
     return d
+
+
+# ---- denoising (rt_denoise_guide / rt_denoise, include/rt_mi355.h) ---------------------------------------------
+# one pixel of the guide plane: the upper half of an rt_hit, the normal normalised
+DENOISE_GUIDE_DTYPE = np.dtype({"names": ["n", "object"], "formats": [("<f4", 3), "<i4"], "offsets": [0, 12], "itemsize": 16})
+DENOISE_DEFAULTS = dict(iterations=4, normal_log2_power=5, sigma_lum=4.0, lum_eps=2.0 ** -10, min_count=4)
+
+
+class RtDenoiseDesc(ctypes.Structure):
+    """``rt_denoise_desc``: surface size, a-trous iterations, the normal weight's power, the luminance weight's scale, the sample count
+    below which the variance is estimated spatially."""
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("iterations", ctypes.c_int32), ("normalLog2Power", ctypes.c_int32),
+                ("sigmaLum", ctypes.c_float), ("lumEps", ctypes.c_float), ("minCount", ctypes.c_int32), ("reserved", ctypes.c_int32 * 5)]
+
+
+assert ctypes.sizeof(RtDenoiseDesc) == 48 and RtDenoiseDesc.sigmaLum.offset == 16 and RtDenoiseDesc.reserved.offset == 28
+assert DENOISE_GUIDE_DTYPE.itemsize == 16 and DENOISE_GUIDE_DTYPE.fields["object"][1] == HIT_DTYPE.fields["object"][1] - 16
+
+
+def make_denoise_desc(width, height, iterations=4, normal_log2_power=5, sigma_lum=4.0, lum_eps=2.0 ** -10, min_count=4):
+    d = RtDenoiseDesc()
+    d.width, d.height, d.iterations, d.normalLog2Power = int(width), int(height), int(iterations), int(normal_log2_power)
+    d.sigmaLum, d.lumEps, d.minCount = float(sigma_lum), float(lum_eps), int(min_count)
+    return d
