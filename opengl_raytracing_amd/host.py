@@ -259,7 +259,11 @@ def parse_scene(text, max_objects=512, max_lights=64):
                                        _ptr(lts), max_lights, ctypes.byref(nl))
     if rc:
         raise RtError(rc, "rt_scene_parse")
-    return objs[: no.value].copy(), lts[: nl.value].copy()
+    # (a copy() of a padded record array leaves the padding bytes of the new array uninitialised: assign into zeros instead,
+    #  so the same text always gives the same bytes, as the library wrote them)
+    out_o, out_l = np.zeros(no.value, dtype=L.OBJECT_DTYPE), np.zeros(nl.value, dtype=L.LIGHT_DTYPE)
+    out_o[:], out_l[:] = objs[: no.value], lts[: nl.value]
+    return out_o, out_l
 
 
 def write_scene(objects, lights):

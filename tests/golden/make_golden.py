@@ -18,6 +18,10 @@ Per config the fixture holds
     feed the restatement the same constant and compare the rest bit-for-bit.
 Also writes probes.npz: llvmpipe outputs of the GLSL built-ins / expression shapes whose
 lowering the restatement depends on.
+
+`--only refscenes` renders the three scene files the reference ships (tests/golden/scenes) into ref_default / ref_simple /
+ref_performance_test, `--only ref_frame` the reference's post chain on its own frame of two of them into ref_frame_* (see
+make_refscenes / make_ref_frame); these fixtures hold no timings, so two runs write identical arrays.
 """
 import argparse
 import os
@@ -30,12 +34,61 @@ REPO = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 sys.path.insert(0, REPO)
 
 from opengl_raytracing_amd import host, scenes  # noqa: E402
+from opengl_raytracing_amd import layout as L  # noqa: E402
 from oracle import binding as O  # noqa: E402
 
 OUT = os.path.dirname(os.path.abspath(__file__))
 SHARDS = {"c5_8k": [["objects", "lights", "params", "tan_bits", "frame_count", "max_ray_depth", "strip_dispatch_s",
                      "column_dispatch_s", "win8k_origins", "win8k_color", "renderer"], ["win8k_pos", "win8k_normal"]],
           "trig": [["trig_in", "trig_out"], ["fov_in", "fov_tan", "explog_in"], ["explog_out"]]}
+
+
+# ---- the reference's own scene files (tests/golden/scenes, verbatim copies of res/Scene) --------------------------------------
+REF_SCENES = {"ref_default": "default.scene", "ref_simple": "SIMPLE.scene", "ref_performance_test": "performance_test.scene"}
+REF_FULL = 800                        # WIDTH = HEIGHT of the reference's window
+REF_DEPTH = 3                         # MAX_RAY_DEPTH as shipped
+# whole-frame size per view: 96 for every view would take the three fixtures past 4 MiB; `corner` keeps 96 because at 64 its
+# frame of default.scene (23 % hits) holds 892 distinct red values, under the 1000 the case checks of the tests ask of a view
+REF_VIEW_SIZES = {"shipped": 128, "corner": 96}
+REF_VIEW_SIZE = 64
+# view -> (position, yaw, pitch): Camera::UpdateVectors' angles (the shipped pose is yaw -90, pitch 0 at the origin)
+REF_VIEWS = {"shipped": ((0.0, 0.0, 0.0), -90.0, 0.0), "down": ((0.0, 4.0, 2.0), -90.0, -60.0),
+             "corner": ((-8.0, -8.0, 8.0), -45.0, 20.0), "inglass": ((0.0, 2.0, -3.0), -60.0, -15.0),
+             "behind": ((0.0, 1.0, -9.0), 90.0, 0.0), "steep": ((1.0, 6.0, -4.0), -90.0, -89.0)}
+# setting -> (MAX_RAY_DEPTH, shadowType written into every light); rendered for the views of REF_SETTING_VIEWS
+REF_SETTINGS = {"noshadow": (1, 0), "pcss": (8, 2)}
+REF_SETTING_VIEWS = ("shipped", "steep")
+REF_CASES = list(REF_VIEWS) + [f"{v}_{s}" for v in REF_SETTING_VIEWS for s in REF_SETTINGS]
+# One case more in ref_performance_test.  Every plane normal of the three files is of unit length ("LeftWall -10 0 0 1 1 0 0" is
+# position, radius 1, normal (1, 0, 0)), so an intersectPlane that normalised its normal would pass all of the above.  `wall_tilted`
+# is that file with LeftWall's / RightWall's normals set to (1, 1, 0) / (-1, -1, 0) and the AABBs regenerated, seen from a pose
+# that faces LeftWall: half of the frame's last hits lie on the tilted walls.
+REF_TILTED = ("ref_performance_test", "wall_tilted", ((-2.0, 3.0, 0.0), 180.0, -30.0), {"LeftWall": (1.0, 1.0, 0.0), "RightWall": (-1.0, -1.0, 0.0)})
+REF_FRAME_SCENES = {"ref_frame_default": "default.scene", "ref_frame_performance_test": "performance_test.scene"}
+REF_FRAME_SIZE = 128                  # the size at which all eleven bloom stages of the oracle equal llvmpipe's bit for bit
+
+
+def _case_keys(case):
+    return [f"{case}_{k}" for k in ("params", "color", "pos", "normal")]
+
+
+def _ref_scene_shards(name):
+    head = ["objects", "lights", "frame_count", "has_noise", "has_skybox", "full_size", "max_ray_depth", "tan_bits", "renderer",
+            "cases", "shipped_fc7_params"] + [f"{s}_lights" for s in REF_SETTINGS]
+    wins = ["win_params", "win_origins", "win_color", "win_pos", "win_normal"]
+    views = [v for v in REF_VIEWS if v != "shipped"]
+    extra = ["tilted_objects"] + _case_keys(REF_TILTED[1]) if name == REF_TILTED[0] else []
+    return [head + _case_keys("shipped") + wins, sum((_case_keys(f"shipped_{s}") for s in REF_SETTINGS), []),
+            sum((_case_keys(v) for v in views), []) + sum((_case_keys(f"steep_{s}") for s in REF_SETTINGS), []) + extra]
+
+
+def _ref_frame_shards():
+    head = ["objects", "lights", "frame_count", "has_noise", "has_skybox", "params", "renderer", "blend", "scene", "combined"]
+    return [head, ["stages"]] + [[f"taa{k}_{n}" for n in ("params", "current", "history", "normal", "out")] for k in range(3)]
+
+
+SHARDS.update({name: _ref_scene_shards(name) for name in REF_SCENES})
+SHARDS.update({name: _ref_frame_shards() for name in REF_FRAME_SCENES})
 
 
 def save_sharded(name, data):
@@ -468,6 +521,144 @@ void main(){ uint i=gl_GlobalInvocationID.x; float a=xin[i]; xout[4u*i]=log2(a);
     print("  [trig] written", flush=True)
 
 
+def _ref_scene(fname, view="shipped", pose=None):
+    """One of the reference's shipped scene files (tests/golden/scenes: the bytes of res/Scene) through host.parse_scene, with the
+    camera of Camera::UpdateVectors at `view` and the reference's window and depth."""
+    path = os.path.join(OUT, "scenes", fname)
+    text = open(path).read()
+    theirs = os.path.join("/root/reference/res/Scene", fname)
+    assert open(theirs, "rb").read() == open(path, "rb").read(), f"{fname} is no longer the reference's file"
+    objs, lts = host.parse_scene(text)
+    pos, yaw, pitch = pose or REF_VIEWS[view]
+    f, r, u = host.camera_vectors(yaw, pitch)
+    cam = dict(cam_pos=pos, cam_dir=f, cam_right=r, cam_up=u, fov_deg=45.0)
+    return scenes.Scene(fname, objs, lts, REF_FULL, REF_FULL, REF_DEPTH, cam)
+
+
+def _same_surfaces(a, b):
+    return all(np.array_equal(np.asarray(x, np.float32), np.asarray(y, np.float32), equal_nan=True) for x, y in zip(a[:3], b[:3]))
+
+
+def make_refscenes(name):
+    """ref_default / ref_simple / ref_performance_test: the scene files the reference ships, as its own shader draws them on
+    llvmpipe -- six views (REF_VIEWS), `shipped` and `steep` also without shadows at depth 1 and with PCSS on every light at
+    depth 8 (the NaN pixels stay in), and eight 32x32 windows of the real 800x800 frame.  Checked here and not stored: the shipped
+    16x16 dispatch writes the bytes of the exact one, and frameCount 7 the bytes of frameCount 0 (no noise texture is bound, no
+    object has a diffuseStrength)."""
+    fname = REF_SCENES[name]
+    sc = _ref_scene(fname)
+    data = {"objects": np.frombuffer(sc.objects.tobytes(), dtype=np.uint8).copy(),
+            "lights": np.frombuffer(sc.lights.tobytes(), dtype=np.uint8).copy(),
+            "frame_count": np.int32(0), "has_noise": np.int32(0), "has_skybox": np.int32(0),
+            "full_size": np.array([REF_FULL, REF_FULL], dtype=np.int32), "max_ray_depth": np.int32(REF_DEPTH),
+            "tan_bits": np.int32(probe_tan(45.0)), "cases": np.array(REF_CASES)}
+    for view in REF_VIEWS:
+        sc = _ref_scene(fname, view)
+        size = REF_VIEW_SIZES.get(view, REF_VIEW_SIZE)
+        settings = [(view, None, REF_DEPTH, None)]
+        if view in REF_SETTING_VIEWS:
+            settings += [(f"{view}_{s}", s, depth, stype) for s, (depth, stype) in REF_SETTINGS.items()]
+        for case, setting, depth, stype in settings:
+            if setting is not None:
+                sc.lights["shadowType"] = stype
+                data[f"{setting}_lights"] = np.frombuffer(sc.lights.tobytes(), dtype=np.uint8).copy()
+            p = sc.params(width=size, height=size, max_ray_depth=depth)
+            col, pos, nrm, info = run(sc, p, f"{name} {case}")
+            data[f"{case}_params"] = params_bytes(p)
+            data[f"{case}_color"], data[f"{case}_pos"], data[f"{case}_normal"] = col, pos, nrm
+            if case == "shipped":
+                shipped = O.run_reference(sc, p, repeat=0, shipped_dispatch=True)
+                assert _same_surfaces(shipped, (col, pos, nrm.astype(np.float32))), "16x16 dispatch differs from the exact one"
+                p7 = L.copy_params(p, frameCount=7)
+                fc7 = O.run_reference(sc, p7, repeat=0)
+                assert _same_surfaces(fc7, (col, pos, nrm.astype(np.float32))), "frameCount 7 differs from frameCount 0"
+                print(f"  [{name}] shipped 16x16 dispatch == exact dispatch; frameCount 7 == frameCount 0 (bytes)", flush=True)
+                data["shipped_fc7_params"] = params_bytes(p7)
+    if name == REF_TILTED[0]:
+        _, case, pose, normals = REF_TILTED
+        sc = _ref_scene(fname, pose=pose)
+        names = [ln.split()[2] for ln in open(os.path.join(OUT, "scenes", fname)) if ln.startswith("OBJECT")]
+        for wall, n in normals.items():
+            sc.objects["normal"][names.index(wall)] = n
+        host.generate_aabb(sc.objects)
+        data["tilted_objects"] = np.frombuffer(sc.objects.tobytes(), dtype=np.uint8).copy()
+        p = sc.params(width=REF_VIEW_SIZE, height=REF_VIEW_SIZE)
+        col, pos, nrm, info = run(sc, p, f"{name} {case}")
+        data[f"{case}_params"] = params_bytes(p)
+        data[f"{case}_color"], data[f"{case}_pos"], data[f"{case}_normal"] = col, pos, nrm
+        data["cases"] = np.array(REF_CASES + [case])
+    data["renderer"] = np.array(info["renderer"] + " / " + info["version"])
+    # the real frame: 800x800, shipped pose, the window's own 16x16 dispatch checked against the exact one
+    sc = _ref_scene(fname)
+    p = sc.params()
+    col, pos, nrm, info = run(sc, p, f"{name} full")
+    shipped = O.run_reference(sc, p, repeat=0, shipped_dispatch=True)
+    assert _same_surfaces(shipped, (col, pos, nrm.astype(np.float32))), "800x800: 16x16 dispatch differs from the exact one"
+    print(f"  [{name}] 800x800: shipped 16x16 dispatch == exact dispatch (bytes)", flush=True)
+    wins = windows(REF_FULL, REF_FULL)
+    data["win_params"] = params_bytes(p)
+    data["win_origins"] = np.array(wins, dtype=np.int32)
+    data["win_color"] = np.stack([col[y:y + WIN, x:x + WIN] for x, y in wins])
+    data["win_pos"] = np.stack([pos[y:y + WIN, x:x + WIN] for x, y in wins])
+    data["win_normal"] = np.stack([nrm[y:y + WIN, x:x + WIN] for x, y in wins])
+    save_sharded(name, data)       # (no timings in these fixtures: two runs of the generator write identical arrays)
+
+
+def _taa_blend_default():
+    """m_TAABlendFactor's initialiser in the reference's UI header: the blend factor a user who touches nothing runs with."""
+    import re
+    m = re.search(r"m_TAABlendFactor\s*=\s*([0-9.]+)f", open("/root/reference/src/ImGUIManager.h", errors="replace").read())
+    return float(np.float32(m.group(1)))
+
+
+def make_ref_frame(name):
+    """ref_frame_default / ref_frame_performance_test: the post chain of ForwardShadingPipeline.cpp:189-259 on llvmpipe's OWN
+    raytraced frame of the shipped view at 128x128 -- extract (threshold 1.0), ten alternating blurs starting horizontal,
+    combine (strength 0.5), then three TAA frames (frameCount 0, 1, 2; history ping-pong from zeros, the UI's default blend)."""
+    R = "/root/reference/shader/"
+    VS = R + "outputVs.glsl"
+    W = H = REF_FRAME_SIZE
+    sc = _ref_scene(REF_FRAME_SCENES[name])
+    p = sc.params(width=W, height=H)
+    cur, _, nrm, info = run(sc, p, name)
+    out = {"objects": np.frombuffer(sc.objects.tobytes(), dtype=np.uint8).copy(),
+           "lights": np.frombuffer(sc.lights.tobytes(), dtype=np.uint8).copy(),
+           "frame_count": np.int32(0), "has_noise": np.int32(0), "has_skybox": np.int32(0), "params": params_bytes(p),
+           "renderer": np.array(info["renderer"] + " / " + info["version"])}
+    assert (cur[..., 3] == 1).all()
+    tex = O.run_postfx(VS, R + "brightness_extractFS.glsl", W, H, [("hdrTexture", cur, dict(linear=True))],
+                       [("threshold", 1.0)], out_half=True)
+    stages = [tex]
+    horizontal = True
+    for _ in range(10):
+        tex = O.run_postfx(VS, R + "gaussian_blurFs.glsl", W, H, [("image", tex, dict(half=True, linear=True, clamp=True))],
+                           [("horizontal", int(horizontal))], out_half=True)
+        stages.append(tex)
+        horizontal = not horizontal
+    out["scene"] = cur
+    out["stages"] = np.stack(stages).astype(np.float16)      # exact: the targets are rgba16f
+    out["combined"] = O.run_postfx(VS, R + "bloom_combineFs.glsl", W, H,
+                                   [("scene", cur, dict(linear=True)), ("bloomBlur", tex, dict(half=True, linear=True, clamp=True))],
+                                   [("bloomStrength", 0.5)])
+    blend = _taa_blend_default()
+    out["blend"] = np.float64(blend)
+    hist = [np.zeros((H, W, 4), np.float32), np.zeros((H, W, 4), np.float32)]
+    for fc in range(3):
+        pf = L.copy_params(p, frameCount=fc)
+        cur, _, nrm, _ = run(sc, pf, f"{name} frameCount {fc}")
+        jx, jy = host.taa_jitter(fc, W, H)
+        k = fc % 2                                           # currentHistory (ForwardShadingPipeline.cpp:142)
+        res = O.run_postfx(VS, R + "taaFs.glsl", W, H,
+                           [("uCurrentFrame", cur, dict(linear=True)), ("uHistory", hist[1 - k], dict(linear=True, clamp=True)),
+                            ("gNormal", nrm.astype(np.float32), dict(half=True))],
+                           [("uBlendFactor", float(blend)), ("uJitterX", float(jx)), ("uJitterY", float(jy))])
+        out[f"taa{fc}_params"] = np.array([fc, blend, jx, jy], dtype=np.float64)
+        out[f"taa{fc}_current"], out[f"taa{fc}_history"], out[f"taa{fc}_normal"], out[f"taa{fc}_out"] = cur, hist[1 - k].copy(), nrm, res
+        hist[k] = res
+    save_sharded(name, out)
+    print(f"  [{name}] written (blend {blend})", flush=True)
+
+
 def make_surface_probes():
     """rgba16f imageStore rounding + cubemap sampling through a render-mode job with a tiny
     custom shader is not needed: both are exercised by the c5/nan fixtures.  (Kept as a hook.)"""
@@ -480,7 +671,7 @@ def main():
     args = ap.parse_args()
     if not O.harness_available():
         sys.exit("gl_harness or /root/reference is not available: goldens can only be generated in the build container")
-    names = [s for s in args.only.split(",") if s] or list(PLAN) + ["probes", "taa", "bloom", "ssao", "cubemap", "c5_8k", "trig"]
+    names = [s for s in args.only.split(",") if s] or list(PLAN) + ["probes", "taa", "bloom", "ssao", "cubemap", "c5_8k", "trig", "refscenes", "ref_frame"]
     for nme in names:
         print(f"== {nme}", flush=True)
         if nme == "probes":
@@ -497,6 +688,12 @@ def main():
             make_c5_8k()
         elif nme == "trig":
             make_trig()
+        elif nme == "refscenes":
+            for ref in REF_SCENES:
+                make_refscenes(ref)
+        elif nme == "ref_frame":
+            for ref in REF_FRAME_SCENES:
+                make_ref_frame(ref)
         else:
             make_config(nme, args.skip_fullres)
 
