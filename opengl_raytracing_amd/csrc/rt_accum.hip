@@ -11,16 +11,17 @@
 // to 134 global atomics on the one 1 KiB state, which is the suspect, not a measured cause.  The accumulator's loads and stores
 // are non-temporal (RT_ACCUM_NT): neutral while accumulator and image fit the Infinity Cache (1080p), 15 % faster where they
 // do not (4K).  DESIGN.md 20 has the figures of every form.
-// The statistics are built the way rt_meter_hist_kernel's are (rt_display.hip): one LDS histogram per wave, same-bin lanes merged
-// by ballot before the LDS atomic (a converged image puts a whole wave into one or two bins), the counters in registers for
-// the whole loop, reduced once per wave and once per workgroup, then one no-return integer atomic per workgroup for every
-// non-empty bin and counter.  minCount accumulates as the maximum of the complement, so that the cleared state is neutral.
+// The statistics are built the way rt_meter_hist_kernel's are (rt_display.hip), from the same pieces (rt_wave.h): one LDS histogram
+// per wave behind rt_wave_hist_add (a converged image puts a whole wave into one or two bins), the counters in registers for the
+// whole loop, reduced once per wave and once per workgroup, then one no-return integer atomic per workgroup for every non-empty
+// bin and counter.  minCount accumulates as the maximum of the complement, so that the cleared state is neutral.
 // No workgroup waits for another; the solve sees the complete histogram because it is the next launch on the stream.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "rt_accum.h"
 #include "rt_accum_solve.h"
+#include "rt_wave.h"
 
 #ifndef RT_ACCUM_PPL
 #define RT_ACCUM_PPL 4            // pixels per lane and chunk: 3 * PPL 16-byte loads in flight
@@ -40,18 +41,6 @@ namespace {
 typedef float f4 __attribute__((ext_vector_type(4)));
 
 constexpr size_t AS_CLEAR_BYTES = AS_FRAMES * 4;        // everything in front of `frames`
-
-// A commutative reduction over the 64 lanes of a full wave: four DPP rotations inside each row of 16 lanes, then the four rows
-// through v_readlane (rt_display.hip's meter_wave_reduce).  The result is wave-uniform.
-template <class Op>
-__device__ __forceinline__ unsigned accum_wave_reduce(unsigned v, Op op) {
-    v = op(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x128, 0xf, 0xf, false));
-    v = op(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x124, 0xf, 0xf, false));
-    v = op(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x122, 0xf, 0xf, false));
-    v = op(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x121, 0xf, 0xf, false));
-    return op(op((unsigned)__builtin_amdgcn_readlane((int)v, 0), (unsigned)__builtin_amdgcn_readlane((int)v, 16)),
-              op((unsigned)__builtin_amdgcn_readlane((int)v, 32), (unsigned)__builtin_amdgcn_readlane((int)v, 48)));
-}
 
 template <bool NT>
 __device__ __forceinline__ f4 accum_load(const f4 *p) {
@@ -120,7 +109,7 @@ __global__ __launch_bounds__(256) void rt_accum_add_kernel(const f4 *__restrict_
             const f4 s = x[k];
             float mY = mo[k].x, M2 = mo[k].y;
             unsigned count = __float_as_uint(mo[k].z);
-            const bool inRange = fabsf(s.x) <= 0x1p48f && fabsf(s.y) <= 0x1p48f && fabsf(s.z) <= 0x1p48f && fabsf(s.w) <= 0x1p48f;
+            const bool inRange = fabsf(s.x) <= kRtSampleLimit && fabsf(s.y) <= kRtSampleLimit && fabsf(s.z) <= kRtSampleLimit && fabsf(s.w) <= kRtSampleLimit;
             const bool accept = have && inRange && count < (1u << 24);
             if (accept) {
                 count += 1u;
@@ -130,7 +119,7 @@ __global__ __launch_bounds__(256) void rt_accum_add_kernel(const f4 *__restrict_
                 m.y = m.y + (s.y - m.y) / nf;
                 m.z = m.z + (s.z - m.z) / nf;
                 m.w = m.w + (s.w - m.w) / nf;
-                const float Y = (0.2126f * s.x + 0.7152f * s.y) + 0.0722f * s.z;
+                const float Y = rt_luma(s.x, s.y, s.z);
                 const float dY = Y - mY;
                 mY = mY + dY / nf;
                 M2 = M2 + dY * (Y - mY);
@@ -140,37 +129,24 @@ __global__ __launch_bounds__(256) void rt_accum_add_kernel(const f4 *__restrict_
             }
             cRejected += (have && !accept) ? 1u : 0u;
             const RtAccumJudged j = rt_accum_judge(mY, M2, count, rule);
-            bool binned = have && j.sampled;
+            const bool binned = have && j.sampled;
             cUnsampled += (have && !j.sampled) ? 1u : 0u;
             cConverged += (have && j.converged) ? 1u : 0u;
             mnC = max(mnC, have ? ~count : 0u);
             mxCount = max(mxCount, have ? count : 0u);
             mxR2 = max(mxR2, binned ? __float_as_uint(j.r2) : 0u);
-            const unsigned bin = j.bin;
-            unsigned long long todo = __builtin_amdgcn_ballot_w64(binned);
-#pragma unroll
-            for (int it = 0; it < RT_ACCUM_PEER; it++) {
-                if (todo == 0ull) break;                    // (wave-uniform)
-                const unsigned leader = (unsigned)__builtin_ctzll(todo);
-                const unsigned lb = (unsigned)__builtin_amdgcn_readlane((int)bin, (int)leader);
-                const bool same = binned && bin == lb;
-                const unsigned long long peers = __builtin_amdgcn_ballot_w64(same);
-                if (lane == leader) atomicAdd(&wh[lb], (unsigned)__builtin_popcountll(peers));
-                binned = binned && !same;
-                todo &= ~peers;
-            }
-            if (binned) atomicAdd(&wh[bin], 1u);
+            rt_wave_hist_add<RT_ACCUM_PEER>(wh, j.bin, binned, lane);
         }
     }
     // once per wave: reduce the registers across the lanes, lane 0 carries the wave's figures into the workgroup's
     const auto add = [](unsigned a, unsigned b) { return a + b; };
     const auto umax = [](unsigned a, unsigned b) { return max(a, b); };
-    cUnsampled = accum_wave_reduce(cUnsampled, add);
-    cConverged = accum_wave_reduce(cConverged, add);
-    cRejected = accum_wave_reduce(cRejected, add);
-    mnC = accum_wave_reduce(mnC, umax);
-    mxCount = accum_wave_reduce(mxCount, umax);
-    mxR2 = accum_wave_reduce(mxR2, umax);
+    cUnsampled = rt_wave_reduce(cUnsampled, add);
+    cConverged = rt_wave_reduce(cConverged, add);
+    cRejected = rt_wave_reduce(cRejected, add);
+    mnC = rt_wave_reduce(mnC, umax);
+    mxCount = rt_wave_reduce(mxCount, umax);
+    mxR2 = rt_wave_reduce(mxR2, umax);
     if (lane == 0u) {
         if (cUnsampled) atomicAdd(&red[0], cUnsampled);
         if (cConverged) atomicAdd(&red[1], cConverged);
@@ -201,15 +177,7 @@ __global__ __launch_bounds__(256) void rt_accum_solve_kernel(unsigned *__restric
     const unsigned b = threadIdx.x;
     const bool isBin = b < (unsigned)kAccumBins;
     const unsigned count = isBin ? state[b] : 0u;
-    if (isBin) scan[0][b] = count;
-    __syncthreads();
-    int cur = 0;
-#pragma unroll
-    for (unsigned d = 1; d < (unsigned)kAccumBins; d <<= 1) {
-        if (isBin) scan[cur ^ 1][b] = scan[cur][b] + (b >= d ? scan[cur][b - d] : 0u);
-        cur ^= 1;
-        __syncthreads();
-    }
+    const int cur = rt_block_scan(scan, b, count);
     if (isBin) {
         const uint64_t n = scan[cur][kAccumBins - 1], c = scan[cur][b];
         if (rt_accum_bin_reaches(c, count, rt_accum_rank(n, 500))) state[AS_MEDIANBIN] = b;
@@ -244,14 +212,9 @@ __global__ __launch_bounds__(256) void rt_accum_view_kernel(const f4 *__restrict
 }
 
 hipError_t rt_launch_accum_add(const void *image, void *accum, void *state, unsigned nPixels, const RtAccumRule &rule, hipStream_t s) {
-    static const int nCU = [] {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-        return n;
-    }();
     constexpr unsigned chunkPixels = 256u * RT_ACCUM_PPL;
     const unsigned nChunks = (nPixels + chunkPixels - 1u) / chunkPixels;
-    const unsigned cap = RT_ACCUM_WGS_PER_CU ? (unsigned)nCU * RT_ACCUM_WGS_PER_CU : nChunks;
+    const unsigned cap = RT_ACCUM_WGS_PER_CU ? (unsigned)rt_cu_count() * RT_ACCUM_WGS_PER_CU : nChunks;
     hipError_t e = hipMemsetAsync(state, 0, AS_CLEAR_BYTES, s);
     if (e != hipSuccess) return e;
     f4 *mean = (f4 *)accum;

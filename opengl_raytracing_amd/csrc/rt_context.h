@@ -1,6 +1,6 @@
-// rt_context.h -- what the files that implement context entry points share (rt_abi.cpp, rt_display.cpp, rt_resample.cpp): the context itself,
-// the way an entry point reports a failure, and the stream an entry point works on.  Nothing else knows the context's layout
-// (rt_mgpu.cpp drives contexts through the public ABI).  Not part of the public ABI.
+// rt_context.h -- what the files that implement context entry points share (rt_abi.cpp, and with rt_args.h's checks on top of it
+// rt_display.cpp, rt_resample.cpp, rt_accum.cpp, rt_denoise.cpp): the context itself, the way an entry point reports a failure, and the
+// stream it works on.  Nothing else knows the context's layout (rt_mgpu.cpp drives contexts through the public ABI).  Not part of the public ABI.
 #pragma once
 #include <string>
 #include <vector>
@@ -81,6 +81,13 @@ inline int fail(rt_context *c, int code, const char *what, hipError_t e = hipSuc
     do {                                                        \
         hipError_t e_ = (call);                                 \
         if (e_ != hipSuccess) return fail(c, RT_ERR_HIP, #call, e_); \
+    } while (0)
+
+// a check of the entry point's own (a validate_* function, rt_args.h): its refusal, which has set the error text, is passed on
+#define RT_TRY(check)                                           \
+    do {                                                        \
+        const int rc_ = (check);                                \
+        if (rc_) return rc_;                                    \
     } while (0)
 
 // a call of the scheduler's: the error string names the HIP call that failed inside it

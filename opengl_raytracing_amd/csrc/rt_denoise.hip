@@ -25,6 +25,7 @@
 
 #include "rt_denoise.h"
 #include "rt_mesa_math.h"
+#include "rt_wave.h"
 
 #ifndef RT_DENOISE_LDS
 #define RT_DENOISE_LDS 1            // 1: steps 1 and 2 fetch their taps from an LDS tile; 0: every step gathers from global memory
@@ -43,19 +44,14 @@ namespace {
 
 typedef float f4 __attribute__((ext_vector_type(4)));
 
-__device__ __forceinline__ float dn_lum(const f4 c) { return (0.2126f * c.x + 0.7152f * c.y) + 0.0722f * c.z; }
-__device__ __forceinline__ bool dn_usable(const f4 c) { return fabsf(c.x) <= 0x1p48f && fabsf(c.y) <= 0x1p48f && fabsf(c.z) <= 0x1p48f; }
+__device__ __forceinline__ bool dn_usable(const f4 c) { return fabsf(c.x) <= kRtSampleLimit && fabsf(c.y) <= kRtSampleLimit && fabsf(c.z) <= kRtSampleLimit; }
 __device__ __forceinline__ bool dn_skipped(float var) { return (__float_as_uint(var) >> 31) != 0u; }      // the sign bit of var is the mark
 __device__ __forceinline__ float dn_max0(float x) { return x > 0.0f ? x : 0.0f; }
 __device__ __forceinline__ float dn_min1(float x) { return x < 1.0f ? x : 1.0f; }
 
 // the tile a workgroup works on, or -1 when the grid's padding gave it none
 __device__ __forceinline__ int dn_tile(int nTiles) {
-#if RT_DENOISE_XCD
-    const int tile = (int)(blockIdx.x & 7u) * (int)(gridDim.x >> 3) + (int)(blockIdx.x >> 3);
-#else
-    const int tile = (int)blockIdx.x;
-#endif
+    const int tile = RT_DENOISE_XCD ? rt_xcd_tile() : (int)blockIdx.x;
     return tile < nTiles ? tile : -1;
 }
 
@@ -114,7 +110,7 @@ __global__ __launch_bounds__(256) void rt_denoise_prepare_kernel(const f4 *__res
                 const size_t qi = (size_t)qy * W + qx;
                 const f4 q = image[qi];
                 if (__float_as_int(guide[qi].w) != obj || !dn_usable(q)) continue;
-                const float Y = dn_lum(q);
+                const float Y = rt_luma(q.x, q.y, q.z);
                 sY = sY + Y;
                 sYY = sYY + Y * Y;
                 k++;
@@ -193,7 +189,7 @@ __global__ __launch_bounds__(256) void rt_denoise_iter_kernel(const f4 *__restri
     }
     const float gv = sg > 0.0f ? sgv / sg : 0.0f;
     const float sl = sigmaLum * sqrtf(gv) + lumEps;
-    const float Yp = dn_lum(cp);
+    const float Yp = rt_luma(cp.x, cp.y, cp.z);
     float sw = 0.0f, sr = 0.0f, sgr = 0.0f, sb = 0.0f, sv = 0.0f;
 #pragma unroll
     for (int dy = -2; dy <= 2; dy++) {
@@ -215,7 +211,7 @@ __global__ __launch_bounds__(256) void rt_denoise_iter_kernel(const f4 *__restri
             float c = dn_min1(dn_max0((gp.x * gq.x + gp.y * gq.y) + gp.z * gq.z));
             for (int k = 0; k < power; k++) c = c * c;
             const float wn = objP < 0 ? 1.0f : c;
-            const float wl = skipP ? 0.0f : fabsf(Yp - dn_lum(cq)) / sl;
+            const float wl = skipP ? 0.0f : fabsf(Yp - rt_luma(cq.x, cq.y, cq.z)) / sl;
             const float hx = dx == 0 ? 0.375f : (dx == 1 || dx == -1) ? 0.25f : 0.0625f;
             const float hy = dy == 0 ? 0.375f : (dy == 1 || dy == -1) ? 0.25f : 0.0625f;
             const float w = ((hx * hy) * wn) * rtm::exp_(-wl);

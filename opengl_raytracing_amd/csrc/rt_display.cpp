@@ -6,37 +6,34 @@
 
 #include <string>
 
-#include "rt_context.h"
+#include "rt_args.h"
 #include "rt_display.h"
 #include "rt_meter.h"
 
 namespace {
 
 // the rules an RGBA8 and a YUV description share, in the order both check them
-int validate_common(rt_context *c, uint32_t flags, float exposure, const int32_t *reserved, int nReserved, const void *dImage) {
+template <size_t N>
+int validate_common(rt_context *c, uint32_t flags, float exposure, const int32_t (&reserved)[N], const void *dImage) {
     if (flags & ~RT_DISPLAY_FLIP_ROWS) return fail(c, RT_ERR_INVALID_ARG, "unknown display flag bits");
     if (!(exposure > 0.0f) || !(exposure < HUGE_VALF)) return fail(c, RT_ERR_INVALID_ARG, "exposure must be finite and > 0");
-    for (int k = 0; k < nReserved; k++)
-        if (reserved[k]) return fail(c, RT_ERR_INVALID_ARG, "reserved words must be zero");
-    if (!dImage || ((uintptr_t)dImage & 15u)) return fail(c, RT_ERR_INVALID_ARG, "the image pointer must be non-NULL and 16-byte aligned");
-    return RT_OK;
+    RT_TRY(rt_check_reserved(c, reserved));
+    return rt_check_pointers(c, {{dImage, "image"}});
 }
 
 int validate_display(rt_context *c, const void *dImage, const rt_display_desc *d) {
     if (!d) return fail(c, RT_ERR_INVALID_ARG, "display description is NULL");
     if (d->width <= 0 || d->height <= 0) return fail(c, RT_ERR_INVALID_ARG, "width/height must be positive");
     if (d->format != RT_DISPLAY_RGBA8_LINEAR && d->format != RT_DISPLAY_RGBA8_SRGB) return fail(c, RT_ERR_INVALID_ARG, "unknown display format");
-    int rc = validate_common(c, d->flags, d->exposure, d->reserved, 3, dImage);
-    if (rc) return rc;
+    RT_TRY(validate_common(c, d->flags, d->exposure, d->reserved, dImage));
     if ((((uint64_t)d->width + 3) / 4) * (uint64_t)d->height > 0xffffff00ull) return fail(c, RT_ERR_TOO_LARGE, "frame too large for one pack launch");
     return RT_OK;
 }
 
 // A pack's output: `entry` is the entry point's name, outBytes what it writes behind dOut (the image is npx float4).
 int validate_output(rt_context *c, const char *entry, const void *dImage, size_t npx, const void *dOut, size_t outBytes) {
-    if (!dOut || ((uintptr_t)dOut & 15u)) return fail(c, RT_ERR_INVALID_ARG, "the output pointer must be non-NULL and 16-byte aligned");
-    const uintptr_t i0 = (uintptr_t)dImage, o0 = (uintptr_t)dOut;
-    if (i0 < o0 + outBytes && o0 < i0 + npx * 16)
+    RT_TRY(rt_check_pointers(c, {{dOut, "output"}}));
+    if (overlaps({dImage, npx * 16}, {dOut, outBytes}))
         return fail(c, RT_ERR_INVALID_ARG, (std::string(entry) + " cannot run in place: image and output overlap").c_str());
     return RT_OK;
 }
@@ -55,7 +52,7 @@ int validate_tone(rt_context *c, const rt_tone_desc *t, ToneArgs *out) {
     if (t->op == RT_TONE_REINHARD && (!(t->white >= 1.0f / 256.0f) || !(t->white < HUGE_VALF)))
         return fail(c, RT_ERR_INVALID_ARG, "Reinhard's white must be finite and >= 1/256");
     if ((uintptr_t)t->dExposure & 3u) return fail(c, RT_ERR_INVALID_ARG, "dExposure must be 4-byte aligned");
-    if (t->reserved[0] || t->reserved[1] || t->reserved[2] || t->reserved[3]) return fail(c, RT_ERR_INVALID_ARG, "reserved words must be zero");
+    RT_TRY(rt_check_reserved(c, t->reserved));
     out->op = t->op;
     out->invW2 = t->op == RT_TONE_REINHARD ? 1.0f / (t->white * t->white) : 0.0f;
     out->dExposure = t->dExposure;
@@ -71,12 +68,11 @@ hipError_t launch_rgba8(const void *dImage, void *dOut, const rt_display_desc *d
 int display_pack(rt_context *c, const char *entry, const void *dImage, void *dOut, const rt_display_desc *d, const rt_tone_desc *tone,
                  void *hipStream) {
     if (!c) return RT_ERR_INVALID_ARG;
-    int rc = validate_display(c, dImage, d);
-    if (rc) return rc;
+    RT_TRY(validate_display(c, dImage, d));
     ToneArgs t;
-    if ((rc = validate_tone(c, tone, &t))) return rc;
+    RT_TRY(validate_tone(c, tone, &t));
     const size_t npx = (size_t)d->width * d->height;
-    if ((rc = validate_output(c, entry, dImage, npx, dOut, npx * 4))) return rc;
+    RT_TRY(validate_output(c, entry, dImage, npx, dOut, npx * 4));
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, launch_rgba8(dImage, dOut, d, t, stream_or_own(c, hipStream)));
     return RT_OK;
@@ -86,10 +82,9 @@ int display_pack(rt_context *c, const char *entry, const void *dImage, void *dOu
 int present_submit(rt_context *c, const void *dImage, const rt_display_desc *d, const rt_tone_desc *tone, void *hipStream, uint64_t *ticket) {
     if (!c) return RT_ERR_INVALID_ARG;
     if (!ticket) return fail(c, RT_ERR_INVALID_ARG, "ticket is NULL");
-    int rc = validate_display(c, dImage, d);
-    if (rc) return rc;
+    RT_TRY(validate_display(c, dImage, d));
     ToneArgs t;
-    if ((rc = validate_tone(c, tone, &t))) return rc;
+    RT_TRY(validate_tone(c, tone, &t));
     PRESENT_TRY(c, enqueue((size_t)d->width * d->height * 4, stream_or_own(c, hipStream), ticket,
                            [&](void *stage, hipStream_t s) { return launch_rgba8(dImage, stage, d, t, s); }));
     return RT_OK;
@@ -108,9 +103,8 @@ int validate_yuv(rt_context *c, const void *dImage, const rt_yuv_desc *d, const 
     if (d->format != RT_YUV_NV12 && d->format != RT_YUV_I420) return fail(c, RT_ERR_INVALID_ARG, "unknown YUV format");
     if (rt_display_yuv_coeffs(d->matrix, d->range, out->coef) != RT_OK) return fail(c, RT_ERR_INVALID_ARG, "unknown YUV matrix or range");
     if (d->transfer != RT_DISPLAY_RGBA8_LINEAR && d->transfer != RT_DISPLAY_RGBA8_SRGB) return fail(c, RT_ERR_INVALID_ARG, "unknown transfer");
-    int rc = validate_common(c, d->flags, d->exposure, d->reserved, 4, dImage);
-    if (rc) return rc;
-    if (tone && (rc = validate_tone(c, tone, &out->tone))) return rc;
+    RT_TRY(validate_common(c, d->flags, d->exposure, d->reserved, dImage));
+    if (tone) RT_TRY(validate_tone(c, tone, &out->tone));
     if (rt_display_yuv_blocks(d->width, d->height) > 0xffffff00ull) return fail(c, RT_ERR_TOO_LARGE, "frame too large for one pack launch");
     size_t offset[3], pitch[3];
     (void)rt_display_yuv_layout(d, offset, pitch, &out->bytes);
@@ -131,8 +125,7 @@ int validate_meter_desc(rt_context *c, const rt_meter_desc *d) {
     if (!(d->adapt > 0.0f) || !(d->adapt <= 1.0f)) return fail(c, RT_ERR_INVALID_ARG, "adapt must be in (0, 1]");
     if (d->lowPermille < 0 || d->highPermille < 0 || (int64_t)d->lowPermille + d->highPermille >= 1000)
         return fail(c, RT_ERR_INVALID_ARG, "permilles: >= 0 and lowPermille + highPermille < 1000");
-    if (d->reserved[0] || d->reserved[1] || d->reserved[2] || d->reserved[3]) return fail(c, RT_ERR_INVALID_ARG, "reserved words must be zero");
-    return RT_OK;
+    return rt_check_reserved(c, d->reserved);
 }
 
 }  // namespace
@@ -189,9 +182,8 @@ int rt_display_yuv_layout(const rt_yuv_desc *d, size_t offset[3], size_t pitch[3
 int rt_display_pack_yuv(rt_context *c, const void *dImage, void *dOut, const rt_yuv_desc *d, const rt_tone_desc *tone, void *hipStream) {
     if (!c) return RT_ERR_INVALID_ARG;
     YuvArgs a;
-    int rc = validate_yuv(c, dImage, d, tone, &a);
-    if (rc) return rc;
-    if ((rc = validate_output(c, "rt_display_pack_yuv", dImage, (size_t)d->width * d->height, dOut, a.bytes))) return rc;
+    RT_TRY(validate_yuv(c, dImage, d, tone, &a));
+    RT_TRY(validate_output(c, "rt_display_pack_yuv", dImage, (size_t)d->width * d->height, dOut, a.bytes));
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, launch_yuv(dImage, dOut, d, a, stream_or_own(c, hipStream)));
     return RT_OK;
@@ -200,12 +192,10 @@ int rt_display_pack_yuv(rt_context *c, const void *dImage, void *dOut, const rt_
 // ---- exposure metering (the solve is rt_meter.h's, here and on the device)
 int rt_meter(rt_context *c, const void *dImage, const rt_meter_desc *d, void *dState, void *hipStream) {
     if (!c) return RT_ERR_INVALID_ARG;
-    int rc = validate_meter_desc(c, d);
-    if (rc) return rc;
-    if (!dImage || ((uintptr_t)dImage & 15u)) return fail(c, RT_ERR_INVALID_ARG, "the image pointer must be non-NULL and 16-byte aligned");
-    if (!dState || ((uintptr_t)dState & 15u)) return fail(c, RT_ERR_INVALID_ARG, "the state pointer must be non-NULL and 16-byte aligned");
-    const uint64_t npx = (uint64_t)d->width * (uint64_t)d->height;
-    if (npx > 0x7fffffffull) return fail(c, RT_ERR_TOO_LARGE, "more than 2^31 - 1 pixels");
+    RT_TRY(validate_meter_desc(c, d));
+    RT_TRY(rt_check_pointers(c, {{dImage, "image"}, {dState, "state"}}));
+    uint64_t npx;
+    RT_TRY(rt_check_pixels(c, d->width, d->height, &npx));
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, rt_launch_meter(dImage, dState, (unsigned)npx, d->key, d->minExposure, d->maxExposure, d->adapt, d->lowPermille,
                                d->highPermille, stream_or_own(c, hipStream)));
@@ -214,8 +204,7 @@ int rt_meter(rt_context *c, const void *dImage, const rt_meter_desc *d, void *dS
 
 int rt_meter_solve_host(const rt_meter_state *in, const rt_meter_desc *d, rt_meter_state *out) {
     if (!in || !out) return RT_ERR_INVALID_ARG;
-    int rc = validate_meter_desc(nullptr, d);
-    if (rc) return rc;
+    RT_TRY(validate_meter_desc(nullptr, d));
     uint64_t n = 0;
     for (int b = 0; b < 256; b++) n += in->hist[b];
     if (n > 0xffffffffull) return RT_ERR_TOO_LARGE;
@@ -263,8 +252,7 @@ int rt_present_submit_yuv(rt_context *c, const void *dImage, const rt_yuv_desc *
     if (!c) return RT_ERR_INVALID_ARG;
     if (!ticket) return fail(c, RT_ERR_INVALID_ARG, "ticket is NULL");
     YuvArgs a;
-    int rc = validate_yuv(c, dImage, d, tone, &a);
-    if (rc) return rc;
+    RT_TRY(validate_yuv(c, dImage, d, tone, &a));
     PRESENT_TRY(c, enqueue(a.bytes, stream_or_own(c, hipStream), ticket,
                            [&](void *stage, hipStream_t s) { return launch_yuv(dImage, stage, d, a, s); }));
     return RT_OK;

@@ -13,6 +13,7 @@
 #include "rt_display.h"
 #include "rt_fastmath.h"
 #include "rt_meter.h"
+#include "rt_wave.h"
 
 // =========================================================================================
 // Display packing: any rgba32f surface -> RGBA8, the quantisation an 8-bit default framebuffer applies to what
@@ -359,13 +360,12 @@ hipError_t rt_launch_display_pack_yuv(const void *image, void *out, int W, int H
 // 1 KiB state), and the code base's one device-wide reduction: integer atomics only, so the state is bit-identical from run to run.
 // Grid sized to the chip -- RT_METER_WGS_PER_CU workgroups of 256 threads per CU, a grid-stride loop over quads of four consecutive
 // pixels of the flat surface (four 16-B loads in flight per lane) -- so a frame flushes (workgroups x non-empty bins) global atomics
-// however large it is.  Every wave keeps a histogram of its own in LDS (ds_add_u32, no return).  Coherent content (a floor, the sky)
-// puts all 64 lanes of a wave into one or two bins, and same-address LDS atomics serialise: before touching LDS the wave takes up to
-// RT_METER_PEER rounds of "the first pending lane's bin, a ballot of the lanes that share it, ONE add of the popcount"; lanes still
-// pending after that add 1 each.  The counters and the extremes stay in registers for the whole loop and are reduced once per wave
-// (DPP rotations inside the rows of 16 lanes, v_readlane across the four rows), then once per workgroup through LDS: one global atomic per
-// workgroup and quantity.  minLum accumulates as the maximum of the complemented bit pattern (positive floats order like their bits),
-// so that the cleared state -- zero bytes, one hipMemsetAsync in front of the kernel -- is its neutral element.
+// however large it is.  Every wave keeps a histogram of its own in LDS (ds_add_u32, no return), filled through rt_wave_hist_add
+// (rt_wave.h): coherent content (a floor, the sky) puts all 64 lanes of a wave into one or two bins, so same-bin lanes are merged by
+// ballot for RT_METER_PEER rounds before the LDS atomic.  The counters and the extremes stay in registers for the whole loop and are
+// reduced once per wave (rt_wave_reduce), then once per workgroup through LDS: one global atomic per workgroup and
+// quantity.  minLum accumulates as the maximum of the complemented bit pattern (positive floats order like their bits), so that
+// the cleared state -- zero bytes, one hipMemsetAsync in front of the kernel -- is its neutral element.
 // No workgroup waits for another anywhere; the solve sees the complete histogram because it is the next launch on the stream.
 // =========================================================================================
 #ifndef RT_METER_WGS_PER_CU
@@ -380,17 +380,6 @@ namespace {
 enum { MS_NPIXELS = 256, MS_NNONPOS = 257, MS_NNAN = 258, MS_NINF = 259, MS_MINLUM = 260, MS_MAXLUM = 261, MS_NMETERED = 262,
        MS_MEANLOG2 = 263, MS_TARGET = 264, MS_EXPOSURE = 265, MS_FRAMES = 266, MS_RESERVED = 267, MS_WORDS = 272 };
 constexpr size_t MS_CLEAR_BYTES = MS_NMETERED * 4;      // hist, the counters, minLum / maxLum: what the histogram kernel accumulates into
-// A commutative reduction over the 64 lanes of a full wave: four DPP rotations inside each row of 16 lanes (row_ror:8, 4, 2, 1 leave
-// the row's result in every one of its lanes), then the four rows through v_readlane.  The result is wave-uniform.
-template <class Op>
-__device__ __forceinline__ unsigned meter_wave_reduce(unsigned v, Op op) {
-    v = op(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x128, 0xf, 0xf, false));
-    v = op(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x124, 0xf, 0xf, false));
-    v = op(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x122, 0xf, 0xf, false));
-    v = op(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x121, 0xf, 0xf, false));
-    return op(op((unsigned)__builtin_amdgcn_readlane((int)v, 0), (unsigned)__builtin_amdgcn_readlane((int)v, 16)),
-              op((unsigned)__builtin_amdgcn_readlane((int)v, 32), (unsigned)__builtin_amdgcn_readlane((int)v, 48)));
-}
 }  // namespace
 
 __global__ __launch_bounds__(256) void rt_meter_hist_kernel(const float4 *__restrict__ in, unsigned nPixels, unsigned nQuads,
@@ -415,10 +404,10 @@ __global__ __launch_bounds__(256) void rt_meter_hist_kernel(const float4 *__rest
 #pragma unroll
         for (int k = 0; k < 4; k++) {
             const bool have = (unsigned)k < r;
-            const float Y = (0.2126f * p[k].x + 0.7152f * p[k].y) + 0.0722f * p[k].z;
+            const float Y = rt_luma(p[k].x, p[k].y, p[k].z);
             const unsigned bits = __float_as_uint(Y);
             const bool isNaN = Y != Y, isInf = Y == __builtin_huge_valf(), pos = Y > 0.0f;
-            bool metered = have && pos && !isInf;
+            const bool metered = have && pos && !isInf;
             cNaN += (have && isNaN) ? 1u : 0u;
             cInf += (have && isInf) ? 1u : 0u;
             cNonPos += (have && !pos && !isNaN) ? 1u : 0u;
@@ -426,29 +415,17 @@ __global__ __launch_bounds__(256) void rt_meter_hist_kernel(const float4 *__rest
             const unsigned bin = (unsigned)min(max(e, 0), 255);
             mnC = max(mnC, metered ? ~bits : 0u);
             mx = max(mx, metered ? bits : 0u);
-            unsigned long long todo = __builtin_amdgcn_ballot_w64(metered);
-#pragma unroll
-            for (int it = 0; it < RT_METER_PEER; it++) {
-                if (todo == 0ull) break;                    // (wave-uniform)
-                const unsigned leader = (unsigned)__builtin_ctzll(todo);
-                const unsigned lb = (unsigned)__builtin_amdgcn_readlane((int)bin, (int)leader);
-                const bool same = metered && bin == lb;
-                const unsigned long long peers = __builtin_amdgcn_ballot_w64(same);
-                if (lane == leader) atomicAdd(&wh[lb], (unsigned)__builtin_popcountll(peers));
-                metered = metered && !same;
-                todo &= ~peers;
-            }
-            if (metered) atomicAdd(&wh[bin], 1u);
+            rt_wave_hist_add<RT_METER_PEER>(wh, bin, metered, lane);
         }
     }
     // once per wave: reduce the registers across the lanes, lane 0 carries the wave's figures into the workgroup's
     const auto add = [](unsigned a, unsigned b) { return a + b; };
     const auto umax = [](unsigned a, unsigned b) { return max(a, b); };
-    cNonPos = meter_wave_reduce(cNonPos, add);
-    cNaN = meter_wave_reduce(cNaN, add);
-    cInf = meter_wave_reduce(cInf, add);
-    mnC = meter_wave_reduce(mnC, umax);
-    mx = meter_wave_reduce(mx, umax);
+    cNonPos = rt_wave_reduce(cNonPos, add);
+    cNaN = rt_wave_reduce(cNaN, add);
+    cInf = rt_wave_reduce(cInf, add);
+    mnC = rt_wave_reduce(mnC, umax);
+    mx = rt_wave_reduce(mx, umax);
     if (lane == 0u) {
         if (cNonPos) atomicAdd(&red[0], cNonPos);
         if (cNaN) atomicAdd(&red[1], cNaN);
@@ -480,16 +457,8 @@ __global__ __launch_bounds__(256) void rt_meter_solve_kernel(unsigned *__restric
     __shared__ unsigned lq[8];
     const unsigned b = threadIdx.x;
     const unsigned count = state[b];
-    scan[0][b] = count;
-    if (b < 8u) lq[b] = a.tab.log2q16[b];
-    __syncthreads();
-    int cur = 0;
-#pragma unroll
-    for (unsigned d = 1; d < 256u; d <<= 1) {
-        scan[cur ^ 1][b] = scan[cur][b] + (b >= d ? scan[cur][b - d] : 0u);
-        cur ^= 1;
-        __syncthreads();
-    }
+    if (b < 8u) lq[b] = a.tab.log2q16[b];                   // (visible behind the scan's barriers)
+    const int cur = rt_block_scan(scan, b, count);
     RtMeterSolveIn in;
     in.key = a.key; in.minExposure = a.minExposure; in.maxExposure = a.maxExposure; in.adapt = a.adapt;
     in.lowPermille = a.lowPermille; in.highPermille = a.highPermille;
@@ -525,13 +494,8 @@ const RtMeterTables &rt_meter_tables_ref() {
 // Three stream operations: clear the accumulators, histogram, solve.  nPixels <= 2^31 - 1 (callers refuse larger frames first).
 hipError_t rt_launch_meter(const void *image, void *state, unsigned nPixels, float key, float minExposure, float maxExposure, float adapt,
                            int lowPermille, int highPermille, hipStream_t s) {
-    static const int nCU = [] {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-        return n;
-    }();
     const unsigned nQuads = (nPixels + 3u) / 4u;
-    const unsigned want = (nQuads + 255u) / 256u, cap = (unsigned)nCU * RT_METER_WGS_PER_CU;
+    const unsigned want = (nQuads + 255u) / 256u, cap = (unsigned)rt_cu_count() * RT_METER_WGS_PER_CU;
     hipError_t e = hipMemsetAsync(state, 0, MS_CLEAR_BYTES, s);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(rt_meter_hist_kernel, dim3(want < cap ? want : cap), dim3(256), 0, s, (const float4 *)image, nPixels, nQuads, (unsigned *)state);

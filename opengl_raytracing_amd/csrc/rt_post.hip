@@ -16,6 +16,7 @@
 #include <string.h>
 
 #include "rt_fastmath.h"
+#include "rt_wave.h"
 
 #ifndef RT_TAA_LDS
 #define RT_TAA_LDS 0   // 1: stage the current-frame tile (+halo) in LDS; 0: neighbourhood straight from L1/L2.
@@ -433,13 +434,8 @@ __global__ __launch_bounds__(256) void rt_bloom_hv_kernel(const void *__restrict
             else preH[j] = ((const uint2 *)inV)[(size_t)gy * W + gx];
         }
     };
-#if RT_BLOOM_XCD
-    // workgroups go to the 8 XCDs round-robin by id: give each XCD one contiguous band of tiles, so that the aprons a tile shares
-    // with its neighbours are served by the SAME L2 instead of being fetched from HBM once per XCD
-    int tile = (int)(blockIdx.x & 7u) * (int)(gridDim.x >> 3) + (int)(blockIdx.x >> 3);
-#else
-    int tile = blockIdx.x;
-#endif
+    // (one band of tiles per XCD: the aprons a tile shares with its neighbours come from the SAME L2, not from HBM once per XCD)
+    int tile = RT_BLOOM_XCD ? rt_xcd_tile() : (int)blockIdx.x;
     if (tile < nTiles) request(tile);
     for (; tile < nTiles; tile += (RT_BLOOM_TPW == 1 ? nTiles : (int)gridDim.x)) {      // (one trip when RT_BLOOM_TPW == 1)
     const int x0 = (tile % tilesX) * FX, y0 = (tile / tilesX) * FY;

@@ -6,7 +6,7 @@
 
 #include <new>
 
-#include "rt_context.h"
+#include "rt_args.h"
 #include "rt_resample.h"
 
 namespace {
@@ -93,8 +93,7 @@ int rt_resample_build_axis(int S, int D, int filter, int *nTaps, RtResampleAxis 
 int ResampleTables::update(Axis &a, int S, int D, int filter, bool transposed) {
     if (a.filter == filter && a.S == S && a.D == D) return RT_OK;
     RtResampleAxis t;
-    const int rc = rt_resample_build_axis(S, D, filter, nullptr, &t);
-    if (rc) return rc;
+    RT_TRY(rt_resample_build_axis(S, D, filter, nullptr, &t));
     auto hip = [&](const char *call, hipError_t e) {
         if (e == hipSuccess) return false;
         failed = call;
@@ -164,12 +163,10 @@ int rt_display_resample(rt_context *c, const void *dSrc, void *dDst, const rt_re
     if (d->filter != RT_RESAMPLE_AREA && d->filter != RT_RESAMPLE_TRIANGLE && d->filter != RT_RESAMPLE_LANCZOS3)
         return fail(c, RT_ERR_INVALID_ARG, "unknown resample filter");
     if (d->flags) return fail(c, RT_ERR_INVALID_ARG, "unknown resample flag bits");
-    if (d->reserved[0] || d->reserved[1]) return fail(c, RT_ERR_INVALID_ARG, "reserved words must be zero");
-    if (!dSrc || ((uintptr_t)dSrc & 15u)) return fail(c, RT_ERR_INVALID_ARG, "the source pointer must be non-NULL and 16-byte aligned");
-    if (!dDst || ((uintptr_t)dDst & 15u)) return fail(c, RT_ERR_INVALID_ARG, "the destination pointer must be non-NULL and 16-byte aligned");
-    const uintptr_t s0 = (uintptr_t)dSrc, d0 = (uintptr_t)dDst;
+    RT_TRY(rt_check_reserved(c, d->reserved));
+    RT_TRY(rt_check_pointers(c, {{dSrc, "source"}, {dDst, "destination"}}));
     const size_t srcBytes = (size_t)d->srcWidth * d->srcHeight * 16, dstBytes = (size_t)d->dstWidth * d->dstHeight * 16;
-    if (s0 < d0 + dstBytes && d0 < s0 + srcBytes) return fail(c, RT_ERR_INVALID_ARG, "rt_display_resample cannot run in place: source and destination overlap");
+    if (overlaps({dSrc, srcBytes}, {dDst, dstBytes})) return fail(c, RT_ERR_INVALID_ARG, "rt_display_resample cannot run in place: source and destination overlap");
     HIP_TRY(c, hipSetDevice(c->device));
     int rc;
     try {

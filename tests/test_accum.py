@@ -245,6 +245,38 @@ def test_planted_accumulator(rt):
     assert np.isposinf(AO.view(acc, "relerr", **desc)[6:, :, 0]).any()
 
 
+@pytest.mark.parametrize("w", [256, 250])
+@pytest.mark.parametrize("k", [1, 2, 3, 64])
+def test_distinct_bins_in_one_ballot(rt, k, w):
+    """One chunk, four waves: slot j of thread t is pixel 256j + t, so every 64 consecutive pixels meet in one ballot of the
+    histogram add (csrc/rt_wave.h).  The accumulator is planted as _planted's row 1 is (the sample's luminance is the planted mean:
+    the count alone moves, 100 -> 101) with M2 in the middle of chosen bins, k distinct ones per 64 pixels: one round suffices (1),
+    exactly the two rounds there are (2), one bin left to the lanes that add for themselves (3), every lane alone (64).  Width 250:
+    the last wave's last ballot has 40 lanes, and 24 without a pixel."""
+    h = 4
+    desc = dict(rel_error=0.05, lum_floor=2.0 ** -40, min_samples=101, done_permille=500)
+    Yc = np.float64(AO.luminance(np.ones((1, 1, 4), dtype=np.float32))[0, 0])
+    group, lane = np.divmod(np.arange(w * h), 64)
+    want_bin = 10 + (7 * lane + group) % k + group
+    r2 = (((396 + want_bin).astype(np.uint32) << 21) | (1 << 20)).view(np.float32)            # the middle of the bin
+    acc0 = AO.empty(w, h)
+    acc0[0] = 1.0
+    acc0[1, ..., 0] = F(Yc)
+    acc0[1, ..., 1] = (r2.astype(np.float64) * 101 * 100 * Yc ** 2).astype(np.float32).reshape(h, w)
+    AO.set_counts(acc0, np.ones((h, w), dtype=bool), 100)
+    img = np.ones((h, w, 4), dtype=np.float32)
+    acc, want = AO.accumulate(acc0, img, 0, **desc)
+    bins = AO.judge(acc, **desc)["bin"].reshape(-1)
+    assert (bins == want_bin).all() and (AO.counts(acc) == 101).all()
+    for g in range((w * h + 63) // 64):
+        assert len(set(bins[64 * g: 64 * g + 64].tolist())) == min(k, w * h - 64 * g)
+    dev = Device(w, h, acc0)
+    got_acc, got_state = dev.add(rt, img, **desc)
+    check_accum(got_acc, acc, (k, w))
+    check_state(got_state, want, (k, w))
+    assert int(got_state["hist"].sum()) == w * h and int((got_state["hist"] != 0).sum()) == len(set(want_bin.tolist()))
+
+
 def test_rejected_samples_leave_the_pixel_untouched(rt):
     """A frame of nothing but refused samples over a used accumulator: all 32 bytes of every pixel stay, and the state still reports."""
     rng = np.random.default_rng(12)

@@ -118,6 +118,27 @@ def test_coherent_content(rt, tables, kind):
         assert np.isposinf(got["minLum"]) and got["maxLum"] == 0.0
 
 
+@pytest.mark.parametrize("w", [64, 63])
+@pytest.mark.parametrize("k", [1, 2, 3, 64])
+def test_distinct_bins_in_one_ballot(rt, tables, k, w):
+    """One wave, 64 quads: slot j of lane t is pixel 4t + j, so the 64 lanes' slot-j pixels meet in one ballot of the histogram add
+    (csrc/rt_wave.h).  Every slot holds k distinct bins among its lanes: one round suffices (1), exactly the two rounds there are
+    (2), one bin left to the lanes that add for themselves (3), every lane alone (64).  Width 63: the last lane has no pixel."""
+    lanes = w                                                   # 4 rows of w pixels are w quads
+    t, j = np.divmod(np.arange(4 * lanes), 4)
+    want_bin = 40 + 3 * ((7 * t + j) % k) + j
+    grey = (((888 + want_bin).astype(np.uint32) << 20) | (1 << 19)).view(np.float32)          # the middle of the bin
+    img = np.ones((4, w, 4), dtype=np.float32)
+    img.reshape(-1, 4)[:, :3] = grey[:, None]
+    bins = MO.bins_of(MO.luminance(img)).reshape(-1)
+    assert (bins == want_bin).all()
+    for slot in range(4):
+        assert len(set(bins[slot::4].tolist())) == min(k, lanes)
+    got = meter_once(rt, img)
+    check(got, MO.meter(img, ZERO, tables), (k, w))
+    assert got["nMetered"] == 4 * lanes and int((got["hist"] != 0).sum()) == len(set(want_bin.tolist()))
+
+
 # ---- 3. bin edges ------------------------------------------------------------------------------------------------------------------
 def test_bin_edges(rt, tables):
     """Edge k (k = 0..256) is the float32 with bits (888 + k) << 20: the lower end of bin k (k = 256: the first value clamped into bin
