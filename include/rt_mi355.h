@@ -800,6 +800,88 @@ int rt_denoise_layout(int width, int height, size_t offset[2], size_t *bytes);
 int rt_denoise(rt_context *ctx, const void *dImage, const void *dMoments, const void *dGuide, void *dScratch, void *dOut,
                const rt_denoise_desc *desc, void *hipStream);
 
+/* ---- reprojection: the temporal half of SVGF -- the accumulator of the previous view carried over to a new camera, so that a camera
+ *      move no longer means rt_accum_reset.  The scene is taken as static between the two views (a moved object is the caller's
+ *      reason to reset).  Device buffers, all caller-owned and 16-byte aligned:
+ *        dAccumPrev: the previous view's accumulator, both planes (rt_accum_layout; rt_reproject_layout gives the same answer);
+ *        dHitsPrev, dHitsCur: width*height rt_hit records of rt_camera_rays -> rt_trace_rays(RT_QUERY_CLOSEST) for the previous and
+ *                    the current view (the current ones are what rt_denoise_guide needs anyway);
+ *        dAccumCur:  a second accumulator, written in full: the history every current pixel can legitimately keep, as it stands an
+ *                    input of rt_accum_add, rt_denoise and the display path;
+ *        dReport:    one rt_reproject_report (64 B).
+ *      Asynchronous on hipStream (NULL = the context's stream), no host synchronisation, and the context keeps no state of the
+ *      feature: a clear of the report (two memsets), then one kernel, in stream order.  All arithmetic is fp32, never fused, with IEEE divide and
+ *      sqrt; dot(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z.
+ *      VIEWS.  Of desc.prev and desc.cur only camPos, camDir, camRight, camUp, fovDeg, focalLength, width and height are read; both
+ *        widths and heights must equal desc.width / desc.height.  The basis is taken as orthonormal, which is what rt_camera_vectors
+ *        produces; with any other basis the projection is merely wrong, and the tap tests below turn that into lost history, never
+ *        into false history.  Per view, on the host, exactly as the render does (rtm::tan_ of csrc/rt_mesa_math.h):
+ *          tanFov = tan_((fovDeg * 0.017453292519943295f) * 0.5f);  sx = ((float)width / (float)height) * tanFov * focalLength;
+ *          sy = tanFov * focalLength;   and for both  hx = 0.5f*(float)width,  hy = 0.5f*(float)height.
+ *      PROJECTION proj(V, P):  v = P - camPos per component;  z = dot(v, camDir);  x = dot(v, camRight);  y = dot(v, camUp);
+ *          valid iff z > 0 (a NaN fails);  fx = ((x / z) / sx + 1.0f) * hx - 0.5f;  fy = ((y / z) / sy + 1.0f) * hy - 0.5f.
+ *        This inverts generateCameraRay's pixel -> uv map without its jitter: the centre of pixel (px, py) projects to (px, py).
+ *        rt_reproject_project runs it on the host (one source for host and device): f[2] = {fx, fy}, *valid = 0 / 1.
+ *      MOTION.  rt_camera_rays jitters every ray by up to a pixel, so the hit P of pixel p = (px, py) is not at the pixel's centre.
+ *        The jitter is removed to first order by projecting P into BOTH views:  m = proj(prev, P) - proj(cur, P) per component;
+ *        g = ((float)px + m.x, (float)py + m.y).  With identical views m is exactly (0, 0).
+ *      CATEGORIES.  Every pixel falls into exactly one, in this order, and the report counts each:
+ *        MISS:      object_p < 0.  Sky is not reprojected.
+ *        OFFSCREEN: either projection is invalid, or g is not finite, or not (-1 < gx < (float)width and -1 < gy < (float)height)
+ *                   -- tested in float before any conversion to integer.
+ *        REJECTED:  no tap below is kept.
+ *        REUSED:    otherwise.
+ *        All but REUSED store 32 zero bytes: an empty pixel, exactly what rt_accum_reset leaves.
+ *      TAPS.  x0 = (int)floorf(gx);  ax = gx - (float)x0;  likewise y0, ay.  The four taps q = (x0+i, y0+j), i, j = 0, 1, have the
+ *        bilinear weights w = (i ? ax : 1.0f - ax) * (j ? ay : 1.0f - ay).  With n^ = (s = dot(n, n)) > 0 ? n / sqrtf(s) per
+ *        component : 0 (rt_denoise_guide's rule) for the current normal n^p and the tap's n^q, a tap is DROPPED when any of
+ *          w == 0;   q outside the image;   count_q == 0;   object_q != object_p;   dot(n^p, n^q) < normalCosMin;
+ *          fabsf(dot(P - P_q, n^p)) > planeTol * t_p
+ *        holds (comparisons as written: a NaN operand does not drop).  The last asks whether the previous hit lies in the current
+ *        hit's tangent plane: exact for planes, second order for spheres, insensitive to the sub-pixel offsets of the two jitters.
+ *      RESULT.  Sums run over the kept taps in the order (0,0), (1,0), (0,1), (1,1), starting at +0:
+ *          sw = sum(w);   mean' = sum(w*mean_q) / sw per channel (alpha too);   mY' = sum(w*mY_q) / sw;
+ *          s2_q = count_q >= 2 ? M2_q / (float)(count_q - 1) : 0;   s2' = sum(w*s2_q) / sw;
+ *          n' = min(min over the kept taps of count_q, maxHistory);   M2' = s2' * (float)(n' - 1);
+ *        plane 0 = mean', plane 1 = {mY', M2', bits(n'), 0}.  A single kept tap of weight 1 reproduces its mean and mY bit for bit
+ *        (+0 + 1*x = x, x / 1 = x; a -0 comes out as +0) and M2 within two roundings.  Capping n' at maxHistory makes the next
+ *        rt_accum_add weigh its sample at least 1 / (maxHistory + 1): that bounds the lag of a moving view.
+ *        With the accumulator's own bounds (|mean|, |mY| <= 2^48; M2 <= count * 2^98, so s2_q <= 2^99) every sum stays finite: the
+ *        weights are products of two numbers in [0, 1] that sum to at most 1 + 2^-22, so sum(w*x) <= 2^49 and sum(w*s2) <= 2^100; a
+ *        quotient by sw is a weighted mean up to rounding -- at most twice the largest term even when w is denormal -- so
+ *        |mean'|, |mY'| <= 2^50, s2' <= 2^101 and M2' <= 2^101 * 2^24 = 2^125 < 2^128.  2^24 further samples add at most 2^122.
+ *      REPORT.  nReused + nRejected + nOffscreen + nMiss == nPixels = width*height;  minCount / maxCount = min / max of n' over the
+ *        REUSED pixels (2^32 - 1 and 0 when there is none);  sumCount = sum of n' over them.  Every field is built with integer atomics: it
+ *        is bit-identical from run to run, as is the accumulator (every pixel is a pure function of the inputs).
+ *      Refused before anything is enqueued, with RT_ERR_INVALID_ARG: NULL context, descriptor or pointer; a pointer not 16-byte
+ *      aligned; dAccumCur or dReport overlapping an input or each other; width or height < 1; a view whose width / height differ
+ *      from the descriptor's; a fovDeg or focalLength for which sx or sy is not finite and > 0; normalCosMin not finite or outside
+ *      [-1, 1]; planeTol not finite or < 0; maxHistory outside 1..2^24-1; non-zero reserved words.  RT_ERR_TOO_LARGE: width*height
+ *      > 2^31 - 1.  The context stays usable.  rt_reproject_project refuses NULL pointers and such a view the same way.  The loop:
+ *          view changes:  rt_camera_rays(ctx, &cur, dRays, s);  rt_trace_rays(ctx, dRays, n, RT_QUERY_CLOSEST, dHitsCur, s);
+ *                         rt_accum_reproject(ctx, dAccumPrev, dHitsPrev, dHitsCur, dAccumCur, &desc, dReport, s);
+ *                         swap(prev, cur) of the accumulators and of the hits;  rt_denoise_guide on the new hits
+ *          every frame:   rt_render;  rt_accum_add(ctx, dColor, dAccum, &a, dState, s);  rt_denoise(...);  rt_present_submit_toned(...) */
+typedef struct rt_reproject_desc {
+    int32_t width, height;           /* >= 1 */
+    rt_params prev, cur;             /* the two views; see VIEWS for the fields that are read */
+    float normalCosMin;              /* finite, in [-1, 1]: a tap whose normal is turned further from the current one is dropped */
+    float planeTol;                  /* finite, >= 0: distance of the tap's hit from the current tangent plane, in units of t_p */
+    int32_t maxHistory;              /* 1..2^24-1: the most samples a reprojected pixel counts for */
+    int32_t reserved[3];             /* zero */
+} rt_reproject_desc;
+typedef struct rt_reproject_report {
+    uint32_t nPixels, nReused, nRejected, nOffscreen, nMiss;
+    uint32_t minCount, maxCount;     /* of n' over the reused pixels; 2^32 - 1 and 0 when there is none */
+    uint32_t reserved0;              /* zero */
+    uint64_t sumCount;               /* of n' over the reused pixels */
+    uint32_t reserved[6];            /* zero */
+} rt_reproject_report;
+int rt_reproject_layout(int width, int height, size_t offset[2], size_t *bytes);
+int rt_reproject_project(const rt_params *view, const float P[3], float f[2], int *valid);
+int rt_accum_reproject(rt_context *ctx, const void *dAccumPrev, const void *dHitsPrev, const void *dHitsCur, void *dAccumCur,
+                       const rt_reproject_desc *desc, void *dReport, void *hipStream);
+
 /* ---- multi-GPU strip helpers */
 /* Number of local rows a rank owns for interleaved strips. */
 int rt_strip_local_rows(int height, int stripRows, int stripCount, int stripIndex);
@@ -913,6 +995,11 @@ RT_SA(sizeof(rt_accum_state) == 1024 && offsetof(rt_accum_state, nPixels) == 512
 RT_SA(sizeof(rt_denoise_guide_rec) == 16 && offsetof(rt_denoise_guide_rec, object) == 12, "rt_denoise_guide_rec is the upper half of rt_hit");
 RT_SA(sizeof(rt_denoise_desc) == 48 && offsetof(rt_denoise_desc, iterations) == 8 && offsetof(rt_denoise_desc, sigmaLum) == 16 &&
       offsetof(rt_denoise_desc, minCount) == 24 && offsetof(rt_denoise_desc, reserved) == 28, "rt_denoise_desc is 48 B");
+RT_SA(sizeof(rt_reproject_desc) == 288 && offsetof(rt_reproject_desc, prev) == 8 && offsetof(rt_reproject_desc, cur) == 136 &&
+      offsetof(rt_reproject_desc, normalCosMin) == 264 && offsetof(rt_reproject_desc, maxHistory) == 272 &&
+      offsetof(rt_reproject_desc, reserved) == 276, "rt_reproject_desc is 288 B");
+RT_SA(sizeof(rt_reproject_report) == 64 && offsetof(rt_reproject_report, minCount) == 20 && offsetof(rt_reproject_report, sumCount) == 32 &&
+      offsetof(rt_reproject_report, reserved) == 40, "rt_reproject_report is 64 B");
 #undef RT_SA
 #endif
 

@@ -45,6 +45,7 @@ EXPORTS = [
     "rt_resample_taps", "rt_display_resample",
     "rt_accum_layout", "rt_accum_reset", "rt_accum_add", "rt_accum_solve_host", "rt_accum_view",
     "rt_denoise_guide", "rt_denoise_layout", "rt_denoise",
+    "rt_reproject_layout", "rt_reproject_project", "rt_accum_reproject",
 ]
 
 
@@ -187,6 +188,9 @@ def load_library(build_if_missing=True):
     lib.rt_denoise_guide.argtypes = [vp, vp, vp, ci, ci, vp]
     lib.rt_denoise_layout.argtypes = [ci, ci, P(ctypes.c_size_t), P(ctypes.c_size_t)]
     lib.rt_denoise.argtypes = [vp, vp, vp, vp, vp, vp, P(L.RtDenoiseDesc), vp]
+    lib.rt_reproject_layout.argtypes = [ci, ci, P(ctypes.c_size_t), P(ctypes.c_size_t)]
+    lib.rt_reproject_project.argtypes = [P(L.RtParams), P(ctypes.c_float), P(ctypes.c_float), P(ci)]
+    lib.rt_accum_reproject.argtypes = [vp, vp, vp, vp, vp, P(L.RtReprojectDesc), vp, vp]
     for name in EXPORTS:
         if name not in ("rt_last_error", "rt_mgpu_last_error", "rt_wire_bytes"):
             getattr(lib, name).restype = ci
@@ -434,6 +438,38 @@ def denoise_layout(width, height):
     if rc:
         raise RtError(rc, "rt_denoise_layout")
     return DenoiseLayout(tuple(off), n.value)
+
+
+ReprojectLayout = collections.namedtuple("ReprojectLayout", "offset bytes")
+ReprojectLayout.__doc__ = """rt_reproject_layout's answer: byte offsets of the two planes of reproject's output accumulator and its size."""
+
+
+def reproject_layout(width, height):
+    """Where the two planes of the accumulator rt_accum_reproject writes lie (rt_reproject_layout; the same answer as accum_layout's)
+    -> ReprojectLayout.  Needs no GPU."""
+    off, n = (ctypes.c_size_t * 2)(), ctypes.c_size_t(0)
+    rc = load_library().rt_reproject_layout(int(width), int(height), off, ctypes.byref(n))
+    if rc:
+        raise RtError(rc, "rt_reproject_layout")
+    return ReprojectLayout(tuple(off), n.value)
+
+
+def reproject_project(view, point):
+    """rt_accum_reproject's projection on the host (rt_reproject_project): the world position `point` (3 floats) through the
+    RtParams `view` -> ((fx, fy) as np.float32 in pixel coordinates, pixel centres at integers; valid: the point lies in front of
+    the camera).  Needs no GPU."""
+    P3 = (ctypes.c_float * 3)(*[float(x) for x in point])
+    f, valid = (ctypes.c_float * 2)(), ctypes.c_int(0)
+    rc = load_library().rt_reproject_project(ctypes.byref(view), P3, f, ctypes.byref(valid))
+    if rc:
+        raise RtError(rc, "rt_reproject_project")
+    return (np.float32(f[0]), np.float32(f[1])), bool(valid.value)
+
+
+def reproject_report(d_report):
+    """The read-back of a reproject report (a CUDA tensor of 64 bytes; waits for the device) as one layout.REPROJECT_REPORT_DTYPE
+    record: nPixels, nReused, nRejected, nOffscreen, nMiss, minCount, maxCount, sumCount."""
+    return d_report.cpu().numpy().view(np.uint8).reshape(-1)[:L.REPROJECT_REPORT_BYTES].view(L.REPROJECT_REPORT_DTYPE)[0]
 
 
 def _dev_ptr(x):
@@ -831,6 +867,25 @@ class RayTracer:
         self._on_torch_stream(stream, lambda h: self._check(self.lib.rt_denoise(
             self.ctx, _dev_ptr(d_image), mom, _dev_ptr(d_guide), _dev_ptr(d_scratch), _dev_ptr(d_out), ctypes.byref(d),
             ctypes.c_void_p(h)), "rt_denoise"))
+
+    # ---- reprojection ------------------------------------------------------------------------
+    def reproject(self, d_accum_prev, d_hits_prev, d_hits_cur, d_accum_cur, d_report, prev, cur, normal_cos_min=0.9, plane_tol=0.01,
+                  max_history=32, stream=None):
+        """Carry the accumulator of the view `prev` over to the view `cur` (rt_accum_reproject; both RtParams of one size): every
+        current pixel keeps the history its first hit (d_hits_cur) finds on its own surface in the previous view's hits and
+        accumulator, capped at max_history samples, or becomes empty; d_accum_cur is written in full and is accum_add's,
+        denoise's and the display path's input as it stands, d_report takes the 64-byte report (reproject_report reads it).  Raw
+        device pointers or CUDA tensors, 16-byte aligned; asynchronous on torch stream `stream` (default
+        torch.cuda.current_stream()): a clear and one launch, no host synchronisation.  The caller swaps the accumulators and
+        the hits afterwards."""
+        d = L.make_reproject_desc(prev, cur, normal_cos_min, plane_tol, max_history)
+        self._on_torch_stream(stream, lambda h: self._check(self.lib.rt_accum_reproject(
+            self.ctx, _dev_ptr(d_accum_prev), _dev_ptr(d_hits_prev), _dev_ptr(d_hits_cur), _dev_ptr(d_accum_cur), ctypes.byref(d),
+            _dev_ptr(d_report), ctypes.c_void_p(h)), "rt_accum_reproject"))
+
+    reproject_layout = staticmethod(reproject_layout)
+    reproject_project = staticmethod(reproject_project)
+    reproject_report = staticmethod(reproject_report)
 
     @staticmethod
     def accum_moments(d_accum, width, height):

@@ -386,3 +386,44 @@ def make_denoise_desc(width, height, iterations=4, normal_log2_power=5, sigma_lu
     d.width, d.height, d.iterations, d.normalLog2Power = int(width), int(height), int(iterations), int(normal_log2_power)
     d.sigmaLum, d.lumEps, d.minCount = float(sigma_lum), float(lum_eps), int(min_count)
     return d
+
+
+# ---- reprojection (rt_accum_reproject, include/rt_mi355.h) ---------------------------------------------
+REPROJECT_DEFAULTS = dict(normal_cos_min=0.9, plane_tol=0.01, max_history=32)
+REPROJECT_REPORT_BYTES = 64
+
+
+class RtReprojectDesc(ctypes.Structure):
+    """``rt_reproject_desc``: surface size, the previous and the current view, the two tap tests' thresholds, the history cap."""
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("prev", RtParams), ("cur", RtParams),
+                ("normalCosMin", ctypes.c_float), ("planeTol", ctypes.c_float), ("maxHistory", ctypes.c_int32),
+                ("reserved", ctypes.c_int32 * 3)]
+
+
+class RtReprojectReport(ctypes.Structure):
+    """``rt_reproject_report``: the 64 bytes rt_accum_reproject leaves on the device."""
+    _fields_ = [("nPixels", ctypes.c_uint32), ("nReused", ctypes.c_uint32), ("nRejected", ctypes.c_uint32),
+                ("nOffscreen", ctypes.c_uint32), ("nMiss", ctypes.c_uint32), ("minCount", ctypes.c_uint32),
+                ("maxCount", ctypes.c_uint32), ("reserved0", ctypes.c_uint32), ("sumCount", ctypes.c_uint64),
+                ("reserved", ctypes.c_uint32 * 6)]
+
+
+# the same record as a numpy dtype (what a read-back of the report is viewed as)
+REPROJECT_REPORT_DTYPE = np.dtype({
+    "names": ["nPixels", "nReused", "nRejected", "nOffscreen", "nMiss", "minCount", "maxCount", "reserved0", "sumCount", "reserved"],
+    "formats": ["<u4"] * 8 + ["<u8", ("<u4", (6,))],
+    "offsets": [4 * k for k in range(8)] + [32, 40], "itemsize": 64})
+
+assert ctypes.sizeof(RtReprojectDesc) == 288 and RtReprojectDesc.cur.offset == 136 and RtReprojectDesc.normalCosMin.offset == 264
+assert RtReprojectDesc.reserved.offset == 276
+assert ctypes.sizeof(RtReprojectReport) == REPROJECT_REPORT_BYTES == REPROJECT_REPORT_DTYPE.itemsize
+assert all(REPROJECT_REPORT_DTYPE.fields[k][1] == getattr(RtReprojectReport, k).offset for k in REPROJECT_REPORT_DTYPE.names)
+
+
+def make_reproject_desc(prev, cur, normal_cos_min=0.9, plane_tol=0.01, max_history=32):
+    """prev, cur: the RtParams of the two views; the surface size is the current view's."""
+    d = RtReprojectDesc()
+    d.width, d.height = int(cur.width), int(cur.height)
+    d.prev, d.cur = prev, cur
+    d.normalCosMin, d.planeTol, d.maxHistory = float(normal_cos_min), float(plane_tol), int(max_history)
+    return d
