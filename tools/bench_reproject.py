@@ -12,89 +12,24 @@
       reprojection EVERY frame, ping-pong accumulators): the frame-loop residual.
 
 Writes one record per size to --out (default profiles/reproject_bench.json)."""
-import argparse, ctypes, json, math, os, statistics, sys, time
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import numpy as np
+import argparse, ctypes, json, math
+import stagebench as sb                                         # (puts the repository on sys.path)
 import torch
 from opengl_raytracing_amd import host, scenes
 from opengl_raytracing_amd import layout as L
 
 ap = argparse.ArgumentParser()
-ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "reproject_bench.json"))
-ap.add_argument("--parent-lib", default=None, help="librt_mi355.so built from the parent commit (build_library(out=...))")
-ap.add_argument("--variant", action="append", default=[], help="NAME=PATH of a library built with other RT_REPROJECT_* macros")
-ap.add_argument("--frames", type=int, default=100)
-ap.add_argument("--repeats", type=int, default=5)
-ap.add_argument("--launches", type=int, default=50)
+sb.add_common_args(ap, "reproject_bench.json", launches=50, variant_macros="RT_REPROJECT_")
 args = ap.parse_args()
+variant_libs = sb.parse_variants(args.variant)
+WARM = 5                                                        # launches of each candidate in front of the first timed batch
 
-
-def tracer(path):
-    """A RayTracer on the library at `path` (None: this build's)."""
-    host._LIB = None
-    if path:
-        os.environ["RT_LIB"] = path
-    try:
-        return host.RayTracer(0)
-    finally:
-        os.environ.pop("RT_LIB", None)
-        host._LIB = None
-
-
-new = tracer(None)
-old = tracer(args.parent_lib) if args.parent_lib else new
-variants = {"this": new}
-for spec in args.variant:
-    name, _, path = spec.partition("=")
-    variants[name] = tracer(path)
+new, old, variants = sb.open_tracers(args.parent_lib, variant_libs)
+tracers = sb.distinct([new, old, *variants.values()])
 sc = scenes.make_scene(2, host.generate_aabb)
-for t in {id(x): x for x in [new, old, *variants.values()]}.values():
+for t in tracers:
     t.load(sc)
-side = torch.cuda.Stream()
-blocker_a = torch.zeros(256 << 20, dtype=torch.uint8, device="cuda")
-blocker_b = torch.empty_like(blocker_a)
-
-
-def hold(stream):
-    """Keep `stream` busy for a few milliseconds so that the launches timed behind it are all queued before the first one starts."""
-    with torch.cuda.stream(stream):
-        for _ in range(40):
-            blocker_b.copy_(blocker_a)
-
-
-def device_us(launch, K):
-    """Microseconds per call of launch() from device events around K back-to-back calls on `side`."""
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    hold(side)
-    e0.record(side)
-    for _ in range(K):
-        launch()
-    e1.record(side)
-    side.synchronize()
-    return e0.elapsed_time(e1) / K * 1e3
-
-
-def alternate(launches, K, repeats):
-    """launches: {name: callable}; every repeat times each once, in alternating order -> {name: [us per repeat]}."""
-    for f in launches.values():
-        for _ in range(5):
-            f()
-    side.synchronize()
-    us = {k: [] for k in launches}
-    for r in range(repeats):
-        for k in (list(launches) if r % 2 == 0 else list(launches)[::-1]):
-            us[k].append(device_us(launches[k], K))
-    return us
-
-
-def put(rec, key, us):
-    rec[key + "_us"] = round(statistics.median(us), 2)
-    rec[key + "_us_all"] = [round(x, 2) for x in us]
-
-
-def check(t, rc, what):
-    if rc:
-        raise host.RtError(rc, f"{what}: {t.lib.rt_last_error(t.ctx).decode()}")
+side = sb.side()
 
 
 # ---- the warp: a plane at z = -8 behind 43 x 24 spheres of radius 0.06 at z = -4, 0.14 apart
@@ -143,22 +78,17 @@ def first_hits(p, gen):
 def loop(t, p, accum, reproject=None):
     """n frames of rt_render + rt_accum_add with `accum` = (d_accum, d_state, desc) on t's own stream; with `reproject` = (d_hits_prev,
     d_hits_cur, d_accum_other, desc, d_report) a reprojection in front of every add, the two accumulators taking turns."""
-    lib, ctx, d_color, vp = t.lib, t.ctx, ctypes.c_void_p(), ctypes.c_void_p
-    check(t, lib.rt_render(ctx, ctypes.byref(p)), "rt_render")
-    check(t, lib.rt_get_surfaces(ctx, ctypes.byref(d_color), None, None), "rt_get_surfaces")
+    lib, ctx, vp = t.lib, t.ctx, ctypes.c_void_p
     acc = [accum[0].data_ptr(), reproject[2].data_ptr() if reproject else 0]
 
-    def run(n):
-        for k in range(n):
-            check(t, lib.rt_render(ctx, ctypes.byref(p)), "rt_render")
-            cur = 0
-            if reproject:
-                cur = (k + 1) & 1
-                check(t, lib.rt_accum_reproject(ctx, vp(acc[cur ^ 1]), vp(reproject[0].data_ptr()), vp(reproject[1].data_ptr()), vp(acc[cur]),
-                                                ctypes.byref(reproject[3]), vp(reproject[4].data_ptr()), None), "rt_accum_reproject")
-            check(t, lib.rt_accum_add(ctx, d_color, vp(acc[cur]), ctypes.byref(accum[2]), vp(accum[1].data_ptr()), None), "rt_accum_add")
-        t.sync()
-    return run
+    def stage(d_color, k):
+        cur = 0
+        if reproject:
+            cur = (k + 1) & 1
+            sb.check(t, lib.rt_accum_reproject(ctx, vp(acc[cur ^ 1]), vp(reproject[0].data_ptr()), vp(reproject[1].data_ptr()), vp(acc[cur]),
+                                               ctypes.byref(reproject[3]), vp(reproject[4].data_ptr()), None), "rt_accum_reproject")
+        sb.check(t, lib.rt_accum_add(ctx, d_color, vp(acc[cur]), ctypes.byref(accum[2]), vp(accum[1].data_ptr()), None), "rt_accum_add")
+    return sb.render_loop(t, p, [stage])
 
 
 records = []
@@ -187,9 +117,9 @@ for (w, h) in [(1920, 1080), (3840, 2160)]:
     for name, t in variants.items():
         launches[f"reproject_{name}"] = lambda t=t: t.reproject(d_prev, d_hits_a, d_hits_b, d_cur, d_report, pa, pb, stream=side)
     with torch.cuda.stream(side):
-        us = alternate(launches, args.launches, args.repeats)
+        us = sb.alternate(launches, args.launches, args.repeats, WARM)
     for k, v in us.items():
-        put(rec, k, v)
+        sb.summarise(rec, k, v, "us")
     nbytes = w * h * 128
     rec["copy128_TBps"] = round(nbytes / rec["copy128_us"] * 1e-6, 3)
     out_this = None
@@ -216,28 +146,15 @@ for (w, h) in [(1920, 1080), (3840, 2160)]:
     adesc, rdesc = L.make_accum_desc(w, h), L.make_reproject_desc(pa, pb)
     loops = {"render_accum_parent": loop(old, p, (d_prev, d_state, adesc)), "render_accum_this": loop(new, p, (d_prev, d_state, adesc)),
              "render_reproject_accum": loop(new, p, (d_prev, d_state, adesc), (d_hits_a, d_hits_b, d_cur, rdesc, d_report))}
-    times = {k: [] for k in loops}
-    for f in loops.values():
-        f(20)
-    for r in range(args.repeats):
-        for k in (list(loops) if r % 2 == 0 else list(loops)[::-1]):
-            t0 = time.perf_counter()
-            loops[k](args.frames)
-            times[k].append((time.perf_counter() - t0) / args.frames * 1e3)
+    times = sb.time_host_loops(loops, args.frames, args.repeats)
     for k, v in times.items():
-        rec[k + "_ms"] = round(statistics.median(v), 4)
-        rec[k + "_ms_all"] = [round(x, 4) for x in v]
-    rec["render_accum_parent_spread_ms"] = round(max(times["render_accum_parent"]) - min(times["render_accum_parent"]), 4)
+        sb.summarise(rec, k, v, "ms")
+    rec["render_accum_parent_spread_ms"] = round(sb.spread(times["render_accum_parent"]), 4)
     rec["render_accum_this_minus_parent_ms"] = round(rec["render_accum_this_ms"] - rec["render_accum_parent_ms"], 4)
     rec["reproject_residual_ms"] = round(rec["render_reproject_accum_ms"] - rec["render_accum_this_ms"], 4)
     del d_prev, d_cur, d_state, d_hits_a, d_hits_b, base, out_this
     print(json.dumps(rec), flush=True)
     records.append(rec)
 
-os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-with open(args.out, "w") as f:
-    json.dump({"tool": "tools/bench_reproject.py", "scene": "C2", "variants": {k: v for k, v in (s.split("=", 1) for s in args.variant)},
-               "records": records}, f, indent=1)
-    f.write("\n")
-for t in {id(x): x for x in [new, old, *variants.values()]}.values():
-    t.close()
+sb.write_records(args.out, "tools/bench_reproject.py", records, scene="C2", variants=variant_libs)
+sb.close_all(tracers)

@@ -13,76 +13,24 @@
       supersampled 1080p frame.
 
 Writes --out (default profiles/resample_bench.json)."""
-import argparse, ctypes, json, os, statistics, sys, time
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import argparse, ctypes, itertools, json
+import stagebench as sb                                         # (puts the repository on sys.path)
 import torch
 from opengl_raytracing_amd import host, scenes
 from opengl_raytracing_amd import layout as L
 
 ap = argparse.ArgumentParser()
-ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "resample_bench.json"))
-ap.add_argument("--parent-lib", default=None, help="librt_mi355.so built from the parent commit (build_library(out=...))")
+sb.add_common_args(ap, "resample_bench.json", launches=100)
 ap.add_argument("--variant-lib", default=None, help="another build of this library to time beside it")
 ap.add_argument("--variant-name", default="variant")
-ap.add_argument("--frames", type=int, default=100)
-ap.add_argument("--repeats", type=int, default=5)
-ap.add_argument("--launches", type=int, default=100)
 ap.add_argument("--rotate-mib", type=int, default=640)
 ap.add_argument("--note", default=None, help="free text stored with the records")
 args = ap.parse_args()
+WARM = 20                                                       # launches of each candidate in front of the first timed batch
 
-
-def tracer(path):
-    """A RayTracer on the library at `path` (None: this build's)."""
-    host._LIB = None
-    if path:
-        os.environ["RT_LIB"] = path
-    try:
-        return host.RayTracer(0)
-    finally:
-        os.environ.pop("RT_LIB", None)
-        host._LIB = None
-
-
-new = tracer(None)
-variant = tracer(args.variant_lib) if args.variant_lib else None
-old = tracer(args.parent_lib) if args.parent_lib else new
-side = torch.cuda.Stream()
-blocker_a = torch.zeros(256 << 20, dtype=torch.uint8, device="cuda")
-blocker_b = torch.empty_like(blocker_a)
-
-
-def hold(stream):
-    """Keep `stream` busy for a few milliseconds so that the launches timed behind it are all queued before the first one starts."""
-    with torch.cuda.stream(stream):
-        for _ in range(40):
-            blocker_b.copy_(blocker_a)
-
-
-def device_us(launch, K):
-    """Microseconds per call of launch(k) from device events around K back-to-back calls on `side`."""
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    hold(side)
-    e0.record(side)
-    for k in range(K):
-        launch(k)
-    e1.record(side)
-    side.synchronize()
-    return e0.elapsed_time(e1) / K * 1e3
-
-
-def alternate(launches, K, repeats):
-    """launches: {name: callable(k)}; every repeat times each once, in alternating order -> {name: [us per repeat]}."""
-    for f in launches.values():
-        for k in range(20):
-            f(k)
-    side.synchronize()
-    us = {k: [] for k in launches}
-    for r in range(repeats):
-        for k in (list(launches) if r % 2 == 0 else list(launches)[::-1]):
-            us[k].append(device_us(launches[k], K))
-    return us
-
+new, old, variants = sb.open_tracers(args.parent_lib, {args.variant_name: args.variant_lib} if args.variant_lib else {})
+variant = variants[args.variant_name] if args.variant_lib else None
+side = sb.side()
 
 records = []
 gen = torch.Generator(device="cuda").manual_seed(1)
@@ -98,19 +46,20 @@ for (sw, sh), (dw, dh) in [((3840, 2160), (1920, 1080)), ((1920, 1080), (3840, 2
     rec = {"src": [sw, sh], "dst": [dw, dh], "compulsory_bytes": src_bytes + dst_bytes, "launches": args.launches, "repeats": args.repeats,
            "source_buffers": n_src, "copy_source_buffers": n_copy, "rotate_mib": args.rotate_mib}
 
-    def copy(k):
+    turn = itertools.count()                                    # every launch reads the buffer after the one the launch before it read
+
+    def copy():
         with torch.cuda.stream(side):
-            copy_dst.copy_(copy_src[k % n_copy])
+            copy_dst.copy_(copy_src[next(turn) % n_copy])
 
     launches = {"copy": copy}
     for f in ("area", "triangle", "lanczos3"):
-        launches[f] = (lambda f: lambda k: new.resample(srcs[k % n_src], dst, sw, sh, dw, dh, filter=f, stream=side))(f)
+        launches[f] = lambda f=f: new.resample(srcs[next(turn) % n_src], dst, sw, sh, dw, dh, filter=f, stream=side)
         if variant is not None:
-            launches[f"{f}_{args.variant_name}"] = (lambda f: lambda k: variant.resample(srcs[k % n_src], dst, sw, sh, dw, dh, filter=f, stream=side))(f)
-    us = alternate(launches, args.launches, args.repeats)
+            launches[f"{f}_{args.variant_name}"] = lambda f=f: variant.resample(srcs[next(turn) % n_src], dst, sw, sh, dw, dh, filter=f, stream=side)
+    us = sb.alternate(launches, args.launches, args.repeats, WARM)
     for k, v in us.items():
-        rec[k + "_us"] = round(statistics.median(v), 2)
-        rec[k + "_us_all"] = [round(x, 2) for x in v]
+        sb.summarise(rec, k, v, "us")
     for k in us:
         if k != "copy":
             rec[k + "_over_copy"] = round(rec[k + "_us"] / rec["copy_us"], 3)
@@ -123,7 +72,7 @@ for (sw, sh), (dw, dh) in [((3840, 2160), (1920, 1080)), ((1920, 1080), (3840, 2
 
 # ---- (c) the 1080p frame loop off a 4K render
 sc = scenes.make_scene(2, host.generate_aabb)
-for t in {id(new): new, id(old): old}.values():
+for t in sb.distinct([new, old]):
     t.load(sc)
 W4, H4, W2, H2 = 3840, 2160, 1920, 1080
 p4 = sc.params(width=W4, height=H4)
@@ -131,61 +80,28 @@ d_small = torch.empty((H2, W2, 4), dtype=torch.float32, device="cuda")
 torch.cuda.synchronize()
 
 
-def frame_loop(t, kind, filter):
+def deliver_loop(t, filter):
     lib, ctx = t.lib, t.ctx
-    d_color = ctypes.c_void_p()
     desc = L.make_display_desc(W2, H2, "srgb", flip=True)
     rdesc = L.make_resample_desc(W4, H4, W2, H2, filter)
     small = ctypes.c_void_p(d_small.data_ptr())
 
-    def check(rc, what):
-        if rc:
-            raise host.RtError(rc, f"{what}: {lib.rt_last_error(ctx).decode()}")
-
-    check(lib.rt_render(ctx, ctypes.byref(p4)), "rt_render")
-    check(lib.rt_get_surfaces(ctx, ctypes.byref(d_color), None, None), "rt_get_surfaces")
-
-    def loop(n):
-        px, nb, tk = ctypes.c_void_p(), ctypes.c_size_t(), ctypes.c_uint64()
-        prev = None
-        for _ in range(n):
-            check(lib.rt_render(ctx, ctypes.byref(p4)), "rt_render")
-            if kind == "render":
-                continue
-            check(lib.rt_display_resample(ctx, d_color, small, ctypes.byref(rdesc), None), "rt_display_resample")
-            check(lib.rt_present_submit(ctx, small, ctypes.byref(desc), None, ctypes.byref(tk)), "rt_present_submit")
-            if prev is not None:
-                check(lib.rt_present_wait(ctx, prev, ctypes.byref(px), ctypes.byref(nb)), "rt_present_wait")
-            prev = tk.value
-        if prev is not None:
-            check(lib.rt_present_wait(ctx, prev, ctypes.byref(px), ctypes.byref(nb)), "rt_present_wait")
-        t.sync()
-    return loop
+    def submit(d_color, tk):
+        sb.check(t, lib.rt_display_resample(ctx, d_color, small, ctypes.byref(rdesc), None), "rt_display_resample")
+        sb.check(t, lib.rt_present_submit(ctx, small, ctypes.byref(desc), None, tk), "rt_present_submit")
+    return sb.present_loop(t, p4, submit)
 
 
-loops = {"render4k_only_parent": frame_loop(old, "render", "area"), "render4k_only": frame_loop(new, "render", "area")}
+loops = {"render4k_only_parent": sb.render_loop(old, p4), "render4k_only": sb.render_loop(new, p4)}
 for f in ("area", "triangle", "lanczos3"):
-    loops[f"render4k_resample_{f}_present1080"] = frame_loop(new, "deliver", f)
-times = {k: [] for k in loops}
-for f in loops.values():
-    f(20)
-for r in range(args.repeats):
-    for k in (list(loops) if r % 2 == 0 else list(loops)[::-1]):
-        t0 = time.perf_counter()
-        loops[k](args.frames)
-        times[k].append((time.perf_counter() - t0) / args.frames * 1e3)
+    loops[f"render4k_resample_{f}_present1080"] = deliver_loop(new, f)
 loop_rec = {"scene": "C2", "render": [W4, H4], "deliver": [W2, H2], "frames": args.frames, "repeats": args.repeats,
             "yardstick": "parent" if args.parent_lib else "this build"}
-for k, v in times.items():
-    loop_rec[k + "_ms"] = round(statistics.median(v), 4)
-    loop_rec[k + "_ms_all"] = [round(x, 4) for x in v]
+for k, v in sb.time_host_loops(loops, args.frames, args.repeats).items():
+    sb.summarise(loop_rec, k, v, "ms")
 for f in ("area", "triangle", "lanczos3"):
     loop_rec[f"residual_{f}_ms"] = round(loop_rec[f"render4k_resample_{f}_present1080_ms"] - loop_rec["render4k_only_parent_ms"], 4)
 print(json.dumps(loop_rec), flush=True)
 
-os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-with open(args.out, "w") as f:
-    json.dump({"tool": "tools/bench_resample.py", "note": args.note, "records": records, "frame_loop": loop_rec}, f, indent=1)
-    f.write("\n")
-for t in {id(x): x for x in (new, old, variant) if x is not None}.values():
-    t.close()
+sb.write_records(args.out, "tools/bench_resample.py", records, note=args.note, tail={"frame_loop": loop_rec})
+sb.close_all([new, old, *variants.values()])
