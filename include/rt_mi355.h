@@ -882,6 +882,65 @@ int rt_reproject_project(const rt_params *view, const float P[3], float f[2], in
 int rt_accum_reproject(rt_context *ctx, const void *dAccumPrev, const void *dHitsPrev, const void *dHitsCur, void *dAccumCur,
                        const rt_reproject_desc *desc, void *dReport, void *hipStream);
 
+/* ---- adaptive sampling: the accumulator's convergence report as a scheduler -- trace only the pixels that have not converged.
+ *      Three stages around rt_shade_rays; every call is asynchronous on hipStream (NULL = the context's stream), none synchronises
+ *      with the host, every buffer is the caller's and the context keeps no state of this feature.
+ *      rt_accum_select: dAccum (an accumulator, see above; read only) -> the list of pixels that still need samples.
+ *        A pixel is SELECTED when it is not CONVERGED by exactly rt_accum_add's rule (desc's relError, lumFloor, minSamples; a pixel
+ *        with count < 2 is unconverged) and its count < maxSamples.  maxSamples (1..2^24) is a budget cap: pixels that are unconverged
+ *        but at the cap are counted in nCapped and not selected.  desc->donePermille is validated and not used.
+ *        ORDER, part of the contract: the image is cut into tiles of 8 x 8 pixels; tiles go in raster order (tile = (y/8) *
+ *        ceil(width/8) + x/8), pixels in raster order inside a tile; ragged tiles have fewer pixels.  64 consecutive entries lie in a
+ *        few neighbouring tiles, which keeps rt_shade_rays' waves coherent and rt_accum_add_at's accesses compact.
+ *        dPixels (device, rt_pixel, 8-byte aligned, room for `capacity` entries; may be NULL when capacity == 0): exactly the first
+ *        nListed = min(nSelected, capacity) entries of that order are written and nothing behind them is touched; every store is
+ *        checked against the capacity.  capacity == 0 gives a pure count.
+ *        dSelState (device, one rt_select_state of 64 B, 16-byte aligned) is written whole by every call: nPixels; nSelected, the full
+ *        number whatever the capacity; nListed; capacity (saturated at 2^32 - 1); overflow = nSelected > capacity; nCapped.
+ *        dScratch (device, 16-byte aligned, rt_accum_select_layout's scratchBytes; content unspecified, need not be cleared).
+ *        Form: per-tile ballots and popcounts, an exclusive integer scan of the totals, the emit -- three launches (two when
+ *        capacity == 0) ordered by the stream alone; no workgroup waits for another; the result is bit-identical from run to run.
+ *      rt_camera_rays_at: ray k (dRays: device, n rt_ray, 16-byte aligned) is the primary ray of IMAGE pixel dPixels[k] (device, n
+ *        rt_pixel, 8-byte aligned) of rt_render_to(p): noise jitter, frameCount, the GL's tan, tMax = p->maxRayDistance -- bit-identical
+ *        to the record rt_camera_rays(p) writes for that pixel.  The window and strip fields of p are ignored (p is validated with an
+ *        identity window, as in rt_pick).  An entry outside the image gives the all-zero record and is never used as an address.
+ *        n == 0 is a no-op.  Ordered with rt_set_noise as rt_camera_rays is.
+ *      rt_accum_add_at: dSamples[k] (device, n rgba32f, 16-byte aligned -- rt_shade_rays' colour) is one more sample of pixel
+ *        dPixels[k].  Per pixel the arithmetic is rt_accum_add's, to the letter: the same accept / reject (finite, |x| <= 2^48,
+ *        count < 2^24), the same mean and Welford updates in the same order, unfused, IEEE division; a rejected sample leaves the
+ *        pixel's 32 bytes untouched and counts in nRejected.  An entry with x >= width or y >= height is skipped, counted in
+ *        nRejected and never forms an address.  Pixels not listed are not written at all.  The list must name a pixel at most once
+ *        (rt_accum_select's lists do); with duplicates, which of the duplicate samples a pixel keeps is unspecified, but every access
+ *        stays inside the accumulator.  Afterwards the statistics of rt_accum_add run over EVERY pixel on the state the accumulator
+ *        now holds, then the solve with frames + 1: dState comes out exactly as rt_accum_add defines it (hist, nUnsampled,
+ *        nConverged, min / max count, maxR2Bits, the bins, done).  n == 0 is legal -- a frame in which nothing needed sampling: it
+ *        refreshes the report and counts a frame; dSamples and dPixels may then be NULL.
+ *      Refused before anything is enqueued, with RT_ERR_INVALID_ARG: NULL context, descriptor or required pointer; a pointer not
+ *      16-byte aligned (dPixels: 8); dPixels, dScratch, dSelState, dSamples or dState overlapping the accumulator; width or height
+ *      < 1 and the accumulator descriptor's other refusals; maxSamples outside 1..2^24; non-zero reserved words; for
+ *      rt_camera_rays_at whatever rt_pick's validation of p refuses.  RT_ERR_TOO_LARGE: width*height > 2^31 - 1; n beyond one grid
+ *      (2^31 - 1 workgroups of 256).  The context stays usable after a refusal.  The loop, once the share rt_accum_select reports has
+ *      dropped below the crossover (DESIGN.md 25 has the measurement; above it full frames -- rt_render + rt_accum_add -- are cheaper):
+ *          every k frames:  rt_accum_select(ctx, dAccum, &a, maxSamples, dPixels, capacity, dScratch, dSel, s);
+ *                           an 8-byte read of dSel + offsetof(rt_select_state, nSelected): nSelected and nListed (they differ
+ *                           exactly when `overflow` is set) -- the read that already fetches rt_accum_state.done
+ *          every frame:     p.frameCount++;  rt_camera_rays_at(ctx, &p, dPixels, nListed, dRays, s);
+ *                           rt_shade_rays(ctx, &p, dRays, dPixels, nListed, dSamples, NULL, NULL, s);
+ *                           rt_accum_add_at(ctx, dSamples, dPixels, nListed, dAccum, &a, dState, s);
+ *      A list reused for k frames gives a few pixels a few samples more than they needed, which is harmless.  Stopping a pixel on
+ *      its own estimated error biases it slightly (the known price of adaptive sampling); a pixel whose samples are always rejected
+ *      is selected for ever, and `done` never counts it either. */
+typedef struct rt_select_state {
+    uint32_t nPixels, nSelected, nListed, capacity, overflow, nCapped;
+    uint32_t reserved[10];           /* zero */
+} rt_select_state;
+int rt_accum_select_layout(int width, int height, size_t *scratchBytes);
+int rt_accum_select(rt_context *ctx, const void *dAccum, const rt_accum_desc *desc, uint32_t maxSamples, void *dPixels, size_t capacity,
+                    void *dScratch, void *dSelState, void *hipStream);
+int rt_camera_rays_at(rt_context *ctx, const rt_params *p, const void *dPixels, size_t n, void *dRays, void *hipStream);
+int rt_accum_add_at(rt_context *ctx, const void *dSamples, const void *dPixels, size_t n, void *dAccum, const rt_accum_desc *desc,
+                    void *dState, void *hipStream);
+
 /* ---- multi-GPU strip helpers */
 /* Number of local rows a rank owns for interleaved strips. */
 int rt_strip_local_rows(int height, int stripRows, int stripCount, int stripIndex);
@@ -1000,6 +1059,8 @@ RT_SA(sizeof(rt_reproject_desc) == 288 && offsetof(rt_reproject_desc, prev) == 8
       offsetof(rt_reproject_desc, reserved) == 276, "rt_reproject_desc is 288 B");
 RT_SA(sizeof(rt_reproject_report) == 64 && offsetof(rt_reproject_report, minCount) == 20 && offsetof(rt_reproject_report, sumCount) == 32 &&
       offsetof(rt_reproject_report, reserved) == 40, "rt_reproject_report is 64 B");
+RT_SA(sizeof(rt_select_state) == 64 && offsetof(rt_select_state, nSelected) == 4 && offsetof(rt_select_state, overflow) == 16 &&
+      offsetof(rt_select_state, reserved) == 24, "rt_select_state is 64 B");
 #undef RT_SA
 #endif
 

@@ -330,6 +330,34 @@ int rt_camera_rays(rt_context *c, const rt_params *p, void *dRays, void *hipStre
     return RT_OK;
 }
 
+// The adaptive loop's ray stage: the rays of listed image pixels.  Like rt_pick, only the camera, image size and ray fields of p
+// matter, so p is validated with an identity window; like rt_camera_rays it reads the noise texture and records its launch.
+int rt_camera_rays_at(rt_context *c, const rt_params *p, const void *dPixels, size_t n, void *dRays, void *hipStream) {
+    if (!c) return RT_ERR_INVALID_ARG;
+    if (!p) return fail(c, RT_ERR_INVALID_ARG, "params is NULL");
+    rt_params q = *p;
+    q.x0 = q.y0 = 0;
+    q.regionW = q.width;
+    q.regionH = q.height;
+    q.stripRows = q.stripCount = 1;
+    q.stripIndex = q.stripCycleRows = q.stripOffsetRows = 0;
+    int rc = validate_params(c, &q);
+    if (rc) return rc;
+    if (n == 0) return RT_OK;
+    if (!dPixels || !dRays) return fail(c, RT_ERR_INVALID_ARG, "NULL pixel list or ray pointer");
+    if ((uintptr_t)dPixels & 7u) return fail(c, RT_ERR_INVALID_ARG, "pixel list pointer must be 8-byte aligned");
+    if ((uintptr_t)dRays & 15u) return fail(c, RT_ERR_INVALID_ARG, "ray pointer must be 16-byte aligned");
+    if (n > ((size_t)0x7fffffff) * 256) return fail(c, RT_ERR_TOO_LARGE, "too many pixels in one call");
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t s;
+    if ((rc = caller_stream(c, hipStream, &s))) return rc;
+    RtFrame f;
+    build_frame(c, &q, &f);
+    HIP_TRY(c, rt_launch_camera_rays_at(f, c->dNoise, (const uint2 *)dPixels, n, (float4 *)dRays, s));
+    SCHED_TRY(c, recordLaunch(s));      // rt_set_noise drains it before freeing the texture
+    return RT_OK;
+}
+
 // ---- ray shading (rt_shade.inc): the query stream protocol; it also reads the noise texture and the skybox, which
 // rt_set_noise / rt_set_skybox / an installing rt_equirect_to_cubemap free only after draining every recorded stream.
 int rt_shade_rays(rt_context *c, const rt_params *p, const void *dRays, const void *dPixels, size_t nRays, void *dColor,

@@ -8,10 +8,8 @@
 #include "rt_accum.h"
 #include "rt_accum_solve.h"
 
-namespace {
-
-// the description's own rules, in the order the header lists them; *rule is what the kernels take
-int validate_accum_desc(rt_context *c, const rt_accum_desc *d, RtAccumRule *rule) {
+// the description's own rules, in the order the header lists them; *rule is what the kernels take (rt_adaptive.cpp asks too)
+int rt_validate_accum_desc(rt_context *c, const rt_accum_desc *d, RtAccumRule *rule) {
     if (!d) return fail(c, RT_ERR_INVALID_ARG, "accumulation description is NULL");
     if (d->width < 1 || d->height < 1) return fail(c, RT_ERR_INVALID_ARG, "width/height must be positive");
     if (!(d->relError > 0.0f) || !(d->relError < HUGE_VALF)) return fail(c, RT_ERR_INVALID_ARG, "relError must be finite and > 0");
@@ -27,8 +25,6 @@ int validate_accum_desc(rt_context *c, const rt_accum_desc *d, RtAccumRule *rule
     }
     return RT_OK;
 }
-
-}  // namespace
 
 extern "C" {
 
@@ -51,7 +47,7 @@ int rt_accum_reset(rt_context *c, void *dAccum, void *dState, int width, int hei
 int rt_accum_add(rt_context *c, const void *dImage, void *dAccum, const rt_accum_desc *d, void *dState, void *hipStream) {
     if (!c) return RT_ERR_INVALID_ARG;
     RtAccumRule rule;
-    RT_TRY(validate_accum_desc(c, d, &rule));
+    RT_TRY(rt_validate_accum_desc(c, d, &rule));
     RT_TRY(rt_check_pointers(c, {{dImage, "image"}, {dAccum, "accumulator"}, {dState, "state"}}));
     uint64_t npx;
     RT_TRY(rt_check_pixels(c, d->width, d->height, &npx));
@@ -65,7 +61,7 @@ int rt_accum_add(rt_context *c, const void *dImage, void *dAccum, const rt_accum
 int rt_accum_view(rt_context *c, const void *dAccum, void *dOut, const rt_accum_desc *d, int mode, void *hipStream) {
     if (!c) return RT_ERR_INVALID_ARG;
     RtAccumRule rule;
-    RT_TRY(validate_accum_desc(c, d, &rule));
+    RT_TRY(rt_validate_accum_desc(c, d, &rule));
     if (mode != RT_ACCUM_VIEW_RELERR && mode != RT_ACCUM_VIEW_COUNT && mode != RT_ACCUM_VIEW_CONVERGED)
         return fail(c, RT_ERR_INVALID_ARG, "unknown accumulation view mode");
     RT_TRY(rt_check_pointers(c, {{dAccum, "accumulator"}, {dOut, "output"}}));
@@ -79,7 +75,7 @@ int rt_accum_view(rt_context *c, const void *dAccum, void *dOut, const rt_accum_
 
 int rt_accum_solve_host(const rt_accum_state *in, const rt_accum_desc *d, rt_accum_state *out) {
     if (!in || !out) return RT_ERR_INVALID_ARG;
-    RT_TRY(validate_accum_desc(nullptr, d, nullptr));
+    RT_TRY(rt_validate_accum_desc(nullptr, d, nullptr));
     uint64_t n = in->nUnsampled;
     for (int b = 0; b < kAccumBins; b++) n += in->hist[b];
     if (n > 0xffffffffull) return RT_ERR_TOO_LARGE;

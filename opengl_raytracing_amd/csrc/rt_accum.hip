@@ -55,27 +55,6 @@ __device__ __forceinline__ void accum_store(f4 *p, f4 v) {
 
 }  // namespace
 
-// What a pixel's moments say, the one rule rt_accum_add's statistics and rt_accum_view's maps share.
-struct RtAccumJudged {
-    bool sampled;                   // count >= 2: the pixel is binned; otherwise r2 / bin / converged mean nothing
-    bool converged;
-    float r2;
-    unsigned bin;
-};
-
-__device__ __forceinline__ RtAccumJudged rt_accum_judge(float mY, float M2, unsigned count, const RtAccumRule &rule) {
-    RtAccumJudged j;
-    j.sampled = count >= 2u;
-    const float nf = (float)count;
-    const float q = M2 / (nf * (nf - 1.0f));
-    const float m = fmaxf(mY, rule.lumFloor);
-    j.r2 = q / (m * m);
-    const int e = (int)(__float_as_uint(j.r2) >> 21) - 396;
-    j.bin = j.r2 > 0.0f ? (unsigned)min(max(e, 0), kAccumBins - 1) : 0u;
-    j.converged = j.sampled && count >= rule.minSamples && j.r2 <= rule.thr2;
-    return j;
-}
-
 template <int PPL, bool NT>
 __global__ __launch_bounds__(256) void rt_accum_add_kernel(const f4 *__restrict__ image, f4 *__restrict__ mean, f4 *__restrict__ moments,
                                                            unsigned nPixels, unsigned nChunks, const RtAccumRule rule,
@@ -220,7 +199,11 @@ hipError_t rt_launch_accum_add(const void *image, void *accum, void *state, unsi
     f4 *mean = (f4 *)accum;
     hipLaunchKernelGGL((rt_accum_add_kernel<RT_ACCUM_PPL, RT_ACCUM_NT != 0>), dim3(nChunks < cap ? nChunks : cap), dim3(256), 0, s,
                        (const f4 *)image, mean, mean + nPixels, nPixels, nChunks, rule, (unsigned *)state);
-    hipLaunchKernelGGL(rt_accum_solve_kernel, dim3(1), dim3(256), 0, s, (unsigned *)state, nPixels, rule.donePermille);
+    return rt_launch_accum_solve(state, nPixels, rule.donePermille, s);
+}
+
+hipError_t rt_launch_accum_solve(void *state, unsigned nPixels, int donePermille, hipStream_t s) {
+    hipLaunchKernelGGL(rt_accum_solve_kernel, dim3(1), dim3(256), 0, s, (unsigned *)state, nPixels, donePermille);
     return hipGetLastError();
 }
 

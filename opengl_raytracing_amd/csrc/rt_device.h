@@ -110,6 +110,8 @@ hipError_t rt_launch_deinterleave(const void *src, void *dst, int width, int hei
 hipError_t rt_launch_trace_rays(const float4 *dRays, size_t nRays, const float4 *dCompiled, int nObj, int anyHit, void *dOut,
                                 hipStream_t s);
 hipError_t rt_launch_camera_rays(const RtFrame &f, const uint8_t *dNoise, float4 *dRays, hipStream_t s);
+// rt_camera_rays_at: f built from an identity window; dPixels: one uint2 (rt_pixel) per ray
+hipError_t rt_launch_camera_rays_at(const RtFrame &f, const uint8_t *dNoise, const uint2 *dPixels, size_t n, float4 *dRays, hipStream_t s);
 hipError_t rt_launch_pick(const RtFrame &f, const uint8_t *dNoise, const float4 *dCompiled, int px, int py, float4 *dOut,
                           hipStream_t s);
 // rt_debug_device_math: one rt_device_math_op on n records of four words, one record per thread (rt_kernels.hip).

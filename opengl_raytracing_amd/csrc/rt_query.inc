@@ -133,6 +133,23 @@ __global__ __launch_bounds__(RT_Q_BLOCK) void rt_camera_rays_kernel(const RtFram
     out[2 * k + 1] = w1;
 }
 
+// The primary rays of listed image pixels (rt_camera_rays_at): ray k is pixel pixels[k]'s, the record rt_camera_rays_kernel writes
+// for it under an identity window.  An entry outside the image: the all-zero ray, and never an address.
+__global__ __launch_bounds__(RT_Q_BLOCK) void rt_camera_rays_at_kernel(const RtFrame f, const uint8_t *__restrict__ noise,
+                                                                        const uint2 *__restrict__ pixels, size_t n, float4 *__restrict__ out) {
+    const size_t k = (size_t)blockIdx.x * RT_Q_BLOCK + threadIdx.x;
+    if (k >= n) return;
+    const uint2 px = pixels[k];
+    float4 w0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), w1 = w0;
+    if (px.x < (unsigned)f.p.width && px.y < (unsigned)f.p.height) {
+        const Ray r = q_camera_ray(f, noise, (int)px.x, (int)px.y);
+        w0 = make_float4(r.o.x, r.o.y, r.o.z, f.p.maxRayDistance);
+        w1 = make_float4(r.d.x, r.d.y, r.d.z, 0.0f);
+    }
+    out[2 * k] = w0;
+    out[2 * k + 1] = w1;
+}
+
 // rt_pick: the camera ray of image pixel (px, py) and its closest hit, one wave (lane 0 live).
 __global__ __launch_bounds__(64) void rt_pick_kernel(const RtFrame f, const uint8_t *__restrict__ noise,
                                                      const float4 *__restrict__ hot, int px, int py, float4 *__restrict__ out) {
@@ -165,6 +182,14 @@ hipError_t rt_launch_camera_rays(const RtFrame &f, const uint8_t *dNoise, float4
     const size_t blocks = (n + RT_Q_BLOCK - 1) / RT_Q_BLOCK;
     if (blocks > 0x7fffffffull) return hipErrorInvalidValue;
     hipLaunchKernelGGL(rt_camera_rays_kernel, dim3((unsigned)blocks), dim3(RT_Q_BLOCK), 0, s, f, dNoise, dRays);
+    return hipGetLastError();
+}
+
+hipError_t rt_launch_camera_rays_at(const RtFrame &f, const uint8_t *dNoise, const uint2 *dPixels, size_t n, float4 *dRays, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    const size_t blocks = (n + RT_Q_BLOCK - 1) / RT_Q_BLOCK;
+    if (blocks > 0x7fffffffull) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(rt_camera_rays_at_kernel, dim3((unsigned)blocks), dim3(RT_Q_BLOCK), 0, s, f, dNoise, dPixels, n, dRays);
     return hipGetLastError();
 }
 

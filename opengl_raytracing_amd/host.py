@@ -46,6 +46,7 @@ EXPORTS = [
     "rt_accum_layout", "rt_accum_reset", "rt_accum_add", "rt_accum_solve_host", "rt_accum_view",
     "rt_denoise_guide", "rt_denoise_layout", "rt_denoise",
     "rt_reproject_layout", "rt_reproject_project", "rt_accum_reproject",
+    "rt_accum_select_layout", "rt_accum_select", "rt_camera_rays_at", "rt_accum_add_at",
 ]
 
 
@@ -191,6 +192,10 @@ def load_library(build_if_missing=True):
     lib.rt_reproject_layout.argtypes = [ci, ci, P(ctypes.c_size_t), P(ctypes.c_size_t)]
     lib.rt_reproject_project.argtypes = [P(L.RtParams), P(ctypes.c_float), P(ctypes.c_float), P(ci)]
     lib.rt_accum_reproject.argtypes = [vp, vp, vp, vp, vp, P(L.RtReprojectDesc), vp, vp]
+    lib.rt_accum_select_layout.argtypes = [ci, ci, P(ctypes.c_size_t)]
+    lib.rt_accum_select.argtypes = [vp, vp, P(L.RtAccumDesc), ctypes.c_uint32, vp, ctypes.c_size_t, vp, vp, vp]
+    lib.rt_camera_rays_at.argtypes = [vp, P(L.RtParams), vp, ctypes.c_size_t, vp, vp]
+    lib.rt_accum_add_at.argtypes = [vp, vp, vp, ctypes.c_size_t, vp, P(L.RtAccumDesc), vp, vp]
     for name in EXPORTS:
         if name not in ("rt_last_error", "rt_mgpu_last_error", "rt_wire_bytes"):
             getattr(lib, name).restype = ci
@@ -427,6 +432,15 @@ def accum_solve_host(state, width, height, **desc):
     return out[0]
 
 
+def accum_select_layout(width, height):
+    """The scratch bytes rt_accum_select needs for a width x height accumulator (rt_accum_select_layout).  Needs no GPU."""
+    n = ctypes.c_size_t(0)
+    rc = load_library().rt_accum_select_layout(int(width), int(height), ctypes.byref(n))
+    if rc:
+        raise RtError(rc, "rt_accum_select_layout")
+    return n.value
+
+
 DenoiseLayout = collections.namedtuple("DenoiseLayout", "offset bytes")
 DenoiseLayout.__doc__ = """rt_denoise_layout's answer: byte offsets of the two scratch planes of rt_denoise and the size of both."""
 
@@ -636,6 +650,20 @@ class RayTracer:
             self.ctx, ctypes.byref(params), ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(h)), "rt_camera_rays"))
         return out
 
+    def camera_rays_at(self, params, d_pixels, n, out=None, stream=None):
+        """The primary rays of render(params) for listed image pixels (rt_camera_rays_at): d_pixels holds n rt_pixel records (a raw
+        device pointer or a CUDA tensor, 8-byte aligned; e.g. accum_select's list) -> CUDA float32 [n, 8] (rt_ray; `out` may supply
+        it, or a raw pointer to write at, which is then returned as given), asynchronous on `stream` (default
+        torch.cuda.current_stream()).  The window and strip fields of params are ignored; an entry outside the image gives the
+        all-zero ray."""
+        import torch
+        n = int(n)
+        if out is None:
+            out = torch.empty((n, 8), dtype=torch.float32, device="cuda")
+        self._on_torch_stream(stream, lambda h: self._check(self.lib.rt_camera_rays_at(
+            self.ctx, ctypes.byref(params), _dev_ptr(d_pixels), n, _dev_ptr(out), ctypes.c_void_p(h)), "rt_camera_rays_at"))
+        return out
+
     def shade_rays(self, params, rays, pixels=None, out=None, stream=None, position=True, normal=True):
         """main() of the shader on the given rays (rt_shade_rays): what the renderer computes along each ray.
 
@@ -824,6 +852,41 @@ class RayTracer:
         d = L.make_accum_desc(width, height, rel_error, lum_floor, min_samples, done_permille)
         self._on_torch_stream(stream, lambda h: self._check(self.lib.rt_accum_add(
             self.ctx, _dev_ptr(d_image), _dev_ptr(d_accum), ctypes.byref(d), _dev_ptr(d_state), ctypes.c_void_p(h)), "rt_accum_add"))
+
+    # ---- adaptive sampling (the loop: accum_select every k frames; camera_rays_at -> shade_rays -> accum_add_at every frame) ----
+    accum_select_layout = staticmethod(accum_select_layout)
+
+    def accum_select_alloc(self, width, height, capacity):
+        """(d_pixels, d_scratch, d_sel_state) for accum_select on the current device: the list (torch int32 [capacity, 2], rt_pixel
+        rows), the scratch (torch uint8, accum_select_layout(width, height) bytes; its content means nothing) and a zeroed
+        rt_select_state (torch uint8, 64 bytes)."""
+        import torch
+        return (torch.zeros((max(int(capacity), 1), 2), dtype=torch.int32, device="cuda")[:int(capacity)],
+                torch.empty(accum_select_layout(width, height), dtype=torch.uint8, device="cuda"),
+                torch.zeros(L.SELECT_STATE_BYTES, dtype=torch.uint8, device="cuda"))
+
+    def accum_select(self, d_accum, d_pixels, capacity, d_scratch, d_sel_state, width, height, max_samples=L.SELECT_MAX_SAMPLES,
+                     rel_error=0.02, lum_floor=2.0 ** -10, min_samples=16, done_permille=950, stream=None):
+        """The pixels of d_accum that still need samples (rt_accum_select): unconverged by accum_add's rule and with fewer than
+        max_samples samples, as rt_pixel records in tile order (8 x 8 tiles in raster order, raster order inside a tile) at d_pixels
+        -- the first min(nSelected, capacity) of them; capacity 0 counts only and d_pixels may be None.  d_sel_state receives the 64
+        bytes of rt_select_state (layout.SELECT_STATE_DTYPE).  Raw device pointers or CUDA tensors; asynchronous on `stream`
+        (default torch.cuda.current_stream()), no host synchronisation."""
+        d = L.make_accum_desc(width, height, rel_error, lum_floor, min_samples, done_permille)
+        self._on_torch_stream(stream, lambda h: self._check(self.lib.rt_accum_select(
+            self.ctx, _dev_ptr(d_accum), ctypes.byref(d), int(max_samples), _dev_ptr(d_pixels), int(capacity), _dev_ptr(d_scratch),
+            _dev_ptr(d_sel_state), ctypes.c_void_p(h)), "rt_accum_select"))
+
+    def accum_add_at(self, d_samples, d_pixels, n, d_accum, d_state, width, height, rel_error=0.02, lum_floor=2.0 ** -10, min_samples=16,
+                     done_permille=950, stream=None):
+        """One more sample of the n listed pixels only (rt_accum_add_at): d_samples[k] (rgba32f, e.g. shade_rays' colour) goes into
+        pixel d_pixels[k] of d_accum by accum_add's arithmetic, no other pixel is written, and d_state receives accum_add's report
+        over every pixel, `frames` advanced.  n = 0 refreshes the report only (d_samples and d_pixels may be None).  A pixel may be
+        listed at most once.  Raw device pointers or CUDA tensors; asynchronous on `stream` (default torch.cuda.current_stream())."""
+        d = L.make_accum_desc(width, height, rel_error, lum_floor, min_samples, done_permille)
+        self._on_torch_stream(stream, lambda h: self._check(self.lib.rt_accum_add_at(
+            self.ctx, _dev_ptr(d_samples), _dev_ptr(d_pixels), int(n), _dev_ptr(d_accum), ctypes.byref(d), _dev_ptr(d_state),
+            ctypes.c_void_p(h)), "rt_accum_add_at"))
 
     def accum_view(self, d_accum, d_out, width, height, mode="relerr", rel_error=0.02, lum_floor=2.0 ** -10, min_samples=16,
                    done_permille=950, stream=None):

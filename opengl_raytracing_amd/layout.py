@@ -364,6 +364,29 @@ def make_accum_desc(width, height, rel_error=0.02, lum_floor=2.0 ** -10, min_sam
     return d
 
 
+# ---- adaptive sampling (rt_accum_select / rt_camera_rays_at / rt_accum_add_at, include/rt_mi355.h) ----------------------------
+SELECT_STATE_BYTES = 64
+SELECT_TILE = 8                # the list's order: tiles of 8 x 8 pixels in raster order, raster order inside a tile
+SELECT_MAX_SAMPLES = 1 << 24   # the largest budget cap
+
+
+class RtSelectState(ctypes.Structure):
+    """``rt_select_state``: the 64 bytes rt_accum_select leaves on the device."""
+    _fields_ = [("nPixels", ctypes.c_uint32), ("nSelected", ctypes.c_uint32), ("nListed", ctypes.c_uint32), ("capacity", ctypes.c_uint32),
+                ("overflow", ctypes.c_uint32), ("nCapped", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 10)]
+
+
+# the same record as a numpy dtype (what a read-back of the select state is viewed as)
+SELECT_STATE_DTYPE = np.dtype({
+    "names": ["nPixels", "nSelected", "nListed", "capacity", "overflow", "nCapped", "reserved"],
+    "formats": ["<u4"] * 6 + [("<u4", (10,))], "offsets": [4 * k for k in range(7)], "itemsize": 64})
+SELECT_NSELECTED_OFFSET = 4    # offsetof(rt_select_state, nSelected): 8 bytes from here are nSelected and nListed, the loop's read
+
+assert ctypes.sizeof(RtSelectState) == SELECT_STATE_BYTES == SELECT_STATE_DTYPE.itemsize
+assert all(SELECT_STATE_DTYPE.fields[k][1] == getattr(RtSelectState, k).offset for k in SELECT_STATE_DTYPE.names)
+assert RtSelectState.nSelected.offset == SELECT_NSELECTED_OFFSET and RtSelectState.nListed.offset == 8
+
+
 # ---- denoising (rt_denoise_guide / rt_denoise, include/rt_mi355.h) ---------------------------------------------
 # one pixel of the guide plane: the upper half of an rt_hit, the normal normalised
 DENOISE_GUIDE_DTYPE = np.dtype({"names": ["n", "object"], "formats": [("<f4", 3), "<i4"], "offsets": [0, 12], "itemsize": 16})
