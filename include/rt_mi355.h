@@ -197,6 +197,13 @@ int rt_count_rays_traced(rt_context *ctx, const rt_params *p, uint64_t *rays);
  * frame k+1's longest-first workgroup order; scheduling only, no pixel depends on it). */
 int rt_set_variant(rt_context *ctx, int variant);
 
+/* First-hit reuse (default kernel, on unless the variant carries 0x400 or RT_FIRST_HIT_REUSE=0 was set at rt_create): while
+ * the scene, the textures and every rt_params field stay what they were -- frameCount may advance as long as no noise texture
+ * is loaded -- the second such frame also records every pixel's first hit and direct lighting, and the following ones replay
+ * them instead of tracing depth 0 again.  The surfaces are the same bits either way.  counts[0..2] = frames of this context
+ * that ran normal / recording / replaying since rt_create (instrumented and variant-0 launches are not counted). */
+int rt_debug_first_hit(rt_context *ctx, uint64_t counts[3]);
+
 /* Diagnostics of the last rt_count_rays launch: out[0] rays, out[1] wave-level ray packets,
  * out[2] candidate objects summed over packets (after packet culling), out[3] 64-object cull
  * passes.  [1..3] are zero for variant 0 (no packet culling). */

@@ -85,8 +85,43 @@ void build_frame(const rt_context *c, const rt_params *p, RtFrame *f) {
     for (int i = 0; i < 4; i++) hemi_local((float)i / 4.0f, halton_host(i, 2), f->sssHemi[i]);   // :320
 }
 
+// The first-hit reuse of a launch the scheduler may order (packet kernel, no ray counter): which of rt_firsthit.h's three modes
+// it is, with the record buffer in place for a recording one.  A buffer that cannot be had (or a window above the cap, which
+// decide() has already turned down) is no error: the frame is a normal one, and HIP's error state is cleared.
+RtFirstHit::Mode first_hit_mode(rt_context *c, const RtFirstHitKey &key) {
+    RtFirstHit::Mode mode = c->firstHit.decide(key);
+    if (mode == RtFirstHit::RECORD) {
+        const size_t bytes = rt_first_hit_bytes(key.p.regionW, key.p.regionH);
+        if (!c->dFirstHit.holds(bytes)) {
+            // replays of an earlier, smaller window may still read the old buffer on any stream
+            hipError_t e = c->sched.drain();
+            if (e == hipSuccess) e = c->dFirstHit.grow(bytes);
+            if (e != hipSuccess) {
+                (void)hipGetLastError();
+                c->firstHit.refuse(key);
+                mode = RtFirstHit::NORMAL;
+            }
+        }
+    }
+    return mode;
+}
+
+int launch_frame(rt_context *c, const rt_params *p, float4 *dColor, float4 *dPos, uint2 *dNormal,
+                 unsigned long long *counter, hipStream_t s, bool timed, int countMode, bool imageStores, bool reusable);
+
+// One frame.  Whatever goes wrong in a launch that could have recorded or replayed (a refusal, a failed HIP call) leaves the
+// first-hit state empty: the next frame is a normal one.
 int launch(rt_context *c, const rt_params *p, float4 *dColor, float4 *dPos, uint2 *dNormal,
            unsigned long long *counter, hipStream_t s, bool timed, int countMode = 1, bool imageStores = false) {
+    // instrumented launches and the exhaustive kernel always trace the whole frame and leave the cache as it is
+    const bool reusable = c->variant == 1 && !counter;
+    const int rc = launch_frame(c, p, dColor, dPos, dNormal, counter, s, timed, countMode, imageStores, reusable);
+    if (rc != RT_OK && reusable) c->firstHit.invalidate();
+    return rc;
+}
+
+int launch_frame(rt_context *c, const rt_params *p, float4 *dColor, float4 *dPos, uint2 *dNormal,
+                 unsigned long long *counter, hipStream_t s, bool timed, int countMode, bool imageStores, bool reusable) {
     RtFrame f;
     build_frame(c, p, &f);
     f.imageStores = imageStores ? 1 : 0;
@@ -98,15 +133,32 @@ int launch(rt_context *c, const rt_params *p, float4 *dColor, float4 *dPos, uint
     if (!c->dCompiled) return fail(c, RT_ERR_INVALID_ARG, "rt_set_scene has not been called");
     if (c->variant != 1 && (c->nObj > RT_EXHAUSTIVE_MAX_OBJECTS || c->nLt > RT_EXHAUSTIVE_MAX_LIGHTS))
         return fail(c, RT_ERR_TOO_LARGE, "the exhaustive cross-check kernel stages the scene in LDS: at most 512 objects / 64 lights (use the default kernel)");
+    RtFirstHit::Mode mode = RtFirstHit::NORMAL;
+    RtFirstHitKey key;
+    // (with reuse switched off nothing below differs from a context that never had it)
+    const bool reuse = reusable && c->firstHit.on();
+    if (reuse) {
+        key = rt_first_hit_key(c->sceneGen, c->texGen, c->nObj, c->nLt, c->variant, c->dNoise != nullptr, c->dSky != nullptr, *p);
+        mode = first_hit_mode(c, key);
+    }
     RtTileScheduler::Plan plan;
-    SCHED_TRY(c, begin(f, sc, s, c->variant == 1 && !counter, ((unsigned long long)c->sceneGen << 32) | c->texGen, &plan));
+    SCHED_TRY(c, begin(f, sc, s, c->variant == 1 && !counter, ((unsigned long long)c->sceneGen << 32) | c->texGen, &plan,
+                       mode == RtFirstHit::REPLAY ? 1 : 0));
+    if (mode == RtFirstHit::RECORD) SCHED_TRY(c, beforeFirstHitRecord(s));
+    if (mode == RtFirstHit::REPLAY) SCHED_TRY(c, beforeFirstHitReplay(s, plan.rec));
     if (timed) HIP_TRY(c, hipEventRecord(c->evStart, s));
-    HIP_TRY(c, rt_launch_render(f, sc, dColor, dPos, dNormal, counter, c->variant, s, countMode));
+    HIP_TRY(c, rt_launch_render(f, sc, dColor, dPos, dNormal, counter, c->variant, s, countMode, (int)mode,
+                                mode == RtFirstHit::NORMAL ? nullptr : (void *)c->dFirstHit.ptr));
     if (timed) {
         HIP_TRY(c, hipEventRecord(c->evStop, s));
         c->timed = true;
     }
+    if (mode == RtFirstHit::RECORD) SCHED_TRY(c, afterFirstHitRecord(s, plan.rec));
     SCHED_TRY(c, end(plan, s));
+    if (reusable) {
+        if (reuse) c->firstHit.launched(mode, key);
+        else c->firstHit.counts[RtFirstHit::NORMAL]++;
+    }
     return RT_OK;
 }
 
@@ -145,6 +197,7 @@ int rt_create(rt_context **out, int deviceId) {
     if (!c) return RT_ERR_HIP;
     c->device = deviceId;
     if (const char *e = getenv("RT_ST_BUILD")) c->stOnePhase = strcmp(e, "full") == 0;
+    if (const char *e = getenv("RT_FIRST_HIT_REUSE")) c->firstHit.envOn = atoi(e) != 0;
     if (const char *e = getenv("RT_ST_GEOM")) {        // "Kcube,Kplan,NB": measurement override of the shadow-table geometry
         int kc = 0, kp = 0, nb = 0;
         if (sscanf(e, "%d,%d,%d", &kc, &kp, &nb) == 3 && kc >= 4 && kc <= 128 && kp >= 4 && kp <= 256 && nb >= 1 && nb <= 128)
@@ -190,6 +243,7 @@ int rt_set_scene(rt_context *c, const void *objects, int nObj, const void *light
         return RT_OK;
     c->lastScene.clear();                  // (refilled at the end: a failed update must not look like the current scene)
     c->sceneGen++;
+    c->firstHit.invalidate();              // changed bytes: the recorded first hits are another scene's (identical bytes keep them)
     HIP_TRY(c, c->dObjects.grow(objBytes));
     HIP_TRY(c, c->dLights.grow(ltBytes));
     HIP_TRY(c, c->dCompiled.grow(rt_compiled_total_f4(nObj, nLt)));
@@ -242,6 +296,7 @@ int rt_set_noise(rt_context *c, const uint8_t *r8, int w, int h) {
     HIP_TRY(c, hipSetDevice(c->device));
     SCHED_TRY(c, drain());                 // frames on every stream read the texture
     c->texGen++;
+    c->firstHit.invalidate();
     HIP_TRY(c, c->dNoise.release());
     c->noiseW = c->noiseH = 0;
     if (!r8) return RT_OK;
@@ -258,6 +313,7 @@ int rt_set_skybox(rt_context *c, const uint16_t *rgb16f, int size) {
     HIP_TRY(c, hipSetDevice(c->device));
     SCHED_TRY(c, drain());
     c->texGen++;
+    c->firstHit.invalidate();
     HIP_TRY(c, c->dSky.release());
     c->skySize = 0;
     if (!rgb16f) return RT_OK;
@@ -483,8 +539,18 @@ static int count_rays_impl(rt_context *c, const rt_params *p, uint64_t *rays, in
 
 int rt_set_variant(rt_context *c, int variant) {
     if (!c) return RT_ERR_INVALID_ARG;
+    // another kernel, or first-hit reuse switched (bit 10, 0x400 = off): the next frame is a normal one
+    const bool reuseOn = (variant & 0x400) == 0;
+    if ((variant & 0xff) != c->variant || reuseOn != c->firstHit.variantOn) c->firstHit.invalidate();
+    c->firstHit.variantOn = reuseOn;
     c->variant = variant & 0xff;
     c->sched.setMode(variant);         // bits 8 and 9: the tile order
+    return RT_OK;
+}
+
+int rt_debug_first_hit(rt_context *c, uint64_t counts[3]) {
+    if (!c || !counts) return RT_ERR_INVALID_ARG;
+    for (int k = 0; k < 3; k++) counts[k] = c->firstHit.counts[k];
     return RT_OK;
 }
 
@@ -612,6 +678,7 @@ int rt_equirect_to_cubemap(rt_context *c, const float *hEquirectRGB, int width, 
     if (install) {
         SCHED_TRY(c, drain());          // frames and shades on every stream read the old skybox
         c->texGen++;
+        c->firstHit.invalidate();
         c->dSky.swap(faces);            // (the old one goes with `faces`)
         c->skySize = size;
     }

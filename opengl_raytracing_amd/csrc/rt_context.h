@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "rt_device.h"
+#include "rt_firsthit.h"
 #include "rt_present.h"
 #include "rt_resample.h"
 #include "rt_sched.h"
@@ -41,6 +42,8 @@ struct rt_context {
     int variant = 1;   // 1 = wavefront-packet kernel (default), 0 = exhaustive per-lane loop
     unsigned long long lastStats[32] = {};   // rt_count_rays diagnostics (rt_debug_stats)
     RtTileScheduler sched;                     // tile order of the packet kernel's frames; the record of every stream launches go to
+    RtFirstHit firstHit;                       // which launches record / replay their first hit (rt_firsthit.h) ...
+    DevBuf<uint8_t> dFirstHit;                 // ... and the records: rt_first_hit_bytes() of the recorded window, allocated by the first recording frame
     DevBuf<uint2> dBloom[2];                   // rgba16f ping-pong targets of rt_bloom
     DevBuf<float> dSsaoDepth;                  // gPosition.z plane of rt_ssao
     ScratchUse bloomUse, ssaoUse;              // who ran last in dBloom / dSsaoDepth, on whichever stream

@@ -82,7 +82,10 @@ static inline size_t rt_compiled_f4(int nObj, int nLt) {
 hipError_t rt_launch_compile_scene(const uint8_t *dObjects, int nObj, const uint8_t *dLights, int nLt,
                                    float4 *dCompiled, hipStream_t s);
 hipError_t rt_launch_render(const RtFrame &f, const RtDeviceScene &sc, float4 *dColor, float4 *dPos,
-                            uint2 *dNormal, unsigned long long *dRayCounter, int variant, hipStream_t s, int countMode = 1);
+                            uint2 *dNormal, unsigned long long *dRayCounter, int variant, hipStream_t s, int countMode = 1,
+                            int firstMode = 0, void *dFirstHit = nullptr);
+// bytes of the first-hit records of a regionW x regionH window (render_packet, FIRST != 0): (t, hit) and three floats of colour per pixel
+static inline size_t rt_first_hit_bytes(int regionW, int regionH) { return (size_t)regionW * (size_t)regionH * (sizeof(uint2) + 3 * sizeof(float)); }
 // Tile geometry of the packet kernel for a given scene size / window (so the ABI layer can size the
 // feedback buffers): workgroup threads, tile edge, tiles per row, total tiles.
 void rt_packet_geometry(int nObj, int regionW, int regionH, int *bt, int *tile, int *tilesX, int *nTiles);

@@ -1,0 +1,91 @@
+// rt_firsthit.h -- when a packet-kernel frame may reuse the previous frame's first hit and direct lighting,
+// held by value in rt_context (rt_context.h).  Depth 0 of a frame -- the camera ray, its shadow rays and subsurface probes -- is
+// a function of the scene, the textures and every rt_params field except frameCount (which enters depth 0 only through the
+// noise texture): while those stay what they were, the frame after a still one RECORDS what depth 0 ends with, and the frames
+// after that REPLAY it (render_packet's FIRST parameter, rt_packet.inc).  This header decides which of the three a launch is; it
+// holds no HIP type, so it is compiled and tested alone (tests/test_first_hit_host.py).  The record buffer, the events between
+// the streams and the launches themselves are rt_abi.cpp's and rt_sched.cpp's.  Not part of the public ABI.
+#pragma once
+#include <stdint.h>
+#include <string.h>
+
+#include "rt_mi355.h"
+
+// Everything depth 0 of a frame is a function of.  Output pointers, imageStores, the stream and the scheduler's bits are not
+// in it: they decide where and in which tile order the frame is written, not what depth 0 computes.
+struct RtFirstHitKey {
+    uint32_t sceneGen, texGen;       // bumped by every change of the scene's bytes / of a texture
+    int32_t nObj, nLt;
+    int32_t variant;                 // rt_set_variant's low byte
+    int32_t noise, sky;              // 1 = a noise texture / a skybox is loaded
+    rt_params p;                     // every field; frameCount as 0 while no noise texture is loaded
+};
+
+inline RtFirstHitKey rt_first_hit_key(uint32_t sceneGen, uint32_t texGen, int nObj, int nLt, int variant, bool noise, bool sky, const rt_params &p) {
+    RtFirstHitKey k;
+    memset(&k, 0, sizeof k);         // (padding too: keys are compared as bytes)
+    k.sceneGen = sceneGen;
+    k.texGen = texGen;
+    k.nObj = nObj;
+    k.nLt = nLt;
+    k.variant = variant & 0xff;
+    k.noise = noise ? 1 : 0;
+    k.sky = sky ? 1 : 0;
+    // field by field, so that no padding of the caller's struct gets into the key
+    for (int i = 0; i < 3; i++) { k.p.camPos[i] = p.camPos[i]; k.p.camDir[i] = p.camDir[i]; k.p.camUp[i] = p.camUp[i]; k.p.camRight[i] = p.camRight[i]; }
+    k.p.fovDeg = p.fovDeg; k.p.focalLength = p.focalLength; k.p.maxRayDistance = p.maxRayDistance;
+    k.p.noiseScale[0] = p.noiseScale[0]; k.p.noiseScale[1] = p.noiseScale[1];
+    // frameCount reaches depth 0 through sample_noise alone (the bounce sample it also feeds is used from the next direction
+    // on, the roulette starts at depth 3): without a noise texture frames that differ only in it share their first hit
+    k.p.frameCount = noise ? p.frameCount : 0;
+    k.p.useSkybox = p.useSkybox; k.p.maxRayDepth = p.maxRayDepth;
+    k.p.width = p.width; k.p.height = p.height;
+    k.p.x0 = p.x0; k.p.y0 = p.y0; k.p.regionW = p.regionW; k.p.regionH = p.regionH;
+    k.p.stripRows = p.stripRows; k.p.stripCount = p.stripCount; k.p.stripIndex = p.stripIndex; k.p.reserved0 = p.reserved0;
+    k.p.stripCycleRows = p.stripCycleRows; k.p.stripOffsetRows = p.stripOffsetRows;
+    return k;
+}
+
+struct RtFirstHit {
+    enum Mode { NORMAL = 0, RECORD = 1, REPLAY = 2 };
+    // Windows above this many pixels are never recorded (20 bytes per pixel: 320 MiB at the cap, which a 4096 x 4096 window
+    // reaches; 1080p takes 41 MB).  Larger ones render normal frames.
+    static constexpr uint64_t kMaxPixels = (uint64_t)1 << 24;
+
+    bool envOn = true;               // RT_FIRST_HIT_REUSE=0 at rt_create clears it
+    bool variantOn = true;           // rt_set_variant's bit 10 (0x400) clears it
+    bool haveLast = false;           // `last` is the key of the previous eligible launch, with nothing invalidating in between
+    bool valid = false;              // the buffer holds the records of `cached`
+    RtFirstHitKey last, cached;
+    uint64_t refusedPixels = 0;      // a record buffer of this many pixels could not be had: windows that large are not tried again
+    uint64_t counts[3] = {0, 0, 0};  // launches since creation: normal, recorded, replayed (rt_debug_first_hit)
+
+    bool on() const { return envOn && variantOn; }
+
+    // What the next eligible launch (packet kernel, no ray counter) with key k is.  A key other than the cached one drops the
+    // cache: the view has moved on, and only the frame after a still one records again.
+    //   key == the valid cache's key                            -> REPLAY
+    //   else key == the previous launch's key (no valid cache)  -> RECORD
+    //   else                                                    -> NORMAL
+    Mode decide(const RtFirstHitKey &k) {
+        if (!on() || k.p.maxRayDepth < 1 || k.p.regionW <= 0 || k.p.regionH <= 0) return NORMAL;
+        if (valid && memcmp(&k, &cached, sizeof k) == 0) return REPLAY;
+        valid = false;
+        const uint64_t px = (uint64_t)k.p.regionW * (uint64_t)k.p.regionH;
+        if (px > kMaxPixels || (refusedPixels && px >= refusedPixels)) return NORMAL;
+        if (haveLast && memcmp(&k, &last, sizeof k) == 0) return RECORD;
+        return NORMAL;
+    }
+    // the record buffer could not be allocated: the launch decided as RECORD runs as a normal frame, now and from now on
+    void refuse(const RtFirstHitKey &k) { refusedPixels = (uint64_t)k.p.regionW * (uint64_t)k.p.regionH; }
+    // the launch went out as mode m
+    void launched(Mode m, const RtFirstHitKey &k) {
+        counts[m]++;
+        if (!on()) { invalidate(); return; }
+        if (m == RECORD) { cached = k; valid = true; }
+        last = k;
+        haveLast = true;
+    }
+    // a setter changed an input, the launch failed or was refused, or reuse was switched off: the next launch is a normal frame
+    void invalidate() { valid = false; haveLast = false; }
+};

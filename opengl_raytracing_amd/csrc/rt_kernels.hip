@@ -738,11 +738,16 @@ __global__ RT_V0_BOUNDS void rt_render_kernel(const RtFrame f, const RtDeviceSce
 //   round 1 shapes (whole scene in LDS, 4 waves/SIMD)  0.459    5.27    8.25    48.4   (after the fast 1/x, sqrt paths)
 //   LIGHT / HEAVY profiles                             0.404    4.84    8.15    43.2
 // BT and COMPACT are 64 and true in every instantiation; the parameters stay because the kernels' names carry them.
-template <int COUNT, int BT, bool COMPACT, typename PROFILE>
+// FIRST: 0 = the frame as ever, 1 = it also records every pixel's first hit into firstHit, 2 = depth 0 replayed from firstHit
+// (render_packet).  The records come in the `rayCounter` argument, which the launches that reuse (never
+// instrumented: COUNT = 0) have no other use for: one more kernel argument moves the hidden arguments behind it, and FIRST = 0
+// has to stay, to the byte, the kernel it was.
+template <int COUNT, int BT, bool COMPACT, typename PROFILE, int FIRST = 0>
 __global__ __launch_bounds__(BT, PROFILE::waves)
 void rt_render_packet_kernel(const RtFrame f, const RtDeviceScene dsc, float4 *__restrict__ gColor,
                              float4 *__restrict__ gPosition, uint2 *__restrict__ gNormal,
                              unsigned long long *rayCounter) {
+    static_assert(FIRST == 0 || COUNT == 0, "a frame that records or replays first hits has no ray counter");
     static_assert(BT == 64 && COMPACT, "one-wave workgroups, only the AABBs staged in LDS");
     extern __shared__ float4 lds[];
     const int nAll = f.nObj * (RT_HOT_F4 + RT_MAT_F4) + f.nLt * RT_LGT_F4 + 2 * (RT_HALTON_N / 4);
@@ -780,7 +785,8 @@ void rt_render_packet_kernel(const RtFrame f, const RtDeviceScene dsc, float4 *_
     const long long t0 = clock64();
 
     unsigned rays = 0;
-    render_packet<COUNT, BT, PROFILE>(f, dsc, sc, gColor, gPosition, gNormal, rays);
+    if constexpr (FIRST != 0) render_packet<COUNT, BT, PROFILE, FIRST>(f, dsc, sc, gColor, gPosition, gNormal, rays, (uint2 *)rayCounter);
+    else render_packet<COUNT, BT, PROFILE>(f, dsc, sc, gColor, gPosition, gNormal, rays);
 
     if (dsc.tileCost && (threadIdx.x & 63) == 0) {     // one add per wave: tile cost = sum of its waves' cycles / 64
         const unsigned c = (unsigned)(((unsigned long long)(clock64() - t0)) >> 6);
@@ -1061,9 +1067,13 @@ hipError_t rt_launch_shadow_tables(const float4 *dCompiled, int nObj, int nLt, u
 // countMode (only with dRayCounter): 1 = instrumented build that traces every ray the REFERENCE traces (its count is the
 // unit count R of the metric), 2 = instrumented build that keeps the production kernel's provably-dead-ray skips
 // (its count is what the timed kernel actually traverses).
+// firstMode (packet kernel without a ray counter only): 1 = the frame also records its first hits into dFirstHit, 2 = it replays
+// depth 0 from them (rt_first_hit_bytes(regionW, regionH) bytes; render_packet).
 hipError_t rt_launch_render(const RtFrame &f, const RtDeviceScene &sc, float4 *dColor, float4 *dPos,
-                            uint2 *dNormal, unsigned long long *dRayCounter, int variant, hipStream_t s, int countMode) {
+                            uint2 *dNormal, unsigned long long *dRayCounter, int variant, hipStream_t s, int countMode,
+                            int firstMode, void *dFirstHit) {
     if (f.p.regionW <= 0 || f.p.regionH <= 0) return hipSuccess;
+    if (firstMode != 0 && (firstMode < 0 || firstMode > 2 || variant != 1 || dRayCounter || !dFirstHit || f.p.maxRayDepth < 1)) return hipErrorInvalidValue;
     if (variant != 1 && (f.nObj > RT_EXHAUSTIVE_MAX_OBJECTS || f.nLt > RT_EXHAUSTIVE_MAX_LIGHTS)) return hipErrorInvalidValue;      // (the ABI refuses first)
     const size_t sceneBytes = (rt_compiled_f4(f.nObj, f.nLt) + 1) * sizeof(float4);   // exhaustive kernel: whole scene + 16 B block counter
     if (variant == 1) {
@@ -1074,10 +1084,13 @@ hipError_t rt_launch_render(const RtFrame &f, const RtDeviceScene &sc, float4 *d
         // LDS: the AABBs (2 float4 per object) + the 16-byte counter slot + the profile's parking area
         const size_t ldsBytes = ((size_t)((light || PkHeavy::boundsLds) ? f.nObj * 2 : 0) + 1) * sizeof(float4) +
                                 (size_t)PK_PARK_FLOATS * bt * sizeof(float);
+        unsigned long long *const firstArg = (unsigned long long *)dFirstHit;      // (the records travel in the counter's argument: rt_render_packet_kernel)
 #define RT_LAUNCH_PK(PROFILE_)                                                                                                        \
         do {                                                                                                                          \
             if (dRayCounter && countMode == 2) hipLaunchKernelGGL((rt_render_packet_kernel<2, 64, true, PROFILE_>), grid, dim3(64), ldsBytes, s, f, sc, dColor, dPos, dNormal, dRayCounter); \
             else if (dRayCounter) hipLaunchKernelGGL((rt_render_packet_kernel<1, 64, true, PROFILE_>), grid, dim3(64), ldsBytes, s, f, sc, dColor, dPos, dNormal, dRayCounter);            \
+            else if (firstMode == 1) hipLaunchKernelGGL((rt_render_packet_kernel<0, 64, true, PROFILE_, 1>), grid, dim3(64), ldsBytes, s, f, sc, dColor, dPos, dNormal, firstArg);    \
+            else if (firstMode == 2) hipLaunchKernelGGL((rt_render_packet_kernel<0, 64, true, PROFILE_, 2>), grid, dim3(64), ldsBytes, s, f, sc, dColor, dPos, dNormal, firstArg);    \
             else hipLaunchKernelGGL((rt_render_packet_kernel<0, 64, true, PROFILE_>), grid, dim3(64), ldsBytes, s, f, sc, dColor, dPos, dNormal, dRayCounter);                             \
         } while (0)
         // scenes without shadow tables (more than RT_ST_MAX_OBJECTS objects or RT_ST_MAX_LIGHTS lights: rt_set_scene builds none)

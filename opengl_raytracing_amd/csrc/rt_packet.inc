@@ -101,6 +101,12 @@
 #define RT_PK_TIMERS 0          // 1: section timers in the instrumented (COUNT) build (pk_clock; off by default: they serialise the scalar unit)
 #endif
 
+#ifndef RT_FIRST_HIT_NT
+#define RT_FIRST_HIT_NT 1       // a recording frame (render_packet, FIRST = 1) writes its first-hit records with non-temporal stores: they are read a
+                                // frame later by another kernel.  Measured no different from plain stores (C2 recording frame 0.337 / 0.339 ms
+                                // against 0.336 / 0.338, two runs each, tools/bench_first_hit.py)
+#endif
+
 constexpr int PK_PARK_FLOATS = 23;      // floats per lane of the LDS parking area: finalColor, throughput, ray.d, P, N, V, albedo (3 each), metallic, roughness
 
 // ---- profiles ---------------------------------------------------------------------------------------------------------
@@ -202,6 +208,7 @@ constexpr float PK_INF = __builtin_huge_valf();
 // feed the VALU as SGPR operands -- no LDS instruction, no VGPRs.  Per-lane-indexed data
 // (materials by hit index, the cull pass' per-lane AABBs) stays in LDS.
 typedef float pk_f4 __attribute__((ext_vector_type(4)));
+typedef unsigned pk_u2 __attribute__((ext_vector_type(2)));
 typedef const __attribute__((address_space(4))) pk_f4 *pk_uni4_t;
 typedef const __attribute__((address_space(4))) float *pk_uni1_t;
 __device__ __forceinline__ float4 uni_load4(const SceneLds &sc, int f4Index) {
@@ -1306,11 +1313,19 @@ __device__ __forceinline__ float pk_pcf_shadow(const SceneLds &sc, int nObj, v3 
 }
 
 // main() of raytracingCs.glsl (:509-584) for one 64-lane packet of pixels.
-template <int COUNT, int BT, typename PROFILE>
+// FIRST (DESIGN.md section 26; the host side is rt_firsthit.h): 0 = the frame as it always was.  1 = the same frame, which also
+// RECORDS what depth 0 ends with, one record of 20 bytes per pixel of the window at window-local index j * regionW + i:
+// firstHit[idx] = (t of the closest hit, the hit object or -1 for a miss or a pixel outside the image), and behind the regionW *
+// regionH pairs three floats per pixel, finalColor as parked after depth 0.  2 = REPLAY: depth 0 takes (finalColor, t, hit) from the record in place of
+// the closest-hit traversal, the light loop and the subsurface section, recomputes the shading point from them by the
+// expressions of the normal frame, and goes on with the next direction and depth 1 as ever.  Every value is copied bitwise or
+// recomputed by the identical expression, so the three frames are the same bits.
+template <int COUNT, int BT, typename PROFILE, int FIRST = 0>
 __device__ __forceinline__ void render_packet(const RtFrame &f, const RtDeviceScene &dsc, const SceneLds &sc,
                                               float4 *gColor,
-                                              float4 *gPosition, uint2 *gNormal, unsigned &rays) {
+                                              float4 *gPosition, uint2 *gNormal, unsigned &rays, uint2 *firstHit = nullptr) {
     static_assert(BT == 64, "one-wave workgroups: the 8x8 tile and the parking area's stride assume it");
+    static_assert(FIRST == 0 || COUNT == 0, "the instrumented builds always trace the whole frame");
     constexpr int GROUPN = PROFILE::groupN;
     const int nObj = f.nObj;
     const float maxDist = f.p.maxRayDistance;
@@ -1376,12 +1391,72 @@ __device__ __forceinline__ void render_packet(const RtFrame &f, const RtDeviceSc
     rayBox.loz = rayBox.hiz = f.p.camPos[2];
     bool rayBoxFinite = box_finite(rayBox);
 
+    // this lane's first-hit record (FIRST != 0): window-local pixel index, or -1 for the lanes of an edge tile beyond the window
+    [[maybe_unused]] auto firstIndex = [&]() -> long long {
+        const int wave = threadIdx.x >> 6, ln = threadIdx.x & 63;
+        const int i = sc.tileX * 8 + (wave & 1) * 8 + (ln & 7);
+        const int j = sc.tileY * 8 + (wave >> 1) * 8 + (ln >> 3);
+        return (i < f.p.regionW && j < f.p.regionH) ? (long long)j * f.p.regionW + i : -1ll;
+    };
+    // FIRST == 1, the two halves of this lane's record.  (t, hit) go out right behind the closest-hit traversal: held until the
+    // colour is known they would stay live across the whole lighting section, in kernels that have no register to spare ...
+    [[maybe_unused]] auto firstRecordHit = [&](float tHit_, int hit_) {
+        const long long at = firstIndex();
+        if (at >= 0) {
+            const pk_u2 rec = {__float_as_uint(tHit_), (unsigned)hit_};
+#if RT_FIRST_HIT_NT
+            __builtin_nontemporal_store(rec, (pk_u2 *)&firstHit[at]);
+#else
+            *(pk_u2 *)&firstHit[at] = rec;
+#endif
+        }
+    };
+    // ... the colour when depth 0 has ended for this wave: after its lighting, or with every lane a miss or outside the image
+    [[maybe_unused]] auto firstRecordColour = [&]() {
+        asm volatile("" ::: "memory");
+        const float *pk_ = sc.park + threadIdx.x;
+        const long long at = firstIndex();
+        if (at >= 0) {
+            float *col = (float *)(firstHit + (size_t)f.p.regionW * (size_t)f.p.regionH) + 3 * at;
+#pragma unroll
+            for (int k = 0; k < 3; k++) {
+#if RT_FIRST_HIT_NT
+                __builtin_nontemporal_store(pk_[k * BT], col + k);
+#else
+                col[k] = pk_[k * BT];
+#endif
+            }
+        }
+    };
+
     for (int depth = 0; depth < f.p.maxRayDepth; ++depth) {
-        if (!wave_any(alive)) break;
+        if (!wave_any(alive)) {
+            if constexpr (FIRST == 1) { if (depth == 0) { firstRecordHit(maxDist, -1); firstRecordColour(); } }
+            break;
+        }
+        bool replay = false;            // this bounce comes from the record: wave-uniform, and false wherever FIRST != 2
+        if constexpr (FIRST == 2) replay = depth == 0;
         float t;
+        int idx;
+        unsigned long long tHit = 0ull;
+        if (replay) {
+            const long long at = firstIndex();
+            uint2 rec = make_uint2(__float_as_uint(maxDist), 0xffffffffu);
+            v3 recCol = V3(0.0f, 0.0f, 0.0f);
+            if (at >= 0) {
+                const float *col = (const float *)(firstHit + (size_t)f.p.regionW * (size_t)f.p.regionH) + 3 * at;
+                rec = firstHit[at];
+                recCol = V3(col[0], col[1], col[2]);
+            }
+            const int hitRec = (int)rec.y;
+            idx = (hitRec >= 0 && hitRec < nObj) ? hitRec : -1;          // (a record never holds anything else; no gather may leave the scene)
+            t = __uint_as_float(rec.x);
+            float *pk_ = sc.park + threadIdx.x;
+            pk_[0 * BT] = recCol.x; pk_[1 * BT] = recCol.y; pk_[2 * BT] = recCol.z;          // finalColor after depth 0: the sky or zero where it missed
+        } else {
         const unsigned long long tTrace = pk_clock<COUNT>();
-        int idx = pk_trace_closest<COUNT>(sc, nObj, ray, alive, rayBox, rayBoxFinite, maxDist, t, rays);
-        const unsigned long long tHit = pk_clock<COUNT>();
+        idx = pk_trace_closest<COUNT>(sc, nObj, ray, alive, rayBox, rayBoxFinite, maxDist, t, rays);
+        tHit = pk_clock<COUNT>();
         pk_stat<COUNT>(sc, 12, tHit - tTrace);
         const bool missed = alive && idx < 0;
         if (wave_any(missed && f.p.useSkybox && dsc.sky != nullptr)) {
@@ -1392,8 +1467,13 @@ __device__ __forceinline__ void render_packet(const RtFrame &f, const RtDeviceSc
                 pk_[0 * BT] = nf.x; pk_[1 * BT] = nf.y; pk_[2 * BT] = nf.z;
             }
         }
+        }
         alive = alive && idx >= 0;          // a miss ends the path (:533)
-        if (!wave_any(alive)) break;
+        if constexpr (FIRST == 1) { if (depth == 0) firstRecordHit(t, alive ? idx : -1); }
+        if (!wave_any(alive)) {
+            if constexpr (FIRST == 1) { if (depth == 0) firstRecordColour(); }
+            break;
+        }
 
         // Only the fields computePBR reads stay live across the light loop; the bounce / SSS
         // fields are re-read from LDS (per-lane gather by hit index) where they are used.
@@ -1420,8 +1500,9 @@ __device__ __forceinline__ void render_packet(const RtFrame &f, const RtDeviceSc
         }
         v3 V = normalize(-ray.d);
         const v3 shadowOrigin = P + N * 0.001f;
-        // one origin box per bounce serves every shadow / SSS ray leaving these shading points
-        const Box3 shBox = wave_box(shadowOrigin, alive);
+        // one origin box per bounce serves every shadow / SSS ray leaving these shading points (a replayed bounce has none)
+        Box3 shBox = rayBox;
+        if (!replay) shBox = wave_box(shadowOrigin, alive);
         const bool shBoxFinite = box_finite(shBox);
 
         {   // the ray's direction waits in LDS for the next-direction step; the hit's P and N replace the last hit's for the lanes that hit
@@ -1437,6 +1518,8 @@ __device__ __forceinline__ void render_packet(const RtFrame &f, const RtDeviceSc
             pk_[18 * BT] = albedo.x; pk_[19 * BT] = albedo.y; pk_[20 * BT] = albedo.z;
             pk_[21 * BT] = metallic; pk_[22 * BT] = roughness;
         }
+        unsigned long long tAfter = 0ull;
+        if (!replay) {          // (a replayed bounce's direct lighting is in the recorded finalColor)
         // ---- computeLighting (:457-507), light loop wave-uniform
         v3 Lo = V3(0.0f, 0.0f, 0.0f);
         const unsigned long long tLights = pk_clock<COUNT>();
@@ -1634,8 +1717,8 @@ __device__ __forceinline__ void render_packet(const RtFrame &f, const RtDeviceSc
             }
             if (needSss) Lo = Lo + ((sss * V3(m2)) * m2.w) / 4.0f;
         }
-        const unsigned long long tAfter = pk_clock<COUNT>();
-        pk_stat<COUNT>(sc, 27, tAfter - tSss);                                   // [27] subsurface section
+        tAfter = pk_clock<COUNT>();
+        pk_stat<COUNT>(sc, 27, tAfter - tSss);                                 // [27] subsurface section
         if (alive) {        // finalColor += throughput * Lo, in place
             asm volatile("" ::: "memory");
             float *pk_ = sc.park + threadIdx.x;
@@ -1643,6 +1726,8 @@ __device__ __forceinline__ void render_packet(const RtFrame &f, const RtDeviceSc
             const v3 nf = fc + thr * Lo;
             pk_[0 * BT] = nf.x; pk_[1 * BT] = nf.y; pk_[2 * BT] = nf.z;
         }
+        }
+        if constexpr (FIRST == 1) { if (depth == 0) firstRecordColour(); }
         // After the last iteration nothing reads `alive`, `throughput` or the ray again, so its Russian roulette and bounce set-up
         // are dead (SURVEY.md A.1#17: at MAX_RAY_DEPTH = 4 the roulette can never change the output).
         if (depth + 1 >= f.p.maxRayDepth) break;

@@ -65,6 +65,7 @@ hipError_t RtTileScheduler::record(hipStream_t s, StreamRec **out) {
     m->s = s;
     m->predValid = false;
     m->seenGen = 0;                // adoptGen starts at 1 with the first adoption: a new stream always orders itself
+    m->seenFirst = 0;              // (firstGen likewise)
     SCHED_TRY(hipEventRecord(m->last, s));
     *out = m;
     return hipSuccess;
@@ -83,6 +84,31 @@ hipError_t RtTileScheduler::waitForLaunches(hipStream_t t, bool ownToo) {
     return hipSuccess;
 }
 
+// ---- first-hit records (rt_sched.h) ---------------------------------------------------------------------------------------
+
+hipError_t RtTileScheduler::beforeFirstHitRecord(hipStream_t s) {
+    // replays still queued on the other streams read the buffer this frame rewrites; s's own are ahead of it by stream order
+    return waitForLaunches(s);
+}
+
+hipError_t RtTileScheduler::afterFirstHitRecord(hipStream_t s, StreamRec *rec) {
+    SCHED_TRY(evFirst.create(hipEventDisableTiming));
+    SCHED_TRY(hipEventRecord(evFirst, s));
+    firstGen++;
+    rec->seenFirst = firstGen;         // (the recording stream's own replays follow by stream order)
+    return hipSuccess;
+}
+
+hipError_t RtTileScheduler::beforeFirstHitReplay(hipStream_t s, StreamRec *rec) {
+    // the seenGen / adoptGen pattern of measuredBegin: which frame recorded last is context-global, streams are not ordered
+    // with each other, so EVERY stream's first replay after a recording waits for it (a no-op once it has completed)
+    if (rec->seenFirst != firstGen) {
+        SCHED_TRY(hipStreamWaitEvent(s, evFirst, 0));
+        rec->seenFirst = firstGen;
+    }
+    return hipSuccess;
+}
+
 // ---- measured order -------------------------------------------------------------------------------------------------------
 // Longest-first tile order from the previous frames' measured tile costs (same window geometry, any
 // stream).  The first frame of a geometry runs in raster order and only records costs.
@@ -97,9 +123,9 @@ hipError_t RtTileScheduler::measuredBegin(RtDeviceScene &sc, hipStream_t s, Plan
         for (DevBuf<unsigned> *b : {&dTileCost, &dTileSnap, &dTileOrder[0], &dTileOrder[1]}) SCHED_TRY(b->release());
         for (DevBuf<unsigned> *b : {&dTileCost, &dTileSnap, &dTileOrder[0], &dTileOrder[1]}) SCHED_TRY(b->grow(nTiles));
     }
-    *newGeometry = !(fbTiles == nTiles && fbTilesX == plan->tilesX && fbBt == plan->bt);
+    *newGeometry = !(fbTiles == nTiles && fbTilesX == plan->tilesX && fbBt == plan->bt && fbClass == plan->costClass);
     if (*newGeometry) {
-        // New geometry: nobody may still be using the old costs / orders, and a sort of the old geometry must
+        // New geometry (or frames of another cost class: first-hit replays after whole frames, or back): nobody may still be using the old costs / orders, and a sort of the old geometry must
         // never be adopted.  Both order buffers restart as the identity permutation (a launch that reads one
         // before its first sort -- it cannot, fbCur is -1 -- would still visit every tile exactly once).
         SCHED_PASS(waitForLaunches(s));
@@ -161,6 +187,7 @@ hipError_t RtTileScheduler::measuredEnd(const Plan &plan) {
     fbTiles = plan.nTiles;
     fbTilesX = plan.tilesX;
     fbBt = plan.bt;
+    fbClass = plan.costClass;
     return hipSuccess;
 }
 
@@ -286,8 +313,9 @@ hipError_t RtTileScheduler::phaseEnd(const Plan &plan) {
 
 // ---- one frame ------------------------------------------------------------------------------------------------------------
 
-hipError_t RtTileScheduler::begin(const RtFrame &f, RtDeviceScene &sc, hipStream_t s, bool packet, unsigned long long inputsGen, Plan *plan) {
+hipError_t RtTileScheduler::begin(const RtFrame &f, RtDeviceScene &sc, hipStream_t s, bool packet, unsigned long long inputsGen, Plan *plan, int costClass) {
     *plan = Plan();
+    plan->costClass = costClass;
     sc.tileOrder = nullptr;
     sc.tileCost = nullptr;
     SCHED_PASS(record(s, &plan->rec));

@@ -13,6 +13,7 @@ struct RtTileScheduler {
         hipStream_t s = nullptr;
         DevEvent last;
         unsigned seenGen = 0;
+        unsigned seenFirst = 0;                // the first-hit recording it has already ordered itself behind (firstGen)
         // predicted tile order of the last frame issued on this stream, and the inputs it was predicted from
         // (predOrder: the order, then 32 class segments of predCls.cap tile ids each; predCounts: two sets of 32 class sizes, used
         // alternately -- a prediction clears the other set)
@@ -26,6 +27,7 @@ struct RtTileScheduler {
     struct Plan {
         StreamRec *rec = nullptr;
         int nTiles = 0, tilesX = 0, bt = 0;
+        int costClass = 0;                     // what the frame's tile costs are comparable with: 0 = whole frames, 1 = first-hit replays
         int phase = -1;                        // frameCount mod 64 when the frame records into (and sorts) its phase's buffers
         bool sortAfter = false;                // the frame was scheduled: the measured order's bookkeeping runs after it
     };
@@ -40,9 +42,18 @@ struct RtTileScheduler {
     hipError_t drain();                                                 // the host waits for every stream and every sort
 
     // ---- one frame.  `packet`: the launch is one the scheduler may order (packet kernel, no ray counter); `inputsGen`
-    // changes whenever the scene or a texture does.  begin() fills sc.tileOrder / sc.tileCost.
-    hipError_t begin(const RtFrame &f, RtDeviceScene &sc, hipStream_t s, bool packet, unsigned long long inputsGen, Plan *plan);
+    // changes whenever the scene or a texture does.  begin() fills sc.tileOrder / sc.tileCost.  `costClass`: 1 for a frame that
+    // replays its first hit (rt_firsthit.h) -- its tiles cost nothing like a whole frame's, so a change of class restarts the
+    // cost feedback exactly as a new window geometry does (costs cleared, orders reset, sorts on the first two frames, phases forgotten).
+    hipError_t begin(const RtFrame &f, RtDeviceScene &sc, hipStream_t s, bool packet, unsigned long long inputsGen, Plan *plan, int costClass = 0);
     hipError_t end(const Plan &plan, hipStream_t s);
+
+    // ---- the context's first-hit records: one buffer, written by a recording frame, read by replays on any stream.  A
+    // recording frame overwrites it only behind every stream's last launch (beforeFirstHitRecord, ahead of the launch) and
+    // records the event (afterFirstHitRecord) that every stream's first replay after it waits for (beforeFirstHitReplay).
+    hipError_t beforeFirstHitRecord(hipStream_t s);
+    hipError_t afterFirstHitRecord(hipStream_t s, StreamRec *rec);
+    hipError_t beforeFirstHitReplay(hipStream_t s, StreamRec *rec);
 
     // ---- debug read-outs (rt_debug_tile_costs, rt_debug_predicted_classes)
     hipError_t tileCosts(unsigned *out, int cap, int *nTiles, int *tilesX);
@@ -78,6 +89,9 @@ private:
     bool sortPending = false;                  // a sort has been enqueued on the context's own stream, not yet adopted
     unsigned sortAge = 0;                      // fbAge at which it was enqueued
     int fbTiles = 0, fbTilesX = 0, fbBt = 0;   // geometry the current order was measured on (0 = none)
+    int fbClass = 0;                           // ... and the cost class of the frames it was measured on (Plan::costClass)
+    DevEvent evFirst;                          // completion of the last frame that recorded first hits
+    unsigned firstGen = 0;                     // bumped by every such frame
     unsigned fbAge = 0;                        // frames since that geometry was first seen
     unsigned adoptGen = 0;                     // bumped whenever fbCur changes to a freshly sorted buffer
     unsigned fbPeriod = 32;                    // re-sort period in frames (RT_FB_PERIOD overrides, for measurements)

@@ -21,10 +21,11 @@ def one(spec):
     if cr.returncode:
         return f"[{name}] BUILD FAILED\n{cr.stderr[-1500:]}"
     for b_ in cr.stderr.split("Function Name: "):
-        m = re.match(r"_Z23rt_render_packet_kernelILi0ELi(\d+)ELb(\d)E(\S*?)(Pk\w+?)E", b_)
+        # (behind the profile: render_packet's FIRST -- 0 the normal frame, 1 / 2 the frames that record / replay first hits)
+        m = re.match(r"_Z23rt_render_packet_kernelILi0ELi(\d+)ELb(\d)E(\S*?)(Pk\w+?)E(?:Li(\d)E)?", b_)
         if m:
             g = lambda key: (re.search(key + r": (\d+)", b_) or [None, "?"])[1]
-            lines.append(f"[{name}] kernel<0,{m.group(4)}>: VGPR {g('VGPRs')} scratch {g('ScratchSize .bytes.lane.')} "
+            lines.append(f"[{name}] kernel<0,{m.group(4)}{',' + m.group(5) if m.group(5) not in (None, '0') else ''}>: VGPR {g('VGPRs')} scratch {g('ScratchSize .bytes.lane.')} "
                          f"occ {g('Occupancy .waves.SIMD.')} sgpr-spill {g('SGPRs Spill')} vgpr-spill {g('VGPRs Spill')}")
     return "\n".join(lines)
 
