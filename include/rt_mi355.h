@@ -204,6 +204,15 @@ int rt_set_variant(rt_context *ctx, int variant);
  * that ran normal / recording / replaying since rt_create (instrumented and variant-0 launches are not counted). */
 int rt_debug_first_hit(rt_context *ctx, uint64_t counts[3]);
 
+/* Settled tiles (part of first-hit reuse; on unless the variant carries 0x800 or RT_SETTLED_TILES=0 was set at rt_create): an
+ * 8x8 tile of the recorded window none of whose paths read the frame's bounce sample gives the same bits for every frameCount,
+ * so the recording frame keeps its three surface values and replaying frames copy them out instead of tracing the tile.
+ * out[0] = tiles of the cached window, out[1] = how many of them are settled; zeros while no recorded window is cached. */
+int rt_debug_settled_tiles(rt_context *ctx, uint64_t out[2]);
+/* The cached window's flags, one byte per tile in row-major tile order (1 = settled); n must be out[0] of
+ * rt_debug_settled_tiles (0 without a cache).  Both calls wait for the context's work in flight. */
+int rt_debug_settled_map(rt_context *ctx, uint8_t *flags, size_t n);
+
 /* Diagnostics of the last rt_count_rays launch: out[0] rays, out[1] wave-level ray packets,
  * out[2] candidate objects summed over packets (after packet culling), out[3] 64-object cull
  * passes.  [1..3] are zero for variant 0 (no packet culling). */

@@ -96,6 +96,9 @@ RtFirstHit::Mode first_hit_mode(rt_context *c, const RtFirstHitKey &key) {
             // replays of an earlier, smaller window may still read the old buffer on any stream
             hipError_t e = c->sched.drain();
             if (e == hipSuccess) e = c->dFirstHit.grow(bytes);
+            // (zero-initialised when it grows: no flag of the new buffer reads as settled before a recording frame has written it)
+            if (e == hipSuccess) e = hipMemsetAsync(c->dFirstHit.ptr, 0, bytes, c->stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
             if (e != hipSuccess) {
                 (void)hipGetLastError();
                 c->firstHit.refuse(key);
@@ -148,7 +151,8 @@ int launch_frame(rt_context *c, const rt_params *p, float4 *dColor, float4 *dPos
     if (mode == RtFirstHit::REPLAY) SCHED_TRY(c, beforeFirstHitReplay(s, plan.rec));
     if (timed) HIP_TRY(c, hipEventRecord(c->evStart, s));
     HIP_TRY(c, rt_launch_render(f, sc, dColor, dPos, dNormal, counter, c->variant, s, countMode, (int)mode,
-                                mode == RtFirstHit::NORMAL ? nullptr : (void *)c->dFirstHit.ptr));
+                                mode == RtFirstHit::NORMAL ? nullptr
+                                    : (void *)((uintptr_t)c->dFirstHit.ptr | (mode == RtFirstHit::RECORD && !c->settledOn() ? RT_FIRST_HIT_NO_SETTLED : 0))));
     if (timed) {
         HIP_TRY(c, hipEventRecord(c->evStop, s));
         c->timed = true;
@@ -198,6 +202,7 @@ int rt_create(rt_context **out, int deviceId) {
     c->device = deviceId;
     if (const char *e = getenv("RT_ST_BUILD")) c->stOnePhase = strcmp(e, "full") == 0;
     if (const char *e = getenv("RT_FIRST_HIT_REUSE")) c->firstHit.envOn = atoi(e) != 0;
+    if (const char *e = getenv("RT_SETTLED_TILES")) c->settledEnvOn = atoi(e) != 0;
     if (const char *e = getenv("RT_ST_GEOM")) {        // "Kcube,Kplan,NB": measurement override of the shadow-table geometry
         int kc = 0, kp = 0, nb = 0;
         if (sscanf(e, "%d,%d,%d", &kc, &kp, &nb) == 3 && kc >= 4 && kc <= 128 && kp >= 4 && kp <= 256 && nb >= 1 && nb <= 128)
@@ -539,10 +544,12 @@ static int count_rays_impl(rt_context *c, const rt_params *p, uint64_t *rays, in
 
 int rt_set_variant(rt_context *c, int variant) {
     if (!c) return RT_ERR_INVALID_ARG;
-    // another kernel, or first-hit reuse switched (bit 10, 0x400 = off): the next frame is a normal one
-    const bool reuseOn = (variant & 0x400) == 0;
-    if ((variant & 0xff) != c->variant || reuseOn != c->firstHit.variantOn) c->firstHit.invalidate();
+    // another kernel, or first-hit reuse (bit 10, 0x400 = off) or its settled tiles (bit 11, 0x800 = off) switched: the next
+    // frame is a normal one
+    const bool reuseOn = (variant & 0x400) == 0, settledOn = (variant & 0x800) == 0;
+    if ((variant & 0xff) != c->variant || reuseOn != c->firstHit.variantOn || settledOn != c->settledVariantOn) c->firstHit.invalidate();
     c->firstHit.variantOn = reuseOn;
+    c->settledVariantOn = settledOn;
     c->variant = variant & 0xff;
     c->sched.setMode(variant);         // bits 8 and 9: the tile order
     return RT_OK;
@@ -551,6 +558,39 @@ int rt_set_variant(rt_context *c, int variant) {
 int rt_debug_first_hit(rt_context *c, uint64_t counts[3]) {
     if (!c || !counts) return RT_ERR_INVALID_ARG;
     for (int k = 0; k < 3; k++) counts[k] = c->firstHit.counts[k];
+    return RT_OK;
+}
+
+// The flags of the cached window, read back after everything in flight has ended (a recording frame may still be writing them).
+static int settled_flags(rt_context *c, std::vector<uint8_t> *flags) {
+    flags->clear();
+    if (!c->firstHit.valid || !c->dFirstHit.ptr) return RT_OK;
+    const rt_params &p = c->firstHit.cached.p;
+    const RtFirstHitLayout l = rt_first_hit_layout(p.regionW, p.regionH);
+    if (!c->dFirstHit.holds(l.bytes)) return RT_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, c->sched.drain());
+    flags->resize(l.tiles);
+    HIP_TRY(c, hipMemcpy(flags->data(), c->dFirstHit.ptr + l.flags, l.tiles, hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+int rt_debug_settled_tiles(rt_context *c, uint64_t out[2]) {
+    if (!c || !out) return RT_ERR_INVALID_ARG;
+    out[0] = out[1] = 0;
+    std::vector<uint8_t> flags;
+    RT_TRY(settled_flags(c, &flags));
+    out[0] = flags.size();
+    for (uint8_t v : flags) out[1] += v != 0;
+    return RT_OK;
+}
+
+int rt_debug_settled_map(rt_context *c, uint8_t *flags, size_t n) {
+    if (!c || (!flags && n)) return RT_ERR_INVALID_ARG;
+    std::vector<uint8_t> have;
+    RT_TRY(settled_flags(c, &have));
+    if (n != have.size()) return fail(c, RT_ERR_INVALID_ARG, "rt_debug_settled_map: n is not the cached window's tile count (rt_debug_settled_tiles)");
+    if (n) memcpy(flags, have.data(), n);
     return RT_OK;
 }
 

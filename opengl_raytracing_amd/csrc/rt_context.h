@@ -44,6 +44,10 @@ struct rt_context {
     RtTileScheduler sched;                     // tile order of the packet kernel's frames; the record of every stream launches go to
     RtFirstHit firstHit;                       // which launches record / replay their first hit (rt_firsthit.h) ...
     DevBuf<uint8_t> dFirstHit;                 // ... and the records: rt_first_hit_bytes() of the recorded window, allocated by the first recording frame
+    // settled tiles ride on the first-hit cache, same buffer and lifetime; RT_SETTLED_TILES=0 at rt_create /
+    // rt_set_variant's bit 11 (0x800) switch them off
+    bool settledEnvOn = true, settledVariantOn = true;
+    bool settledOn() const { return settledEnvOn && settledVariantOn; }
     DevBuf<uint2> dBloom[2];                   // rgba16f ping-pong targets of rt_bloom
     DevBuf<float> dSsaoDepth;                  // gPosition.z plane of rt_ssao
     ScratchUse bloomUse, ssaoUse;              // who ran last in dBloom / dSsaoDepth, on whichever stream

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "rt_mi355.h"
+#include "rt_firsthit.h"
 
 #define RT_MAX_DEPTH 32      // per-depth bounce-sample table in kernarg memory
 #define RT_HALTON_N 64       // tabulated Halton indices (UI range of pcfSamples is 1..16)
@@ -84,8 +85,11 @@ hipError_t rt_launch_compile_scene(const uint8_t *dObjects, int nObj, const uint
 hipError_t rt_launch_render(const RtFrame &f, const RtDeviceScene &sc, float4 *dColor, float4 *dPos,
                             uint2 *dNormal, unsigned long long *dRayCounter, int variant, hipStream_t s, int countMode = 1,
                             int firstMode = 0, void *dFirstHit = nullptr);
-// bytes of the first-hit records of a regionW x regionH window (render_packet, FIRST != 0): (t, hit) and three floats of colour per pixel
-static inline size_t rt_first_hit_bytes(int regionW, int regionH) { return (size_t)regionW * (size_t)regionH * (sizeof(uint2) + 3 * sizeof(float)); }
+// (the record buffer of a regionW x regionH window, render_packet FIRST != 0: rt_first_hit_bytes() and the offsets of its parts
+// are rt_firsthit.h's.)  Bit 0 of the dFirstHit pointer a RECORDING launch passes switches settled tiles OFF (DESIGN.md
+// section 27: every tile's flag is then written as 0, which is all a replaying launch looks at): the buffer is aligned far
+// beyond that, and one more kernel argument would move the hidden arguments of every instantiation.
+#define RT_FIRST_HIT_NO_SETTLED ((uintptr_t)1)
 // Tile geometry of the packet kernel for a given scene size / window (so the ABI layer can size the
 // feedback buffers): workgroup threads, tile edge, tiles per row, total tiles.
 void rt_packet_geometry(int nObj, int regionW, int regionH, int *bt, int *tile, int *tilesX, int *nTiles);

@@ -4,7 +4,8 @@
 // noise texture): while those stay what they were, the frame after a still one RECORDS what depth 0 ends with, and the frames
 // after that REPLAY it (render_packet's FIRST parameter, rt_packet.inc).  This header decides which of the three a launch is; it
 // holds no HIP type, so it is compiled and tested alone (tests/test_first_hit_host.py).  The record buffer, the events between
-// the streams and the launches themselves are rt_abi.cpp's and rt_sched.cpp's.  Not part of the public ABI.
+// the streams and the launches themselves are rt_abi.cpp's and rt_sched.cpp's; the buffer's layout, which section 27's settled
+// tiles extend, is below.  Not part of the public ABI.
 #pragma once
 #include <stdint.h>
 #include <string.h>
@@ -46,10 +47,57 @@ inline RtFirstHitKey rt_first_hit_key(uint32_t sceneGen, uint32_t texGen, int nO
     return k;
 }
 
+// The record buffer of a regionW x regionH window: four parts in one allocation, each starting on a multiple of 16 bytes.
+//   hits     8 B/pixel   (t, hit object) of the first hit                                   } the first-hit records (section 26),
+//   colours  12 B/pixel  finalColor after depth 0                                           } packed: 20 B/pixel
+//   finals   32 B/pixel  what a settled tile stored to the three surfaces (section 27): two 16-byte halves,
+//                        (colour.xyz, position.x) and (position.y, position.z, the packed normal pair)
+//   flags    1 B/tile    1 = the 8x8 tile is settled, indexed by the window-local tile id tileY * tilesX + tileX
+// Pixels are indexed window-locally, j * regionW + i.  Plain integer arithmetic: the kernel (render_packet), the ABI layer and
+// a host-only test (tests/test_settled_layout_host.py) all take the offsets from here.
+struct RtFirstHitLayout {
+    uint64_t pixels, tiles;
+    uint64_t hits, colours, finals, flags;      // byte offsets of the four parts
+    uint64_t bytes;                             // of the whole buffer
+};
+#if defined(__HIPCC__) || defined(__CUDACC__)
+#define RT_FH_INLINE __host__ __device__ inline
+#else
+#define RT_FH_INLINE inline
+#endif
+RT_FH_INLINE uint64_t rt_first_hit_align16(uint64_t v) { return (v + 15u) & ~(uint64_t)15u; }
+RT_FH_INLINE uint64_t rt_first_hit_tiles(int regionW, int regionH) {
+    return (uint64_t)((regionW + 7) / 8) * (uint64_t)((regionH + 7) / 8);
+}
+RT_FH_INLINE uint64_t rt_first_hit_colours_offset(int regionW, int regionH) {
+    return rt_first_hit_align16((uint64_t)regionW * (uint64_t)regionH * 8u);
+}
+RT_FH_INLINE uint64_t rt_first_hit_finals_offset(int regionW, int regionH) {
+    return rt_first_hit_align16(rt_first_hit_colours_offset(regionW, regionH) + (uint64_t)regionW * (uint64_t)regionH * 12u);
+}
+RT_FH_INLINE uint64_t rt_first_hit_flags_offset(int regionW, int regionH) {
+    return rt_first_hit_finals_offset(regionW, regionH) + (uint64_t)regionW * (uint64_t)regionH * 32u;
+}
+RT_FH_INLINE uint64_t rt_first_hit_bytes(int regionW, int regionH) {
+    return rt_first_hit_flags_offset(regionW, regionH) + rt_first_hit_align16(rt_first_hit_tiles(regionW, regionH));
+}
+inline RtFirstHitLayout rt_first_hit_layout(int regionW, int regionH) {
+    RtFirstHitLayout l;
+    l.pixels = (uint64_t)regionW * (uint64_t)regionH;
+    l.tiles = rt_first_hit_tiles(regionW, regionH);
+    l.hits = 0;
+    l.colours = rt_first_hit_colours_offset(regionW, regionH);
+    l.finals = rt_first_hit_finals_offset(regionW, regionH);
+    l.flags = rt_first_hit_flags_offset(regionW, regionH);
+    l.bytes = rt_first_hit_bytes(regionW, regionH);
+    return l;
+}
+
 struct RtFirstHit {
     enum Mode { NORMAL = 0, RECORD = 1, REPLAY = 2 };
-    // Windows above this many pixels are never recorded (20 bytes per pixel: 320 MiB at the cap, which a 4096 x 4096 window
-    // reaches; 1080p takes 41 MB).  Larger ones render normal frames.
+    // Windows above this many pixels are never recorded (52 bytes per pixel and one per tile: 832 MiB at the cap, which a
+    // 4096 x 4096 window reaches; 1080p takes 108 MB).  Larger ones render normal frames.  The cap stays where section 26 put
+    // it: a buffer that cannot be had is refused at no cost (refuse()), so the cap only bounds what is ever asked for.
     static constexpr uint64_t kMaxPixels = (uint64_t)1 << 24;
 
     bool envOn = true;               // RT_FIRST_HIT_REUSE=0 at rt_create clears it

@@ -742,6 +742,9 @@ __global__ RT_V0_BOUNDS void rt_render_kernel(const RtFrame f, const RtDeviceSce
 // (render_packet).  The records come in the `rayCounter` argument, which the launches that reuse (never
 // instrumented: COUNT = 0) have no other use for: one more kernel argument moves the hidden arguments behind it, and FIRST = 0
 // has to stay, to the byte, the kernel it was.
+#ifndef RT_FB_ACCUM
+#define RT_FB_ACCUM 1
+#endif
 template <int COUNT, int BT, bool COMPACT, typename PROFILE, int FIRST = 0>
 __global__ __launch_bounds__(BT, PROFILE::waves)
 void rt_render_packet_kernel(const RtFrame f, const RtDeviceScene dsc, float4 *__restrict__ gColor,
@@ -749,6 +752,21 @@ void rt_render_packet_kernel(const RtFrame f, const RtDeviceScene dsc, float4 *_
                              unsigned long long *rayCounter) {
     static_assert(FIRST == 0 || COUNT == 0, "a frame that records or replays first hits has no ray counter");
     static_assert(BT == 64 && COMPACT, "one-wave workgroups, only the AABBs staged in LDS");
+    if constexpr (FIRST == 2) {     // a settled tile of a replaying frame: copied out, costed, done
+        const unsigned tile_ = dsc.tileOrder ? dsc.tileOrder[blockIdx.x] : blockIdx.x;
+        if (tile_ < gridDim.x) {
+            const unsigned tilesX_ = (unsigned)(f.p.regionW + 7) / 8u;
+            const long long t0_ = clock64();
+            if (pk_replay_settled_tile(f, (int)(tile_ % tilesX_), (int)(tile_ / tilesX_), (const unsigned char *)rayCounter, gColor, gPosition, gNormal)) {
+                if (dsc.tileCost && (threadIdx.x & 63) == 0) {
+                    const unsigned c_ = (unsigned)(((unsigned long long)(clock64() - t0_)) >> 6);
+                    if (RT_FB_ACCUM) atomicAdd(&dsc.tileCost[tile_], c_);
+                    else dsc.tileCost[tile_] = c_;
+                }
+                return;
+            }
+        }
+    }
     extern __shared__ float4 lds[];
     const int nAll = f.nObj * (RT_HOT_F4 + RT_MAT_F4) + f.nLt * RT_LGT_F4 + 2 * (RT_HALTON_N / 4);
     const int nF4 = PROFILE::boundsLds ? f.nObj * 2 : 0;          // float4 staged in LDS: the objects' two bounds float4
@@ -790,9 +808,6 @@ void rt_render_packet_kernel(const RtFrame f, const RtDeviceScene dsc, float4 *_
 
     if (dsc.tileCost && (threadIdx.x & 63) == 0) {     // one add per wave: tile cost = sum of its waves' cycles / 64
         const unsigned c = (unsigned)(((unsigned long long)(clock64() - t0)) >> 6);
-#ifndef RT_FB_ACCUM
-#define RT_FB_ACCUM 1
-#endif
         // costs accumulate between two sorts: the order then follows the tiles' average cost over the last period, which is what predicts the next
         // frames when frameCount rotates the shared bounce sample from frame to frame
         // (atomic: frames in flight on several streams may add to the same tile at once -- ADVICE r2)

@@ -1312,14 +1312,46 @@ __device__ __forceinline__ float pk_pcf_shadow(const SceneLds &sc, int nObj, v3 
     }
 }
 
+// A replaying frame's SETTLED tile (DESIGN.md section 27; render_packet below has the rule and the recording side): the wave
+// loads its tile's flag, and where it is set every lane copies its final record to the three surfaces -- alpha and the zeros
+// outside the image regenerated as at the end of render_packet -- and the tile is done.  Called at the very top of the kernel
+// with nothing but the kernel's arguments alive and sharing no value with render_packet: placed inside it, the early-out
+// cost the replaying instantiations 6-20 more spilled SGPRs over the whole bounce loop (C3 +2.5 %).
+__device__ __forceinline__ bool pk_replay_settled_tile(const RtFrame &f, int tileX, int tileY, const unsigned char *records, float4 *gColor,
+                                                       float4 *gPosition, uint2 *gNormal) {
+    const int tilesX = (f.p.regionW + 7) / 8;
+    if (__builtin_amdgcn_readfirstlane((int)records[rt_first_hit_flags_offset(f.p.regionW, f.p.regionH) + (size_t)(tileY * tilesX + tileX)]) == 0) return false;
+    const int ln = threadIdx.x & 63;
+    const int i = tileX * 8 + (ln & 7), j = tileY * 8 + (ln >> 3);
+    if (i < f.p.regionW && j < f.p.regionH) {
+        const int gxI = f.p.x0 + i, ly = f.p.y0 + j;
+        const int gyI = (ly / f.p.stripRows) * f.p.stripCycleRows + f.p.stripOffsetRows + ly % f.p.stripRows;
+        const size_t at = (size_t)j * f.p.regionW + i;
+        const size_t out = f.imageStores ? (size_t)gyI * f.p.width + gxI : at;
+        if (gxI < f.p.width && gyI < f.p.height) {
+            const float4 *fin = (const float4 *)(records + rt_first_hit_finals_offset(f.p.regionW, f.p.regionH)) + 2 * at;
+            const float4 a = fin[0], b = fin[1];
+            gColor[out] = make_float4(a.x, a.y, a.z, 1.0f);
+            gPosition[out] = make_float4(a.w, b.x, b.y, 1.0f);
+            gNormal[out] = make_uint2(__float_as_uint(b.z), __float_as_uint(b.w));
+        } else if (!f.imageStores) {   // outside the image: GL discards the imageStore (a whole-image surface has no such pixel)
+            gColor[out] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            gPosition[out] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            gNormal[out] = make_uint2(0u, 0u);
+        }
+    }
+    return true;
+}
+
 // main() of raytracingCs.glsl (:509-584) for one 64-lane packet of pixels.
 // FIRST (DESIGN.md section 26; the host side is rt_firsthit.h): 0 = the frame as it always was.  1 = the same frame, which also
 // RECORDS what depth 0 ends with, one record of 20 bytes per pixel of the window at window-local index j * regionW + i:
-// firstHit[idx] = (t of the closest hit, the hit object or -1 for a miss or a pixel outside the image), and behind the regionW *
-// regionH pairs three floats per pixel, finalColor as parked after depth 0.  2 = REPLAY: depth 0 takes (finalColor, t, hit) from the record in place of
+// firstHit[idx] = (t of the closest hit, the hit object or -1 for a miss or a pixel outside the image), and in the buffer's
+// `colours` part (rt_firsthit.h has the layout) three floats per pixel, finalColor as parked after depth 0.  2 = REPLAY: depth 0 takes (finalColor, t, hit) from the record in place of
 // the closest-hit traversal, the light loop and the subsurface section, recomputes the shading point from them by the
 // expressions of the normal frame, and goes on with the next direction and depth 1 as ever.  Every value is copied bitwise or
-// recomputed by the identical expression, so the three frames are the same bits.
+// recomputed by the identical expression, so the three frames are the same bits.  On top of that the recording frame marks the
+// SETTLED tiles and keeps their surface values, and the replaying frame copies those out (below; DESIGN.md section 27).
 template <int COUNT, int BT, typename PROFILE, int FIRST = 0>
 __device__ __forceinline__ void render_packet(const RtFrame &f, const RtDeviceScene &dsc, const SceneLds &sc,
                                               float4 *gColor,
@@ -1344,6 +1376,27 @@ __device__ __forceinline__ void render_packet(const RtFrame &f, const RtDeviceSc
         outIdx = f.imageStores ? (size_t)gyI * f.p.width + gxI : (size_t)j * f.p.regionW + i;
         return i < f.p.regionW && j < f.p.regionH;
     };
+    // this lane's first-hit record (FIRST != 0): window-local pixel index, or -1 for the lanes of an edge tile beyond the window
+    [[maybe_unused]] auto firstIndex = [&]() -> long long {
+        const int wave = threadIdx.x >> 6, ln = threadIdx.x & 63;
+        const int i = sc.tileX * 8 + (wave & 1) * 8 + (ln & 7);
+        const int j = sc.tileY * 8 + (wave >> 1) * 8 + (ln >> 3);
+        return (i < f.p.regionW && j < f.p.regionH) ? (long long)j * f.p.regionW + i : -1ll;
+    };
+    // SETTLED TILES (FIRST != 0, DESIGN.md section 27).  A lane is TAINTED when, alive after the roulette, it takes the diffuse
+    // branch of the next-direction step: the only reader of f.hemi, which is the only value of the frame's bounce sample that
+    // reaches this function without a noise texture.  A tile none of whose lanes was tainted is SETTLED: its three surface
+    // values are the same bits for every frameCount, so the recording frame keeps them (32 bytes per pixel, the buffer's
+    // `finals` part) with one flag per tile, and a replaying frame whose tile is flagged copies them out and is done
+    // (pk_replay_settled_tile, which the kernel calls ahead of everything else).
+    // Bit 0 of a RECORDING launch's record pointer switches it off (rt_device.h): every flag is then written as 0.  The taint
+    // is one word of LDS, the block counter's slot ahead of the parking area that only the instrumented builds use: nothing
+    // the light loop has to carry in a register; the pointer is masked where it is used for the same reason.  The word travels
+    // between lanes, so every access is volatile: no store may be dropped or forwarded to the load behind the loop (LDS
+    // operations of one wave complete in order, and the workgroup is that one wave).
+    [[maybe_unused]] volatile unsigned *const taintWord = (volatile unsigned *)sc.park - 4;
+    [[maybe_unused]] auto records = [&]() -> unsigned char * { return (unsigned char *)((uintptr_t)firstHit & ~RT_FIRST_HIT_NO_SETTLED); };
+    if constexpr (FIRST == 1) *taintWord = 0u;
     int gxI, gyI;
     size_t outIdx;
     const bool inWindow0 = pixel(gxI, gyI, outIdx);
@@ -1391,13 +1444,6 @@ __device__ __forceinline__ void render_packet(const RtFrame &f, const RtDeviceSc
     rayBox.loz = rayBox.hiz = f.p.camPos[2];
     bool rayBoxFinite = box_finite(rayBox);
 
-    // this lane's first-hit record (FIRST != 0): window-local pixel index, or -1 for the lanes of an edge tile beyond the window
-    [[maybe_unused]] auto firstIndex = [&]() -> long long {
-        const int wave = threadIdx.x >> 6, ln = threadIdx.x & 63;
-        const int i = sc.tileX * 8 + (wave & 1) * 8 + (ln & 7);
-        const int j = sc.tileY * 8 + (wave >> 1) * 8 + (ln >> 3);
-        return (i < f.p.regionW && j < f.p.regionH) ? (long long)j * f.p.regionW + i : -1ll;
-    };
     // FIRST == 1, the two halves of this lane's record.  (t, hit) go out right behind the closest-hit traversal: held until the
     // colour is known they would stay live across the whole lighting section, in kernels that have no register to spare ...
     [[maybe_unused]] auto firstRecordHit = [&](float tHit_, int hit_) {
@@ -1405,9 +1451,9 @@ __device__ __forceinline__ void render_packet(const RtFrame &f, const RtDeviceSc
         if (at >= 0) {
             const pk_u2 rec = {__float_as_uint(tHit_), (unsigned)hit_};
 #if RT_FIRST_HIT_NT
-            __builtin_nontemporal_store(rec, (pk_u2 *)&firstHit[at]);
+            __builtin_nontemporal_store(rec, (pk_u2 *)records() + at);
 #else
-            *(pk_u2 *)&firstHit[at] = rec;
+            ((pk_u2 *)records())[at] = rec;
 #endif
         }
     };
@@ -1417,7 +1463,7 @@ __device__ __forceinline__ void render_packet(const RtFrame &f, const RtDeviceSc
         const float *pk_ = sc.park + threadIdx.x;
         const long long at = firstIndex();
         if (at >= 0) {
-            float *col = (float *)(firstHit + (size_t)f.p.regionW * (size_t)f.p.regionH) + 3 * at;
+            float *col = (float *)(records() + rt_first_hit_colours_offset(f.p.regionW, f.p.regionH)) + 3 * at;
 #pragma unroll
             for (int k = 0; k < 3; k++) {
 #if RT_FIRST_HIT_NT
@@ -1444,7 +1490,7 @@ __device__ __forceinline__ void render_packet(const RtFrame &f, const RtDeviceSc
             uint2 rec = make_uint2(__float_as_uint(maxDist), 0xffffffffu);
             v3 recCol = V3(0.0f, 0.0f, 0.0f);
             if (at >= 0) {
-                const float *col = (const float *)(firstHit + (size_t)f.p.regionW * (size_t)f.p.regionH) + 3 * at;
+                const float *col = (const float *)((const unsigned char *)firstHit + rt_first_hit_colours_offset(f.p.regionW, f.p.regionH)) + 3 * at;
                 rec = firstHit[at];
                 recCol = V3(col[0], col[1], col[2]);
             }
@@ -1754,6 +1800,8 @@ __device__ __forceinline__ void render_packet(const RtFrame &f, const RtDeviceSc
                 if (alive && !stop) thr = div3(thr, cp);
                 alive = alive && !stop;
             }
+            // (alive lanes only: a dead lane gathered object 0's material)
+            if constexpr (FIRST == 1) { if (alive && diffuseStrength > 0.0f) *taintWord = 1u; }
             // ---- next direction (:552-576).  Lanes whose path has ended get the same assignments (nothing reads their ray again):
             // an unconditional write keeps the old origin / direction from staying live across the whole lighting section
             Ray cur; cur.o = Pb; cur.d = rd;
@@ -1807,6 +1855,20 @@ __device__ __forceinline__ void render_packet(const RtFrame &f, const RtDeviceSc
             gColor[outIdxS] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
             gPosition[outIdxS] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
             gNormal[outIdxS] = make_uint2(0u, 0u);
+        }
+    }
+    if constexpr (FIRST == 1) {   // every exit of the bounce loop comes through here: the tile's flag, and a settled tile's final records
+        asm volatile("" ::: "memory");
+        const bool settled = ((uintptr_t)firstHit & RT_FIRST_HIT_NO_SETTLED) == 0 && __builtin_amdgcn_readfirstlane((int)*taintWord) == 0;
+        unsigned char *flags = records() + rt_first_hit_flags_offset(f.p.regionW, f.p.regionH);
+        if ((threadIdx.x & 63) == 0) flags[sc.tileY * ((f.p.regionW + 7) / 8) + sc.tileX] = settled ? 1 : 0;
+        const long long at = firstIndex();
+        if (settled && at >= 0) {
+            pk_f4 *fin = (pk_f4 *)(records() + rt_first_hit_finals_offset(f.p.regionW, f.p.regionH)) + 2 * at;
+            const pk_f4 a = {finalColor.x, finalColor.y, finalColor.z, P.x};
+            const pk_f4 b = {P.y, P.z, __uint_as_float(f2h_rtz(N.x) | (f2h_rtz(N.y) << 16)), __uint_as_float(f2h_rtz(N.z) | (0x3c00u << 16))};
+            __builtin_nontemporal_store(a, fin);
+            __builtin_nontemporal_store(b, fin + 1);
         }
     }
 }

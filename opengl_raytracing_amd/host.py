@@ -32,7 +32,7 @@ _LIB = None
 EXPORTS = [
     "rt_create", "rt_destroy", "rt_set_scene", "rt_set_noise", "rt_set_skybox", "rt_render",
     "rt_render_to", "rt_sync", "rt_readback", "rt_get_surfaces", "rt_last_kernel_ms",
-    "rt_count_rays", "rt_count_rays_traced", "rt_debug_stats", "rt_debug_stats_ex", "rt_debug_first_hit", "rt_debug_tile_costs", "rt_set_variant", "rt_last_error", "rt_generate_aabb", "rt_camera_vectors",
+    "rt_count_rays", "rt_count_rays_traced", "rt_debug_stats", "rt_debug_stats_ex", "rt_debug_first_hit", "rt_debug_settled_tiles", "rt_debug_settled_map", "rt_debug_tile_costs", "rt_set_variant", "rt_last_error", "rt_generate_aabb", "rt_camera_vectors",
     "rt_scene_parse", "rt_scene_write", "rt_taa_resolve", "rt_taa_jitter", "rt_bloom", "rt_ssao", "rt_ssao_blur",
     "rt_camera_matrices", "rt_equirect_to_cubemap", "rt_frame", "rt_frame_surfaces", "rt_strip_local_rows", "rt_deinterleave",
     "rt_wire_bytes", "rt_wire_pack", "rt_wire_unpack", "rt_debug_mesa_math", "rt_debug_shadow_tables", "rt_debug_predicted_classes",
@@ -118,6 +118,8 @@ def load_library(build_if_missing=True):
     lib.rt_debug_stats.argtypes = [vp, P(ctypes.c_uint64)]
     lib.rt_debug_stats_ex.argtypes = [vp, P(ctypes.c_uint64)]
     lib.rt_debug_first_hit.argtypes = [vp, P(ctypes.c_uint64)]
+    lib.rt_debug_settled_tiles.argtypes = [vp, P(ctypes.c_uint64)]
+    lib.rt_debug_settled_map.argtypes = [vp, P(ctypes.c_uint8), ctypes.c_size_t]
     lib.rt_debug_tile_costs.argtypes = [vp, P(ctypes.c_uint32), ci, P(ci), P(ci)]
     lib.rt_last_error.argtypes = [vp]
     lib.rt_last_error.restype = ctypes.c_char_p
@@ -1151,6 +1153,19 @@ class RayTracer:
         out = (ctypes.c_uint64 * 3)()
         self._check(self.lib.rt_debug_first_hit(self.ctx, out), "rt_debug_first_hit")
         return list(out)
+
+    def debug_settled_tiles(self):
+        """[tiles of the cached first-hit window, settled ones among them]; zeros without a valid cache."""
+        out = (ctypes.c_uint64 * 2)()
+        self._check(self.lib.rt_debug_settled_tiles(self.ctx, out), "rt_debug_settled_tiles")
+        return list(out)
+
+    def debug_settled_map(self):
+        """The cached window's settled flags, one uint8 per 8x8 tile in row-major tile order (empty without a valid cache)."""
+        n = self.debug_settled_tiles()[0]
+        flags = (ctypes.c_uint8 * max(n, 1))()
+        self._check(self.lib.rt_debug_settled_map(self.ctx, flags, n), "rt_debug_settled_map")
+        return np.frombuffer(flags, dtype=np.uint8, count=n).copy()
 
     def deinterleave(self, d_src, d_dst, width, height, bytes_per_pixel, strip_rows, strip_count,
                      rank_stride_bytes, stream=None):

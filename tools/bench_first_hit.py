@@ -1,9 +1,10 @@
-"""First-hit reuse A/B inside one process: blocks of C2 frames with reuse on and off (rt_set_variant's bit
-10) alternate on one context, every frame between two events on the launch stream as in bench.py.  Then the two frames reuse
-could make slower: the recording frame, and the frames of a camera that moves every frame with reuse on (which must never run
-anything but the normal kernel).
+"""First-hit reuse A/B inside one process (DESIGN.md sections 26 and 27): blocks of C2 frames in three arms -- `settled` (the
+default: reuse with settled tiles), `on` (reuse without them, rt_set_variant's bit 11) and `off` (no reuse, bit 10) -- alternate
+on one context, every frame between two events on the launch stream as in bench.py.  Then the two frames reuse could make
+slower: the recording frame, and the frames of a camera that moves every frame with reuse on (which must never run anything but
+the normal kernel).
 
-  gain        the `on` frames' p90 lies below the `off` frames' p10
+  gain        the `on` frames' p90 lies below the `off` frames' p10; the `settled` frames' p90 below the `on` frames' p10
   regression  the moving camera's median with reuse on, and the recording frames' median, lie within the [min, max] of the same
               moving views rendered with reuse off (the recording frame is also held to the still view's off frames)
 
@@ -17,6 +18,7 @@ from opengl_raytracing_amd import dist as D
 from opengl_raytracing_amd import host, scenes, layout as L
 
 OFF = 0x400
+ARMS = {"settled": 1, "on": 1 | 0x800, "off": 1 | OFF}      # rt_set_variant's argument of each arm
 
 
 def stats(ms):
@@ -59,20 +61,25 @@ def main():
     def counts():
         return rt.debug_first_hit()
 
-    ms = {"on": [], "off": []}
-    modes = {"on": [], "off": []}
+    ms = {name: [] for name in ARMS}
+    modes = {name: [] for name in ARMS}
+    tiles = {name: [] for name in ARMS}
     for b in range(a.blocks):
-        for name in SB.alternating(["on", "off"], b):
-            rt.set_variant(1 | (0 if name == "on" else OFF))
+        for name in SB.alternating(list(ARMS), b):
+            rt.set_variant(ARMS[name])
             for _ in range(a.warmup):
                 render(base)
             torch.cuda.synchronize()
             c0 = counts()
             ms[name] += timed([base] * a.frames)
             modes[name].append([x - y for x, y in zip(counts(), c0)])
-    # the timed `on` frames must all have replayed, the `off` frames all have run the normal kernel
-    assert all(m == [0, 0, a.frames] for m in modes["on"]), modes["on"]
+            tiles[name].append(rt.debug_settled_tiles())
+    # the timed `settled` and `on` frames must all have replayed, the `off` frames all have run the normal kernel; only the
+    # `settled` arm may have found settled tiles, and it must have found some
+    assert all(m == [0, 0, a.frames] for m in modes["settled"] + modes["on"]), modes
     assert all(m == [a.frames, 0, 0] for m in modes["off"]), modes["off"]
+    assert all(t[0] > 0 and t[1] > 0 for t in tiles["settled"]) and all(t[0] > 0 and t[1] == 0 for t in tiles["on"]), tiles
+    assert all(t == [0, 0] for t in tiles["off"]), tiles["off"]
 
     # a camera that moves every frame: the normal kernel only, with reuse on as with reuse off (the control: the same views)
     x0 = base.camPos[0]
@@ -101,9 +108,12 @@ def main():
     dc = [x - y for x, y in zip(counts(), c0)]
     assert dc == [120, 12, 24], dc
 
-    on, off = stats(ms["on"]), stats(ms["off"])
+    on, off, settled = stats(ms["on"]), stats(ms["off"]), stats(ms["settled"])
     mon, moff = stats(moving_ms["on"]), stats(moving_ms["off"])
     rec = {"config": f"C{a.cfg}", "size": [sc.width, sc.height], "blocks_each": a.blocks, "frames_per_block": a.frames, "warmup_per_block": a.warmup,
+           "settled_ms": settled, "settled_tiles_of_window": tiles["settled"][0],
+           "settled_block_medians_ms": [round(float(np.median(ms["settled"][i * a.frames:(i + 1) * a.frames])), 4) for i in range(a.blocks)],
+           "gain_settled_p90_below_on_p10": bool(settled["p90"] < on["p10"]),
            "on_ms": on, "off_ms": off, "on_block_medians_ms": [round(float(np.median(ms["on"][i * a.frames:(i + 1) * a.frames])), 4) for i in range(a.blocks)],
            "off_block_medians_ms": [round(float(np.median(ms["off"][i * a.frames:(i + 1) * a.frames])), 4) for i in range(a.blocks)],
            "moving_camera_reuse_on_ms": mon, "moving_camera_reuse_off_ms": moff,
@@ -116,10 +126,11 @@ def main():
            "note": "off spread = [min, max] of the reuse-off frames; the moving camera and the recording frame are held to the reuse-off "
                    "frames of the same moving views, the recording frame also to those of the still view"}
     SB.write_records(a.out, "tools/bench_first_hit.py", [rec], device=torch.cuda.get_device_name(0))
-    for key in ("on_ms", "off_ms", "moving_camera_reuse_on_ms", "moving_camera_reuse_off_ms", "stop_and_go_normal_frames_before_recording_ms",
+    for key in ("settled_ms", "on_ms", "off_ms", "moving_camera_reuse_on_ms", "moving_camera_reuse_off_ms", "stop_and_go_normal_frames_before_recording_ms",
                 "recording_frame_ms", "replay_after_recording_ms"):
         print(f"{key:46s} {rec[key]}")
-    for key in ("gain_on_p90_below_off_p10", "moving_camera_within_off_spread", "recording_frame_within_off_spread",
+    print(f"{'settled_tiles_of_window':46s} {rec['settled_tiles_of_window']}")
+    for key in ("gain_settled_p90_below_on_p10", "gain_on_p90_below_off_p10", "moving_camera_within_off_spread", "recording_frame_within_off_spread",
                 "recording_frame_within_still_view_off_spread"):
         print(f"{key:46s} {rec[key]}")
     rt.close()
