@@ -16,6 +16,10 @@
 //   * stores: one float4 per lane to gColor/gPosition (8 lanes = one 128-B line), one
 //     8-byte packed half4 (round-toward-zero) to gNormal.
 //
+// The per-lane path tracer (any-hit, PCF, PCSS, SSS, lighting, the bounce loop) is rt_lane.inc's, shared with rt_shade_rays
+// (rt_shade.inc); this file keeps the arithmetic helpers, the exhaustive kernel's LDS accessor and closest-hit loop (LaneLds),
+// its staging, lane -> pixel map, stores and counter reduction.  The packet kernel is rt_packet.inc.
+//
 // Arithmetic is fp32 in the reference's evaluation order (no FMA contraction: built with
 // -ffp-contract=off; IEEE divide/sqrt) so results are comparable bit-for-bit with the CPU
 // restatement in oracle/ wherever no transcendental is involved.
@@ -161,55 +165,6 @@ __device__ __forceinline__ bool shape_test(const Ray &r, float a, const float4 *
     return false;
 }
 
-// intersectObjects (:155-196), closest hit.  Returns the object index or -1; t = minT.
-template <int COUNT>
-__device__ __forceinline__ int trace_closest(const SceneLds &sc, int nObj, const Ray &r, float maxDist,
-                                              float &tOut, unsigned &rays) {
-    if (COUNT) rays++;
-    v3 inv;
-    rtf::rcp3(r.d.x, r.d.y, r.d.z, inv.x, inv.y, inv.z);
-    float a = dot(r.d, r.d);
-    float minT = maxDist;
-    int hit = -1;
-    for (int i = 0; i < nObj; i++) {
-        const float4 *h = sc.hot + i * RT_HOT_F4;
-        float4 h0 = h[0], h1 = h[1];
-        if (aabb_test(r, inv, h0, h1, maxDist)) {
-            float t;
-            if (shape_test(r, a, h, __float_as_int(h0.w), t) && t > 0.0f && t < minT) {
-                minT = t;
-                hit = i;
-            }
-        }
-    }
-    tOut = minT;
-    return hit;
-}
-
-// Any-hit form for shadow / PCSS blocker rays: true iff some object is hit with
-// 0 < t < limit, limit = min(maxRayDistance, lightDistance) for point/area lights and
-// maxRayDistance for directional ones (exactly the reference's closest-hit test, A.1#14).
-// Lanes that found an occluder idle; the loop ends when the whole wave is done.
-template <int COUNT>
-__device__ __forceinline__ bool trace_any(const SceneLds &sc, int nObj, const Ray &r, float maxDist,
-                                           float limit, unsigned &rays) {
-    if (COUNT) rays++;
-    v3 inv;
-    rtf::rcp3(r.d.x, r.d.y, r.d.z, inv.x, inv.y, inv.z);
-    float a = dot(r.d, r.d);
-    bool occ = false;
-    for (int i = 0; i < nObj; i++) {
-        const float4 *h = sc.hot + i * RT_HOT_F4;
-        float4 h0 = h[0], h1 = h[1];
-        if (!occ && aabb_test(r, inv, h0, h1, maxDist)) {
-            float t;
-            if (shape_test(r, a, h, __float_as_int(h0.w), t) && t > 0.0f && t < limit) occ = true;
-        }
-        if (__builtin_amdgcn_ballot_w64(!occ) == 0ull) break;   // whole wavefront occluded
-    }
-    return occ;
-}
-
 // ---- textures --------------------------------------------------------------------------
 // texture(blueNoiseTex, (gid + frameCount) * noiseScale).r : R8, NEAREST, REPEAT (:513, :359)
 __device__ __forceinline__ float sample_noise(const RtFrame &f, const uint8_t *noise, unsigned gx, unsigned gy) {
@@ -281,16 +236,6 @@ struct Mat {
     v3 albedo; float metallic, roughness, diffuseStrength, ior, transparency;
     v3 sssColor; float sss, scatterDistance;
 };
-
-__device__ __forceinline__ Mat load_mat(const SceneLds &sc, int idx) {
-    const float4 *m = sc.mat + idx * RT_MAT_F4;
-    float4 m0 = m[0], m1 = m[1], m2 = m[2], m3 = m[3];
-    Mat r;
-    r.albedo = V3(m0); r.metallic = m0.w;
-    r.roughness = m1.x; r.diffuseStrength = m1.y; r.ior = m1.z; r.transparency = m1.w;
-    r.sssColor = V3(m2); r.sss = m2.w; r.scatterDistance = m3.x;
-    return r;
-}
 
 // fresnelSchlick (:220-223); pow(x,2.0) folds to x*x on the reference's GL (A.3)
 __device__ __forceinline__ float fresnel_schlick(float cosTheta, float ior) {
@@ -383,117 +328,6 @@ __device__ __forceinline__ v3 hemisphere_dir(v3 h, v3 n) {
     return normalize((tangent * h.x + bitangent * h.z) + n * h.y);
 }
 
-__device__ __forceinline__ float halton_lookup(const float *table, int i, int base) {
-    return (i < RT_HALTON_N) ? table[i] : halton_eval(i, base);
-}
-
-// pcfShadow (:342-397)
-template <int COUNT>
-__device__ __forceinline__ float pcf_shadow(const SceneLds &sc, const RtFrame &f, v3 origin, int ltype,
-                                             int pcfSamples, float filterSize, v3 lightDir, float limit,
-                                             float jitterR, unsigned &rays) {
-    float shadow = 0.0f;
-    v3 tangent = normalize(cross(lightDir, V3(0.0f, 1.0f, 0.0f)));
-    v3 bitangent = cross(lightDir, tangent);
-    for (int i = 0; i < pcfSamples; i++) {
-        float rx = fract(halton_lookup(sc.halton2, i, 2) + jitterR);
-        float ry = fract(halton_lookup(sc.halton3, i, 3) + 0.0f);
-        v3 jd = (lightDir + (tangent * rx) * filterSize) + (bitangent * ry) * filterSize;
-        if (ltype != 1) jd = normalize(jd);
-        Ray sr; sr.o = origin; sr.d = jd;
-        bool occ = trace_any<COUNT>(sc, f.nObj, sr, f.p.maxRayDistance, limit, rays);
-        shadow += occ ? 0.0f : 1.0f;
-    }
-    return shadow / (float)pcfSamples;
-}
-
-// pcssShadow (:400-440): 16 blocker-search rays; any blocker -> plain PCF (penumbra size is dead)
-template <int COUNT>
-__device__ __forceinline__ float pcss_shadow(const SceneLds &sc, const RtFrame &f, v3 origin, int ltype,
-                                              int pcfSamples, float filterSize, float searchSize, v3 lightDir,
-                                              float limit, float jitterR, unsigned &rays) {
-    bool any = false;
-    for (int i = 0; i < 16; i++) {
-        float rr = sc.halton3[i] * 2.0f - 1.0f;
-        v3 sd = (lightDir + splat(rr * searchSize)) + splat(rr * searchSize);
-        Ray sr; sr.o = origin; sr.d = normalize(sd);
-        any |= trace_any<COUNT>(sc, f.nObj, sr, f.p.maxRayDistance, limit, rays);
-    }
-    if (!any) return 1.0f;
-    return pcf_shadow<COUNT>(sc, f, origin, ltype, pcfSamples, filterSize, lightDir, limit, jitterR, rays);
-}
-
-// computeSubsurfaceScattering (:316-339)
-template <int COUNT>
-__device__ v3 compute_sss(const SceneLds &sc, const RtFrame &f, v3 P, v3 N, const Mat &m, unsigned &rays) {
-    v3 sss = V3(0.0f, 0.0f, 0.0f);
-    for (int i = 0; i < 4; i++) {
-        Ray r;
-        r.o = P + N * 0.001f;
-        r.d = hemisphere_dir(V3(f.sssHemi[i][0], f.sssHemi[i][1], f.sssHemi[i][2]), N);
-        float t;
-        int idx = trace_closest<COUNT>(sc, f.nObj, r, f.p.maxRayDistance, t, rays);
-        if (idx >= 0) {
-            float att = det_expf(-t / m.scatterDistance);
-            sss = sss + V3(sc.mat[idx * RT_MAT_F4]) * att;
-        }
-    }
-    return ((sss * m.sssColor) * m.sss) / 4.0f;
-}
-
-// computeLighting (:457-507)
-template <int COUNT>
-__device__ __forceinline__ v3 compute_lighting(const SceneLds &sc, const RtFrame &f, v3 P, v3 N, const Mat &m,
-                                                v3 V, float jitterR, unsigned &rays) {
-    v3 Lo = V3(0.0f, 0.0f, 0.0f);
-    v3 shadowOrigin = P + N * 0.001f;     // :381, :412
-    for (int i = 0; i < f.nLt; i++) {
-        const float4 *lr = sc.lgt + i * RT_LGT_F4;
-        float4 l0 = lr[0], l1 = lr[1], l2 = lr[2], l3 = lr[3];
-        int ltype = __float_as_int(l0.w);
-        v3 lightDir = V3(0.0f, 0.0f, 0.0f);
-        float attenuation = 1.0f, lightDistance = 0.0f;
-        if (ltype == 0) {
-            lightDir = V3(l0) - P;
-            lightDistance = length(lightDir);
-            attenuation = rtf::rcp(1.0f + 0.1f * lightDistance + 0.01f * lightDistance * lightDistance);
-            lightDir = normalize(lightDir);
-        } else if (ltype == 1) {
-            lightDir = V3(l1);             // normalize(-direction), folded by the scene compiler
-            lightDistance = 1e6f;
-        } else if (ltype == 2) {
-            lightDir = V3(l0) - P;
-            // lightDistance*lightDistance = sqrt(q)*sqrt(q) folds to |q| on the reference's GL
-            float q = dot(lightDir, lightDir);
-            lightDistance = length(lightDir);
-            lightDir = normalize(lightDir);
-            attenuation = rtf::rcp(fabsf(q));
-            float lc = fmaxf(dot(lightDir, V3(l1)), 0.0f);   // l1 = normalize(direction)
-            attenuation *= lc;
-        }
-        int shadowType = __float_as_int(l3.x), pcfSamples = __float_as_int(l3.y);
-        float shadowFactor = 1.0f;
-        if (shadowType != 0) {
-            // any-hit limit: closest t < lightDistance for point/area lights (:390-392, :421-423)
-            float limit = (ltype == 1) ? f.p.maxRayDistance : fminf(f.p.maxRayDistance, lightDistance);
-            // NaN lightDistance: the reference's `t < NaN` is false -> never occluded
-            if (ltype != 1 && !(lightDistance == lightDistance)) limit = -1.0f;
-            if (shadowType == 1)
-                shadowFactor = pcf_shadow<COUNT>(sc, f, shadowOrigin, ltype, pcfSamples, l2.w, lightDir, limit, jitterR, rays);
-            else if (shadowType == 2)
-                shadowFactor = pcss_shadow<COUNT>(sc, f, shadowOrigin, ltype, pcfSamples, l2.w, l3.z, lightDir, limit, jitterR, rays);
-            else
-                shadowFactor = 0.0f;       // calculateShadow's `float shadow = 0.0` fall-through (:445)
-        }
-        v3 L = normalize(lightDir);
-        v3 H = normalize(V + L);
-        v3 radiance = (V3(l2) * attenuation) * l1.w;
-        Lo = Lo + compute_pbr(m, N, V, L, H, radiance) * shadowFactor;
-    }
-    if (m.sss > 0.0f) Lo = Lo + compute_sss<COUNT>(sc, f, P, N, m, rays);
-    return Lo;
-}
-
 // calculateRefraction (:256-270)
 __device__ __forceinline__ v3 calc_refraction(const Ray &r, v3 N, float ior) {
     bool entering = dot(r.d, N) < 0.0f;
@@ -510,6 +344,7 @@ __device__ __forceinline__ float random2(float sx, float sy) {
     return fract(det_sinf(d) * 43758.5453123f);
 }
 
+#include "rt_lane.inc"
 #include "rt_shadowtab.inc"
 #include "rt_packet.inc"
 
@@ -592,8 +427,46 @@ __global__ void rt_compile_scene_kernel(const uint8_t *objects, int nObj, const 
 }
 
 // =========================================================================================
-// Render kernel: main() of raytracingCs.glsl (:509-584), one lane per pixel.
+// Render kernel: main() of raytracingCs.glsl (:509-584), one lane per pixel (rt_lane.inc) on the scene in LDS.
 // =========================================================================================
+// rt_lane.inc's accessor over the workgroup's LDS copy of the compiled scene: wave-uniform records by broadcast ds_read_b128.
+struct LaneLds {
+    SceneLds v;
+    int nObj, nLt;
+    static constexpr bool fastPbr = false;
+    __device__ __forceinline__ const float4 *rec(int i) const { return v.hot + i * RT_HOT_F4; }
+    __device__ __forceinline__ float4 light(int i, int k) const { return (v.lgt + i * RT_LGT_F4)[k]; }
+    __device__ __forceinline__ float halton(int which, int i, int base) const {
+        return (i < RT_HALTON_N) ? (which ? v.halton3 : v.halton2)[i] : halton_eval(i, base);
+    }
+    __device__ __forceinline__ const float4 *lane_hot(int idx) const { return v.hot + idx * RT_HOT_F4; }
+    __device__ __forceinline__ const float4 *lane_mat(int idx) const { return v.mat + idx * RT_MAT_F4; }
+    __device__ __forceinline__ bool shape(const Ray &r, float a, const float4 *h, float4 h0, float4, float &t) const {
+        return shape_test(r, a, h, __float_as_int(h0.w), t);
+    }
+    // intersectObjects (:155-196), closest hit: every object, the lowest index wins ties (strict <)
+    __device__ __forceinline__ int closest(const Ray &r, float maxDist, float &tOut) const {
+        v3 inv;
+        rtf::rcp3(r.d.x, r.d.y, r.d.z, inv.x, inv.y, inv.z);
+        float a = dot(r.d, r.d);
+        float minT = maxDist;
+        int hit = -1;
+        for (int i = 0; i < nObj; i++) {
+            const float4 *h = rec(i);
+            const float4 h0 = h[0], h1 = h[1];
+            if (aabb_test(r, inv, h0, h1, maxDist)) {
+                float t;
+                if (shape_test(r, a, h, __float_as_int(h0.w), t) && t > 0.0f && t < minT) {
+                    minT = t;
+                    hit = i;
+                }
+            }
+        }
+        tOut = minT;
+        return hit;
+    }
+};
+
 #ifndef RT_V0_WAVES
 #define RT_V0_WAVES 0
 #endif
@@ -613,12 +486,14 @@ __global__ RT_V0_BOUNDS void rt_render_kernel(const RtFrame f, const RtDeviceSce
     const int nF4 = f.nObj * (RT_HOT_F4 + RT_MAT_F4) + f.nLt * RT_LGT_F4 + 2 * (RT_HALTON_N / 4);
     for (int i = threadIdx.x; i < nF4; i += BLOCK_THREADS) lds[i] = dsc.compiled[i];
     __syncthreads();
-    SceneLds sc;
-    sc.hot = lds;
-    sc.mat = sc.hot + f.nObj * RT_HOT_F4;
-    sc.lgt = sc.mat + f.nObj * RT_MAT_F4;
-    sc.halton2 = (const float *)(sc.lgt + f.nLt * RT_LGT_F4);
-    sc.halton3 = sc.halton2 + RT_HALTON_N;
+    LaneLds sc;
+    sc.nObj = f.nObj;
+    sc.nLt = f.nLt;
+    sc.v.hot = lds;
+    sc.v.mat = sc.v.hot + f.nObj * RT_HOT_F4;
+    sc.v.lgt = sc.v.mat + f.nObj * RT_MAT_F4;
+    sc.v.halton2 = (const float *)(sc.v.lgt + f.nLt * RT_LGT_F4);
+    sc.v.halton3 = sc.v.halton2 + RT_HALTON_N;
 
     // ---- lane -> pixel: wave w owns the 8x8 tile (w&1, w>>1) of the 16x16 workgroup tile
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -639,77 +514,11 @@ __global__ RT_V0_BOUNDS void rt_render_kernel(const RtFrame f, const RtDeviceSce
     } else {
     const unsigned gx = (unsigned)gxI, gy = (unsigned)gyI;
 
-    // jitter (:512-514): .x from the R8 sample, .y of an R8 texture is 0 -> -1 (A.1#3)
     const float nz = sample_noise(f, dsc.noise, gx, gy);
-    const float jx = nz * 2.0f - 1.0f, jy = 0.0f * 2.0f - 1.0f;
+    const LanePath out = lane_path<COUNT>(sc, f, dsc.sky, camera_ray(f, nz, gxI, gyI), f.p.maxRayDistance, gx, gy, nz, rays);
+    const v3 P = out.P, N = out.N;
 
-    // generateCameraRay (:198-217)
-    Ray ray;
-    {
-        float ux = (((float)gxI + 0.5f) + jx) / (float)f.p.width;
-        float uy = (((float)gyI + 0.5f) + jy) / (float)f.p.height;
-        ux = ux * 2.0f - 1.0f;
-        uy = uy * 2.0f - 1.0f;
-        ux *= f.sx;
-        uy *= f.sy;
-        v3 cd = V3(f.p.camDir[0], f.p.camDir[1], f.p.camDir[2]);
-        v3 cr = V3(f.p.camRight[0], f.p.camRight[1], f.p.camRight[2]);
-        v3 cu = V3(f.p.camUp[0], f.p.camUp[1], f.p.camUp[2]);
-        ray.o = V3(f.p.camPos[0], f.p.camPos[1], f.p.camPos[2]);
-        ray.d = normalize((cd + cr * ux) + cu * uy);
-    }
-
-    v3 finalColor = V3(0.0f, 0.0f, 0.0f), throughput = V3(1.0f, 1.0f, 1.0f);
-    v3 P = V3(0.0f, 0.0f, 0.0f), N = V3(0.0f, 0.0f, 0.0f);   // undefined locals read as zero (A.3)
-
-    for (int depth = 0; depth < f.p.maxRayDepth; ++depth) {
-        float t;
-        int idx = trace_closest<COUNT>(sc, f.nObj, ray, f.p.maxRayDistance, t, rays);
-        if (idx < 0) {
-            if (f.p.useSkybox && dsc.sky) finalColor = finalColor + throughput * sample_cube(dsc.sky, f.skySize, ray.d);
-            // else `finalColor += throughput * vec3(0.0)` (:532): x*0.0 folds to 0.0 on the reference's
-            // GL, so a NaN/inf throughput does not poison the colour on a miss (nan fixture).
-            break;
-        }
-        // hit normal (:187-191): sphere = normalize(hit - centre); plane = raw normal
-        {
-            const float4 *h = sc.hot + idx * RT_HOT_F4;
-            if (__float_as_int(h[0].w) == 0) N = normalize((ray.o + ray.d * t) - V3(h[2]));
-            else N = V3(h[3]);
-        }
-        const Mat m = load_mat(sc, idx);
-        P = ray.o + ray.d * t;
-        v3 V = normalize(-ray.d);
-        v3 Lo = compute_lighting<COUNT>(sc, f, P, N, m, V, nz, rays);
-        finalColor = finalColor + throughput * Lo;
-
-        if (depth > 2) {   // Russian roulette (:544-549)
-            float dw = length(m.albedo) * m.diffuseStrength;
-            float cp = fminf(fmaxf(throughput.x, fmaxf(throughput.y, throughput.z)) * 0.95f + dw, 0.99f);
-            float rnd = random2((float)(gx + (unsigned)depth), (float)(gy + (unsigned)depth));
-            if (rnd > cp) break;
-            throughput = div3(throughput, cp);
-        }
-        float F = fresnel_schlick(fmaxf(dot(V, N), 0.0f), m.ior);
-        if (m.diffuseStrength > 0.0f) {          // :555-567
-            const int dd = depth < RT_MAX_DEPTH ? depth : RT_MAX_DEPTH - 1;
-            v3 sd = reflect(ray.d, N);
-            v3 hd = hemisphere_dir(V3(f.hemi[dd][0], f.hemi[dd][1], f.hemi[dd][2]), N);
-            ray.d = normalize(mix_fast(sd, hd, m.roughness));
-            ray.o = P + N * 0.001f;
-            throughput = throughput * (m.albedo * m.diffuseStrength);
-        } else if (m.transparency > 0.0f) {      // :568-571
-            ray.d = calc_refraction(ray, N, m.ior);
-            ray.o = P - N * 0.001f;
-            throughput = throughput * ((m.albedo * (1.0f - F)) * m.transparency);
-        } else {                                  // :572-576
-            ray.d = reflect(ray.d, N);
-            ray.o = P + N * 0.001f;
-            throughput = throughput * (m.albedo * F);
-        }
-    }
-
-    gColor[outIdx] = make_float4(finalColor.x, finalColor.y, finalColor.z, 1.0f);
+    gColor[outIdx] = make_float4(out.color.x, out.color.y, out.color.z, 1.0f);
     gPosition[outIdx] = make_float4(P.x, P.y, P.z, 1.0f);
     gNormal[outIdx] = make_uint2(f2h_rtz(N.x) | (f2h_rtz(N.y) << 16), f2h_rtz(N.z) | (0x3c00u << 16));
 

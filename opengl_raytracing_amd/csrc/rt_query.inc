@@ -1,8 +1,8 @@
 // rt_query.inc -- ray queries on the compiled scene (rt_trace_rays, rt_camera_rays, rt_pick; include/rt_mi355.h).
 // #included at the end of rt_kernels.hip: it reuses the render kernels' helpers (aabb_test, shape_test, rtf::rcp3,
-// normalize, sample_noise, the scalar-load types of rt_packet.inc) without moving them, so a query is the same fp32
-// expression tree as the frame's intersectObjects (raytracingCs.glsl:155-196) and generateCameraRay (:198-217).
-// Design and measurements: DESIGN.md "Ray queries".
+// sample_noise, rt_lane.inc's camera_ray, the scalar-load types of rt_packet.inc), so a query is the same fp32 expression
+// tree as the frame's intersectObjects (raytracingCs.glsl:155-196) and generateCameraRay (:198-217).  q_hot, q_shape and
+// q_trace<false> are also rt_shade.inc's record fetch and closest-hit loop.  Design and measurements: DESIGN.md "Ray queries".
 
 // One object's hot record, read through a wave-uniform address in the constant address space: s_load_dwordx4 into
 // SGPRs, so the bounds and shape operands reach the VALU as scalar operands (no per-lane loads, no LDS staging,
@@ -12,8 +12,18 @@ __device__ __forceinline__ float4 q_hot(const float4 *hot, int f4Index) {
     return make_float4(v.x, v.y, v.z, v.w);
 }
 
+// shape_test of the object whose hot record starts at float4 b and whose h0, h1 the caller holds, operands from SGPRs
+__device__ __forceinline__ bool q_shape(const float4 *hot, int b, const Ray &r, float a, float4 h0, float4 h1, float &t) {
+    if (__float_as_int(h0.w) == 0) {
+        const float4 hs[3] = {h0, h1, q_hot(hot, b + 2)};
+        return shape_test(r, a, hs, 0, t);
+    }
+    const float4 hs[6] = {h0, h1, q_hot(hot, b + 2), q_hot(hot, b + 3), q_hot(hot, b + 4), q_hot(hot, b + 5)};
+    return shape_test(r, a, hs, __float_as_int(h0.w), t);
+}
+
 // intersectObjects (:155-196) with maxRayDistance := tMax.  ANY: stop at the first object with 0 < t < tMax and leave the
-// loop once no lane of the wave is unresolved (trace_any); closest: every object, the lowest index wins ties (strict <).
+// loop once no lane of the wave is unresolved (as lane_any); closest: every object, the lowest index wins ties (strict <).
 // Returns the hit index or -1 (ANY: 0 / -1); t = minT.
 template <bool ANY>
 __device__ __forceinline__ int q_trace(const float4 *hot, int nObj, const Ray &r, float tMax, bool live, float &tOut) {
@@ -27,16 +37,7 @@ __device__ __forceinline__ int q_trace(const float4 *hot, int nObj, const Ray &r
         const float4 h0 = q_hot(hot, b), h1 = q_hot(hot, b + 1);
         if ((!ANY || hit < 0) && aabb_test(r, inv, h0, h1, tMax)) {
             float t;
-            bool ok;
-            if (__float_as_int(h0.w) == 0) {      // shape_test's sphere, operands from SGPRs
-                const float4 s1 = h1, s2 = q_hot(hot, b + 2);
-                const float4 hs[3] = {h0, s1, s2};
-                ok = shape_test(r, a, hs, 0, t);
-            } else {
-                const float4 hs[6] = {h0, h1, q_hot(hot, b + 2), q_hot(hot, b + 3), q_hot(hot, b + 4), q_hot(hot, b + 5)};
-                ok = shape_test(r, a, hs, __float_as_int(h0.w), t);
-            }
-            if (ok && t > 0.0f && t < minT) {
+            if (q_shape(hot, b, r, a, h0, h1, t) && t > 0.0f && t < minT) {
                 minT = ANY ? minT : t;
                 hit = ANY ? 0 : i;
             }
@@ -61,23 +62,9 @@ __device__ __forceinline__ void q_hit_record(const float4 *hot, const Ray &r, in
     w1 = make_float4(N.x, N.y, N.z, __int_as_float(idx));
 }
 
-// generateCameraRay (:198-217) of image pixel (gxI, gyI), exactly as rt_render_kernel / the packet kernel compute it.
+// generateCameraRay (:198-217) of image pixel (gxI, gyI): rt_render_kernel's (rt_lane.inc) on the pixel's noise sample
 __device__ __forceinline__ Ray q_camera_ray(const RtFrame &f, const uint8_t *noise, int gxI, int gyI) {
-    const float nz = sample_noise(f, noise, (unsigned)gxI, (unsigned)gyI);
-    const float jx = nz * 2.0f - 1.0f, jy = 0.0f * 2.0f - 1.0f;
-    float ux = (((float)gxI + 0.5f) + jx) / (float)f.p.width;
-    float uy = (((float)gyI + 0.5f) + jy) / (float)f.p.height;
-    ux = ux * 2.0f - 1.0f;
-    uy = uy * 2.0f - 1.0f;
-    ux *= f.sx;
-    uy *= f.sy;
-    const v3 cd = V3(f.p.camDir[0], f.p.camDir[1], f.p.camDir[2]);
-    const v3 cr = V3(f.p.camRight[0], f.p.camRight[1], f.p.camRight[2]);
-    const v3 cu = V3(f.p.camUp[0], f.p.camUp[1], f.p.camUp[2]);
-    Ray ray;
-    ray.o = V3(f.p.camPos[0], f.p.camPos[1], f.p.camPos[2]);
-    ray.d = normalize((cd + cr * ux) + cu * uy);
-    return ray;
+    return camera_ray(f, sample_noise(f, noise, (unsigned)gxI, (unsigned)gyI), gxI, gyI);
 }
 
 #define RT_Q_BLOCK 256

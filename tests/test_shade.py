@@ -424,3 +424,82 @@ def test_set_scene_during_a_large_shade_leaves_it_unchanged(tracer, host):
         after = tracer.shade_rays(p, tracer.camera_rays(p, stream=s), stream=s)
     s.synchronize()
     assert_surfaces_equal([_np(t) for t in after], render_surfaces(tracer, p), "shade after rt_set_scene sees the new scene")
+
+
+# ---- 8. every branch of the per-lane path tracer, through both of its scene accessors at once ------------------------
+def branch_scene(host, directional_pcf_samples):
+    """Six objects (diffuse floor, diffuse / mirror / glass / subsurface spheres, a mirror wall) under a point light with 70
+    PCF samples (past the Halton tables' 64 entries), a directional PCF light, a PCSS area light and a light of shadowType 3
+    (calculateShadow's fall-through: always shadowed); noise texture and skybox bound."""
+    o = L.default_objects(6)
+    o["diffuseStrength"] = 0.0
+    o[0]["type"] = L.PLANE
+    o[0]["position"], o[0]["normal"], o[0]["size"] = (0.0, -1.0, -4.0), (0.0, 1.0, 0.0), (40.0, 40.0)
+    o[0]["albedo"], o[0]["roughness"], o[0]["diffuseStrength"] = (0.8, 0.7, 0.6), 0.6, 0.5
+    o[1]["position"], o[1]["radius"] = (-3.0, 0.5, -3.0), 1.2                                    # diffuse
+    o[1]["albedo"], o[1]["roughness"], o[1]["diffuseStrength"] = (0.9, 0.3, 0.2), 0.8, 0.8
+    o[2]["position"], o[2]["radius"] = (0.0, 1.0, -5.0), 1.5                                     # mirror
+    o[2]["albedo"], o[2]["metallic"], o[2]["roughness"] = (0.9, 0.9, 0.95), 1.0, 0.05
+    o[3]["position"], o[3]["radius"] = (3.0, 0.5, -2.0), 1.2                                     # glass
+    o[3]["albedo"], o[3]["roughness"], o[3]["ior"], o[3]["transparency"] = (0.9, 1.0, 0.9), 0.05, 1.5, 0.95
+    o[4]["position"], o[4]["radius"] = (-0.5, 0.0, 0.5), 0.9                                     # subsurface
+    o[4]["albedo"], o[4]["diffuseStrength"] = (0.8, 0.6, 0.5), 0.6
+    o[4]["subsurfaceScatter"], o[4]["subsurfaceColor"], o[4]["scatterDistance"] = 0.5, (1.0, 0.6, 0.5), 0.8
+    o[5]["type"] = L.PLANE
+    o[5]["position"], o[5]["normal"], o[5]["size"] = (-4.0, 1.5, -9.0), (0.0, 0.0, 1.0), (6.0, 5.0)
+    o[5]["albedo"], o[5]["roughness"] = (0.7, 0.75, 0.8), 0.4
+    host.generate_aabb(o)
+    lt = L.default_lights(4)
+    lt[0]["type"], lt[0]["position"], lt[0]["intensity"] = L.POINT, (0.0, 6.0, -3.0), 8.0
+    lt[0]["shadowType"], lt[0]["pcfSamples"] = L.SHADOW_PCF, 70
+    lt[1]["type"], lt[1]["direction"], lt[1]["intensity"] = L.DIRECTIONAL, (0.5, -1.0, -0.5), 3.0
+    lt[1]["shadowType"], lt[1]["pcfSamples"] = L.SHADOW_PCF, directional_pcf_samples
+    lt[2]["type"], lt[2]["position"], lt[2]["direction"], lt[2]["intensity"] = L.AREA, (3.0, 8.0, -6.0), (0.0, 1.0, 0.0), 40.0
+    lt[2]["shadowType"], lt[2]["pcfSamples"] = L.SHADOW_PCSS, 4
+    lt[3]["type"], lt[3]["position"], lt[3]["intensity"] = L.POINT, (-4.0, 5.0, 2.0), 4.0
+    lt[3]["shadowType"] = 3
+    return scenes.Scene(f"branches-pcf{directional_pcf_samples}", o, lt, 48, 32, 6, dict(scenes.CAMERA), frame_count=5,
+                        noise=scenes.hash_noise(64, 32, seed=8), skybox=scenes.procedural_skybox(32), use_skybox=True)
+
+
+def branch_params(sc, depth):
+    p = sc.params(max_ray_depth=depth)
+    p.noiseScale[0], p.noiseScale[1] = 1.0 / 64.0, 1.0 / 32.0
+    return p
+
+
+@pytest.mark.parametrize("directional_pcf_samples", [0, 3])
+def test_every_branch_through_both_accessors(host, oracle, directional_pcf_samples):
+    """One 48x32 frame at depth 6: exhaustive render == rt_shade_rays(rt_camera_rays) == packet render == oracle, bit for
+    bit on colour, position and normal.  The exhaustive kernel and rt_shade_rays run the same per-lane tracer
+    (csrc/rt_lane.inc) over the LDS and the scalar-load accessor.
+    pcfSamples 0 on the directional light makes pcfShadow return 0/0, so every hit pixel's colour is NaN at every depth
+    (774 of the 1536 pixels in the oracle's frame) and no colour can differ between two depths: that frame shows the deeper
+    bounces by the positions that differ instead (21 pixels), and the same scene with 3 samples on that light carries the
+    colour check (54 pixels differ between depth 3 and 6)."""
+    import torch
+    sc = branch_scene(host, directional_pcf_samples)
+    p = branch_params(sc, 6)
+    want = oracle.render(sc, p)[:3]
+    shallow = oracle.render(sc, branch_params(sc, 3))[:3]
+    # the oracle's frame alone: not empty, not flat, and bounces past the third matter
+    hit = (want[1][..., :3] != 0).any(-1)
+    assert hit.any() and (~hit).any(), "the frame needs both hit and miss pixels"
+    assert len(np.unique(want[0][..., :3].reshape(-1, 3).view(np.uint32), axis=0)) >= 100, "fewer than 100 distinct colours"
+    differs = lambda a, b: (~((a == b) | (np.isnan(a) & np.isnan(b)))).any(-1)
+    if directional_pcf_samples == 0:
+        assert np.isnan(want[0][hit][:, :3]).all() and not np.isnan(want[0][~hit]).any(), "0/0 shadow factor: NaN on every hit"
+        assert differs(want[1], shallow[1]).any(), "no pixel's position differs between maxRayDepth 3 and 6"
+    else:
+        assert not np.isnan(want[0]).any()
+        assert differs(want[0], shallow[0]).any(), "no pixel's colour differs between maxRayDepth 3 and 6"
+    rt = host.RayTracer(0)
+    try:
+        rt.load(sc)
+        for variant, name in ((0, "exhaustive render"), (1, "packet render")):
+            rt.set_variant(variant)
+            assert_surfaces_equal(render_surfaces(rt, p), want, f"{sc.name}: {name} vs the oracle")
+            assert_surfaces_equal(shade_camera(rt, p), want, f"{sc.name}: rt_shade_rays(rt_camera_rays) vs the oracle")
+        torch.cuda.synchronize()
+    finally:
+        rt.close()
