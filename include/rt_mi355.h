@@ -639,6 +639,75 @@ int rt_display_pack_yuv(rt_context *ctx, const void *dImage, void *dOut, const r
 int rt_present_submit_yuv(rt_context *ctx, const void *dImage, const rt_yuv_desc *desc, const rt_tone_desc *tone, void *hipStream,
                           uint64_t *ticket);
 
+/* ---- baseline JPEG output: the YUV pack's planes compressed on the device into a JFIF file any decoder opens (the chip has no
+ *      encode block).  Every byte below is normative: tests/jpeg_oracle.py restates it in numpy and the device is
+ *      compared with it bit for bit.
+ *      Input: the planes of rt_display_pack_yuv (NV12 or I420, found through rt_display_yuv_layout).  Plane row 0 is the file's
+ *        top row: pack with RT_DISPLAY_FLIP_ROWS for an upright file.  JFIF means full-range BT.601 with centre-sited 4:2:0, which
+ *        is what the pack writes for matrix = RT_YUV_BT601, range = RT_YUV_FULL.
+ *      Geometry: 1 <= width, height <= 65535; 4:2:0; MCU = 16x16 luma, mw = (width+15)/16, mh = (height+15)/16, MCUs in raster order,
+ *        blocks in an MCU Y00 Y01 Y10 Y11 Cb Cr; samples outside a plane replicate its edge (coordinates clamped to width-1 /
+ *        height-1, and to cw-1 / ch-1 in chroma).
+ *      Forward DCT, in int32: M[u][x] = rne(16384 * a(u) * cos((2x+1) u pi / 16)), a(0) = 1/(2 sqrt 2), a(u>0) = 1/2, built in double
+ *        on the host (rt_jpeg_dct_matrix, out[u*8+x]).  With f = sample - 128:
+ *          r[y][u] = (sum_x M[u][x] * f[y][x] + 1024) >> 11        F[v][u] = (sum_y M[v][y] * r[y][u] + 65536) >> 17
+ *        (>> arithmetic).  |AC| <= 1020 and -1024 <= DC <= 1016 over the sign patterns of the 64 basis functions.
+ *      Quantiser: Annex K.1 (luma) / K.2 (chroma) scaled the IJG way, s = quality < 50 ? 5000/quality : 200 - 2*quality,
+ *        Q = clamp((base*s + 50) / 100, 1, 255) (rt_jpeg_quant, natural order);  q = sign(F) * ((|F| + (Q >> 1)) / Q).
+ *      Entropy coding: baseline Huffman, the typical tables K.3 / K.5 (luma) and K.4 / K.6 (chroma).  DC: the difference to the
+ *        previous block of the same component (category 0..11); AC: (run, size) symbols, ZRL 0xF0 for runs above 15, EOB 0x00 when
+ *        zeros trail; magnitude bits v for v >= 0, else v + 2^size - 1; bits MSB first.  A restart segment is restartInterval
+ *        consecutive MCUs (the last may be shorter): the three DC predictors start at 0, the last partial byte is padded with
+ *        1-bits, every 0xFF data byte (a padded one included) is followed by 0x00, and behind every segment but the last comes
+ *        FF D0+(segment & 7).
+ *      Header, 629 bytes: SOI; APP0 JFIF 1.01, units 0, density 1x1, no thumbnail; DQT 0; DQT 1 (own segments, 8-bit, zigzag);
+ *        SOF0 (8, height, width, (1, 0x22, 0), (2, 0x11, 1), (3, 0x11, 1)); DHT DC0, AC0, DC1, AC1; DRI (always); SOS ((1, 0x00),
+ *        (2, 0x11), (3, 0x11), 0, 63, 0).  The stream ends with EOI.  rt_jpeg_header writes the header into buf (cap >= 629).
+ *      rt_jpeg_layout: the scratch of one encode.  offset[0]: the quantised coefficients, int16, zigzag order, 64 per block, 6 blocks
+ *        per MCU, MCU order.  offset[1]: uint32[nSegments + 1], the byte offset of every segment within the entropy-coded data (its
+ *        RST marker counted with it), the last entry their sum.  offset[2]: private -- two uint32 per segment, then room for
+ *        the YUV planes of rt_display_pack_jpeg, so ONE layout serves both entry points.  Both documented planes are complete
+ *        when the encode is, overflow or not.  worstBytes = 629 + nMcu*2488 + 2*(nSegments-1) + 2 (a block is at most 20 + 63*26
+ *        bits, stuffing doubles it); RT_ERR_TOO_LARGE above 2^32 - 1.
+ *      rt_jpeg_encode: dPlanes -> dOut, asynchronous on hipStream (NULL = the context's), no host synchronisation.  Of `planes`
+ *        width, height and format are read.  dState receives one rt_jpeg_state.  When needed > capBytes: overflow = 1, bytes = 0,
+ *        needed still exact, and nothing in dOut is written.  All pointers 16-byte aligned; planes, scratch, output (capBytes) and
+ *        state must not overlap.
+ *      rt_display_pack_jpeg: rt_display_pack_yuv into the scratch's private region, then rt_jpeg_encode; refused unless matrix is
+ *        RT_YUV_BT601 and range RT_YUV_FULL.  rt_present_submit_jpeg: the same through the present ring, one ring and one ticket
+ *        sequence with every other submit; the slot holds [64-byte rt_jpeg_state][stream], capBytes = 0 means worstBytes, the
+ *        scratch is the context's; rt_present_wait returns the slot (64 + capBytes bytes), the stream is `bytes` long behind
+ *        the state.
+ *      Refused with RT_ERR_INVALID_ARG: NULL context, descriptions, pointers or ticket; misaligned or overlapping ranges; width or
+ *      height outside 1..65535; quality outside 1..100; restartInterval outside 1..65535; non-zero reserved words; planes of
+ *      another size or an unknown format; rt_display_pack_yuv's refusals.  rt_jpeg_dct_matrix, rt_jpeg_quant, rt_jpeg_header and
+ *      rt_jpeg_layout need no GPU. */
+typedef struct rt_jpeg_desc {
+    int32_t width, height;           /* 1..65535 */
+    int32_t quality;                 /* 1..100 */
+    int32_t restartInterval;         /* MCUs per restart segment, 1..65535 */
+    int32_t reserved[4];             /* zero */
+} rt_jpeg_desc;
+typedef struct rt_jpeg_state {
+    uint32_t bytes;                  /* the stream's length in dOut; 0 on overflow */
+    uint32_t needed;                 /* the stream's length, whether it fitted or not */
+    uint32_t overflow;               /* 1: needed > capBytes, dOut untouched */
+    uint32_t nSegments, nMcu;
+    uint32_t headerBytes;            /* 629 */
+    uint32_t stuffedBytes;           /* 0x00 bytes inserted behind 0xFF */
+    uint32_t reserved[9];            /* zero */
+} rt_jpeg_state;
+int rt_jpeg_dct_matrix(int32_t out[64]);
+int rt_jpeg_quant(int quality, uint8_t luma[64], uint8_t chroma[64]);
+int rt_jpeg_header(const rt_jpeg_desc *desc, uint8_t *buf, size_t cap, size_t *n);
+int rt_jpeg_layout(const rt_jpeg_desc *desc, size_t offset[3], size_t *scratchBytes, size_t *worstBytes);
+int rt_jpeg_encode(rt_context *ctx, const void *dPlanes, const rt_yuv_desc *planes, const rt_jpeg_desc *desc, void *dScratch, void *dOut,
+                   size_t capBytes, void *dState, void *hipStream);
+int rt_display_pack_jpeg(rt_context *ctx, const void *dImage, const rt_yuv_desc *yuv, const rt_tone_desc *tone, const rt_jpeg_desc *desc,
+                         void *dScratch, void *dOut, size_t capBytes, void *dState, void *hipStream);
+int rt_present_submit_jpeg(rt_context *ctx, const void *dImage, const rt_yuv_desc *yuv, const rt_tone_desc *tone, const rt_jpeg_desc *desc,
+                           size_t capBytes, void *hipStream, uint64_t *ticket);
+
 /* ---- resampling in linear light, in front of rt_meter / rt_display_pack* / rt_present_submit*: render at one size, deliver
  *      another (4K -> 1080p is 4x supersampling; a fraction of the output size scaled up keeps a heavy scene at display rate).
  *      rt_display_resample: dSrc (device, srcWidth*srcHeight rgba32f) -> dDst (device, dstWidth*dstHeight rgba32f), any ratio,
@@ -1060,6 +1129,9 @@ RT_SA(sizeof(rt_meter_state) == 1088 && offsetof(rt_meter_state, nPixels) == 102
 RT_SA(sizeof(rt_tone_desc) == 16 + 2 * sizeof(void *) && offsetof(rt_tone_desc, dExposure) == 8, "rt_tone_desc layout");
 RT_SA(sizeof(rt_yuv_desc) == 48 && offsetof(rt_yuv_desc, transfer) == 20 && offsetof(rt_yuv_desc, flags) == 24 &&
       offsetof(rt_yuv_desc, exposure) == 28 && offsetof(rt_yuv_desc, reserved) == 32, "rt_yuv_desc is 48 B");
+RT_SA(sizeof(rt_jpeg_desc) == 32 && offsetof(rt_jpeg_desc, restartInterval) == 12 && offsetof(rt_jpeg_desc, reserved) == 16, "rt_jpeg_desc is 32 B");
+RT_SA(sizeof(rt_jpeg_state) == 64 && offsetof(rt_jpeg_state, overflow) == 8 && offsetof(rt_jpeg_state, stuffedBytes) == 24 &&
+      offsetof(rt_jpeg_state, reserved) == 28, "rt_jpeg_state is 64 B");
 RT_SA(sizeof(rt_resample_desc) == 32 && offsetof(rt_resample_desc, filter) == 16 && offsetof(rt_resample_desc, flags) == 20 &&
       offsetof(rt_resample_desc, reserved) == 24, "rt_resample_desc is 32 B");
 RT_SA(sizeof(rt_accum_desc) == 40 && offsetof(rt_accum_desc, relError) == 8 && offsetof(rt_accum_desc, minSamples) == 16 &&

@@ -227,6 +227,7 @@ int rt_destroy(rt_context *c) {
     (void)c->bloomUse.drain();         // post passes on caller streams: the scratch they work in goes with the context
     (void)c->ssaoUse.drain();
     (void)c->resample.drain();         // the last launch that read the resampler's tables
+    (void)c->jpegUse.drain();          // the last JPEG submit in the context's scratch
     (void)c->present.drain();          // frames on their way to the pinned buffers (and, before them, their packs)
     delete c;
     return RT_OK;

@@ -1,4 +1,4 @@
-// rt_args.h -- the argument checks the image stages' entry points share (rt_display.cpp, rt_accum.cpp, rt_denoise.cpp,
+// rt_args.h -- the argument checks the image stages' entry points share (rt_display.cpp, rt_jpeg.cpp, rt_accum.cpp, rt_denoise.cpp,
 // rt_resample.cpp): pointers, overlapping device ranges, the pixel limit, reserved words.  One definition each; an entry point
 // keeps its own order of checks.  Not part of the public ABI.
 #pragma once

@@ -1,5 +1,5 @@
 // rt_context.h -- what the files that implement context entry points share (rt_abi.cpp, and with rt_args.h's checks on top of it
-// rt_display.cpp, rt_resample.cpp, rt_accum.cpp, rt_denoise.cpp): the context itself, the way an entry point reports a failure, and the
+// rt_display.cpp, rt_jpeg.cpp, rt_resample.cpp, rt_accum.cpp, rt_denoise.cpp): the context itself, the way an entry point reports a failure, and the
 // stream it works on.  Nothing else knows the context's layout (rt_mgpu.cpp drives contexts through the public ABI).  Not part of the public ABI.
 #pragma once
 #include <string>
@@ -70,6 +70,8 @@ struct rt_context {
     PinnedBuf<rt_hit> hPick;
     PresentRing present;                       // rt_present_*: the frames on their way to the host (rt_present.h)
     ResampleTables resample;                   // rt_display_resample: the device copies of the two axis tables (rt_resample.h)
+    DevBuf<uint8_t> dJpegScratch;              // rt_present_submit_jpeg: rt_jpeg_layout's scratch (YUV planes included) ...
+    ScratchUse jpegUse;                        // ... and who ran last in it, on whichever stream
     std::string err;
 };
 

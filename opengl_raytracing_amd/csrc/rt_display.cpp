@@ -130,6 +130,22 @@ int validate_meter_desc(rt_context *c, const rt_meter_desc *d) {
 
 }  // namespace
 
+int rt_yuv_pack_validate(rt_context *c, const void *dImage, const rt_yuv_desc *d, const rt_tone_desc *tone, RtYuvPack *out) {
+    YuvArgs a;
+    RT_TRY(validate_yuv(c, dImage, d, tone, &a));
+    out->tone = a.tone.op;
+    out->invW2 = a.tone.invW2;
+    out->dExposure = a.tone.dExposure;
+    memcpy(out->coef, a.coef, sizeof a.coef);
+    out->bytes = a.bytes;
+    return RT_OK;
+}
+
+hipError_t rt_yuv_pack_launch(const void *dImage, void *dOut, const rt_yuv_desc *d, const RtYuvPack &p, hipStream_t s) {
+    return rt_launch_display_pack_yuv(dImage, dOut, d->width, d->height, d->format == RT_YUV_I420, d->transfer == RT_DISPLAY_RGBA8_SRGB,
+                                      (d->flags & RT_DISPLAY_FLIP_ROWS) != 0, d->exposure, p.tone, p.invW2, p.dExposure, p.coef, s);
+}
+
 extern "C" {
 
 // ---- RGBA8 packing

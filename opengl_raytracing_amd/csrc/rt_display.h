@@ -3,6 +3,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "rt_mi355.h"
+
 // rgba32f -> RGBA8; `out` rows tightly packed, both pointers 16-byte aligned, W * H below 2^32 quads of 4 pixels
 hipError_t rt_launch_display_pack(const void *image, void *out, int W, int H, int srgb, int flip, float exposure, hipStream_t s);
 const float *rt_display_thresholds();      // the 256 sRGB decision thresholds ([0] = 0), built on the host on first use
@@ -21,3 +23,15 @@ hipError_t rt_launch_meter(const void *image, void *state, unsigned nPixels, flo
                            int lowPermille, int highPermille, hipStream_t s);
 struct RtMeterTables;
 const RtMeterTables &rt_meter_tables_ref();     // the solve's two tables (rt_meter.h), built on the host on first use
+// A validated YUV pack, for an entry point that runs one in front of something else (rt_jpeg.cpp): rt_display_pack_yuv's checks
+// of everything but the output pointer, then its launch.  `bytes` is the frame's size (rt_display_yuv_layout).
+struct rt_context;
+struct RtYuvPack {
+    int tone = 0;
+    float invW2 = 0.0f;
+    const void *dExposure = nullptr;
+    int32_t coef[12] = {};
+    size_t bytes = 0;
+};
+int rt_yuv_pack_validate(rt_context *c, const void *dImage, const rt_yuv_desc *d, const rt_tone_desc *tone, RtYuvPack *out);
+hipError_t rt_yuv_pack_launch(const void *dImage, void *dOut, const rt_yuv_desc *d, const RtYuvPack &p, hipStream_t s);

@@ -47,6 +47,7 @@ EXPORTS = [
     "rt_denoise_guide", "rt_denoise_layout", "rt_denoise",
     "rt_reproject_layout", "rt_reproject_project", "rt_accum_reproject",
     "rt_accum_select_layout", "rt_accum_select", "rt_camera_rays_at", "rt_accum_add_at",
+    "rt_jpeg_dct_matrix", "rt_jpeg_quant", "rt_jpeg_header", "rt_jpeg_layout", "rt_jpeg_encode", "rt_display_pack_jpeg", "rt_present_submit_jpeg",
 ]
 
 
@@ -199,6 +200,13 @@ def load_library(build_if_missing=True):
     lib.rt_accum_select.argtypes = [vp, vp, P(L.RtAccumDesc), ctypes.c_uint32, vp, ctypes.c_size_t, vp, vp, vp]
     lib.rt_camera_rays_at.argtypes = [vp, P(L.RtParams), vp, ctypes.c_size_t, vp, vp]
     lib.rt_accum_add_at.argtypes = [vp, vp, vp, ctypes.c_size_t, vp, P(L.RtAccumDesc), vp, vp]
+    lib.rt_jpeg_dct_matrix.argtypes = [P(ctypes.c_int32)]
+    lib.rt_jpeg_quant.argtypes = [ci, P(ctypes.c_uint8), P(ctypes.c_uint8)]
+    lib.rt_jpeg_header.argtypes = [P(L.RtJpegDesc), P(ctypes.c_uint8), ctypes.c_size_t, P(ctypes.c_size_t)]
+    lib.rt_jpeg_layout.argtypes = [P(L.RtJpegDesc), P(ctypes.c_size_t), P(ctypes.c_size_t), P(ctypes.c_size_t)]
+    lib.rt_jpeg_encode.argtypes = [vp, vp, P(L.RtYuvDesc), P(L.RtJpegDesc), vp, vp, ctypes.c_size_t, vp, vp]
+    lib.rt_display_pack_jpeg.argtypes = [vp, vp, P(L.RtYuvDesc), P(L.RtToneDesc), P(L.RtJpegDesc), vp, vp, ctypes.c_size_t, vp, vp]
+    lib.rt_present_submit_jpeg.argtypes = [vp, vp, P(L.RtYuvDesc), P(L.RtToneDesc), P(L.RtJpegDesc), ctypes.c_size_t, vp, P(ctypes.c_uint64)]
     for name in EXPORTS:
         if name not in ("rt_last_error", "rt_mgpu_last_error", "rt_wire_bytes"):
             getattr(lib, name).restype = ci
@@ -391,6 +399,51 @@ def yuv_planes(frame, width, height, format="nv12"):
     return y, frame[lay.offset[1]: lay.offset[2]].reshape(ch, cw), frame[lay.offset[2]:].reshape(ch, cw)
 
 
+JpegLayout = collections.namedtuple("JpegLayout", "offset scratch_bytes worst_bytes n_mcu n_segments")
+JpegLayout.__doc__ = """rt_jpeg_layout's answer: byte offsets of the coefficient plane (int16 [n_mcu * 6, 64], zigzag), of the segment offsets
+(uint32 [n_segments + 1]) and of the private region within the scratch, the scratch's size and the largest stream the frame can make."""
+
+
+def jpeg_dct_matrix():
+    """M[u, x] of the encoder's integer DCT (rt_jpeg_dct_matrix): int32 [8, 8].  Needs no GPU."""
+    out = np.zeros(64, dtype=np.int32)
+    rc = load_library().rt_jpeg_dct_matrix(out.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)))
+    if rc:
+        raise RtError(rc, "rt_jpeg_dct_matrix")
+    return out.reshape(8, 8)
+
+
+def jpeg_quant(quality):
+    """The two quantisers of `quality` (rt_jpeg_quant) -> (luma uint8 [64], chroma uint8 [64]), natural order.  Needs no GPU."""
+    luma, chroma = np.zeros(64, dtype=np.uint8), np.zeros(64, dtype=np.uint8)
+    u8 = ctypes.POINTER(ctypes.c_uint8)
+    rc = load_library().rt_jpeg_quant(int(quality), luma.ctypes.data_as(u8), chroma.ctypes.data_as(u8))
+    if rc:
+        raise RtError(rc, "rt_jpeg_quant")
+    return luma, chroma
+
+
+def jpeg_header(width, height, quality=90, restart_interval=None):
+    """The 629 bytes in front of the entropy-coded data (rt_jpeg_header) -> uint8 [629].  Needs no GPU."""
+    d = L.make_jpeg_desc(width, height, quality, restart_interval)
+    out, n = np.zeros(L.JPEG_HEADER_BYTES, dtype=np.uint8), ctypes.c_size_t(0)
+    rc = load_library().rt_jpeg_header(ctypes.byref(d), out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), out.size, ctypes.byref(n))
+    if rc:
+        raise RtError(rc, "rt_jpeg_header")
+    return out[:n.value]
+
+
+def jpeg_layout(width, height, quality=90, restart_interval=None):
+    """The scratch of one encode (rt_jpeg_layout) -> JpegLayout.  Needs no GPU."""
+    d = L.make_jpeg_desc(width, height, quality, restart_interval)
+    off, scratch, worst = (ctypes.c_size_t * 3)(), ctypes.c_size_t(0), ctypes.c_size_t(0)
+    rc = load_library().rt_jpeg_layout(ctypes.byref(d), off, ctypes.byref(scratch), ctypes.byref(worst))
+    if rc:
+        raise RtError(rc, "rt_jpeg_layout")
+    n_mcu = ((d.width + 15) // 16) * ((d.height + 15) // 16)
+    return JpegLayout(tuple(off), scratch.value, worst.value, n_mcu, (n_mcu + d.restartInterval - 1) // d.restartInterval)
+
+
 def resample_taps(src, dst, filter="lanczos3"):
     """The tap table of one axis of rt_display_resample, source size `src` -> destination size `dst` (rt_resample_taps):
     (n, first int32[dst], weights float32[dst, n]) -- destination index i reads source pixels clamp(first[i] + k, 0, src - 1),
@@ -511,7 +564,7 @@ def _query_mode(mode):
 
 
 # ---- the device context ---------------------------------------------------------------------
-# what the Python side remembers of a present_submit* ticket: "rgba8" or "yuv", the frame's size, the description's format
+# what the Python side remembers of a present_submit* ticket: "rgba8", "yuv" or "jpeg", the frame's size, the description's format
 _PresentTicket = collections.namedtuple("_PresentTicket", "kind width height format")
 
 
@@ -1004,6 +1057,8 @@ class RayTracer:
         rec = self._present_tickets.get(int(ticket))
         if rec is not None and rec.kind == "yuv":
             raise ValueError(f"ticket {int(ticket)} is a YUV frame (present_submit_yuv): wait for it with present_wait_yuv")
+        if rec is not None and rec.kind == "jpeg":
+            raise ValueError(f"ticket {int(ticket)} is a JPEG stream (present_submit_jpeg): wait for it with present_wait_jpeg")
         view = self._present_pinned(ticket, copy)
         rec = self._present_tickets[int(ticket)]
         assert view.size == rec.height * rec.width * 4
@@ -1054,12 +1109,69 @@ class RayTracer:
         """Block until the YUV frame of `ticket` is in host memory -> (y[H, W], uv[ch, cw, 2]) for NV12, (y[H, W], cb[ch, cw],
         cr[ch, cw]) for I420, uint8.  copy=False returns read-only views of the ring's pinned slot (present_wait's rules)."""
         rec = self._present_tickets.get(int(ticket))
+        if rec is not None and rec.kind == "jpeg":
+            raise ValueError(f"ticket {int(ticket)} is a JPEG stream (present_submit_jpeg), not a YUV frame: wait for it with present_wait_jpeg")
         if rec is None or rec.kind != "yuv":
             raise ValueError(f"ticket {int(ticket)} is not a live YUV frame of present_submit_yuv (RGBA8 tickets: present_wait)")
         frame = self._present_pinned(ticket, copy)
         if frame.size != yuv_layout(rec.width, rec.height, rec.format).bytes:
             raise RtError(-1, f"ticket {int(ticket)} holds {frame.size} bytes, not a {rec.width}x{rec.height} YUV frame")
         return yuv_planes(frame, rec.width, rec.height, rec.format)
+
+    # ---- baseline JPEG output: the file a viewer, a browser or a disk takes ------------------------
+    def jpeg_layout(self, width, height, quality=90, restart_interval=None):
+        """host.jpeg_layout: the scratch jpeg_encode and display_pack_jpeg work in."""
+        return jpeg_layout(width, height, quality, restart_interval)
+
+    def jpeg_encode(self, d_planes, d_scratch, d_out, cap_bytes, d_state, width, height, format="nv12", quality=90, restart_interval=None,
+                    stream=None):
+        """NV12 / I420 planes of display_pack_yuv (row 0 = the file's top row) -> a baseline JPEG stream in d_out, at most cap_bytes
+        long, and one layout.JPEG_STATE_DTYPE record in d_state (rt_jpeg_encode).  d_scratch holds jpeg_layout(...).scratch_bytes.
+        Raw device pointers or CUDA tensors, 16-byte aligned, not overlapping.  Asynchronous on torch stream `stream`."""
+        yd = L.make_yuv_desc(width, height, format, "bt601", "full")
+        jd = L.make_jpeg_desc(width, height, quality, restart_interval)
+        self._on_torch_stream(stream, lambda h: self._check(self.lib.rt_jpeg_encode(
+            self.ctx, _dev_ptr(d_planes), ctypes.byref(yd), ctypes.byref(jd), _dev_ptr(d_scratch), _dev_ptr(d_out), int(cap_bytes),
+            _dev_ptr(d_state), ctypes.c_void_p(h)), "rt_jpeg_encode"))
+
+    def display_pack_jpeg(self, d_image, d_scratch, d_out, cap_bytes, d_state, width, height, format="nv12", quality=90, restart_interval=None,
+                          transfer="srgb", flip=True, exposure=1.0, tone=None, white=1.0, d_exposure=None, stream=None):
+        """rgba32f surface -> JPEG stream on the device (rt_display_pack_jpeg): display_pack_yuv (full-range BT.601, planes in
+        `format`) into the scratch, then jpeg_encode.  flip=True (the default here) makes the file upright."""
+        yd = L.make_yuv_desc(width, height, format, "bt601", "full", transfer, flip, exposure)
+        jd = L.make_jpeg_desc(width, height, quality, restart_interval)
+        td = None if tone is None and d_exposure is None else L.make_tone_desc(tone or "none", white, d_exposure)
+        self._on_torch_stream(stream, lambda h: self._check(self.lib.rt_display_pack_jpeg(
+            self.ctx, _dev_ptr(d_image), ctypes.byref(yd), ctypes.byref(td) if td is not None else None, ctypes.byref(jd), _dev_ptr(d_scratch),
+            _dev_ptr(d_out), int(cap_bytes), _dev_ptr(d_state), ctypes.c_void_p(h)), "rt_display_pack_jpeg"))
+
+    def present_submit_jpeg(self, d_image, width, height, cap_bytes=0, format="nv12", quality=90, restart_interval=None, transfer="srgb",
+                            flip=True, exposure=1.0, tone=None, white=1.0, d_exposure=None, stream=None):
+        """present_submit with display_pack_jpeg's stream: same ring, same ticket sequence; the slot holds the state record and up
+        to cap_bytes of stream (0: the frame's worst case).  Wait for the ticket with present_wait_jpeg."""
+        yd = L.make_yuv_desc(width, height, format, "bt601", "full", transfer, flip, exposure)
+        jd = L.make_jpeg_desc(width, height, quality, restart_interval)
+        td = None if tone is None and d_exposure is None else L.make_tone_desc(tone or "none", white, d_exposure)
+        t = ctypes.c_uint64()
+        self._on_torch_stream(stream, lambda h: self._check(self.lib.rt_present_submit_jpeg(
+            self.ctx, _dev_ptr(d_image), ctypes.byref(yd), ctypes.byref(td) if td is not None else None, ctypes.byref(jd), int(cap_bytes),
+            ctypes.c_void_p(h), ctypes.byref(t)), "rt_present_submit_jpeg"))
+        self._present_issued(t.value, "jpeg", width, height, yd.format)
+        return t.value
+
+    def present_wait_jpeg(self, ticket, copy=True):
+        """Block until the JPEG stream of `ticket` is in host memory -> uint8 [bytes], the whole file.  Raises RtError when the
+        stream did not fit the submit's cap_bytes (the message says how many bytes it needed).  copy=False returns a read-only
+        view of the ring's pinned slot (present_wait's rules)."""
+        rec = self._present_tickets.get(int(ticket))
+        if rec is None or rec.kind != "jpeg":
+            raise ValueError(f"ticket {int(ticket)} is not a live JPEG stream of present_submit_jpeg")
+        slot = self._present_pinned(ticket, False)
+        state = slot[:L.JPEG_STATE_BYTES].view(L.JPEG_STATE_DTYPE)[0]
+        if state["overflow"]:
+            raise RtError(-4, f"ticket {int(ticket)}: the stream needed {int(state['needed'])} bytes, the slot held {slot.size - L.JPEG_STATE_BYTES}")
+        stream = slot[L.JPEG_STATE_BYTES: L.JPEG_STATE_BYTES + int(state["bytes"])]
+        return stream.copy() if copy else stream
 
     def tile_costs(self):
         """(costs[tilesY, tilesX] uint32, cycles/64 per tile) of the last feedback-scheduled launch."""

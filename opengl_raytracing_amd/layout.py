@@ -302,6 +302,35 @@ def make_yuv_desc(width, height, format="nv12", matrix="bt709", range="limited",
     return d
 
 
+# ---- baseline JPEG output (rt_jpeg_encode / rt_display_pack_jpeg / rt_present_submit_jpeg, include/rt_mi355.h) --
+JPEG_HEADER_BYTES = 629
+JPEG_STATE_BYTES = 64
+JPEG_DEFAULT_INTERVAL = 8
+
+
+class RtJpegDesc(ctypes.Structure):
+    """``rt_jpeg_desc``: size of the frame, quality 1..100, MCUs per restart segment."""
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("quality", ctypes.c_int32), ("restartInterval", ctypes.c_int32),
+                ("reserved", ctypes.c_int32 * 4)]
+
+
+assert ctypes.sizeof(RtJpegDesc) == 32
+
+# ``rt_jpeg_state``: what an encode leaves on the device, sixteen uint32
+JPEG_STATE_DTYPE = np.dtype([("bytes", "<u4"), ("needed", "<u4"), ("overflow", "<u4"), ("nSegments", "<u4"), ("nMcu", "<u4"),
+                             ("headerBytes", "<u4"), ("stuffedBytes", "<u4"), ("reserved", "<u4", (9,))])
+assert JPEG_STATE_DTYPE.itemsize == JPEG_STATE_BYTES
+
+
+def make_jpeg_desc(width, height, quality=90, restart_interval=None):
+    """restart_interval None: JPEG_DEFAULT_INTERVAL MCUs -- segments are what the entropy coder runs in parallel, one wave each, and
+    eight MCUs keep a 1080p frame at a thousand waves for 2 bytes of marker, three predictors and a padded byte per segment."""
+    d = RtJpegDesc()
+    d.width, d.height, d.quality = int(width), int(height), int(quality)
+    d.restartInterval = int(restart_interval) if restart_interval is not None else JPEG_DEFAULT_INTERVAL
+    return d
+
+
 # ---- resampling in front of the display path (rt_display_resample / rt_resample_taps, include/rt_mi355.h) --
 RESAMPLE_AREA, RESAMPLE_TRIANGLE, RESAMPLE_LANCZOS3 = 0, 1, 2
 RESAMPLE_MAX_TAPS = 64

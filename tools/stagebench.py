@@ -1,5 +1,5 @@
-"""The measurement procedure of the stage benchmarks (tools/bench_accum.py, bench_denoise.py, bench_meter.py, bench_present.py,
-bench_reproject.py, bench_resample.py, bench_yuv.py), defined once.  Every speed figure those tools record rests on it:
+"""The measurement procedure of the stage benchmarks (tools/bench_accum.py, bench_denoise.py, bench_jpeg.py, bench_meter.py,
+bench_present.py, bench_reproject.py, bench_resample.py, bench_yuv.py), defined once. Every speed figure those tools record rests on it:
 
   device figures  one event pair on the side stream around K back-to-back launches, behind 40 copies between two 256 MiB blockers
                   that keep the stream busy until the whole batch is queued; microseconds per call;
