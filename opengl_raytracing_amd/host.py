@@ -29,28 +29,6 @@ from . import layout as L
 
 _LIB = None
 
-EXPORTS = [
-    "rt_create", "rt_destroy", "rt_set_scene", "rt_set_noise", "rt_set_skybox", "rt_render",
-    "rt_render_to", "rt_sync", "rt_readback", "rt_get_surfaces", "rt_last_kernel_ms",
-    "rt_count_rays", "rt_count_rays_traced", "rt_debug_stats", "rt_debug_stats_ex", "rt_debug_first_hit", "rt_debug_settled_tiles", "rt_debug_settled_map", "rt_debug_tile_costs", "rt_set_variant", "rt_last_error", "rt_generate_aabb", "rt_camera_vectors",
-    "rt_scene_parse", "rt_scene_write", "rt_taa_resolve", "rt_taa_jitter", "rt_bloom", "rt_ssao", "rt_ssao_blur",
-    "rt_camera_matrices", "rt_equirect_to_cubemap", "rt_frame", "rt_frame_surfaces", "rt_strip_local_rows", "rt_deinterleave",
-    "rt_wire_bytes", "rt_wire_pack", "rt_wire_unpack", "rt_debug_mesa_math", "rt_debug_shadow_tables", "rt_debug_predicted_classes",
-    "rt_render_into_image", "rt_context_stream", "rt_mgpu_create", "rt_mgpu_destroy", "rt_mgpu_device_count", "rt_mgpu_set_scene", "rt_mgpu_set_noise",
-    "rt_mgpu_set_skybox", "rt_mgpu_set_strip_rows", "rt_mgpu_render", "rt_mgpu_sync", "rt_mgpu_get_surfaces", "rt_mgpu_readback", "rt_mgpu_last_ms",
-    "rt_mgpu_last_error", "rt_trace_rays", "rt_camera_rays", "rt_pick", "rt_shade_rays", "rt_debug_device_math",
-    "rt_display_pack", "rt_display_srgb_thresholds", "rt_present_configure", "rt_present_submit", "rt_present_poll", "rt_present_wait",
-    "rt_meter", "rt_meter_solve_host", "rt_meter_tables", "rt_display_pack_toned", "rt_present_submit_toned",
-    "rt_display_yuv_coeffs", "rt_display_yuv_layout", "rt_display_pack_yuv", "rt_present_submit_yuv",
-    "rt_resample_taps", "rt_display_resample",
-    "rt_accum_layout", "rt_accum_reset", "rt_accum_add", "rt_accum_solve_host", "rt_accum_view",
-    "rt_denoise_guide", "rt_denoise_layout", "rt_denoise",
-    "rt_reproject_layout", "rt_reproject_project", "rt_accum_reproject",
-    "rt_accum_select_layout", "rt_accum_select", "rt_camera_rays_at", "rt_accum_add_at",
-    "rt_jpeg_dct_matrix", "rt_jpeg_quant", "rt_jpeg_header", "rt_jpeg_layout", "rt_jpeg_encode", "rt_display_pack_jpeg", "rt_present_submit_jpeg",
-]
-
-
 
 class RtFrameDesc(ctypes.Structure):
     """``rt_frame_desc`` of include/rt_mi355.h."""
@@ -73,6 +51,123 @@ class RtError(RuntimeError):
         super().__init__(f"{STATUS_NAMES.get(code, code)}: {msg}")
 
 
+def _signatures():
+    """Every entry point of include/rt_mi355.h, in the header's order: name -> (restype, argtypes).  The one place a prototype is
+    written down on this side; tests/test_binding_host.py holds it to the header."""
+    P = ctypes.POINTER
+    vp, ci, cf, sz, cs = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t, ctypes.c_char_p
+    u8, u32, i32, u64 = ctypes.c_uint8, ctypes.c_uint32, ctypes.c_int32, ctypes.c_uint64
+    params, tone, yuv, jpeg, accum = P(L.RtParams), P(L.RtToneDesc), P(L.RtYuvDesc), P(L.RtJpegDesc), P(L.RtAccumDesc)
+    display = P(L.RtDisplayDesc)
+    return {
+        "rt_create": (ci, [P(vp), ci]),
+        "rt_destroy": (ci, [vp]),
+        "rt_set_scene": (ci, [vp, vp, ci, vp, ci]),
+        "rt_set_noise": (ci, [vp, vp, ci, ci]),
+        "rt_set_skybox": (ci, [vp, vp, ci]),
+        "rt_render": (ci, [vp, params]),
+        "rt_render_to": (ci, [vp, params, vp, vp, vp, vp]),
+        "rt_render_into_image": (ci, [vp, params, vp, vp, vp, vp]),
+        "rt_context_stream": (ci, [vp, P(vp)]),
+        "rt_sync": (ci, [vp]),
+        "rt_readback": (ci, [vp, vp, vp, vp]),
+        "rt_get_surfaces": (ci, [vp, P(vp), P(vp), P(vp)]),
+        "rt_last_kernel_ms": (ci, [vp, P(cf)]),
+        "rt_count_rays": (ci, [vp, params, P(u64)]),
+        "rt_count_rays_traced": (ci, [vp, params, P(u64)]),
+        "rt_set_variant": (ci, [vp, ci]),
+        "rt_debug_first_hit": (ci, [vp, P(u64)]),
+        "rt_debug_settled_tiles": (ci, [vp, P(u64)]),
+        "rt_debug_settled_map": (ci, [vp, P(u8), sz]),
+        "rt_debug_stats": (ci, [vp, P(u64)]),
+        "rt_debug_stats_ex": (ci, [vp, P(u64)]),
+        "rt_debug_tile_costs": (ci, [vp, P(u32), ci, P(ci), P(ci)]),
+        "rt_debug_predicted_classes": (ci, [vp, vp, ci, P(ci)]),
+        "rt_debug_shadow_tables": (ci, [vp, vp, sz, P(sz), P(ci)]),
+        "rt_debug_mesa_math": (ci, [vp, vp, ci]),
+        "rt_debug_device_math": (ci, [vp, ci, vp, vp, sz, vp]),
+        "rt_trace_rays": (ci, [vp, vp, sz, ci, vp, vp]),
+        "rt_camera_rays": (ci, [vp, params, vp, vp]),
+        "rt_pick": (ci, [vp, params, ci, ci, P(L.RtHit)]),
+        "rt_shade_rays": (ci, [vp, params, vp, vp, sz, vp, vp, vp, vp]),
+        "rt_last_error": (cs, [vp]),
+        "rt_generate_aabb": (ci, [vp, ci]),
+        "rt_camera_vectors": (ci, [cf, cf, P(cf), P(cf), P(cf)]),
+        "rt_scene_parse": (ci, [cs, vp, ci, P(ci), vp, ci, P(ci)]),
+        "rt_scene_write": (ci, [vp, ci, vp, ci, vp, vp, cs, sz, P(sz)]),
+        "rt_taa_resolve": (ci, [vp, vp, vp, vp, vp, ci, ci, cf, cf, cf, vp]),
+        "rt_taa_jitter": (ci, [ci, ci, ci, P(cf), P(cf)]),
+        "rt_bloom": (ci, [vp, vp, vp, ci, ci, cf, cf, ci, vp]),
+        "rt_ssao": (ci, [vp, vp, vp, vp, ci, ci, P(cf), ci, ci, P(cf), P(cf), P(cf), vp]),
+        "rt_ssao_blur": (ci, [vp, vp, vp, ci, ci, ci, vp]),
+        "rt_camera_matrices": (ci, [P(cf), P(cf), P(cf), cf, cf, P(cf), P(cf)]),
+        "rt_equirect_to_cubemap": (ci, [vp, P(cf), ci, ci, ci, vp, ci]),
+        "rt_frame": (ci, [vp, params, P(RtFrameDesc), vp]),
+        "rt_frame_surfaces": (ci, [vp, P(vp), P(vp), P(vp), P(vp), P(vp)]),
+        "rt_display_pack": (ci, [vp, vp, vp, display, vp]),
+        "rt_display_srgb_thresholds": (ci, [P(cf)]),
+        "rt_present_configure": (ci, [vp, ci]),
+        "rt_present_submit": (ci, [vp, vp, display, vp, P(u64)]),
+        "rt_present_poll": (ci, [vp, u64, P(ci)]),
+        "rt_present_wait": (ci, [vp, u64, P(vp), P(sz)]),
+        "rt_meter": (ci, [vp, vp, P(L.RtMeterDesc), vp, vp]),
+        "rt_meter_solve_host": (ci, [vp, P(L.RtMeterDesc), vp]),
+        "rt_meter_tables": (ci, [P(cf), P(u32)]),
+        "rt_display_pack_toned": (ci, [vp, vp, vp, display, tone, vp]),
+        "rt_present_submit_toned": (ci, [vp, vp, display, tone, vp, P(u64)]),
+        "rt_display_yuv_coeffs": (ci, [ci, ci, P(i32)]),
+        "rt_display_yuv_layout": (ci, [yuv, P(sz), P(sz), P(sz)]),
+        "rt_display_pack_yuv": (ci, [vp, vp, vp, yuv, tone, vp]),
+        "rt_present_submit_yuv": (ci, [vp, vp, yuv, tone, vp, P(u64)]),
+        "rt_jpeg_dct_matrix": (ci, [P(i32)]),
+        "rt_jpeg_quant": (ci, [ci, P(u8), P(u8)]),
+        "rt_jpeg_header": (ci, [jpeg, P(u8), sz, P(sz)]),
+        "rt_jpeg_layout": (ci, [jpeg, P(sz), P(sz), P(sz)]),
+        "rt_jpeg_encode": (ci, [vp, vp, yuv, jpeg, vp, vp, sz, vp, vp]),
+        "rt_display_pack_jpeg": (ci, [vp, vp, yuv, tone, jpeg, vp, vp, sz, vp, vp]),
+        "rt_present_submit_jpeg": (ci, [vp, vp, yuv, tone, jpeg, sz, vp, P(u64)]),
+        "rt_resample_taps": (ci, [ci, ci, ci, P(ci), P(i32), P(cf), sz]),
+        "rt_display_resample": (ci, [vp, vp, vp, P(L.RtResampleDesc), vp]),
+        "rt_accum_layout": (ci, [ci, ci, P(sz), P(sz)]),
+        "rt_accum_reset": (ci, [vp, vp, vp, ci, ci, vp]),
+        "rt_accum_add": (ci, [vp, vp, vp, accum, vp, vp]),
+        "rt_accum_solve_host": (ci, [vp, accum, vp]),
+        "rt_accum_view": (ci, [vp, vp, vp, accum, ci, vp]),
+        "rt_denoise_guide": (ci, [vp, vp, vp, ci, ci, vp]),
+        "rt_denoise_layout": (ci, [ci, ci, P(sz), P(sz)]),
+        "rt_denoise": (ci, [vp, vp, vp, vp, vp, vp, P(L.RtDenoiseDesc), vp]),
+        "rt_reproject_layout": (ci, [ci, ci, P(sz), P(sz)]),
+        "rt_reproject_project": (ci, [params, P(cf), P(cf), P(ci)]),
+        "rt_accum_reproject": (ci, [vp, vp, vp, vp, vp, P(L.RtReprojectDesc), vp, vp]),
+        "rt_accum_select_layout": (ci, [ci, ci, P(sz)]),
+        "rt_accum_select": (ci, [vp, vp, accum, u32, vp, sz, vp, vp, vp]),
+        "rt_camera_rays_at": (ci, [vp, params, vp, sz, vp, vp]),
+        "rt_accum_add_at": (ci, [vp, vp, vp, sz, vp, accum, vp, vp]),
+        "rt_strip_local_rows": (ci, [ci, ci, ci, ci]),
+        "rt_deinterleave": (ci, [vp, vp, vp, ci, ci, ci, ci, ci, sz, vp]),
+        "rt_wire_bytes": (sz, [sz]),
+        "rt_wire_pack": (ci, [vp, vp, vp, vp, vp, sz, vp]),
+        "rt_wire_unpack": (ci, [vp, vp, sz, sz, vp, vp, vp, ci, vp, vp, vp, ci, ci, ci, ci, vp]),
+        "rt_mgpu_create": (ci, [P(vp), P(ci), ci]),
+        "rt_mgpu_destroy": (ci, [vp]),
+        "rt_mgpu_device_count": (ci, [vp]),
+        "rt_mgpu_set_scene": (ci, [vp, vp, ci, vp, ci]),
+        "rt_mgpu_set_noise": (ci, [vp, vp, ci, ci]),
+        "rt_mgpu_set_skybox": (ci, [vp, vp, ci]),
+        "rt_mgpu_set_strip_rows": (ci, [vp, ci]),
+        "rt_mgpu_render": (ci, [vp, params]),
+        "rt_mgpu_sync": (ci, [vp]),
+        "rt_mgpu_get_surfaces": (ci, [vp, P(vp), P(vp), P(vp), P(vp)]),
+        "rt_mgpu_readback": (ci, [vp, vp, vp, vp]),
+        "rt_mgpu_last_ms": (ci, [vp, P(cf), ci]),
+        "rt_mgpu_last_error": (cs, [vp]),
+    }
+
+
+SIGNATURES = _signatures()
+EXPORTS = list(SIGNATURES)
+
+
 def load_library(build_if_missing=True):
     """dlopen the in-tree librt_mi355.so (building it first if asked and absent)."""
     global _LIB
@@ -84,156 +179,78 @@ def load_library(build_if_missing=True):
             raise RtError(-2, f"{path} not built (run python -m opengl_raytracing_amd.build)")
         _build.build_library()
     lib = ctypes.CDLL(path)
-    if "RT_LIB" in os.environ:          # an experiment build (tools/gpu_try.py) may predate newer entry points: bind what it has
-        class _Lenient:
-            def __init__(self, real):
-                object.__setattr__(self, "_real", real)
-
-            def __getattr__(self, name):
-                try:
-                    return getattr(self._real, name)
-                except AttributeError:
-                    class _Missing:
-                        argtypes = restype = None
-
-                        def __call__(self, *a):
-                            raise RtError(-2, f"{name} is not exported by {path}")
-                    return _Missing()
-        lib = _Lenient(lib)
-    vp, ci = ctypes.c_void_p, ctypes.c_int
-    P = ctypes.POINTER
-    lib.rt_create.argtypes = [P(vp), ci]
-    lib.rt_destroy.argtypes = [vp]
-    lib.rt_set_scene.argtypes = [vp, vp, ci, vp, ci]
-    lib.rt_set_noise.argtypes = [vp, vp, ci, ci]
-    lib.rt_set_skybox.argtypes = [vp, vp, ci]
-    lib.rt_render.argtypes = [vp, P(L.RtParams)]
-    lib.rt_render_to.argtypes = [vp, P(L.RtParams), vp, vp, vp, vp]
-    lib.rt_sync.argtypes = [vp]
-    lib.rt_readback.argtypes = [vp, vp, vp, vp]
-    lib.rt_get_surfaces.argtypes = [vp, P(vp), P(vp), P(vp)]
-    lib.rt_last_kernel_ms.argtypes = [vp, P(ctypes.c_float)]
-    lib.rt_count_rays.argtypes = [vp, P(L.RtParams), P(ctypes.c_uint64)]
-    lib.rt_count_rays_traced.argtypes = [vp, P(L.RtParams), P(ctypes.c_uint64)]
-    lib.rt_set_variant.argtypes = [vp, ci]
-    lib.rt_debug_stats.argtypes = [vp, P(ctypes.c_uint64)]
-    lib.rt_debug_stats_ex.argtypes = [vp, P(ctypes.c_uint64)]
-    lib.rt_debug_first_hit.argtypes = [vp, P(ctypes.c_uint64)]
-    lib.rt_debug_settled_tiles.argtypes = [vp, P(ctypes.c_uint64)]
-    lib.rt_debug_settled_map.argtypes = [vp, P(ctypes.c_uint8), ctypes.c_size_t]
-    lib.rt_debug_tile_costs.argtypes = [vp, P(ctypes.c_uint32), ci, P(ci), P(ci)]
-    lib.rt_last_error.argtypes = [vp]
-    lib.rt_last_error.restype = ctypes.c_char_p
-    lib.rt_generate_aabb.argtypes = [vp, ci]
-    lib.rt_camera_vectors.argtypes = [ctypes.c_float, ctypes.c_float, P(ctypes.c_float), P(ctypes.c_float), P(ctypes.c_float)]
-    lib.rt_scene_parse.argtypes = [ctypes.c_char_p, vp, ci, P(ci), vp, ci, P(ci)]
-    lib.rt_scene_write.argtypes = [vp, ci, vp, ci, vp, vp, ctypes.c_char_p, ctypes.c_size_t, P(ctypes.c_size_t)]
-    cf = ctypes.c_float
-    lib.rt_taa_resolve.argtypes = [vp, vp, vp, vp, vp, ci, ci, cf, cf, cf, vp]
-    lib.rt_taa_jitter.argtypes = [ci, ci, ci, P(cf), P(cf)]
-    lib.rt_bloom.argtypes = [vp, vp, vp, ci, ci, cf, cf, ci, vp]
-    lib.rt_ssao.argtypes = [vp, vp, vp, vp, ci, ci, P(cf), ci, ci, P(cf), P(cf), P(cf), vp]
-    lib.rt_ssao_blur.argtypes = [vp, vp, vp, ci, ci, ci, vp]
-    lib.rt_camera_matrices.argtypes = [P(cf), P(cf), P(cf), cf, cf, P(cf), P(cf)]
-    lib.rt_equirect_to_cubemap.argtypes = [vp, P(cf), ci, ci, ci, vp, ci]
-    lib.rt_frame.argtypes = [vp, P(L.RtParams), P(RtFrameDesc), vp]
-    lib.rt_frame_surfaces.argtypes = [vp, P(vp), P(vp), P(vp), P(vp), P(vp)]
-    lib.rt_strip_local_rows.argtypes = [ci, ci, ci, ci]
-    lib.rt_deinterleave.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, ctypes.c_size_t, vp]
-    lib.rt_wire_bytes.argtypes = [ctypes.c_size_t]
-    lib.rt_wire_bytes.restype = ctypes.c_size_t
-    lib.rt_wire_pack.argtypes = [vp, vp, vp, vp, vp, ctypes.c_size_t, vp]
-    lib.rt_wire_unpack.argtypes = [vp, vp, ctypes.c_size_t, ctypes.c_size_t, vp, vp, vp, ci, vp, vp, vp, ci, ci, ci, ci, vp]
-    lib.rt_debug_mesa_math.argtypes = [vp, vp, ci]
-    lib.rt_debug_shadow_tables.argtypes = [vp, vp, ctypes.c_size_t, P(ctypes.c_size_t), P(ci)]
-    lib.rt_debug_predicted_classes.argtypes = [vp, vp, ci, P(ci)]
-    lib.rt_render_into_image.argtypes = [vp, P(L.RtParams), vp, vp, vp, vp]
-    lib.rt_context_stream.argtypes = [vp, P(vp)]
-    lib.rt_mgpu_create.argtypes = [P(vp), P(ci), ci]
-    lib.rt_mgpu_destroy.argtypes = [vp]
-    lib.rt_mgpu_device_count.argtypes = [vp]
-    lib.rt_mgpu_set_scene.argtypes = [vp, vp, ci, vp, ci]
-    lib.rt_mgpu_set_noise.argtypes = [vp, vp, ci, ci]
-    lib.rt_mgpu_set_skybox.argtypes = [vp, vp, ci]
-    lib.rt_mgpu_set_strip_rows.argtypes = [vp, ci]
-    lib.rt_mgpu_render.argtypes = [vp, P(L.RtParams)]
-    lib.rt_mgpu_sync.argtypes = [vp]
-    lib.rt_mgpu_get_surfaces.argtypes = [vp, P(vp), P(vp), P(vp), P(vp)]
-    lib.rt_mgpu_readback.argtypes = [vp, vp, vp, vp]
-    lib.rt_mgpu_last_ms.argtypes = [vp, P(ctypes.c_float), ci]
-    lib.rt_mgpu_last_error.argtypes = [vp]
-    lib.rt_mgpu_last_error.restype = ctypes.c_char_p
-    lib.rt_trace_rays.argtypes = [vp, vp, ctypes.c_size_t, ci, vp, vp]
-    lib.rt_camera_rays.argtypes = [vp, P(L.RtParams), vp, vp]
-    lib.rt_pick.argtypes = [vp, P(L.RtParams), ci, ci, P(L.RtHit)]
-    lib.rt_shade_rays.argtypes = [vp, P(L.RtParams), vp, vp, ctypes.c_size_t, vp, vp, vp, vp]
-    lib.rt_debug_device_math.argtypes = [vp, ci, vp, vp, ctypes.c_size_t, vp]
-    lib.rt_display_pack.argtypes = [vp, vp, vp, P(L.RtDisplayDesc), vp]
-    lib.rt_display_srgb_thresholds.argtypes = [P(cf)]
-    lib.rt_present_configure.argtypes = [vp, ci]
-    lib.rt_present_submit.argtypes = [vp, vp, P(L.RtDisplayDesc), vp, P(ctypes.c_uint64)]
-    lib.rt_present_poll.argtypes = [vp, ctypes.c_uint64, P(ci)]
-    lib.rt_present_wait.argtypes = [vp, ctypes.c_uint64, P(vp), P(ctypes.c_size_t)]
-    lib.rt_meter.argtypes = [vp, vp, P(L.RtMeterDesc), vp, vp]
-    lib.rt_meter_solve_host.argtypes = [vp, P(L.RtMeterDesc), vp]
-    lib.rt_meter_tables.argtypes = [P(cf), P(ctypes.c_uint32)]
-    lib.rt_display_pack_toned.argtypes = [vp, vp, vp, P(L.RtDisplayDesc), P(L.RtToneDesc), vp]
-    lib.rt_present_submit_toned.argtypes = [vp, vp, P(L.RtDisplayDesc), P(L.RtToneDesc), vp, P(ctypes.c_uint64)]
-    lib.rt_display_yuv_coeffs.argtypes = [ci, ci, P(ctypes.c_int32)]
-    lib.rt_display_yuv_layout.argtypes = [P(L.RtYuvDesc), P(ctypes.c_size_t), P(ctypes.c_size_t), P(ctypes.c_size_t)]
-    lib.rt_display_pack_yuv.argtypes = [vp, vp, vp, P(L.RtYuvDesc), P(L.RtToneDesc), vp]
-    lib.rt_present_submit_yuv.argtypes = [vp, vp, P(L.RtYuvDesc), P(L.RtToneDesc), vp, P(ctypes.c_uint64)]
-    lib.rt_resample_taps.argtypes = [ci, ci, ci, P(ci), P(ctypes.c_int32), P(cf), ctypes.c_size_t]
-    lib.rt_display_resample.argtypes = [vp, vp, vp, P(L.RtResampleDesc), vp]
-    lib.rt_accum_layout.argtypes = [ci, ci, P(ctypes.c_size_t), P(ctypes.c_size_t)]
-    lib.rt_accum_reset.argtypes = [vp, vp, vp, ci, ci, vp]
-    lib.rt_accum_add.argtypes = [vp, vp, vp, P(L.RtAccumDesc), vp, vp]
-    lib.rt_accum_solve_host.argtypes = [vp, P(L.RtAccumDesc), vp]
-    lib.rt_accum_view.argtypes = [vp, vp, vp, P(L.RtAccumDesc), ci, vp]
-    lib.rt_denoise_guide.argtypes = [vp, vp, vp, ci, ci, vp]
-    lib.rt_denoise_layout.argtypes = [ci, ci, P(ctypes.c_size_t), P(ctypes.c_size_t)]
-    lib.rt_denoise.argtypes = [vp, vp, vp, vp, vp, vp, P(L.RtDenoiseDesc), vp]
-    lib.rt_reproject_layout.argtypes = [ci, ci, P(ctypes.c_size_t), P(ctypes.c_size_t)]
-    lib.rt_reproject_project.argtypes = [P(L.RtParams), P(ctypes.c_float), P(ctypes.c_float), P(ci)]
-    lib.rt_accum_reproject.argtypes = [vp, vp, vp, vp, vp, P(L.RtReprojectDesc), vp, vp]
-    lib.rt_accum_select_layout.argtypes = [ci, ci, P(ctypes.c_size_t)]
-    lib.rt_accum_select.argtypes = [vp, vp, P(L.RtAccumDesc), ctypes.c_uint32, vp, ctypes.c_size_t, vp, vp, vp]
-    lib.rt_camera_rays_at.argtypes = [vp, P(L.RtParams), vp, ctypes.c_size_t, vp, vp]
-    lib.rt_accum_add_at.argtypes = [vp, vp, vp, ctypes.c_size_t, vp, P(L.RtAccumDesc), vp, vp]
-    lib.rt_jpeg_dct_matrix.argtypes = [P(ctypes.c_int32)]
-    lib.rt_jpeg_quant.argtypes = [ci, P(ctypes.c_uint8), P(ctypes.c_uint8)]
-    lib.rt_jpeg_header.argtypes = [P(L.RtJpegDesc), P(ctypes.c_uint8), ctypes.c_size_t, P(ctypes.c_size_t)]
-    lib.rt_jpeg_layout.argtypes = [P(L.RtJpegDesc), P(ctypes.c_size_t), P(ctypes.c_size_t), P(ctypes.c_size_t)]
-    lib.rt_jpeg_encode.argtypes = [vp, vp, P(L.RtYuvDesc), P(L.RtJpegDesc), vp, vp, ctypes.c_size_t, vp, vp]
-    lib.rt_display_pack_jpeg.argtypes = [vp, vp, P(L.RtYuvDesc), P(L.RtToneDesc), P(L.RtJpegDesc), vp, vp, ctypes.c_size_t, vp, vp]
-    lib.rt_present_submit_jpeg.argtypes = [vp, vp, P(L.RtYuvDesc), P(L.RtToneDesc), P(L.RtJpegDesc), ctypes.c_size_t, vp, P(ctypes.c_uint64)]
-    for name in EXPORTS:
-        if name not in ("rt_last_error", "rt_mgpu_last_error", "rt_wire_bytes"):
-            getattr(lib, name).restype = ci
+    lib.entry = {}                      # name -> bound function, resolved once: what the _call helpers go through
+    for name, (restype, argtypes) in SIGNATURES.items():
+        if "RT_LIB" in os.environ and not hasattr(lib, name):
+            # an experiment build (tools/gpu_try.py) may predate newer entry points: bind what it has, the rest raises when called
+            def fn(*a, name=name):
+                raise RtError(-2, f"{name} is not exported by {path}")
+            setattr(lib, name, fn)
+        else:
+            fn = getattr(lib, name)
+            fn.restype, fn.argtypes = restype, argtypes
+        lib.entry[name] = fn
     _LIB = lib
     return lib
 
 
+# ---- how the functions below reach the library ---------------------------------------------------
+# A context-free entry point goes through _call, one that takes a handle through the handle's _call, one that is launched in the
+# order of a torch stream through RayTracer._launch.  There are two stream conventions and both stay: the older methods
+# (render_to, the post passes, deinterleave, wire_*) take `stream` as a raw hipStream_t (an int, None = the context's stream) and
+# pass it straight through; the newer ones take a torch stream and go through _on_torch_stream.
+def _call(name, *args, count=False):
+    """The context-free entry point `name`; RtError(rc, name) when it fails.  `count`: it answers a count (returned) or a negative status."""
+    rc = (_LIB or load_library()).entry[name](*args)
+    if rc < 0 if count else rc:
+        raise RtError(rc, name)
+    return rc
+
+
 def _ptr(a):
+    """A host address: a numpy array's data, or None."""
     return a.ctypes.data_as(ctypes.c_void_p) if a is not None else None
+
+
+def _typed(a, ctype):
+    """A numpy array's data as a pointer to `ctype`."""
+    return a.ctypes.data_as(ctypes.POINTER(ctype))
+
+
+def _dev_ptr(x):
+    """A device address: a raw pointer (int), anything with data_ptr() (a torch tensor), or None."""
+    return ctypes.c_void_p(x.data_ptr() if hasattr(x, "data_ptr") else x)
+
+
+def _ref(s):
+    """byref of a description, or None."""
+    return ctypes.byref(s) if s is not None else None
+
+
+def _tone(tone, white, d_exposure):
+    """The optional rt_tone_desc of the pack / submit methods: None unless `tone` or `d_exposure` asks for one."""
+    return None if tone is None and d_exposure is None else L.make_tone_desc(tone or "none", white, d_exposure)
+
+
+def _plane_layout(name, kind, width, height):
+    """The two plane offsets and the size that the rt_*_layout entry point `name` answers, as the namedtuple `kind`."""
+    off, n = (ctypes.c_size_t * 2)(), ctypes.c_size_t(0)
+    _call(name, int(width), int(height), off, ctypes.byref(n))
+    return kind(tuple(off), n.value)
 
 
 # ---- host-side feeders (no GPU) ------------------------------------------------------------
 def generate_aabb(objects):
     """GenerateAABBForObject (/root/reference/src/SceneIO.h:75-104), in place."""
     assert objects.dtype == L.OBJECT_DTYPE and objects.flags["C_CONTIGUOUS"]
-    rc = load_library().rt_generate_aabb(_ptr(objects), len(objects))
-    if rc:
-        raise RtError(rc, "rt_generate_aabb")
+    _call("rt_generate_aabb", _ptr(objects), len(objects))
     return objects
 
 
 def camera_vectors(yaw_deg=-90.0, pitch_deg=0.0):
     """Camera::UpdateVectors (/root/reference/src/Camera.h:26-34) -> (front, right, up)."""
     f, r, u = (ctypes.c_float * 3)(), (ctypes.c_float * 3)(), (ctypes.c_float * 3)()
-    rc = load_library().rt_camera_vectors(yaw_deg, pitch_deg, f, r, u)
-    if rc:
-        raise RtError(rc, "rt_camera_vectors")
+    _call("rt_camera_vectors", yaw_deg, pitch_deg, f, r, u)
     return tuple(f), tuple(r), tuple(u)
 
 
@@ -242,9 +259,7 @@ def camera_matrices(position, front, up, fov_deg=45.0, aspect=16.0 / 9.0):
     projection[16]) float32, column-major."""
     a3 = lambda v: (ctypes.c_float * 3)(*[float(x) for x in v])
     view, proj = (ctypes.c_float * 16)(), (ctypes.c_float * 16)()
-    rc = load_library().rt_camera_matrices(a3(position), a3(front), a3(up), fov_deg, aspect, view, proj)
-    if rc:
-        raise RtError(rc, "rt_camera_matrices")
+    _call("rt_camera_matrices", a3(position), a3(front), a3(up), fov_deg, aspect, view, proj)
     return np.array(view, dtype=np.float32), np.array(proj, dtype=np.float32)
 
 
@@ -275,10 +290,7 @@ def parse_scene(text, max_objects=512, max_lights=64):
     objs = np.zeros(max_objects, dtype=L.OBJECT_DTYPE)
     lts = np.zeros(max_lights, dtype=L.LIGHT_DTYPE)
     no, nl = ctypes.c_int(0), ctypes.c_int(0)
-    rc = load_library().rt_scene_parse(text.encode("utf-8"), _ptr(objs), max_objects, ctypes.byref(no),
-                                       _ptr(lts), max_lights, ctypes.byref(nl))
-    if rc:
-        raise RtError(rc, "rt_scene_parse")
+    _call("rt_scene_parse", text.encode("utf-8"), _ptr(objs), max_objects, ctypes.byref(no), _ptr(lts), max_lights, ctypes.byref(nl))
     # (a copy() of a padded record array leaves the padding bytes of the new array uninitialised: assign into zeros instead,
     #  so the same text always gives the same bytes, as the library wrote them)
     out_o, out_l = np.zeros(no.value, dtype=L.OBJECT_DTYPE), np.zeros(nl.value, dtype=L.LIGHT_DTYPE)
@@ -288,26 +300,19 @@ def parse_scene(text, max_objects=512, max_lights=64):
 
 def write_scene(objects, lights):
     """SceneIO::Save (/root/reference/src/SceneIO.h:124-142) -> text."""
-    lib = load_library()
     objects = np.ascontiguousarray(objects)
     lights = np.ascontiguousarray(lights)
     need = ctypes.c_size_t(0)
-    rc = lib.rt_scene_write(_ptr(objects), len(objects), _ptr(lights), len(lights), None, None, None, 0, ctypes.byref(need))
-    if rc:
-        raise RtError(rc, "rt_scene_write")
+    _call("rt_scene_write", _ptr(objects), len(objects), _ptr(lights), len(lights), None, None, None, 0, ctypes.byref(need))
     buf = ctypes.create_string_buffer(need.value)
-    rc = lib.rt_scene_write(_ptr(objects), len(objects), _ptr(lights), len(lights), None, None, buf, need.value, ctypes.byref(need))
-    if rc:
-        raise RtError(rc, "rt_scene_write")
+    _call("rt_scene_write", _ptr(objects), len(objects), _ptr(lights), len(lights), None, None, buf, need.value, ctypes.byref(need))
     return buf.value.decode()
 
 
 def taa_jitter(frame_count, width, height):
     """uJitterX/uJitterY of /root/reference/src/ForwardShadingPipeline.cpp:241-242."""
     jx, jy = ctypes.c_float(), ctypes.c_float()
-    rc = load_library().rt_taa_jitter(frame_count, width, height, ctypes.byref(jx), ctypes.byref(jy))
-    if rc:
-        raise RtError(rc, "rt_taa_jitter")
+    _call("rt_taa_jitter", frame_count, width, height, ctypes.byref(jx), ctypes.byref(jy))
     return jx.value, jy.value
 
 
@@ -315,35 +320,26 @@ def mesa_math(x):
     """(sin, cos, tan, exp) of float32 x as the HIP path's host side evaluates them (csrc/rt_mesa_math.h)."""
     x = np.ascontiguousarray(x, dtype=np.float32)
     out = np.zeros((len(x), 4), dtype=np.float32)
-    rc = load_library().rt_debug_mesa_math(_ptr(x), _ptr(out), len(x))
-    if rc:
-        raise RtError(rc, "rt_debug_mesa_math")
+    _call("rt_debug_mesa_math", _ptr(x), _ptr(out), len(x))
     return out
 
 
 def strip_local_rows(height, strip_rows, strip_count, strip_index):
-    n = load_library().rt_strip_local_rows(height, strip_rows, strip_count, strip_index)
-    if n < 0:
-        raise RtError(n, "rt_strip_local_rows")
-    return n
+    return _call("rt_strip_local_rows", height, strip_rows, strip_count, strip_index, count=True)
 
 
 def display_srgb_thresholds():
     """The 256 decision thresholds of the sRGB display format (rt_display_srgb_thresholds): float32, [0] = 0; a colour value
     y in (0, 1) becomes the number of entries 1..255 that are <= y.  Needs no GPU."""
     out = np.zeros(256, dtype=np.float32)
-    rc = load_library().rt_display_srgb_thresholds(out.ctypes.data_as(ctypes.POINTER(ctypes.c_float)))
-    if rc:
-        raise RtError(rc, "rt_display_srgb_thresholds")
+    _call("rt_display_srgb_thresholds", _typed(out, ctypes.c_float))
     return out
 
 
 def meter_tables():
     """(pow2neg float32[256], log2q16 uint32[8]): the two tables of rt_meter's solve (rt_meter_tables).  Needs no GPU."""
     p, q = np.zeros(256, dtype=np.float32), np.zeros(8, dtype=np.uint32)
-    rc = load_library().rt_meter_tables(p.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), q.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)))
-    if rc:
-        raise RtError(rc, "rt_meter_tables")
+    _call("rt_meter_tables", _typed(p, ctypes.c_float), _typed(q, ctypes.c_uint32))
     return p, q
 
 
@@ -353,9 +349,7 @@ def meter_solve_host(state, width, height, **desc):
     src = np.ascontiguousarray(np.asarray(state, dtype=L.METER_STATE_DTYPE).reshape(1))
     out = np.zeros(1, dtype=L.METER_STATE_DTYPE)
     d = L.make_meter_desc(width, height, **desc)
-    rc = load_library().rt_meter_solve_host(_ptr(src), ctypes.byref(d), _ptr(out))
-    if rc:
-        raise RtError(rc, "rt_meter_solve_host")
+    _call("rt_meter_solve_host", _ptr(src), ctypes.byref(d), _ptr(out))
     return out[0]
 
 
@@ -369,9 +363,7 @@ def yuv_coeffs(matrix="bt709", range="limited"):
     Needs no GPU."""
     d = L.make_yuv_desc(1, 1, matrix=matrix, range=range)
     out = np.zeros(12, dtype=np.int32)
-    rc = load_library().rt_display_yuv_coeffs(d.matrix, d.range, out.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)))
-    if rc:
-        raise RtError(rc, "rt_display_yuv_coeffs")
+    _call("rt_display_yuv_coeffs", d.matrix, d.range, _typed(out, ctypes.c_int32))
     return out
 
 
@@ -379,9 +371,7 @@ def yuv_layout(width, height, format="nv12"):
     """Where the planes of a width x height NV12 / I420 frame lie (rt_display_yuv_layout) -> YuvLayout.  Needs no GPU."""
     d = L.make_yuv_desc(width, height, format=format)
     off, pitch, n = (ctypes.c_size_t * 3)(), (ctypes.c_size_t * 3)(), ctypes.c_size_t(0)
-    rc = load_library().rt_display_yuv_layout(ctypes.byref(d), off, pitch, ctypes.byref(n))
-    if rc:
-        raise RtError(rc, "rt_display_yuv_layout")
+    _call("rt_display_yuv_layout", ctypes.byref(d), off, pitch, ctypes.byref(n))
     return YuvLayout(tuple(off), tuple(pitch), n.value)
 
 
@@ -407,19 +397,14 @@ JpegLayout.__doc__ = """rt_jpeg_layout's answer: byte offsets of the coefficient
 def jpeg_dct_matrix():
     """M[u, x] of the encoder's integer DCT (rt_jpeg_dct_matrix): int32 [8, 8].  Needs no GPU."""
     out = np.zeros(64, dtype=np.int32)
-    rc = load_library().rt_jpeg_dct_matrix(out.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)))
-    if rc:
-        raise RtError(rc, "rt_jpeg_dct_matrix")
+    _call("rt_jpeg_dct_matrix", _typed(out, ctypes.c_int32))
     return out.reshape(8, 8)
 
 
 def jpeg_quant(quality):
     """The two quantisers of `quality` (rt_jpeg_quant) -> (luma uint8 [64], chroma uint8 [64]), natural order.  Needs no GPU."""
     luma, chroma = np.zeros(64, dtype=np.uint8), np.zeros(64, dtype=np.uint8)
-    u8 = ctypes.POINTER(ctypes.c_uint8)
-    rc = load_library().rt_jpeg_quant(int(quality), luma.ctypes.data_as(u8), chroma.ctypes.data_as(u8))
-    if rc:
-        raise RtError(rc, "rt_jpeg_quant")
+    _call("rt_jpeg_quant", int(quality), _typed(luma, ctypes.c_uint8), _typed(chroma, ctypes.c_uint8))
     return luma, chroma
 
 
@@ -427,9 +412,7 @@ def jpeg_header(width, height, quality=90, restart_interval=None):
     """The 629 bytes in front of the entropy-coded data (rt_jpeg_header) -> uint8 [629].  Needs no GPU."""
     d = L.make_jpeg_desc(width, height, quality, restart_interval)
     out, n = np.zeros(L.JPEG_HEADER_BYTES, dtype=np.uint8), ctypes.c_size_t(0)
-    rc = load_library().rt_jpeg_header(ctypes.byref(d), out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), out.size, ctypes.byref(n))
-    if rc:
-        raise RtError(rc, "rt_jpeg_header")
+    _call("rt_jpeg_header", ctypes.byref(d), _typed(out, ctypes.c_uint8), out.size, ctypes.byref(n))
     return out[:n.value]
 
 
@@ -437,9 +420,7 @@ def jpeg_layout(width, height, quality=90, restart_interval=None):
     """The scratch of one encode (rt_jpeg_layout) -> JpegLayout.  Needs no GPU."""
     d = L.make_jpeg_desc(width, height, quality, restart_interval)
     off, scratch, worst = (ctypes.c_size_t * 3)(), ctypes.c_size_t(0), ctypes.c_size_t(0)
-    rc = load_library().rt_jpeg_layout(ctypes.byref(d), off, ctypes.byref(scratch), ctypes.byref(worst))
-    if rc:
-        raise RtError(rc, "rt_jpeg_layout")
+    _call("rt_jpeg_layout", ctypes.byref(d), off, ctypes.byref(scratch), ctypes.byref(worst))
     n_mcu = ((d.width + 15) // 16) * ((d.height + 15) // 16)
     return JpegLayout(tuple(off), scratch.value, worst.value, n_mcu, (n_mcu + d.restartInterval - 1) // d.restartInterval)
 
@@ -448,17 +429,11 @@ def resample_taps(src, dst, filter="lanczos3"):
     """The tap table of one axis of rt_display_resample, source size `src` -> destination size `dst` (rt_resample_taps):
     (n, first int32[dst], weights float32[dst, n]) -- destination index i reads source pixels clamp(first[i] + k, 0, src - 1),
     k = 0..n-1, with weights[i, k] (zero padding behind a shorter window).  filter "area", "triangle" or "lanczos3".  Needs no GPU."""
-    lib = load_library()
     f = int(L.RESAMPLE_FILTERS.get(filter, filter))
     n = ctypes.c_int(0)
-    rc = lib.rt_resample_taps(int(src), int(dst), f, ctypes.byref(n), None, None, 0)
-    if rc:
-        raise RtError(rc, "rt_resample_taps")
+    _call("rt_resample_taps", int(src), int(dst), f, ctypes.byref(n), None, None, 0)
     first, weights = np.zeros(int(dst), dtype=np.int32), np.zeros((int(dst), n.value), dtype=np.float32)
-    rc = lib.rt_resample_taps(int(src), int(dst), f, ctypes.byref(n), first.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
-                              weights.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), weights.size)
-    if rc:
-        raise RtError(rc, "rt_resample_taps")
+    _call("rt_resample_taps", int(src), int(dst), f, ctypes.byref(n), _typed(first, ctypes.c_int32), _typed(weights, ctypes.c_float), weights.size)
     return n.value, first, weights
 
 
@@ -468,11 +443,7 @@ AccumLayout.__doc__ = """rt_accum_layout's answer: byte offsets of the accumulat
 
 def accum_layout(width, height):
     """Where the two planes of a width x height accumulator lie (rt_accum_layout) -> AccumLayout.  Needs no GPU."""
-    off, n = (ctypes.c_size_t * 2)(), ctypes.c_size_t(0)
-    rc = load_library().rt_accum_layout(int(width), int(height), off, ctypes.byref(n))
-    if rc:
-        raise RtError(rc, "rt_accum_layout")
-    return AccumLayout(tuple(off), n.value)
+    return _plane_layout("rt_accum_layout", AccumLayout, width, height)
 
 
 def accum_solve_host(state, width, height, **desc):
@@ -482,18 +453,14 @@ def accum_solve_host(state, width, height, **desc):
     src = np.ascontiguousarray(np.asarray(state, dtype=L.ACCUM_STATE_DTYPE).reshape(1))
     out = np.zeros(1, dtype=L.ACCUM_STATE_DTYPE)
     d = L.make_accum_desc(width, height, **desc)
-    rc = load_library().rt_accum_solve_host(_ptr(src), ctypes.byref(d), _ptr(out))
-    if rc:
-        raise RtError(rc, "rt_accum_solve_host")
+    _call("rt_accum_solve_host", _ptr(src), ctypes.byref(d), _ptr(out))
     return out[0]
 
 
 def accum_select_layout(width, height):
     """The scratch bytes rt_accum_select needs for a width x height accumulator (rt_accum_select_layout).  Needs no GPU."""
     n = ctypes.c_size_t(0)
-    rc = load_library().rt_accum_select_layout(int(width), int(height), ctypes.byref(n))
-    if rc:
-        raise RtError(rc, "rt_accum_select_layout")
+    _call("rt_accum_select_layout", int(width), int(height), ctypes.byref(n))
     return n.value
 
 
@@ -503,11 +470,7 @@ DenoiseLayout.__doc__ = """rt_denoise_layout's answer: byte offsets of the two s
 
 def denoise_layout(width, height):
     """Where the two scratch planes of a width x height rt_denoise lie (rt_denoise_layout) -> DenoiseLayout.  Needs no GPU."""
-    off, n = (ctypes.c_size_t * 2)(), ctypes.c_size_t(0)
-    rc = load_library().rt_denoise_layout(int(width), int(height), off, ctypes.byref(n))
-    if rc:
-        raise RtError(rc, "rt_denoise_layout")
-    return DenoiseLayout(tuple(off), n.value)
+    return _plane_layout("rt_denoise_layout", DenoiseLayout, width, height)
 
 
 ReprojectLayout = collections.namedtuple("ReprojectLayout", "offset bytes")
@@ -517,11 +480,7 @@ ReprojectLayout.__doc__ = """rt_reproject_layout's answer: byte offsets of the t
 def reproject_layout(width, height):
     """Where the two planes of the accumulator rt_accum_reproject writes lie (rt_reproject_layout; the same answer as accum_layout's)
     -> ReprojectLayout.  Needs no GPU."""
-    off, n = (ctypes.c_size_t * 2)(), ctypes.c_size_t(0)
-    rc = load_library().rt_reproject_layout(int(width), int(height), off, ctypes.byref(n))
-    if rc:
-        raise RtError(rc, "rt_reproject_layout")
-    return ReprojectLayout(tuple(off), n.value)
+    return _plane_layout("rt_reproject_layout", ReprojectLayout, width, height)
 
 
 def reproject_project(view, point):
@@ -530,9 +489,7 @@ def reproject_project(view, point):
     the camera).  Needs no GPU."""
     P3 = (ctypes.c_float * 3)(*[float(x) for x in point])
     f, valid = (ctypes.c_float * 2)(), ctypes.c_int(0)
-    rc = load_library().rt_reproject_project(ctypes.byref(view), P3, f, ctypes.byref(valid))
-    if rc:
-        raise RtError(rc, "rt_reproject_project")
+    _call("rt_reproject_project", ctypes.byref(view), P3, f, ctypes.byref(valid))
     return (np.float32(f[0]), np.float32(f[1])), bool(valid.value)
 
 
@@ -540,11 +497,6 @@ def reproject_report(d_report):
     """The read-back of a reproject report (a CUDA tensor of 64 bytes; waits for the device) as one layout.REPROJECT_REPORT_DTYPE
     record: nPixels, nReused, nRejected, nOffscreen, nMiss, minCount, maxCount, sumCount."""
     return d_report.cpu().numpy().view(np.uint8).reshape(-1)[:L.REPROJECT_REPORT_BYTES].view(L.REPROJECT_REPORT_DTYPE)[0]
-
-
-def _dev_ptr(x):
-    """A device address: a raw pointer (int) or anything with data_ptr() (a torch tensor)."""
-    return ctypes.c_void_p(x.data_ptr() if hasattr(x, "data_ptr") else x)
 
 
 PickHit = collections.namedtuple("PickHit", "object t position normal")
@@ -568,27 +520,33 @@ def _query_mode(mode):
 _PresentTicket = collections.namedtuple("_PresentTicket", "kind width height format")
 
 
-class RayTracer:
-    def __init__(self, device=0):
+class _Handle:
+    """What RayTracer and MultiGpuRayTracer share: a library (`lib`) and a handle of it (`ctx`) whose entry points begin with _PREFIX
+    and take the handle first; its lifetime; the three-surface readback of `_size` pixels."""
+    _PREFIX = None
+
+    def _create(self, failure, *args):
+        """self.lib and self.ctx from <_PREFIX>create(&ctx, *args); RtError(rc, failure) when that fails."""
         self.lib = load_library()
         self.ctx = ctypes.c_void_p()
-        rc = self.lib.rt_create(ctypes.byref(self.ctx), device)
+        rc = getattr(self.lib, self._PREFIX + "create")(ctypes.byref(self.ctx), *args)
         if rc:
             self.ctx = None
-            raise RtError(rc, "rt_create (is a HIP device present?)")
-        self._region = None
-        self._present_tickets = {}                    # ticket -> _PresentTicket, for present_wait / present_wait_yuv
-        v = int(os.environ.get("RT_VARIANT", "-1"))   # A/B switch for measurements and tests
-        if v >= 0:
-            self.set_variant(v)
+            raise RtError(rc, failure)
+        self._size = None                             # (width, height) of the last render: what readback() fetches
 
     def _check(self, rc, what):
         if rc:
-            raise RtError(rc, f"{what}: {self.lib.rt_last_error(self.ctx).decode()}")
+            raise RtError(rc, f"{what}: {getattr(self.lib, self._PREFIX + 'last_error')(self.ctx).decode()}")
+
+    def _call(self, name, *args):
+        """The entry point `name` of self.lib on this handle; a failure goes through _check."""
+        if rc := self.lib.entry[name](self.ctx, *args):
+            self._check(rc, name)
 
     def close(self):
         if getattr(self, "ctx", None):
-            self.lib.rt_destroy(self.ctx)
+            getattr(self.lib, self._PREFIX + "destroy")(self.ctx)
             self.ctx = None
 
     def __del__(self):
@@ -603,27 +561,49 @@ class RayTracer:
     def __exit__(self, *exc):
         self.close()
 
+    def sync(self):
+        self._call(self._PREFIX + "sync")
+
+    def readback(self):
+        """-> (gColor float32[h,w,4], gPosition float32[h,w,4], gNormal float16[h,w,4]); row 0 = bottom."""
+        w, h = self._size
+        col = np.empty((h, w, 4), dtype=np.float32)
+        pos = np.empty((h, w, 4), dtype=np.float32)
+        nrm = np.empty((h, w, 4), dtype=np.float16)
+        self._call(self._PREFIX + "readback", _ptr(col), _ptr(pos), _ptr(nrm))
+        return col, pos, nrm
+
+
+class RayTracer(_Handle):
+    _PREFIX = "rt_"
+
+    def __init__(self, device=0):
+        self._create("rt_create (is a HIP device present?)", device)
+        self._present_tickets = {}                    # ticket -> _PresentTicket, for present_wait / present_wait_yuv
+        v = int(os.environ.get("RT_VARIANT", "-1"))   # A/B switch for measurements and tests
+        if v >= 0:
+            self.set_variant(v)
+
     def set_scene(self, objects, lights):
         objects = np.ascontiguousarray(objects)
         lights = np.ascontiguousarray(lights)
         assert objects.dtype.itemsize == L.OBJECT_STRIDE and lights.dtype.itemsize == L.LIGHT_STRIDE
-        self._check(self.lib.rt_set_scene(self.ctx, _ptr(objects) if len(objects) else None, len(objects),
-                                          _ptr(lights) if len(lights) else None, len(lights)), "rt_set_scene")
+        self._call("rt_set_scene", _ptr(objects) if len(objects) else None, len(objects), _ptr(lights) if len(lights) else None, len(lights))
 
     def set_noise(self, r8):
         if r8 is None:
-            self._check(self.lib.rt_set_noise(self.ctx, None, 0, 0), "rt_set_noise")
+            self._call("rt_set_noise", None, 0, 0)
             return
         r8 = np.ascontiguousarray(r8, dtype=np.uint8)
-        self._check(self.lib.rt_set_noise(self.ctx, _ptr(r8), r8.shape[1], r8.shape[0]), "rt_set_noise")
+        self._call("rt_set_noise", _ptr(r8), r8.shape[1], r8.shape[0])
 
     def set_skybox(self, faces):
         if faces is None:
-            self._check(self.lib.rt_set_skybox(self.ctx, None, 0), "rt_set_skybox")
+            self._call("rt_set_skybox", None, 0)
             return
         faces = np.ascontiguousarray(faces, dtype=np.float16)
         assert faces.ndim == 4 and faces.shape[0] == 6 and faces.shape[1] == faces.shape[2] and faces.shape[3] == 3
-        self._check(self.lib.rt_set_skybox(self.ctx, _ptr(faces), faces.shape[1]), "rt_set_skybox")
+        self._call("rt_set_skybox", _ptr(faces), faces.shape[1])
 
     def load(self, scene):
         """Upload a scenes.Scene (objects, lights, noise, skybox)."""
@@ -632,19 +612,22 @@ class RayTracer:
         self.set_skybox(scene.skybox if scene.use_skybox else None)
 
     def set_variant(self, v):
-        self._check(self.lib.rt_set_variant(self.ctx, int(v)), "rt_set_variant")
+        self._call("rt_set_variant", int(v))
 
     def render(self, params):
-        self._check(self.lib.rt_render(self.ctx, ctypes.byref(params)), "rt_render")
-        self._region = (params.regionW, params.regionH)
+        self._call("rt_render", ctypes.byref(params))
+        self._size = (params.regionW, params.regionH)
 
     def render_to(self, params, d_color, d_position, d_normal, stream=None):
         """Render into caller-owned device memory (raw device pointers as ints)."""
-        self._check(self.lib.rt_render_to(self.ctx, ctypes.byref(params), ctypes.c_void_p(d_color),
-                                          ctypes.c_void_p(d_position), ctypes.c_void_p(d_normal),
-                                          ctypes.c_void_p(stream) if stream else None), "rt_render_to")
+        self._call("rt_render_to", ctypes.byref(params), _dev_ptr(d_color), _dev_ptr(d_position), _dev_ptr(d_normal), _dev_ptr(stream))
 
     # ---- ray queries -------------------------------------------------------------------------
+    def _launch(self, stream, name, *args, after=()):
+        """_call(name, *args, hipStream_t, *after) in the order of torch stream `stream` (_on_torch_stream): the stream handle
+        follows `args`, and `after` holds what the entry point takes behind it (the ticket of the present submits)."""
+        self._on_torch_stream(stream, lambda h: self._call(name, *args, ctypes.c_void_p(h), *after))
+
     def _on_torch_stream(self, stream, launch):
         """launch(hipStream_t) asynchronously in the order of torch stream `stream` (default: the current one).  torch's
         default stream has the handle 0, which the C ABI reads as "the context's stream": then the launch goes to the
@@ -657,7 +640,7 @@ class RayTracer:
             return
         if not hasattr(self, "_ctx_stream"):
             cs = ctypes.c_void_p()
-            self._check(self.lib.rt_context_stream(self.ctx, ctypes.byref(cs)), "rt_context_stream")
+            self._call("rt_context_stream", ctypes.byref(cs))
             self._ctx_stream = torch.cuda.ExternalStream(cs.value)
         self._ctx_stream.wait_stream(s)
         launch(self._ctx_stream.cuda_stream)
@@ -693,8 +676,7 @@ class RayTracer:
                    else torch.empty(shape, dtype=torch.int32, device=rays.device))
         assert out.is_contiguous() and out.numel() * out.element_size() == rays.numel() // 8 * (32 if m == L.QUERY_CLOSEST else 4)
         n = rays.numel() // 8
-        self._on_torch_stream(stream, lambda h: self._check(self.lib.rt_trace_rays(
-            self.ctx, ctypes.c_void_p(rays.data_ptr()), n, m, ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(h)), "rt_trace_rays"))
+        self._launch(stream, "rt_trace_rays", _dev_ptr(rays), n, m, _dev_ptr(out))
         return out
 
     def camera_rays(self, params, stream=None):
@@ -702,8 +684,7 @@ class RayTracer:
         asynchronous on `stream` (default torch.cuda.current_stream())."""
         import torch
         out = torch.empty((params.regionH, params.regionW, 8), dtype=torch.float32, device="cuda")
-        self._on_torch_stream(stream, lambda h: self._check(self.lib.rt_camera_rays(
-            self.ctx, ctypes.byref(params), ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(h)), "rt_camera_rays"))
+        self._launch(stream, "rt_camera_rays", ctypes.byref(params), _dev_ptr(out))
         return out
 
     def camera_rays_at(self, params, d_pixels, n, out=None, stream=None):
@@ -716,8 +697,7 @@ class RayTracer:
         n = int(n)
         if out is None:
             out = torch.empty((n, 8), dtype=torch.float32, device="cuda")
-        self._on_torch_stream(stream, lambda h: self._check(self.lib.rt_camera_rays_at(
-            self.ctx, ctypes.byref(params), _dev_ptr(d_pixels), n, _dev_ptr(out), ctypes.c_void_p(h)), "rt_camera_rays_at"))
+        self._launch(stream, "rt_camera_rays_at", ctypes.byref(params), _dev_ptr(d_pixels), n, _dev_ptr(out))
         return out
 
     def shade_rays(self, params, rays, pixels=None, out=None, stream=None, position=True, normal=True):
@@ -760,10 +740,7 @@ class RayTracer:
         for k, (on, dt) in enumerate(((True, torch.float32), (position, torch.float32), (normal, torch.float16))):
             if res[k] is None and on:
                 res[k] = torch.empty(shape + (4,), dtype=dt, device=rays.device)
-        ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
-        self._on_torch_stream(stream, lambda h: self._check(self.lib.rt_shade_rays(
-            self.ctx, ctypes.byref(params), ptr(rays), ptr(pixels), n, ptr(res[0]), ptr(res[1]), ptr(res[2]),
-            ctypes.c_void_p(h)), "rt_shade_rays"))
+        self._launch(stream, "rt_shade_rays", ctypes.byref(params), _dev_ptr(rays), _dev_ptr(pixels), n, *[_dev_ptr(t) for t in res])
         return tuple(res)
 
     def device_math(self, op, inputs, n=None, out=None):
@@ -787,62 +764,46 @@ class RayTracer:
             if h.ndim != 2 or h.shape[1] != 4 or h.dtype.itemsize != 4 or len(h) < n:
                 raise ValueError("out: [>= n, 4] records of 32-bit words")
             d_out = torch.from_numpy(h.view(np.int32).copy()).cuda()
-        self._on_torch_stream(None, lambda s: self._check(self.lib.rt_debug_device_math(
-            self.ctx, int(o), ctypes.c_void_p(d_in.data_ptr()), ctypes.c_void_p(d_out.data_ptr()), n, ctypes.c_void_p(s)),
-            "rt_debug_device_math"))
+        self._launch(None, "rt_debug_device_math", int(o), _dev_ptr(d_in), _dev_ptr(d_out), n)
         torch.cuda.current_stream().synchronize()
         return d_out.cpu().numpy().view(np.uint32)
 
     def pick(self, params, x, y):
         """Closest hit of the primary ray of image pixel (x, y), row 0 = bottom (rt_pick) -> PickHit."""
         h = L.RtHit()
-        self._check(self.lib.rt_pick(self.ctx, ctypes.byref(params), int(x), int(y), ctypes.byref(h)), "rt_pick")
+        self._call("rt_pick", ctypes.byref(params), int(x), int(y), ctypes.byref(h))
         return PickHit(h.object, h.t, np.array(h.position, dtype=np.float32), np.array(h.normal, dtype=np.float32))
-
-    def sync(self):
-        self._check(self.lib.rt_sync(self.ctx), "rt_sync")
-
-    def readback(self):
-        """-> (gColor float32[h,w,4], gPosition float32[h,w,4], gNormal float16[h,w,4]); row 0 = bottom."""
-        w, h = self._region
-        col = np.empty((h, w, 4), dtype=np.float32)
-        pos = np.empty((h, w, 4), dtype=np.float32)
-        nrm = np.empty((h, w, 4), dtype=np.float16)
-        self._check(self.lib.rt_readback(self.ctx, _ptr(col), _ptr(pos), _ptr(nrm)), "rt_readback")
-        return col, pos, nrm
 
     def get_surfaces(self):
         """Device pointers (ints) of the context-owned gColor, gPosition, gNormal of the last rt_render."""
         dc, dp, dn = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
-        self._check(self.lib.rt_get_surfaces(self.ctx, ctypes.byref(dc), ctypes.byref(dp), ctypes.byref(dn)), "rt_get_surfaces")
+        self._call("rt_get_surfaces", ctypes.byref(dc), ctypes.byref(dp), ctypes.byref(dn))
         return dc.value, dp.value, dn.value
 
     def last_kernel_ms(self):
         ms = ctypes.c_float()
-        self._check(self.lib.rt_last_kernel_ms(self.ctx, ctypes.byref(ms)), "rt_last_kernel_ms")
+        self._call("rt_last_kernel_ms", ctypes.byref(ms))
         return ms.value
 
     def count_rays(self, params):
         n = ctypes.c_uint64()
-        self._check(self.lib.rt_count_rays(self.ctx, ctypes.byref(params), ctypes.byref(n)), "rt_count_rays")
+        self._call("rt_count_rays", ctypes.byref(params), ctypes.byref(n))
         return n.value
 
     def count_rays_traced(self, params):
         """Rays the production kernel traverses (keeps its dead-ray skips); <= count_rays."""
         n = ctypes.c_uint64()
-        self._check(self.lib.rt_count_rays_traced(self.ctx, ctypes.byref(params), ctypes.byref(n)), "rt_count_rays_traced")
+        self._call("rt_count_rays_traced", ctypes.byref(params), ctypes.byref(n))
         return n.value
 
     def taa_resolve(self, d_current, d_history, d_normal, d_out, width, height, blend, jx, jy, stream=None):
         """TAA resolve pass on device surfaces (raw device pointers as ints)."""
-        self._check(self.lib.rt_taa_resolve(self.ctx, ctypes.c_void_p(d_current), ctypes.c_void_p(d_history),
-                                            ctypes.c_void_p(d_normal), ctypes.c_void_p(d_out), width, height, blend, jx, jy,
-                                            ctypes.c_void_p(stream) if stream else None), "rt_taa_resolve")
+        self._call("rt_taa_resolve", _dev_ptr(d_current), _dev_ptr(d_history), _dev_ptr(d_normal), _dev_ptr(d_out), width, height,
+                   blend, jx, jy, _dev_ptr(stream))
 
     def bloom(self, d_scene, d_out, width, height, threshold=1.0, strength=0.5, iterations=10, stream=None):
         """Bloom chain on device surfaces (raw device pointers as ints)."""
-        self._check(self.lib.rt_bloom(self.ctx, ctypes.c_void_p(d_scene), ctypes.c_void_p(d_out), width, height, threshold,
-                                      strength, iterations, ctypes.c_void_p(stream) if stream else None), "rt_bloom")
+        self._call("rt_bloom", _dev_ptr(d_scene), _dev_ptr(d_out), width, height, threshold, strength, iterations, _dev_ptr(stream))
 
     # ---- display packing and delivery to the host ------------------------------------------
     def display_pack(self, d_image, d_out, width, height, format="linear", flip=False, exposure=1.0, stream=None,
@@ -853,13 +814,11 @@ class RayTracer:
         With `tone` ("none", "reinhard" with `white`, "aces") or `d_exposure` (the address of a device float the exposure is
         multiplied by, e.g. a meter state's + layout.METER_EXPOSURE_OFFSET) the call is rt_display_pack_toned."""
         d = L.make_display_desc(width, height, format, flip, exposure)
-        if tone is None and d_exposure is None:
-            self._on_torch_stream(stream, lambda h: self._check(self.lib.rt_display_pack(
-                self.ctx, _dev_ptr(d_image), _dev_ptr(d_out), ctypes.byref(d), ctypes.c_void_p(h)), "rt_display_pack"))
-            return
-        t = L.make_tone_desc(tone or "none", white, d_exposure)
-        self._on_torch_stream(stream, lambda h: self._check(self.lib.rt_display_pack_toned(
-            self.ctx, _dev_ptr(d_image), _dev_ptr(d_out), ctypes.byref(d), ctypes.byref(t), ctypes.c_void_p(h)), "rt_display_pack_toned"))
+        t = _tone(tone, white, d_exposure)
+        if t is None:
+            self._launch(stream, "rt_display_pack", _dev_ptr(d_image), _dev_ptr(d_out), ctypes.byref(d))
+        else:
+            self._launch(stream, "rt_display_pack_toned", _dev_ptr(d_image), _dev_ptr(d_out), ctypes.byref(d), ctypes.byref(t))
 
     def resample(self, d_src, d_dst, src_w, src_h, dst_w, dst_h, filter="lanczos3", stream=None):
         """rgba32f surface src_w x src_h -> rgba32f surface dst_w x dst_h on the device, in linear light, in front of meter /
@@ -867,8 +826,7 @@ class RayTracer:
         aligned, not overlapping.  filter "area" (exact coverage), "triangle" or "lanczos3"; the taps are resample_taps'.
         Asynchronous on torch stream `stream` (default torch.cuda.current_stream())."""
         d = L.make_resample_desc(src_w, src_h, dst_w, dst_h, filter)
-        self._on_torch_stream(stream, lambda h: self._check(self.lib.rt_display_resample(
-            self.ctx, _dev_ptr(d_src), _dev_ptr(d_dst), ctypes.byref(d), ctypes.c_void_p(h)), "rt_display_resample"))
+        self._launch(stream, "rt_display_resample", _dev_ptr(d_src), _dev_ptr(d_dst), ctypes.byref(d))
 
     def meter(self, d_image, d_state, width, height, key=0.18, min_exposure=2.0 ** -10, max_exposure=2.0 ** 10, adapt=1.0,
               low_permille=0, high_permille=0, stream=None):
@@ -879,8 +837,7 @@ class RayTracer:
         present_submit as d_exposure = state address + layout.METER_EXPOSURE_OFFSET, or read the state back
         (layout.METER_STATE_DTYPE) when the host wants the figures."""
         d = L.make_meter_desc(width, height, key, min_exposure, max_exposure, adapt, low_permille, high_permille)
-        self._on_torch_stream(stream, lambda h: self._check(self.lib.rt_meter(
-            self.ctx, _dev_ptr(d_image), ctypes.byref(d), _dev_ptr(d_state), ctypes.c_void_p(h)), "rt_meter"))
+        self._launch(stream, "rt_meter", _dev_ptr(d_image), ctypes.byref(d), _dev_ptr(d_state))
 
     # ---- progressive accumulation ----------------------------------------------------------
     def accum_alloc(self, width, height):
@@ -893,8 +850,7 @@ class RayTracer:
     def accum_reset(self, d_accum, d_state, width, height, stream=None):
         """Empty the accumulator and zero the state, `frames` included (rt_accum_reset): two asynchronous memsets on torch
         stream `stream` (default torch.cuda.current_stream())."""
-        self._on_torch_stream(stream, lambda h: self._check(self.lib.rt_accum_reset(
-            self.ctx, _dev_ptr(d_accum), _dev_ptr(d_state), int(width), int(height), ctypes.c_void_p(h)), "rt_accum_reset"))
+        self._launch(stream, "rt_accum_reset", _dev_ptr(d_accum), _dev_ptr(d_state), int(width), int(height))
 
     def accum_add(self, d_image, d_accum, d_state, width, height, rel_error=0.02, lum_floor=2.0 ** -10, min_samples=16,
                   done_permille=950, stream=None):
@@ -906,8 +862,7 @@ class RayTracer:
         read the 4 bytes at state address + layout.ACCUM_DONE_OFFSET every few frames, or the whole state
         (layout.ACCUM_STATE_DTYPE) when the host wants the figures."""
         d = L.make_accum_desc(width, height, rel_error, lum_floor, min_samples, done_permille)
-        self._on_torch_stream(stream, lambda h: self._check(self.lib.rt_accum_add(
-            self.ctx, _dev_ptr(d_image), _dev_ptr(d_accum), ctypes.byref(d), _dev_ptr(d_state), ctypes.c_void_p(h)), "rt_accum_add"))
+        self._launch(stream, "rt_accum_add", _dev_ptr(d_image), _dev_ptr(d_accum), ctypes.byref(d), _dev_ptr(d_state))
 
     # ---- adaptive sampling (the loop: accum_select every k frames; camera_rays_at -> shade_rays -> accum_add_at every frame) ----
     accum_select_layout = staticmethod(accum_select_layout)
@@ -929,9 +884,8 @@ class RayTracer:
         bytes of rt_select_state (layout.SELECT_STATE_DTYPE).  Raw device pointers or CUDA tensors; asynchronous on `stream`
         (default torch.cuda.current_stream()), no host synchronisation."""
         d = L.make_accum_desc(width, height, rel_error, lum_floor, min_samples, done_permille)
-        self._on_torch_stream(stream, lambda h: self._check(self.lib.rt_accum_select(
-            self.ctx, _dev_ptr(d_accum), ctypes.byref(d), int(max_samples), _dev_ptr(d_pixels), int(capacity), _dev_ptr(d_scratch),
-            _dev_ptr(d_sel_state), ctypes.c_void_p(h)), "rt_accum_select"))
+        self._launch(stream, "rt_accum_select", _dev_ptr(d_accum), ctypes.byref(d), int(max_samples), _dev_ptr(d_pixels), int(capacity),
+                     _dev_ptr(d_scratch), _dev_ptr(d_sel_state))
 
     def accum_add_at(self, d_samples, d_pixels, n, d_accum, d_state, width, height, rel_error=0.02, lum_floor=2.0 ** -10, min_samples=16,
                      done_permille=950, stream=None):
@@ -940,9 +894,8 @@ class RayTracer:
         over every pixel, `frames` advanced.  n = 0 refreshes the report only (d_samples and d_pixels may be None).  A pixel may be
         listed at most once.  Raw device pointers or CUDA tensors; asynchronous on `stream` (default torch.cuda.current_stream())."""
         d = L.make_accum_desc(width, height, rel_error, lum_floor, min_samples, done_permille)
-        self._on_torch_stream(stream, lambda h: self._check(self.lib.rt_accum_add_at(
-            self.ctx, _dev_ptr(d_samples), _dev_ptr(d_pixels), int(n), _dev_ptr(d_accum), ctypes.byref(d), _dev_ptr(d_state),
-            ctypes.c_void_p(h)), "rt_accum_add_at"))
+        self._launch(stream, "rt_accum_add_at", _dev_ptr(d_samples), _dev_ptr(d_pixels), int(n), _dev_ptr(d_accum), ctypes.byref(d),
+                     _dev_ptr(d_state))
 
     def accum_view(self, d_accum, d_out, width, height, mode="relerr", rel_error=0.02, lum_floor=2.0 ** -10, min_samples=16,
                    done_permille=950, stream=None):
@@ -951,8 +904,7 @@ class RayTracer:
         rule for the same keywords).  Asynchronous on torch stream `stream`."""
         d = L.make_accum_desc(width, height, rel_error, lum_floor, min_samples, done_permille)
         m = int(L.ACCUM_VIEWS.get(mode, mode))
-        self._on_torch_stream(stream, lambda h: self._check(self.lib.rt_accum_view(
-            self.ctx, _dev_ptr(d_accum), _dev_ptr(d_out), ctypes.byref(d), m, ctypes.c_void_p(h)), "rt_accum_view"))
+        self._launch(stream, "rt_accum_view", _dev_ptr(d_accum), _dev_ptr(d_out), ctypes.byref(d), m)
 
     # ---- denoising ------------------------------------------------------------------------
     def denoise_guide(self, d_hits, width, height, out=None, stream=None):
@@ -963,8 +915,7 @@ class RayTracer:
         import torch
         if out is None:
             out = torch.empty(int(width) * int(height) * 16, dtype=torch.uint8, device="cuda")
-        self._on_torch_stream(stream, lambda h: self._check(self.lib.rt_denoise_guide(
-            self.ctx, _dev_ptr(d_hits), _dev_ptr(out), int(width), int(height), ctypes.c_void_p(h)), "rt_denoise_guide"))
+        self._launch(stream, "rt_denoise_guide", _dev_ptr(d_hits), _dev_ptr(out), int(width), int(height))
         return out
 
     def denoise_alloc(self, width, height):
@@ -982,10 +933,8 @@ class RayTracer:
         pack and every present submit take as it stands.  Raw device pointers or CUDA tensors, 16-byte aligned; asynchronous on
         torch stream `stream` (default torch.cuda.current_stream()): 1 + iterations launches, no host synchronisation."""
         d = L.make_denoise_desc(width, height, iterations, normal_log2_power, sigma_lum, lum_eps, min_count)
-        mom = _dev_ptr(d_moments) if d_moments is not None else None
-        self._on_torch_stream(stream, lambda h: self._check(self.lib.rt_denoise(
-            self.ctx, _dev_ptr(d_image), mom, _dev_ptr(d_guide), _dev_ptr(d_scratch), _dev_ptr(d_out), ctypes.byref(d),
-            ctypes.c_void_p(h)), "rt_denoise"))
+        self._launch(stream, "rt_denoise", _dev_ptr(d_image), _dev_ptr(d_moments), _dev_ptr(d_guide), _dev_ptr(d_scratch), _dev_ptr(d_out),
+                     ctypes.byref(d))
 
     # ---- reprojection ------------------------------------------------------------------------
     def reproject(self, d_accum_prev, d_hits_prev, d_hits_cur, d_accum_cur, d_report, prev, cur, normal_cos_min=0.9, plane_tol=0.01,
@@ -998,9 +947,8 @@ class RayTracer:
         torch.cuda.current_stream()): a clear and one launch, no host synchronisation.  The caller swaps the accumulators and
         the hits afterwards."""
         d = L.make_reproject_desc(prev, cur, normal_cos_min, plane_tol, max_history)
-        self._on_torch_stream(stream, lambda h: self._check(self.lib.rt_accum_reproject(
-            self.ctx, _dev_ptr(d_accum_prev), _dev_ptr(d_hits_prev), _dev_ptr(d_hits_cur), _dev_ptr(d_accum_cur), ctypes.byref(d),
-            _dev_ptr(d_report), ctypes.c_void_p(h)), "rt_accum_reproject"))
+        self._launch(stream, "rt_accum_reproject", _dev_ptr(d_accum_prev), _dev_ptr(d_hits_prev), _dev_ptr(d_hits_cur),
+                     _dev_ptr(d_accum_cur), ctypes.byref(d), _dev_ptr(d_report))
 
     reproject_layout = staticmethod(reproject_layout)
     reproject_project = staticmethod(reproject_project)
@@ -1024,7 +972,7 @@ class RayTracer:
     def present_configure(self, slots):
         """Number of frames that can be on their way to the host at once (2..8, default 3); expires every earlier ticket and
         is refused while one is outstanding (submitted, not yet waited for or polled ready)."""
-        self._check(self.lib.rt_present_configure(self.ctx, int(slots)), "rt_present_configure")
+        self._call("rt_present_configure", int(slots))
 
     def present_submit(self, d_image, width, height, format="linear", flip=False, exposure=1.0, stream=None,
                        tone=None, white=1.0, d_exposure=None):
@@ -1033,21 +981,18 @@ class RayTracer:
         Ordered on torch stream `stream` (default torch.cuda.current_stream()): later work on that stream may overwrite d_image
         at once, and the copy overlaps it.  Does not block the host."""
         d = L.make_display_desc(width, height, format, flip, exposure)
-        t = ctypes.c_uint64()
-        if tone is None and d_exposure is None:
-            self._on_torch_stream(stream, lambda h: self._check(self.lib.rt_present_submit(
-                self.ctx, _dev_ptr(d_image), ctypes.byref(d), ctypes.c_void_p(h), ctypes.byref(t)), "rt_present_submit"))
+        td, t = _tone(tone, white, d_exposure), ctypes.c_uint64()
+        if td is None:
+            self._launch(stream, "rt_present_submit", _dev_ptr(d_image), ctypes.byref(d), after=(ctypes.byref(t),))
         else:
-            td = L.make_tone_desc(tone or "none", white, d_exposure)
-            self._on_torch_stream(stream, lambda h: self._check(self.lib.rt_present_submit_toned(
-                self.ctx, _dev_ptr(d_image), ctypes.byref(d), ctypes.byref(td), ctypes.c_void_p(h), ctypes.byref(t)), "rt_present_submit_toned"))
+            self._launch(stream, "rt_present_submit_toned", _dev_ptr(d_image), ctypes.byref(d), ctypes.byref(td), after=(ctypes.byref(t),))
         self._present_issued(t.value, "rgba8", width, height, d.format)
         return t.value
 
     def present_poll(self, ticket):
         """True once present_wait(ticket) would not block."""
         ready = ctypes.c_int(0)
-        self._check(self.lib.rt_present_poll(self.ctx, int(ticket), ctypes.byref(ready)), "rt_present_poll")
+        self._call("rt_present_poll", int(ticket), ctypes.byref(ready))
         return bool(ready.value)
 
     def present_wait(self, ticket, copy=True):
@@ -1073,7 +1018,7 @@ class RayTracer:
     def _present_pinned(self, ticket, copy):
         """rt_present_wait -> the ticket's bytes, uint8 [n]: a copy, or a read-only view of the ring's pinned slot."""
         p, n = ctypes.c_void_p(), ctypes.c_size_t(0)
-        self._check(self.lib.rt_present_wait(self.ctx, int(ticket), ctypes.byref(p), ctypes.byref(n)), "rt_present_wait")
+        self._call("rt_present_wait", int(ticket), ctypes.byref(p), ctypes.byref(n))
         view = np.frombuffer((ctypes.c_uint8 * n.value).from_address(p.value), dtype=np.uint8)
         if copy:
             return view.copy()
@@ -1088,20 +1033,15 @@ class RayTracer:
         display_pack's for format=`transfer` with the same `exposure`, `tone`, `white` and `d_exposure`; matrix "bt709" / "bt601",
         range "limited" / "full"; `flip` makes output row 0 the top image row.  Asynchronous on torch stream `stream`."""
         d = L.make_yuv_desc(width, height, format, matrix, range, transfer, flip, exposure)
-        t = None if tone is None and d_exposure is None else L.make_tone_desc(tone or "none", white, d_exposure)
-        self._on_torch_stream(stream, lambda h: self._check(self.lib.rt_display_pack_yuv(
-            self.ctx, _dev_ptr(d_image), _dev_ptr(d_out), ctypes.byref(d), ctypes.byref(t) if t is not None else None, ctypes.c_void_p(h)),
-            "rt_display_pack_yuv"))
+        self._launch(stream, "rt_display_pack_yuv", _dev_ptr(d_image), _dev_ptr(d_out), ctypes.byref(d), _ref(_tone(tone, white, d_exposure)))
 
     def present_submit_yuv(self, d_image, width, height, format="nv12", matrix="bt709", range="limited", transfer="srgb",
                            flip=False, exposure=1.0, tone=None, white=1.0, d_exposure=None, stream=None):
         """present_submit with display_pack_yuv's frame: same ring, same ticket sequence.  Wait for the ticket with present_wait_yuv."""
         d = L.make_yuv_desc(width, height, format, matrix, range, transfer, flip, exposure)
-        td = None if tone is None and d_exposure is None else L.make_tone_desc(tone or "none", white, d_exposure)
         t = ctypes.c_uint64()
-        self._on_torch_stream(stream, lambda h: self._check(self.lib.rt_present_submit_yuv(
-            self.ctx, _dev_ptr(d_image), ctypes.byref(d), ctypes.byref(td) if td is not None else None, ctypes.c_void_p(h), ctypes.byref(t)),
-            "rt_present_submit_yuv"))
+        self._launch(stream, "rt_present_submit_yuv", _dev_ptr(d_image), ctypes.byref(d), _ref(_tone(tone, white, d_exposure)),
+                     after=(ctypes.byref(t),))
         self._present_issued(t.value, "yuv", width, height, d.format)
         return t.value
 
@@ -1130,9 +1070,8 @@ class RayTracer:
         Raw device pointers or CUDA tensors, 16-byte aligned, not overlapping.  Asynchronous on torch stream `stream`."""
         yd = L.make_yuv_desc(width, height, format, "bt601", "full")
         jd = L.make_jpeg_desc(width, height, quality, restart_interval)
-        self._on_torch_stream(stream, lambda h: self._check(self.lib.rt_jpeg_encode(
-            self.ctx, _dev_ptr(d_planes), ctypes.byref(yd), ctypes.byref(jd), _dev_ptr(d_scratch), _dev_ptr(d_out), int(cap_bytes),
-            _dev_ptr(d_state), ctypes.c_void_p(h)), "rt_jpeg_encode"))
+        self._launch(stream, "rt_jpeg_encode", _dev_ptr(d_planes), ctypes.byref(yd), ctypes.byref(jd), _dev_ptr(d_scratch), _dev_ptr(d_out),
+                     int(cap_bytes), _dev_ptr(d_state))
 
     def display_pack_jpeg(self, d_image, d_scratch, d_out, cap_bytes, d_state, width, height, format="nv12", quality=90, restart_interval=None,
                           transfer="srgb", flip=True, exposure=1.0, tone=None, white=1.0, d_exposure=None, stream=None):
@@ -1140,10 +1079,8 @@ class RayTracer:
         `format`) into the scratch, then jpeg_encode.  flip=True (the default here) makes the file upright."""
         yd = L.make_yuv_desc(width, height, format, "bt601", "full", transfer, flip, exposure)
         jd = L.make_jpeg_desc(width, height, quality, restart_interval)
-        td = None if tone is None and d_exposure is None else L.make_tone_desc(tone or "none", white, d_exposure)
-        self._on_torch_stream(stream, lambda h: self._check(self.lib.rt_display_pack_jpeg(
-            self.ctx, _dev_ptr(d_image), ctypes.byref(yd), ctypes.byref(td) if td is not None else None, ctypes.byref(jd), _dev_ptr(d_scratch),
-            _dev_ptr(d_out), int(cap_bytes), _dev_ptr(d_state), ctypes.c_void_p(h)), "rt_display_pack_jpeg"))
+        self._launch(stream, "rt_display_pack_jpeg", _dev_ptr(d_image), ctypes.byref(yd), _ref(_tone(tone, white, d_exposure)), ctypes.byref(jd),
+                     _dev_ptr(d_scratch), _dev_ptr(d_out), int(cap_bytes), _dev_ptr(d_state))
 
     def present_submit_jpeg(self, d_image, width, height, cap_bytes=0, format="nv12", quality=90, restart_interval=None, transfer="srgb",
                             flip=True, exposure=1.0, tone=None, white=1.0, d_exposure=None, stream=None):
@@ -1151,11 +1088,9 @@ class RayTracer:
         to cap_bytes of stream (0: the frame's worst case).  Wait for the ticket with present_wait_jpeg."""
         yd = L.make_yuv_desc(width, height, format, "bt601", "full", transfer, flip, exposure)
         jd = L.make_jpeg_desc(width, height, quality, restart_interval)
-        td = None if tone is None and d_exposure is None else L.make_tone_desc(tone or "none", white, d_exposure)
         t = ctypes.c_uint64()
-        self._on_torch_stream(stream, lambda h: self._check(self.lib.rt_present_submit_jpeg(
-            self.ctx, _dev_ptr(d_image), ctypes.byref(yd), ctypes.byref(td) if td is not None else None, ctypes.byref(jd), int(cap_bytes),
-            ctypes.c_void_p(h), ctypes.byref(t)), "rt_present_submit_jpeg"))
+        self._launch(stream, "rt_present_submit_jpeg", _dev_ptr(d_image), ctypes.byref(yd), _ref(_tone(tone, white, d_exposure)), ctypes.byref(jd),
+                     int(cap_bytes), after=(ctypes.byref(t),))
         self._present_issued(t.value, "jpeg", width, height, yd.format)
         return t.value
 
@@ -1175,15 +1110,14 @@ class RayTracer:
 
     def tile_costs(self):
         """(costs[tilesY, tilesX] uint32, cycles/64 per tile) of the last feedback-scheduled launch."""
-        import numpy as _np
         n, tx = ctypes.c_int(0), ctypes.c_int(0)
         probe = (ctypes.c_uint32 * 1)()
-        self._check(self.lib.rt_debug_tile_costs(self.ctx, probe, 0, ctypes.byref(n), ctypes.byref(tx)), "rt_debug_tile_costs")
+        self._call("rt_debug_tile_costs", probe, 0, ctypes.byref(n), ctypes.byref(tx))
         if n.value == 0:
-            return _np.zeros((0, 0), dtype=_np.uint32)
+            return np.zeros((0, 0), dtype=np.uint32)
         out = (ctypes.c_uint32 * n.value)()
-        self._check(self.lib.rt_debug_tile_costs(self.ctx, out, n.value, ctypes.byref(n), ctypes.byref(tx)), "rt_debug_tile_costs")
-        return _np.frombuffer(out, dtype=_np.uint32).reshape(-1, tx.value).copy()
+        self._call("rt_debug_tile_costs", out, n.value, ctypes.byref(n), ctypes.byref(tx))
+        return np.frombuffer(out, dtype=np.uint32).reshape(-1, tx.value).copy()
 
     def frame(self, params, enable_ao=True, enable_taa=True, taa_blend=0.1, bloom_threshold=1.0, bloom_strength=0.5,
               bloom_iterations=10, ao_samples=None, ao_noise=None, d_display=None):
@@ -1198,14 +1132,13 @@ class RayTracer:
             for name, arr, n in (("aoSamples", ao_samples, 192), ("aoNoise", ao_noise, 64)):
                 a = np.ascontiguousarray(arr, dtype=np.float32).reshape(n)
                 keep.append(a)
-                setattr(d, name, a.ctypes.data_as(ctypes.POINTER(ctypes.c_float)))
-        self._check(self.lib.rt_frame(self.ctx, ctypes.byref(params), ctypes.byref(d),
-                                      ctypes.c_void_p(d_display) if d_display else None), "rt_frame")
+                setattr(d, name, _typed(a, ctypes.c_float))
+        self._call("rt_frame", ctypes.byref(params), ctypes.byref(d), _dev_ptr(d_display))
 
     def frame_surfaces(self):
         """(dColor, dPosition, dNormal, dAO, dHistory) device pointers (ints or None) after rt_frame."""
         ptrs = [ctypes.c_void_p() for _ in range(5)]
-        self._check(self.lib.rt_frame_surfaces(self.ctx, *[ctypes.byref(q) for q in ptrs]), "rt_frame_surfaces")
+        self._call("rt_frame_surfaces", *[ctypes.byref(q) for q in ptrs])
         return tuple(q.value for q in ptrs)
 
     def equirect_to_cubemap(self, equirect_rgb, size, d_faces_out=None, install=False):
@@ -1213,9 +1146,7 @@ class RayTracer:
         (d_faces_out: raw pointer, 6*size*size*3 halfs) and / or installed as this context's skybox."""
         e = np.ascontiguousarray(equirect_rgb, dtype=np.float32)
         h, w = e.shape[:2]
-        self._check(self.lib.rt_equirect_to_cubemap(self.ctx, e.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), w, h, size,
-                                                    ctypes.c_void_p(d_faces_out) if d_faces_out else None, int(bool(install))),
-                    "rt_equirect_to_cubemap")
+        self._call("rt_equirect_to_cubemap", _typed(e, ctypes.c_float), w, h, size, _dev_ptr(d_faces_out), int(bool(install)))
 
     def ssao(self, d_position, d_normal, d_out, width, height, noise, samples, projection, view, stream=None):
         """SSAO on the G-buffer surfaces (raw device pointers as ints); noise [nh,nw,4], samples [64,3],
@@ -1223,150 +1154,104 @@ class RayTracer:
         fa = lambda x, n: np.ascontiguousarray(x, dtype=np.float32).reshape(n)
         noise = np.ascontiguousarray(noise, dtype=np.float32)
         nh, nw = noise.shape[:2]
-        fp = lambda x: x.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
+        fp = lambda x: _typed(x, ctypes.c_float)
         nz, sm, pj, vw = fa(noise, nh * nw * 4), fa(samples, 192), fa(projection, 16), fa(view, 16)
-        self._check(self.lib.rt_ssao(self.ctx, ctypes.c_void_p(d_position), ctypes.c_void_p(d_normal), ctypes.c_void_p(d_out),
-                                     width, height, fp(nz), nw, nh, fp(sm), fp(pj), fp(vw),
-                                     ctypes.c_void_p(stream) if stream else None), "rt_ssao")
+        self._call("rt_ssao", _dev_ptr(d_position), _dev_ptr(d_normal), _dev_ptr(d_out), width, height, fp(nz), nw, nh, fp(sm), fp(pj),
+                   fp(vw), _dev_ptr(stream))
 
     def ssao_blur(self, d_in, d_out, width, height, horizontal=False, stream=None):
-        self._check(self.lib.rt_ssao_blur(self.ctx, ctypes.c_void_p(d_in), ctypes.c_void_p(d_out), width, height,
-                                          int(bool(horizontal)), ctypes.c_void_p(stream) if stream else None), "rt_ssao_blur")
+        self._call("rt_ssao_blur", _dev_ptr(d_in), _dev_ptr(d_out), width, height, int(bool(horizontal)), _dev_ptr(stream))
 
     def predicted_classes(self, n_tiles):
         """Cost classes (uint8[n_tiles], raster tile order) of the last predicted launch."""
         out = np.zeros(n_tiles, dtype=np.uint8)
         n = ctypes.c_int(0)
-        self._check(self.lib.rt_debug_predicted_classes(self.ctx, _ptr(out), n_tiles, ctypes.byref(n)), "rt_debug_predicted_classes")
+        self._call("rt_debug_predicted_classes", _ptr(out), n_tiles, ctypes.byref(n))
         return out
 
     def shadow_tables(self):
         """(dwords uint32[n], words per cell) of the current scene's shadow tables (headers + cells), or (None, 0)."""
         n, w = ctypes.c_size_t(0), ctypes.c_int(0)
-        self._check(self.lib.rt_debug_shadow_tables(self.ctx, None, 0, ctypes.byref(n), ctypes.byref(w)), "rt_debug_shadow_tables")
+        self._call("rt_debug_shadow_tables", None, 0, ctypes.byref(n), ctypes.byref(w))
         if n.value == 0:
             return None, 0
         out = np.zeros(n.value, dtype=np.uint32)
-        self._check(self.lib.rt_debug_shadow_tables(self.ctx, _ptr(out), n.value, ctypes.byref(n), ctypes.byref(w)), "rt_debug_shadow_tables")
+        self._call("rt_debug_shadow_tables", _ptr(out), n.value, ctypes.byref(n), ctypes.byref(w))
         return out, w.value
 
-    def debug_stats(self):
-        out = (ctypes.c_uint64 * 4)()
-        self._check(self.lib.rt_debug_stats(self.ctx, out), "rt_debug_stats")
+    def _counters(self, name, n):
+        """The n uint64 counters that the rt_debug_* entry point `name` fills, as a list."""
+        out = (ctypes.c_uint64 * n)()
+        self._call(name, out)
         return list(out)
 
+    def debug_stats(self):
+        return self._counters("rt_debug_stats", 4)
+
     def debug_stats_ex(self):
-        out = (ctypes.c_uint64 * 32)()
-        self._check(self.lib.rt_debug_stats_ex(self.ctx, out), "rt_debug_stats_ex")
-        return list(out)
+        return self._counters("rt_debug_stats_ex", 32)
 
     def debug_first_hit(self):
         """[normal, recorded, replayed] packet-kernel frames of this context since its creation (first-hit reuse)."""
-        out = (ctypes.c_uint64 * 3)()
-        self._check(self.lib.rt_debug_first_hit(self.ctx, out), "rt_debug_first_hit")
-        return list(out)
+        return self._counters("rt_debug_first_hit", 3)
 
     def debug_settled_tiles(self):
         """[tiles of the cached first-hit window, settled ones among them]; zeros without a valid cache."""
-        out = (ctypes.c_uint64 * 2)()
-        self._check(self.lib.rt_debug_settled_tiles(self.ctx, out), "rt_debug_settled_tiles")
-        return list(out)
+        return self._counters("rt_debug_settled_tiles", 2)
 
     def debug_settled_map(self):
         """The cached window's settled flags, one uint8 per 8x8 tile in row-major tile order (empty without a valid cache)."""
         n = self.debug_settled_tiles()[0]
         flags = (ctypes.c_uint8 * max(n, 1))()
-        self._check(self.lib.rt_debug_settled_map(self.ctx, flags, n), "rt_debug_settled_map")
+        self._call("rt_debug_settled_map", flags, n)
         return np.frombuffer(flags, dtype=np.uint8, count=n).copy()
 
     def deinterleave(self, d_src, d_dst, width, height, bytes_per_pixel, strip_rows, strip_count,
                      rank_stride_bytes, stream=None):
-        self._check(self.lib.rt_deinterleave(self.ctx, ctypes.c_void_p(d_src), ctypes.c_void_p(d_dst), width,
-                                             height, bytes_per_pixel, strip_rows, strip_count, rank_stride_bytes,
-                                             ctypes.c_void_p(stream) if stream else None), "rt_deinterleave")
+        self._call("rt_deinterleave", _dev_ptr(d_src), _dev_ptr(d_dst), width, height, bytes_per_pixel, strip_rows, strip_count,
+                   rank_stride_bytes, _dev_ptr(stream))
 
     def wire_pack(self, d_color, d_pos, d_normal, d_wire, n_pixels, stream=None):
         """This rank's three surfaces -> the 30 B/pixel gather wire format (device pointers as ints)."""
-        self._check(self.lib.rt_wire_pack(self.ctx, ctypes.c_void_p(d_color), ctypes.c_void_p(d_pos), ctypes.c_void_p(d_normal),
-                                          ctypes.c_void_p(d_wire), n_pixels, ctypes.c_void_p(stream) if stream else None),
-                    "rt_wire_pack")
+        self._call("rt_wire_pack", _dev_ptr(d_color), _dev_ptr(d_pos), _dev_ptr(d_normal), _dev_ptr(d_wire), n_pixels, _dev_ptr(stream))
 
     def wire_unpack(self, d_wire, rank_stride_bytes, rank_pixels, d_color, d_pos, d_normal, width, height, strip_rows,
                     strip_count, root=None, root_strips=1, stream=None):
         """Gathered wire buffers -> full rgba surfaces in image order (alpha restored to 1.0).  root = (d_color,
         d_pos, d_normal) of rank 0's own local surfaces: its rows are copied from there instead of wire slot 0."""
-        r = [ctypes.c_void_p(x) for x in root] if root else [None, None, None]
-        self._check(self.lib.rt_wire_unpack(self.ctx, ctypes.c_void_p(d_wire), rank_stride_bytes, rank_pixels, r[0], r[1], r[2],
-                                            root_strips, ctypes.c_void_p(d_color), ctypes.c_void_p(d_pos),
-                                            ctypes.c_void_p(d_normal), width, height, strip_rows, strip_count,
-                                            ctypes.c_void_p(stream) if stream else None), "rt_wire_unpack")
+        self._call("rt_wire_unpack", _dev_ptr(d_wire), rank_stride_bytes, rank_pixels, *[_dev_ptr(x) for x in root or (None,) * 3],
+                   root_strips, _dev_ptr(d_color), _dev_ptr(d_pos), _dev_ptr(d_normal), width, height, strip_rows, strip_count,
+                   _dev_ptr(stream))
 
 
-class MultiGpuRayTracer:
+class MultiGpuRayTracer(_Handle):
     """rt_mgpu_*: one frame on N devices from one process; the devices' kernels store their strips straight into device 0's frame
     (include/rt_mi355.h).  `devices` may repeat an id (the N-way plan on one GPU)."""
+    _PREFIX = "rt_mgpu_"
+    m = property(lambda self: self.ctx, doc="the rt_mgpu handle")
 
     def __init__(self, devices, strip_rows=8):
-        self.lib = load_library()
-        self.m = ctypes.c_void_p()
-        arr = (ctypes.c_int * len(devices))(*devices)
-        rc = self.lib.rt_mgpu_create(ctypes.byref(self.m), arr, len(devices))
-        if rc:
-            self.m = None
-            raise RtError(rc, "rt_mgpu_create (peer access between the devices?)")
+        self._create("rt_mgpu_create (peer access between the devices?)", (ctypes.c_int * len(devices))(*devices), len(devices))
         self.n = len(devices)
-        self._check(self.lib.rt_mgpu_set_strip_rows(self.m, strip_rows), "rt_mgpu_set_strip_rows")
-        self._size = None
-
-    def _check(self, rc, what):
-        if rc:
-            raise RtError(rc, f"{what}: {self.lib.rt_mgpu_last_error(self.m).decode()}")
-
-    def close(self):
-        if getattr(self, "m", None):
-            self.lib.rt_mgpu_destroy(self.m)
-            self.m = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._call("rt_mgpu_set_strip_rows", strip_rows)
 
     def load(self, scene):
         objects, lights = np.ascontiguousarray(scene.objects), np.ascontiguousarray(scene.lights)
-        self._check(self.lib.rt_mgpu_set_scene(self.m, _ptr(objects) if len(objects) else None, len(objects),
-                                               _ptr(lights) if len(lights) else None, len(lights)), "rt_mgpu_set_scene")
+        self._call("rt_mgpu_set_scene", _ptr(objects) if len(objects) else None, len(objects),
+                   _ptr(lights) if len(lights) else None, len(lights))
         if scene.noise is None:
-            self._check(self.lib.rt_mgpu_set_noise(self.m, None, 0, 0), "rt_mgpu_set_noise")
+            self._call("rt_mgpu_set_noise", None, 0, 0)
         else:
             r8 = np.ascontiguousarray(scene.noise, dtype=np.uint8)
-            self._check(self.lib.rt_mgpu_set_noise(self.m, _ptr(r8), r8.shape[1], r8.shape[0]), "rt_mgpu_set_noise")
+            self._call("rt_mgpu_set_noise", _ptr(r8), r8.shape[1], r8.shape[0])
         faces = np.ascontiguousarray(scene.skybox, dtype=np.float16) if scene.use_skybox else None
-        self._check(self.lib.rt_mgpu_set_skybox(self.m, _ptr(faces), faces.shape[1] if faces is not None else 0), "rt_mgpu_set_skybox")
+        self._call("rt_mgpu_set_skybox", _ptr(faces), faces.shape[1] if faces is not None else 0)
 
     def render(self, params):
-        self._check(self.lib.rt_mgpu_render(self.m, ctypes.byref(params)), "rt_mgpu_render")
+        self._call("rt_mgpu_render", ctypes.byref(params))
         self._size = (params.width, params.height)
-
-    def sync(self):
-        self._check(self.lib.rt_mgpu_sync(self.m), "rt_mgpu_sync")
-
-    def readback(self):
-        w, h = self._size
-        col = np.empty((h, w, 4), dtype=np.float32)
-        pos = np.empty((h, w, 4), dtype=np.float32)
-        nrm = np.empty((h, w, 4), dtype=np.float16)
-        self._check(self.lib.rt_mgpu_readback(self.m, _ptr(col), _ptr(pos), _ptr(nrm)), "rt_mgpu_readback")
-        return col, pos, nrm
 
     def last_ms(self):
         out = (ctypes.c_float * self.n)()
-        self._check(self.lib.rt_mgpu_last_ms(self.m, out, self.n), "rt_mgpu_last_ms")
+        self._call("rt_mgpu_last_ms", out, self.n)
         return list(out)

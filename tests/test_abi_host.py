@@ -5,7 +5,6 @@ and the host-side feeders (AABB generation, camera vectors, scene text parser) b
 the reference's host code.  No compute call is made here."""
 import ctypes
 import os
-import re
 import subprocess
 
 import numpy as np
@@ -19,8 +18,8 @@ HEADER = os.path.join(REPO, "include", "rt_mi355.h")
 
 
 def declared_symbols():
-    text = open(HEADER).read()
-    return sorted(set(re.findall(r"^(?:int|size_t|const char \*)\s*\*?(rt_[a-z_0-9]+)\s*\(", text, flags=re.M)))
+    from test_binding_host import prototypes
+    return sorted({p.name for p in prototypes(HEADER)})
 
 
 def test_library_exports_every_declared_symbol(host):

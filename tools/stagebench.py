@@ -130,8 +130,9 @@ def close_all(tracers):
 
 
 def check(t, rc, what):
+    """t._check(rc, what) when rc says failure: for the stage benchmarks that call the library directly inside timed loops."""
     if rc:
-        raise host.RtError(rc, f"{what}: {t.lib.rt_last_error(t.ctx).decode()}")
+        t._check(rc, what)
 
 
 @functools.cache
@@ -175,10 +176,10 @@ def _rendered(t, p):
     lib, ctx, d_color = t.lib, t.ctx, ctypes.c_void_p()
 
     def render():
-        check(t, lib.rt_render(ctx, ctypes.byref(p)), "rt_render")
+        t._check(lib.rt_render(ctx, ctypes.byref(p)), "rt_render")
 
     render()
-    check(t, lib.rt_get_surfaces(ctx, ctypes.byref(d_color), None, None), "rt_get_surfaces")
+    t._check(lib.rt_get_surfaces(ctx, ctypes.byref(d_color), None, None), "rt_get_surfaces")
     return render, d_color
 
 
@@ -207,8 +208,8 @@ def present_loop(t, p, submit):
             render()
             submit(d_color, ctypes.byref(tk))
             if prev is not None:
-                check(t, t.lib.rt_present_wait(t.ctx, prev, ctypes.byref(px), ctypes.byref(nb)), "rt_present_wait")
+                t._check(t.lib.rt_present_wait(t.ctx, prev, ctypes.byref(px), ctypes.byref(nb)), "rt_present_wait")
             prev = tk.value
-        check(t, t.lib.rt_present_wait(t.ctx, prev, ctypes.byref(px), ctypes.byref(nb)), "rt_present_wait")
+        t._check(t.lib.rt_present_wait(t.ctx, prev, ctypes.byref(px), ctypes.byref(nb)), "rt_present_wait")
         t.sync()
     return loop
