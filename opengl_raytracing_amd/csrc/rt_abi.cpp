@@ -1,8 +1,9 @@
-// rt_abi.cpp -- implementation of the C ABI declared in include/rt_mi355.h: context,
-// device buffers, per-frame constants, launches, readback, timing.  Each entry point
+// rt_abi.cpp -- the tracer's entry points of the C ABI declared in include/rt_mi355.h: context,
+// device buffers, per-frame constants, launches, ray queries and shading, readback, timing, the debug views.  Each entry point
 // stands in for a piece of the reference's dispatch site
 // (/root/reference/src/ForwardShadingPipeline.cpp:155-182); see the header for the map.
-// The tile order of a frame and the stream records are rt_sched.cpp's.
+// The tile order of a frame and the stream records are rt_sched.cpp's; the post passes and rt_frame are rt_post.cpp's, the
+// strip transport rt_wire.cpp's, the display path rt_display.cpp's.
 #include <math.h>
 #include <stdio.h>
 #include <string.h>
@@ -40,21 +41,19 @@ void hemi_local(float rx, float ry, float out[4]) {
     out[3] = 0.0f;
 }
 
-int validate_params(rt_context *c, const rt_params *p) {
-    if (!p) return fail(c, RT_ERR_INVALID_ARG, "params is NULL");
-    if (p->width <= 0 || p->height <= 0) return fail(c, RT_ERR_INVALID_ARG, "width/height must be positive");
-    if (p->regionW < 0 || p->regionH < 0 || p->x0 < 0 || p->y0 < 0)
-        return fail(c, RT_ERR_INVALID_ARG, "negative window");
-    if (p->stripRows <= 0) return fail(c, RT_ERR_INVALID_ARG, "bad strip mapping");
-    if (p->stripCycleRows > 0) {
-        if (p->stripOffsetRows < 0 || p->stripOffsetRows + p->stripRows > p->stripCycleRows)
-            return fail(c, RT_ERR_INVALID_ARG, "bad strip mapping (offset + rows exceed the cycle)");
-    } else if (p->stripCycleRows < 0 || p->stripCount <= 0 || p->stripIndex < 0 || p->stripIndex >= p->stripCount) {
-        return fail(c, RT_ERR_INVALID_ARG, "bad strip mapping");
-    }
-    if (p->maxRayDepth < 0 || p->maxRayDepth > RT_MAX_DEPTH)
-        return fail(c, RT_ERR_INVALID_ARG, "maxRayDepth outside [0, 32]");
-    return RT_OK;
+// The most items (rays, pixels, records) of one launch: 2^31 - 1 workgroups of 256
+constexpr size_t kMaxLaunchItems = ((size_t)0x7fffffff) * 256;
+
+// rt_pick / rt_camera_rays_at: only the camera, image size and ray fields of p matter, so p is validated, and the frame built,
+// with an identity window
+rt_params identity_window(const rt_params &p) {
+    rt_params q = p;
+    q.x0 = q.y0 = 0;
+    q.regionW = q.width;
+    q.regionH = q.height;
+    q.stripRows = q.stripCount = 1;
+    q.stripIndex = q.stripCycleRows = q.stripOffsetRows = 0;
+    return q;
 }
 
 void build_frame(const rt_context *c, const rt_params *p, RtFrame *f) {
@@ -109,20 +108,8 @@ RtFirstHit::Mode first_hit_mode(rt_context *c, const RtFirstHitKey &key) {
     return mode;
 }
 
-int launch_frame(rt_context *c, const rt_params *p, float4 *dColor, float4 *dPos, uint2 *dNormal,
-                 unsigned long long *counter, hipStream_t s, bool timed, int countMode, bool imageStores, bool reusable);
-
-// One frame.  Whatever goes wrong in a launch that could have recorded or replayed (a refusal, a failed HIP call) leaves the
-// first-hit state empty: the next frame is a normal one.
-int launch(rt_context *c, const rt_params *p, float4 *dColor, float4 *dPos, uint2 *dNormal,
-           unsigned long long *counter, hipStream_t s, bool timed, int countMode = 1, bool imageStores = false) {
-    // instrumented launches and the exhaustive kernel always trace the whole frame and leave the cache as it is
-    const bool reusable = c->variant == 1 && !counter;
-    const int rc = launch_frame(c, p, dColor, dPos, dNormal, counter, s, timed, countMode, imageStores, reusable);
-    if (rc != RT_OK && reusable) c->firstHit.invalidate();
-    return rc;
-}
-
+// The launches of one frame (launch(), below, is what the entry points call): the first-hit mode, the scheduler's plan, the
+// render kernel between the timing events.
 int launch_frame(rt_context *c, const rt_params *p, float4 *dColor, float4 *dPos, uint2 *dNormal,
                  unsigned long long *counter, hipStream_t s, bool timed, int countMode, bool imageStores, bool reusable) {
     RtFrame f;
@@ -164,6 +151,17 @@ int launch_frame(rt_context *c, const rt_params *p, float4 *dColor, float4 *dPos
         else c->firstHit.counts[RtFirstHit::NORMAL]++;
     }
     return RT_OK;
+}
+
+// One frame.  Whatever goes wrong in a launch that could have recorded or replayed (a refusal, a failed HIP call) leaves the
+// first-hit state empty: the next frame is a normal one.
+int launch(rt_context *c, const rt_params *p, float4 *dColor, float4 *dPos, uint2 *dNormal,
+           unsigned long long *counter, hipStream_t s, bool timed, int countMode = 1, bool imageStores = false) {
+    // instrumented launches and the exhaustive kernel always trace the whole frame and leave the cache as it is
+    const bool reusable = c->variant == 1 && !counter;
+    const int rc = launch_frame(c, p, dColor, dPos, dNormal, counter, s, timed, countMode, imageStores, reusable);
+    if (rc != RT_OK && reusable) c->firstHit.invalidate();
+    return rc;
 }
 
 // A launch on the caller's stream (null = the context's own) that reads the device scene: a foreign stream first orders
@@ -366,7 +364,7 @@ int rt_trace_rays(rt_context *c, const void *dRays, size_t nRays, int mode, void
     if (nRays == 0) return RT_OK;
     if (!dRays || !dOut) return fail(c, RT_ERR_INVALID_ARG, "NULL ray or result pointer");
     if (((uintptr_t)dRays | (uintptr_t)dOut) & 15u) return fail(c, RT_ERR_INVALID_ARG, "ray and result pointers must be 16-byte aligned");
-    if (nRays > ((size_t)0x7fffffff) * 256) return fail(c, RT_ERR_TOO_LARGE, "too many rays in one call");
+    if (nRays > kMaxLaunchItems) return fail(c, RT_ERR_TOO_LARGE, "too many rays in one call");
     HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t s;
     int rc = caller_stream(c, hipStream, &s);
@@ -397,19 +395,14 @@ int rt_camera_rays(rt_context *c, const rt_params *p, void *dRays, void *hipStre
 int rt_camera_rays_at(rt_context *c, const rt_params *p, const void *dPixels, size_t n, void *dRays, void *hipStream) {
     if (!c) return RT_ERR_INVALID_ARG;
     if (!p) return fail(c, RT_ERR_INVALID_ARG, "params is NULL");
-    rt_params q = *p;
-    q.x0 = q.y0 = 0;
-    q.regionW = q.width;
-    q.regionH = q.height;
-    q.stripRows = q.stripCount = 1;
-    q.stripIndex = q.stripCycleRows = q.stripOffsetRows = 0;
+    const rt_params q = identity_window(*p);
     int rc = validate_params(c, &q);
     if (rc) return rc;
     if (n == 0) return RT_OK;
     if (!dPixels || !dRays) return fail(c, RT_ERR_INVALID_ARG, "NULL pixel list or ray pointer");
     if ((uintptr_t)dPixels & 7u) return fail(c, RT_ERR_INVALID_ARG, "pixel list pointer must be 8-byte aligned");
     if ((uintptr_t)dRays & 15u) return fail(c, RT_ERR_INVALID_ARG, "ray pointer must be 16-byte aligned");
-    if (n > ((size_t)0x7fffffff) * 256) return fail(c, RT_ERR_TOO_LARGE, "too many pixels in one call");
+    if (n > kMaxLaunchItems) return fail(c, RT_ERR_TOO_LARGE, "too many pixels in one call");
     HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t s;
     if ((rc = caller_stream(c, hipStream, &s))) return rc;
@@ -435,7 +428,7 @@ int rt_shade_rays(rt_context *c, const rt_params *p, const void *dRays, const vo
     if (((uintptr_t)dRays | (uintptr_t)dColor | (uintptr_t)dPosition) & 15u)
         return fail(c, RT_ERR_INVALID_ARG, "ray, colour and position pointers must be 16-byte aligned");
     if (((uintptr_t)dPixels | (uintptr_t)dNormal) & 7u) return fail(c, RT_ERR_INVALID_ARG, "pixel and normal pointers must be 8-byte aligned");
-    if (nRays > ((size_t)0x7fffffff) * 256) return fail(c, RT_ERR_TOO_LARGE, "too many rays in one call");
+    if (nRays > kMaxLaunchItems) return fail(c, RT_ERR_TOO_LARGE, "too many rays in one call");
     HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t s;
     if ((rc = caller_stream(c, hipStream, &s))) return rc;
@@ -451,13 +444,7 @@ int rt_pick(rt_context *c, const rt_params *p, int px, int py, rt_hit *hit) {
     if (!c) return RT_ERR_INVALID_ARG;
     if (!hit) return fail(c, RT_ERR_INVALID_ARG, "NULL hit pointer");
     if (!p) return fail(c, RT_ERR_INVALID_ARG, "params is NULL");
-    // only the camera, image size and ray fields matter: validate them with an identity window
-    rt_params q = *p;
-    q.x0 = q.y0 = 0;
-    q.regionW = q.width;
-    q.regionH = q.height;
-    q.stripRows = q.stripCount = 1;
-    q.stripIndex = q.stripCycleRows = q.stripOffsetRows = 0;
+    const rt_params q = identity_window(*p);
     int rc = validate_params(c, &q);
     if (rc) return rc;
     if (px < 0 || py < 0 || px >= q.width || py >= q.height) return fail(c, RT_ERR_INVALID_ARG, "pixel outside the image");
@@ -517,9 +504,6 @@ int rt_last_kernel_ms(rt_context *c, float *ms) {
     return RT_OK;
 }
 
-static int count_rays_impl(rt_context *c, const rt_params *p, uint64_t *rays, int countMode);
-int rt_count_rays(rt_context *c, const rt_params *p, uint64_t *rays) { return count_rays_impl(c, p, rays, 1); }
-int rt_count_rays_traced(rt_context *c, const rt_params *p, uint64_t *rays) { return count_rays_impl(c, p, rays, 2); }
 static int count_rays_impl(rt_context *c, const rt_params *p, uint64_t *rays, int countMode) {
     if (!c || !rays) return RT_ERR_INVALID_ARG;
     int rc = validate_params(c, p);
@@ -542,6 +526,8 @@ static int count_rays_impl(rt_context *c, const rt_params *p, uint64_t *rays, in
     for (int k = 0; k < 32; k++) c->lastStats[k] = v[k];
     return rc;
 }
+int rt_count_rays(rt_context *c, const rt_params *p, uint64_t *rays) { return count_rays_impl(c, p, rays, 1); }
+int rt_count_rays_traced(rt_context *c, const rt_params *p, uint64_t *rays) { return count_rays_impl(c, p, rays, 2); }
 
 int rt_set_variant(rt_context *c, int variant) {
     if (!c) return RT_ERR_INVALID_ARG;
@@ -638,37 +624,6 @@ int rt_debug_tile_costs(rt_context *c, unsigned *out, int cap, int *nTiles, int 
     return RT_OK;
 }
 
-int rt_taa_resolve(rt_context *c, const void *dCurrent, const void *dHistory, const void *dNormal, void *dOut, int width,
-                   int height, float blendFactor, float jitterX, float jitterY, void *hipStream) {
-    if (!c) return RT_ERR_INVALID_ARG;
-    if (!dCurrent || !dHistory || !dNormal || !dOut || width <= 0 || height <= 0)
-        return fail(c, RT_ERR_INVALID_ARG, "bad rt_taa_resolve arguments");
-    if (dOut == dCurrent || dOut == dHistory) return fail(c, RT_ERR_INVALID_ARG, "rt_taa_resolve cannot run in place");
-    HIP_TRY(c, hipSetDevice(c->device));
-    hipStream_t s = stream_or_own(c, hipStream);
-    HIP_TRY(c, rt_launch_taa_resolve(dCurrent, dHistory, dNormal, dOut, width, height, blendFactor, jitterX, jitterY, s));
-    return RT_OK;
-}
-
-int rt_bloom(rt_context *c, const void *dScene, void *dOut, int width, int height, float threshold, float strength,
-             int iterations, void *hipStream) {
-    if (!c) return RT_ERR_INVALID_ARG;
-    if (!dScene || !dOut || width <= 0 || height <= 0 || iterations < 0) return fail(c, RT_ERR_INVALID_ARG, "bad rt_bloom arguments");
-    if (dOut == dScene) return fail(c, RT_ERR_INVALID_ARG, "rt_bloom cannot run in place");     // the fused passes read neighbouring tiles' scene texels
-    HIP_TRY(c, hipSetDevice(c->device));
-    hipStream_t s = stream_or_own(c, hipStream);
-    const size_t npx = (size_t)width * height;
-    if (!(c->dBloom[0].holds(npx) && c->dBloom[1].holds(npx))) {
-        HIP_TRY(c, c->bloomUse.drain());       // the last pass in the old targets, on whichever stream it ran
-        HIP_TRY(c, c->dBloom[0].grow(npx));
-        HIP_TRY(c, c->dBloom[1].grow(npx));
-    }
-    HIP_TRY(c, c->bloomUse.acquire(s));
-    HIP_TRY(c, rt_launch_bloom(dScene, c->dBloom[0], c->dBloom[1], dOut, width, height, threshold, strength, iterations, s));
-    HIP_TRY(c, c->bloomUse.release(s));
-    return RT_OK;
-}
-
 const char *rt_last_error(rt_context *c) { return c ? c->err.c_str() : "NULL context"; }
 
 int rt_debug_mesa_math(const float *in, float *out, int n) {
@@ -690,198 +645,10 @@ int rt_debug_device_math(rt_context *c, int op, const void *dIn, void *dOut, siz
     if (n == 0) return RT_OK;
     if (!dIn || !dOut) return fail(c, RT_ERR_INVALID_ARG, "NULL input or output pointer");
     if (((uintptr_t)dIn | (uintptr_t)dOut) & 15u) return fail(c, RT_ERR_INVALID_ARG, "input and output pointers must be 16-byte aligned");
-    if (n > ((size_t)0x7fffffff) * 256) return fail(c, RT_ERR_TOO_LARGE, "too many records in one call");
+    if (n > kMaxLaunchItems) return fail(c, RT_ERR_TOO_LARGE, "too many records in one call");
     HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t s = stream_or_own(c, hipStream);
     HIP_TRY(c, rt_launch_device_math(op, (const uint4 *)dIn, (uint4 *)dOut, n, s));
-    return RT_OK;
-}
-
-int rt_equirect_to_cubemap(rt_context *c, const float *hEquirectRGB, int width, int height, int size, void *dFacesOut,
-                           int install) {
-    if (!c) return RT_ERR_INVALID_ARG;
-    if (!hEquirectRGB || width <= 0 || height <= 0 || size <= 0) return fail(c, RT_ERR_INVALID_ARG, "bad rt_equirect_to_cubemap arguments");
-    if (!dFacesOut && !install) return fail(c, RT_ERR_INVALID_ARG, "nowhere to put the faces");
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    const size_t npx = (size_t)width * height, faceBytes = (size_t)6 * size * size * 3 * sizeof(uint16_t);
-    DevBuf<float> rgb;
-    DevBuf<uint2> tex;                  // rgba16f
-    DevBuf<uint16_t> faces;
-    hipError_t e = rgb.grow(npx * 3);
-    if (e == hipSuccess) e = tex.grow(npx);
-    if (e == hipSuccess) e = faces.grow(faceBytes / sizeof(uint16_t));
-    if (e == hipSuccess) e = hipMemcpyAsync(rgb, hEquirectRGB, npx * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = rt_launch_equirect_to_cubemap(rgb, tex, width, height, size, faces, c->stream);
-    if (e == hipSuccess && dFacesOut) e = hipMemcpyAsync(dFacesOut, faces, faceBytes, hipMemcpyDeviceToDevice, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) return fail(c, RT_ERR_HIP, "rt_equirect_to_cubemap", e);
-    if (install) {
-        SCHED_TRY(c, drain());          // frames and shades on every stream read the old skybox
-        c->texGen++;
-        c->firstHit.invalidate();
-        c->dSky.swap(faces);            // (the old one goes with `faces`)
-        c->skySize = size;
-    }
-    return RT_OK;
-}
-
-int rt_ssao(rt_context *c, const void *dPosition, const void *dNormal, void *dOut, int width, int height, const float *hNoise,
-            int noiseW, int noiseH, const float *hSamples, const float *hProjection, const float *hView, void *hipStream) {
-    if (!c) return RT_ERR_INVALID_ARG;
-    if (!dPosition || !dNormal || !dOut || !hNoise || !hSamples || !hProjection || !hView || width <= 0 || height <= 0)
-        return fail(c, RT_ERR_INVALID_ARG, "bad rt_ssao arguments");
-    if (noiseW <= 0 || noiseH <= 0 || noiseW * noiseH > 16) return fail(c, RT_ERR_TOO_LARGE, "rotation texture larger than 16 texels");
-    if (dOut == dPosition || dOut == dNormal) return fail(c, RT_ERR_INVALID_ARG, "rt_ssao cannot run in place");   // samples read other pixels' G-buffer
-    HIP_TRY(c, hipSetDevice(c->device));
-    hipStream_t s = stream_or_own(c, hipStream);
-    const size_t npx = (size_t)width * height;
-    if (!c->dSsaoDepth.holds(npx)) {
-        HIP_TRY(c, c->ssaoUse.drain());        // the last pass that read the old plane, on whichever stream it ran
-        HIP_TRY(c, c->dSsaoDepth.grow(npx));
-    }
-    HIP_TRY(c, c->ssaoUse.acquire(s));
-    HIP_TRY(c, rt_launch_ssao(dPosition, dNormal, c->dSsaoDepth, dOut, width, height, hNoise, noiseW, noiseH, hSamples, hProjection,
-                              hView, s));
-    HIP_TRY(c, c->ssaoUse.release(s));
-    return RT_OK;
-}
-
-int rt_ssao_blur(rt_context *c, const void *dIn, void *dOut, int width, int height, int horizontal, void *hipStream) {
-    if (!c) return RT_ERR_INVALID_ARG;
-    if (!dIn || !dOut || width <= 0 || height <= 0) return fail(c, RT_ERR_INVALID_ARG, "bad rt_ssao_blur arguments");
-    if (dIn == dOut) return fail(c, RT_ERR_INVALID_ARG, "rt_ssao_blur cannot run in place");
-    HIP_TRY(c, hipSetDevice(c->device));
-    hipStream_t s = stream_or_own(c, hipStream);
-    HIP_TRY(c, rt_launch_ssao_blur(dIn, dOut, width, height, horizontal, s));
-    return RT_OK;
-}
-
-int rt_frame(rt_context *c, const rt_params *p, const rt_frame_desc *d, void *dDisplay) {
-    if (!c) return RT_ERR_INVALID_ARG;
-    if (!d) return fail(c, RT_ERR_INVALID_ARG, "frame description is NULL");
-    if (d->enableAO && (!d->aoSamples || !d->aoNoise)) return fail(c, RT_ERR_INVALID_ARG, "AO needs its kernel samples and rotation texture");
-    if (d->bloomIterations < 0) return fail(c, RT_ERR_INVALID_ARG, "bloomIterations < 0");
-    int rc = validate_params(c, p);
-    if (rc) return rc;
-    if (p->x0 != 0 || p->y0 != 0 || p->regionW != p->width || p->regionH != p->height || p->stripCycleRows != 0 || p->stripCount != 1)
-        return fail(c, RT_ERR_INVALID_ARG, "rt_frame renders the whole image on one device");
-    const int W = p->width, H = p->height;
-    const size_t npx = (size_t)W * H;
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (!(c->dFrameAO[0].holds(npx) && c->dFrameAO[1].holds(npx) && c->dHistory[0].holds(npx) && c->dHistory[1].holds(npx) &&
-          c->dFrameDisplay.holds(npx))) {
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        for (int k = 0; k < 2; k++) {
-            HIP_TRY(c, c->dFrameAO[k].grow(npx));
-            HIP_TRY(c, c->dHistory[k].grow(npx));
-        }
-        HIP_TRY(c, c->dFrameDisplay.grow(npx));
-        c->frameW = c->frameH = 0;
-    }
-    if (c->frameW != W || c->frameH != H) {      // new size: the history starts as zeros (glTexImage2D(..., nullptr))
-        HIP_TRY(c, hipMemsetAsync(c->dHistory[0], 0, npx * sizeof(float4), c->stream));
-        HIP_TRY(c, hipMemsetAsync(c->dHistory[1], 0, npx * sizeof(float4), c->stream));
-        c->frameW = W;
-        c->frameH = H;
-        c->lastHistory = -1;
-    }
-    rc = rt_render(c, p);                                                   // :155-182
-    if (rc) return rc;
-    c->frameAOValid = false;
-    if (d->enableAO) {                                                      // :185-187, AO.cpp:86-117
-        float view[16], proj[16];
-        rc = rt_camera_matrices(p->camPos, p->camDir, p->camUp, p->fovDeg, (float)W / (float)H, view, proj);
-        if (rc) return fail(c, rc, "rt_camera_matrices");
-        rc = rt_ssao(c, c->dPos, c->dNormal, c->dFrameAO[0], W, H, d->aoNoise, 4, 4, d->aoSamples, proj, view, nullptr);
-        if (rc) return rc;
-        rc = rt_ssao_blur(c, c->dFrameAO[0], c->dFrameAO[1], W, H, 0, nullptr);   // `horizontal` is never set upstream
-        if (rc) return rc;
-        c->frameAOValid = true;
-    }
-    rc = rt_bloom(c, c->dColor, dDisplay ? dDisplay : (void *)c->dFrameDisplay, W, H, d->bloomThreshold, d->bloomStrength,
-                  d->bloomIterations, nullptr);                             // :189-228
-    if (rc) return rc;
-    if (d->enableTAA) {                                                     // :231-258
-        const int cur = ((p->frameCount % 2) + 2) % 2;
-        float jx, jy;
-        rc = rt_taa_jitter(p->frameCount, W, H, &jx, &jy);
-        if (rc) return fail(c, rc, "rt_taa_jitter");
-        rc = rt_taa_resolve(c, c->dColor, c->dHistory[1 - cur], c->dNormal, c->dHistory[cur], W, H, d->taaBlendFactor, jx, jy, nullptr);
-        if (rc) return rc;
-        c->lastHistory = cur;
-    }
-    return RT_OK;
-}
-
-int rt_frame_surfaces(rt_context *c, void **dColor, void **dPosition, void **dNormal, void **dAO, void **dHistory) {
-    if (!c) return RT_ERR_INVALID_ARG;
-    if (dColor) *dColor = c->dColor;
-    if (dPosition) *dPosition = c->dPos;
-    if (dNormal) *dNormal = c->dNormal;
-    if (dAO) *dAO = c->frameAOValid ? c->dFrameAO[1] : nullptr;
-    if (dHistory) *dHistory = c->lastHistory >= 0 ? c->dHistory[c->lastHistory] : nullptr;
-    return RT_OK;
-}
-
-int rt_strip_local_rows(int height, int stripRows, int stripCount, int stripIndex) {
-    if (height < 0 || stripRows <= 0 || stripCount <= 0 || stripIndex < 0 || stripIndex >= stripCount) return RT_ERR_INVALID_ARG;
-    int nStrips = (height + stripRows - 1) / stripRows;
-    int rows = 0;
-    for (int s = stripIndex; s < nStrips; s += stripCount) {
-        int r0 = s * stripRows, r1 = r0 + stripRows;
-        if (r1 > height) r1 = height;
-        rows += r1 - r0;
-    }
-    return rows;
-}
-
-int rt_deinterleave(rt_context *c, const void *src, void *dst, int width, int height, int bytesPerPixel,
-                    int stripRows, int stripCount, size_t rankStrideBytes, void *hipStream) {
-    if (!c) return RT_ERR_INVALID_ARG;
-    if (!src || !dst || width <= 0 || height <= 0 || bytesPerPixel <= 0 || stripRows <= 0 || stripCount <= 0)
-        return fail(c, RT_ERR_INVALID_ARG, "bad deinterleave arguments");
-    if (((size_t)width * bytesPerPixel) % 4 != 0 || rankStrideBytes % 4 != 0)
-        return fail(c, RT_ERR_INVALID_ARG, "row bytes and rank stride must be multiples of 4");
-    HIP_TRY(c, hipSetDevice(c->device));
-    hipStream_t s = stream_or_own(c, hipStream);
-    HIP_TRY(c, rt_launch_deinterleave(src, dst, width, height, bytesPerPixel, stripRows, stripCount, rankStrideBytes, s));
-    return RT_OK;
-}
-
-size_t rt_wire_bytes(size_t nPixels) { return (nPixels * 30 + 15) / 16 * 16; }
-
-int rt_wire_pack(rt_context *c, const void *dColor, const void *dPosition, const void *dNormal, void *dWire, size_t nPixels,
-                 void *hipStream) {
-    if (!c) return RT_ERR_INVALID_ARG;
-    if (!dColor || !dPosition || !dNormal || !dWire) return fail(c, RT_ERR_INVALID_ARG, "bad wire_pack arguments");
-    HIP_TRY(c, hipSetDevice(c->device));
-    hipStream_t s = stream_or_own(c, hipStream);
-    HIP_TRY(c, rt_launch_wire_pack(dColor, dPosition, dNormal, dWire, nPixels, s));
-    return RT_OK;
-}
-
-int rt_wire_unpack(rt_context *c, const void *dWire, size_t rankStrideBytes, size_t rankPixels, const void *dRootColor,
-                   const void *dRootPosition, const void *dRootNormal, int rootStrips, void *dColor, void *dPosition,
-                   void *dNormal, int width, int height, int stripRows, int stripCount, void *hipStream) {
-    if (!c) return RT_ERR_INVALID_ARG;
-    if (!dWire || !dColor || !dPosition || !dNormal || width <= 0 || height <= 0 || stripRows <= 0 || stripCount <= 0 ||
-        rootStrips <= 0)
-        return fail(c, RT_ERR_INVALID_ARG, "bad wire_unpack arguments");
-    const bool rootLocal = dRootColor || dRootPosition || dRootNormal;
-    if (rootLocal && !(dRootColor && dRootPosition && dRootNormal))
-        return fail(c, RT_ERR_INVALID_ARG, "the root's three local surfaces must be given together");
-    if (!rootLocal && rootStrips != 1) return fail(c, RT_ERR_INVALID_ARG, "a larger root share needs the root's local surfaces");
-    // every rank buffer must hold the rank's whole strips, and the f32 / f16 planes must stay aligned
-    const int cycleRows = (rootStrips + stripCount - 1) * stripRows;
-    const int nCycles = (height + cycleRows - 1) / cycleRows;
-    const size_t needPixels = (size_t)nCycles * stripRows * width;
-    if (rankPixels < needPixels || rankStrideBytes % 4 != 0 || rankStrideBytes < rankPixels * 30)
-        return fail(c, RT_ERR_INVALID_ARG, "rank buffers too small or misaligned for this strip plan");
-    HIP_TRY(c, hipSetDevice(c->device));
-    hipStream_t s = stream_or_own(c, hipStream);
-    HIP_TRY(c, rt_launch_wire_unpack(dWire, rankStrideBytes, rankPixels, dRootColor, dRootPosition, dRootNormal,
-                                     rootStrips * stripRows, dColor, dPosition, dNormal, width, height, stripRows, stripCount, s));
     return RT_OK;
 }
 

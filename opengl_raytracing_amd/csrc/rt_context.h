@@ -1,6 +1,7 @@
-// rt_context.h -- what the files that implement context entry points share (rt_abi.cpp, and with rt_args.h's checks on top of it
-// rt_display.cpp, rt_jpeg.cpp, rt_resample.cpp, rt_accum.cpp, rt_denoise.cpp): the context itself, the way an entry point reports a failure, and the
-// stream it works on.  Nothing else knows the context's layout (rt_mgpu.cpp drives contexts through the public ABI).  Not part of the public ABI.
+// rt_context.h -- what the files that implement context entry points share (rt_abi.cpp, rt_post.cpp, rt_wire.cpp, and with
+// rt_args.h's checks on top of it rt_display.cpp, rt_jpeg.cpp, rt_resample.cpp, rt_accum.cpp, rt_denoise.cpp, rt_reproject.cpp,
+// rt_adaptive.cpp): the context itself, the way an entry point reports a failure, the stream it works on, and the rules a frame's
+// rt_params obey.  Nothing else knows the context's layout (rt_mgpu.cpp drives contexts through the public ABI).  Not part of the public ABI.
 #pragma once
 #include <string>
 #include <vector>
@@ -115,3 +116,21 @@ inline int fail(rt_context *c, int code, const char *what, hipError_t e = hipSuc
 
 // the ABI's `void *hipStream`: the caller's stream, or the context's own when it is NULL
 inline hipStream_t stream_or_own(const rt_context *c, void *hipStream) { return hipStream ? (hipStream_t)hipStream : c->stream.s; }
+
+// the rt_params of a frame, as the renders, the queries and rt_frame check them
+inline int validate_params(rt_context *c, const rt_params *p) {
+    if (!p) return fail(c, RT_ERR_INVALID_ARG, "params is NULL");
+    if (p->width <= 0 || p->height <= 0) return fail(c, RT_ERR_INVALID_ARG, "width/height must be positive");
+    if (p->regionW < 0 || p->regionH < 0 || p->x0 < 0 || p->y0 < 0)
+        return fail(c, RT_ERR_INVALID_ARG, "negative window");
+    if (p->stripRows <= 0) return fail(c, RT_ERR_INVALID_ARG, "bad strip mapping");
+    if (p->stripCycleRows > 0) {
+        if (p->stripOffsetRows < 0 || p->stripOffsetRows + p->stripRows > p->stripCycleRows)
+            return fail(c, RT_ERR_INVALID_ARG, "bad strip mapping (offset + rows exceed the cycle)");
+    } else if (p->stripCycleRows < 0 || p->stripCount <= 0 || p->stripIndex < 0 || p->stripIndex >= p->stripCount) {
+        return fail(c, RT_ERR_INVALID_ARG, "bad strip mapping");
+    }
+    if (p->maxRayDepth < 0 || p->maxRayDepth > RT_MAX_DEPTH)
+        return fail(c, RT_ERR_INVALID_ARG, "maxRayDepth outside [0, 32]");
+    return RT_OK;
+}

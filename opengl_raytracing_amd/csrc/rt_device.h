@@ -1,5 +1,6 @@
-// rt_device.h -- shared declarations between the HIP kernels (rt_kernels.hip, rt_post.hip) and the
-// C-ABI implementation (rt_abi.cpp).  The display path's are in rt_display.h.  Not part of the public ABI.
+// rt_device.h -- shared declarations between the tracer's HIP kernels (rt_kernels.hip) and the C-ABI
+// implementation (rt_abi.cpp, rt_sched.cpp): per-launch constants, the device scene, buffer sizes, launch wrappers.  The post
+// passes' are in rt_post.h, the strip transport's in rt_wire.h, the display path's in rt_display.h.  Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -79,7 +80,7 @@ static inline size_t rt_compiled_f4(int nObj, int nLt) {
     return (size_t)nObj * (RT_HOT_F4 + RT_MAT_F4) + (size_t)nLt * RT_LGT_F4 + 2 * (RT_HALTON_N / 4);
 }
 
-// Launch wrappers implemented in rt_kernels.hip (the post passes': rt_post.hip)
+// Launch wrappers implemented in rt_kernels.hip
 hipError_t rt_launch_compile_scene(const uint8_t *dObjects, int nObj, const uint8_t *dLights, int nLt,
                                    float4 *dCompiled, hipStream_t s);
 hipError_t rt_launch_render(const RtFrame &f, const RtDeviceScene &sc, float4 *dColor, float4 *dPos,
@@ -98,21 +99,6 @@ hipError_t rt_launch_predict_order(const RtFrame &f, const RtDeviceScene &sc, in
                                    unsigned *dCursors, unsigned *dNextCursors, unsigned char *dCls, unsigned *dOrder, hipStream_t s);
 hipError_t rt_launch_lpt_sort(unsigned *dCost, unsigned *dSnap, unsigned *dOrder, int nTiles, hipStream_t s, unsigned *dAccum = nullptr);
 hipError_t rt_launch_iota(unsigned *dOrder, int n, hipStream_t s);      // dOrder[i] = i (identity tile order)
-hipError_t rt_launch_taa_resolve(const void *current, const void *history, const void *normal, void *out, int W, int H,
-                                 float blend, float jx, float jy, hipStream_t s);
-hipError_t rt_launch_ssao(const void *position, const void *normal, void *depthPlane, void *out, int W, int H, const float *noise,
-                          int nW, int nH, const float *samples, const float *projection, const float *view, hipStream_t s);
-hipError_t rt_launch_ssao_blur(const void *in, void *out, int W, int H, int horizontal, hipStream_t s);
-hipError_t rt_launch_equirect_to_cubemap(const float *dRgb, void *dTex, int W, int H, int S, void *dFaces, hipStream_t s);
-hipError_t rt_launch_bloom(const void *scene, void *tmpA, void *tmpB, void *out, int W, int H, float threshold, float strength,
-                           int iterations, hipStream_t s);
-hipError_t rt_launch_wire_pack(const void *dColor, const void *dPos, const void *dNormal, void *dWire, size_t nPixels,
-                               hipStream_t s);
-hipError_t rt_launch_wire_unpack(const void *dWire, size_t rankStrideBytes, size_t rankPixels, const void *dRootColor,
-                                 const void *dRootPos, const void *dRootNormal, int rootRows, void *dColor, void *dPos,
-                                 void *dNormal, int width, int height, int stripRows, int stripCount, hipStream_t s);
-hipError_t rt_launch_deinterleave(const void *src, void *dst, int width, int height, int bytesPerPixel,
-                                  int stripRows, int stripCount, size_t rankStrideBytes, hipStream_t s);
 // Ray queries (rt_query.inc).  dRays / dOut: 2 float4 per ray / hit (rt_ray / rt_hit), anyHit: one int per ray.
 hipError_t rt_launch_trace_rays(const float4 *dRays, size_t nRays, const float4 *dCompiled, int nObj, int anyHit, void *dOut,
                                 hipStream_t s);

@@ -18,12 +18,17 @@
 //
 // The per-lane path tracer (any-hit, PCF, PCSS, SSS, lighting, the bounce loop) is rt_lane.inc's, shared with rt_shade_rays
 // (rt_shade.inc); this file keeps the arithmetic helpers, the exhaustive kernel's LDS accessor and closest-hit loop (LaneLds),
-// its staging, lane -> pixel map, stores and counter reduction.  The packet kernel is rt_packet.inc.
+// its staging, lane -> pixel map, stores and counter reduction.  The packet kernel is rt_packet.inc.  Besides the render
+// kernels this translation unit holds the scene compiler, the shadow tables' builder, the tile scheduler's kernels, the ray
+// queries, ray shading and rt_debug_device_math (which runs the tracer's inline primitives here, under this file's flags), and
+// still the strip transport's three copy kernels (declared in rt_wire.h, entry points in rt_wire.cpp): in a file of their own
+// they are the same code, but the frame loop with a submit then measured outside the parent's spread.
 //
 // Arithmetic is fp32 in the reference's evaluation order (no FMA contraction: built with
 // -ffp-contract=off; IEEE divide/sqrt) so results are comparable bit-for-bit with the CPU
 // restatement in oracle/ wherever no transcendental is involved.
 #include "rt_device.h"
+#include "rt_wire.h"
 #include "rt_mesa_math.h"
 #include "rt_fastmath.h"
 

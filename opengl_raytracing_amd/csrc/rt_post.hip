@@ -7,8 +7,7 @@
 //
 // Layout: 256-thread workgroup = 64x4 pixels, one lane per pixel, 16-B loads and one float4 store per
 // lane.  The 3x3 neighbourhood, the jittered bilinear tap, history's 4 taps (normally collapsing onto
-// one texel) and the gNormal tap(s) are served by L1/L2 (RT_TAA_LDS=1 stages the current tile + halo in
-// LDS instead: measured equal).
+// one texel) and the gNormal tap(s) are served by L1/L2.
 #include <hip/hip_fp16.h>
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -16,28 +15,81 @@
 #include <string.h>
 
 #include "rt_fastmath.h"
+#include "rt_post.h"
 #include "rt_wave.h"
 
-#ifndef RT_TAA_LDS
-#define RT_TAA_LDS 0   // 1: stage the current-frame tile (+halo) in LDS; 0: neighbourhood straight from L1/L2.
-#endif                // Measured equal within noise (29-31 us @1080p for every tile shape): the pass is limited by the
-                      // memory pipeline, not by how the 3x3 taps are fetched; the simpler form is the default.  An XCD-aware
-                      // tile order (one contiguous band of tiles per XCD, as in the bloom kernels) measured 3 % slower here.
+// ---- the tunables of this file (-D overrides them; each is described where it is used)
+#ifndef RT_TAA_ROWS
+#define RT_TAA_ROWS 8           // rows a lane of the register-window TAA kernel walks
+#endif
+#ifndef RT_BLOOM_XCD
+#define RT_BLOOM_XCD 1          // XCD-aware tile order of the fused bloom kernels
+#endif
+#ifndef RT_SSAO_UNROLL
+#define RT_SSAO_UNROLL 8        // unroll of the 64-sample loop
+#endif
+#ifndef RT_SSAO_TILE_W
+#define RT_SSAO_TILE_W 8        // wave tile width in pixels (height = 64 / width)
+#endif
+#ifndef RT_SSAO_FASTDIV
+#define RT_SSAO_FASTDIV 1       // 0 = the compiler's IEEE divisions in the sample loop
+#endif
+// Settled, and built one way only (the figure is why the other form is gone):
+//   the TAA tile + halo staged in LDS, at any tile shape: equal within noise (29-31 us @1080p) -- the pass is limited by the memory pipeline;
+//   an XCD-aware TAA tile order (one band of tiles per XCD, as in the bloom kernels): 3 % slower;
+//   the one-texel-per-lane TAA kernel for every frame instead of the register window: 28.8 against 27.1 us @1080p, 135 / 118 @4K;
+//   several bloom tiles per workgroup with the next patch in flight: 72 / 79 / 81 / 96 / 104 us at 1, 2, 3, 4, 6 tiles @1080p;
+//   an XCD-aware SSAO block order: neutral at 1080p (387 vs 386 us), 1.5 % slower at 4K -- the kernel is VALU-bound, not L2-bound.
 
 namespace {
 
-#ifndef RT_TAA_TX
-#define RT_TAA_TX 64
-#endif
-constexpr int TX = RT_TAA_TX, TY = 256 / RT_TAA_TX, HALO = 1;
-[[maybe_unused]] constexpr int LW = TX + 2 * HALO, LH = TY + 2 * HALO;
+constexpr int TX = 64, TY = 4;      // the one-texel-per-lane kernel's workgroup tile
 
 __device__ __forceinline__ int wrapi(int i, int n) { int r = i % n; return r < 0 ? r + n : r; }
 __device__ __forceinline__ int clampi(int i, int n) { return i < 0 ? 0 : (i > n - 1 ? n - 1 : i); }
 
 struct rgb { float x, y, z; };
+__device__ __forceinline__ rgb rgb_of(float4 q) { rgb r; r.x = q.x; r.y = q.y; r.z = q.z; return r; }
 __device__ __forceinline__ rgb lerp3(rgb a, rgb b, float w) {   // a + w*(b-a), per llvmpipe's float path
     rgb r; r.x = a.x + w * (b.x - a.x); r.y = a.y + w * (b.y - a.y); r.z = a.z + w * (b.z - a.z); return r;
+}
+
+// ---- the resolve arithmetic both TAA kernels share (taaFs.glsl); how a texel is fetched is each kernel's own
+// LINEAR: four texels around a sample, weights = the sample's fractional position
+__device__ __forceinline__ rgb taa_bilinear(rgb t00, rgb t10, rgb t01, rgb t11, float wx, float wy) {
+    const rgb a = lerp3(t00, t10, wx), b = lerp3(t01, t11, wx);
+    return lerp3(a, b, wy);
+}
+// one more texel into the neighbourhood colour box; texelFetch reads 0 outside the image                    :30-37
+__device__ __forceinline__ void taa_box(rgb &mn, rgb &mx, rgb q, bool inb) {
+    const float nx = inb ? q.x : 0.0f, ny = inb ? q.y : 0.0f, nz = inb ? q.z : 0.0f;
+    mn.x = fminf(mn.x, nx); mn.y = fminf(mn.y, ny); mn.z = fminf(mn.z, nz);
+    mx.x = fmaxf(mx.x, nx); mx.y = fmaxf(mx.y, ny); mx.z = fmaxf(mx.z, nz);
+}
+__device__ __forceinline__ float taa_half(unsigned h) { return __half2float(__ushort_as_half((unsigned short)h)); }
+// normal check, NEAREST / REPEAT: the blend factor of a pixel whose normal and jittered normal disagree, else 0     :40-45
+__device__ __forceinline__ float taa_normal_blend(const uint2 *normal, int W, int H, float u, float v, float ju, float jv,
+                                                  float blendFactor) {
+    const int px = wrapi((int)floorf(u * (float)W), W), py = wrapi((int)floorf(v * (float)H), H);
+    const int cx = wrapi((int)floorf(ju * (float)W), W), cy = wrapi((int)floorf(jv * (float)H), H);
+    const uint2 pn = normal[(size_t)py * W + px];
+    const uint2 cn = (cx == px && cy == py) ? pn : normal[(size_t)cy * W + cx];   // sub-texel jitter: same texel
+    const float pnx = taa_half(pn.x & 0xffffu), pny = taa_half(pn.x >> 16), pnz = taa_half(pn.y & 0xffffu);
+    const float cnx = taa_half(cn.x & 0xffffu), cny = taa_half(cn.x >> 16), cnz = taa_half(cn.y & 0xffffu);
+    const float d = (pnz * cnz + pny * cny) + pnx * cnx;
+    return d < 0.9f ? blendFactor * 0.2f : 0.0f;
+}
+// clipAABB (:13-19) then mix(history, current, blendFactor) (:51), one channel
+__device__ __forceinline__ float taa_clip_mix(float h, float c, float lo, float hi, float bf) {
+    const float center = 0.5f * (hi + lo), extents = 0.5f * (hi - lo);
+    float clip = h - center;
+    clip = fminf(fmaxf(clip, -extents), extents);
+    const float hc = center + clip;
+    return hc + bf * (c - hc);
+}
+__device__ __forceinline__ float4 taa_resolve(rgb his, rgb cur, rgb mn, rgb mx, float bf) {
+    return make_float4(taa_clip_mix(his.x, cur.x, mn.x, mx.x, bf), taa_clip_mix(his.y, cur.y, mn.y, mx.y, bf),
+                       taa_clip_mix(his.z, cur.z, mn.z, mx.z, bf), 1.0f);
 }
 
 }  // namespace
@@ -47,34 +99,13 @@ __global__ __launch_bounds__(256) void rt_taa_resolve_kernel(const float4 *__res
                                                              const uint2 *__restrict__ normal,   // half4 per pixel
                                                              float4 *__restrict__ out, int W, int H, float blendFactor,
                                                              float jitterX, float jitterY) {
-#if RT_TAA_LDS
-    __shared__ float4 tile[LH][LW];
-#endif
     const int bx = blockIdx.x * TX, by = blockIdx.y * TY;
-    // stage the current-frame tile; texels outside the image are stored with REPEAT addressing (what the
-    // bilinear tap needs); the 3x3 clamp below substitutes 0 for them itself (texelFetch out of range)
-#if RT_TAA_LDS
-    for (int k = threadIdx.x; k < LW * LH; k += 256) {
-        const int lx = k % LW, ly = k / LW;
-        const int gx = wrapi(bx + lx - HALO, W), gy = wrapi(by + ly - HALO, H);
-        tile[ly][lx] = current[(size_t)gy * W + gx];
-    }
-    __syncthreads();
-#endif
     const int tx = threadIdx.x % TX, ty = threadIdx.x / TX;
     const int i = bx + tx, j = by + ty;
     if (i >= W || j >= H) return;
 
     auto cur_at = [&](int x, int y) -> rgb {   // REPEAT-addressed current texel (x, y may be any integer)
-        const int lx = x - bx + HALO, ly = y - by + HALO;
-        float4 q;
-#if RT_TAA_LDS
-        if (lx >= 0 && lx < LW && ly >= 0 && ly < LH) q = tile[ly][lx];
-        else
-#endif
-        q = current[(size_t)wrapi(y, H) * W + wrapi(x, W)];
-        (void)lx; (void)ly;
-        rgb r; r.x = q.x; r.y = q.y; r.z = q.z; return r;
+        return rgb_of(current[(size_t)wrapi(y, H) * W + wrapi(x, W)]);
     };
 
     const float u = ((float)i + 0.5f) / (float)W, v = ((float)j + 0.5f) / (float)H;   // TexCoords
@@ -86,9 +117,7 @@ __global__ __launch_bounds__(256) void rt_taa_resolve_kernel(const float4 *__res
         const float fx = floorf(x), fy = floorf(y);
         const float wx = x - fx, wy = y - fy;
         const int x0 = (int)fx, y0 = (int)fy;
-        rgb a = lerp3(cur_at(x0, y0), cur_at(x0 + 1, y0), wx);
-        rgb b = lerp3(cur_at(x0, y0 + 1), cur_at(x0 + 1, y0 + 1), wx);
-        cur = lerp3(a, b, wy);
+        cur = taa_bilinear(cur_at(x0, y0), cur_at(x0 + 1, y0), cur_at(x0, y0 + 1), cur_at(x0 + 1, y0 + 1), wx, wy);
     }
     // history = texture(uHistory, TexCoords): LINEAR, CLAMP_TO_EDGE                   :27
     rgb his;
@@ -97,12 +126,10 @@ __global__ __launch_bounds__(256) void rt_taa_resolve_kernel(const float4 *__res
         const float fx = floorf(x), fy = floorf(y);
         const float wx = x - fx, wy = y - fy;
         const int x0 = clampi((int)fx, W), x1 = clampi((int)fx + 1, W), y0 = clampi((int)fy, H), y1 = clampi((int)fy + 1, H);
-        auto h_at = [&](int xx, int yy) -> rgb { float4 q = history[(size_t)yy * W + xx]; rgb r; r.x = q.x; r.y = q.y; r.z = q.z; return r; };
-        rgb a = lerp3(h_at(x0, y0), h_at(x1, y0), wx);
-        rgb b = lerp3(h_at(x0, y1), h_at(x1, y1), wx);
-        his = lerp3(a, b, wy);
+        auto h_at = [&](int xx, int yy) -> rgb { return rgb_of(history[(size_t)yy * W + xx]); };
+        his = taa_bilinear(h_at(x0, y0), h_at(x1, y0), h_at(x0, y1), h_at(x1, y1), wx, wy);
     }
-    // neighbourhood colour box, texelFetch (0 outside the image)                       :30-37
+    // neighbourhood colour box
     rgb mn = cur, mx = cur;
 #pragma unroll
     for (int dx = -1; dx <= 1; dx++) {
@@ -110,40 +137,22 @@ __global__ __launch_bounds__(256) void rt_taa_resolve_kernel(const float4 *__res
         for (int dy = -1; dy <= 1; dy++) {
             const int x = i + dx, y = j + dy;
             const bool inb = x >= 0 && y >= 0 && x < W && y < H;
-#if RT_TAA_LDS
-            const float4 q = tile[ty + dy + HALO][tx + dx + HALO];
-#else
-            const float4 q = current[(size_t)clampi(y, H) * W + clampi(x, W)];
-#endif
-            const float nx = inb ? q.x : 0.0f, ny = inb ? q.y : 0.0f, nz = inb ? q.z : 0.0f;
-            mn.x = fminf(mn.x, nx); mn.y = fminf(mn.y, ny); mn.z = fminf(mn.z, nz);
-            mx.x = fmaxf(mx.x, nx); mx.y = fmaxf(mx.y, ny); mx.z = fmaxf(mx.z, nz);
+            taa_box(mn, mx, rgb_of(current[(size_t)clampi(y, H) * W + clampi(x, W)]), inb);
         }
     }
-    // normal check, NEAREST / REPEAT                                                   :40-45
+    // (taa_normal_blend, written out: through the function this kernel's schedule gains an s_nop, and the shipped code stays as it is)
     float bf = 0.0f;
     {
         const int px = wrapi((int)floorf(u * (float)W), W), py = wrapi((int)floorf(v * (float)H), H);
         const int cx = wrapi((int)floorf(ju * (float)W), W), cy = wrapi((int)floorf(jv * (float)H), H);
         const uint2 pn = normal[(size_t)py * W + px];
-        const uint2 cn = (cx == px && cy == py) ? pn : normal[(size_t)cy * W + cx];   // sub-texel jitter: same texel
-        const float pnx = __half2float(__ushort_as_half((unsigned short)(pn.x & 0xffffu))), pny = __half2float(__ushort_as_half((unsigned short)(pn.x >> 16)));
-        const float pnz = __half2float(__ushort_as_half((unsigned short)(pn.y & 0xffffu)));
-        const float cnx = __half2float(__ushort_as_half((unsigned short)(cn.x & 0xffffu))), cny = __half2float(__ushort_as_half((unsigned short)(cn.x >> 16)));
-        const float cnz = __half2float(__ushort_as_half((unsigned short)(cn.y & 0xffffu)));
+        const uint2 cn = (cx == px && cy == py) ? pn : normal[(size_t)cy * W + cx];
+        const float pnx = taa_half(pn.x & 0xffffu), pny = taa_half(pn.x >> 16), pnz = taa_half(pn.y & 0xffffu);
+        const float cnx = taa_half(cn.x & 0xffffu), cny = taa_half(cn.x >> 16), cnz = taa_half(cn.y & 0xffffu);
         const float d = (pnz * cnz + pny * cny) + pnx * cnx;
         if (d < 0.9f) bf = blendFactor * 0.2f;
     }
-    // clipAABB (:13-19) then mix(history, current, blendFactor) (:51)
-    auto resolve = [&](float h, float c, float lo, float hi) -> float {
-        const float center = 0.5f * (hi + lo), extents = 0.5f * (hi - lo);
-        float clip = h - center;
-        clip = fminf(fmaxf(clip, -extents), extents);
-        const float hc = center + clip;
-        return hc + bf * (c - hc);
-    };
-    out[(size_t)j * W + i] = make_float4(resolve(his.x, cur.x, mn.x, mx.x), resolve(his.y, cur.y, mn.y, mx.y),
-                                         resolve(his.z, cur.z, mn.z, mx.z), 1.0f);
+    out[(size_t)j * W + i] = taa_resolve(his, cur, mn, mx, bf);
 }
 
 // The same resolve with a REGISTER WINDOW: one lane per column walks RT_TAA_ROWS consecutive rows and keeps three rows x three
@@ -160,9 +169,6 @@ __global__ __launch_bounds__(256) void rt_taa_resolve_kernel(const float4 *__res
 // neighbouring columns from the adjacent lanes (DPP wave shifts), one row ahead of its use -- a quarter of the loads again, but
 // 136 VGPRs / 3 waves and two loads in flight per wave: 36 / 139 / 531 us; and both surfaces staged as 64 x 8..32 pixel tiles in
 // LDS (1.2 loads per pixel and surface, taps from LDS): 30 / 118 / 415 us at best.
-#ifndef RT_TAA_ROWS
-#define RT_TAA_ROWS 8
-#endif
 __global__ __launch_bounds__(256) void rt_taa_resolve_rows_kernel(const float4 *__restrict__ current, const float4 *__restrict__ history,
                                                                   const uint2 *__restrict__ normal, float4 *__restrict__ out, int W, int H,
                                                                   float blendFactor, float jitterX, float jitterY) {
@@ -177,8 +183,8 @@ __global__ __launch_bounds__(256) void rt_taa_resolve_rows_kernel(const float4 *
         const size_t o = (size_t)clampi(y, H) * W;
         const float4 c0 = current[o + xl], c1 = current[o + i], c2 = current[o + xr];
         const float4 h0 = history[o + xl], h1 = history[o + i], h2 = history[o + xr];
-        c[slot][0] = {c0.x, c0.y, c0.z}; c[slot][1] = {c1.x, c1.y, c1.z}; c[slot][2] = {c2.x, c2.y, c2.z};
-        h[slot][0] = {h0.x, h0.y, h0.z}; h[slot][1] = {h1.x, h1.y, h1.z}; h[slot][2] = {h2.x, h2.y, h2.z};
+        c[slot][0] = rgb_of(c0); c[slot][1] = rgb_of(c1); c[slot][2] = rgb_of(c2);
+        h[slot][0] = rgb_of(h0); h[slot][1] = rgb_of(h1); h[slot][2] = rgb_of(h2);
     };
     auto sel = [](bool first, rgb a, rgb b) -> rgb { rgb r; r.x = first ? a.x : b.x; r.y = first ? a.y : b.y; r.z = first ? a.z : b.z; return r; };
     load_row(0, j0 - 1);
@@ -208,11 +214,10 @@ __global__ __launch_bounds__(256) void rt_taa_resolve_rows_kernel(const float4 *
             rgb t01 = sel(up, sel(left, c[sm][0], c[sm][1]), sel(left, c[sb][0], c[sb][1]));
             rgb t11 = sel(up, sel(left, c[sm][1], c[sm][2]), sel(left, c[sb][1], c[sb][2]));
             if (!inWin) {                                    // image border (REPEAT wraps around) or a jitter of a texel and more
-                auto cur_at = [&](int xx, int yy) -> rgb { const float4 q = current[(size_t)wrapi(yy, H) * W + wrapi(xx, W)]; rgb t; t.x = q.x; t.y = q.y; t.z = q.z; return t; };
+                auto cur_at = [&](int xx, int yy) -> rgb { return rgb_of(current[(size_t)wrapi(yy, H) * W + wrapi(xx, W)]); };
                 t00 = cur_at(x0, y0); t10 = cur_at(x0 + 1, y0); t01 = cur_at(x0, y0 + 1); t11 = cur_at(x0 + 1, y0 + 1);
             }
-            const rgb a = lerp3(t00, t10, wx), b = lerp3(t01, t11, wx);
-            cur = lerp3(a, b, wy);
+            cur = taa_bilinear(t00, t10, t01, t11, wx, wy);
         }
         // history = texture(uHistory, TexCoords): LINEAR, CLAMP_TO_EDGE                   :27
         rgb his;
@@ -230,60 +235,30 @@ __global__ __launch_bounds__(256) void rt_taa_resolve_rows_kernel(const float4 *
             rgb t11 = sel(up, sel(left, h[sm][1], h[sm][2]), sel(left, h[sb][1], h[sb][2]));
             if (!inWin) {
                 const int x0 = clampi((int)fx, W), x1 = clampi((int)fx + 1, W), y0 = clampi((int)fy, H), y1 = clampi((int)fy + 1, H);
-                auto h_at = [&](int xx, int yy) -> rgb { const float4 q = history[(size_t)yy * W + xx]; rgb t; t.x = q.x; t.y = q.y; t.z = q.z; return t; };
+                auto h_at = [&](int xx, int yy) -> rgb { return rgb_of(history[(size_t)yy * W + xx]); };
                 t00 = h_at(x0, y0); t10 = h_at(x1, y0); t01 = h_at(x0, y1); t11 = h_at(x1, y1);
             }
-            const rgb a = lerp3(t00, t10, wx), b = lerp3(t01, t11, wx);
-            his = lerp3(a, b, wy);
+            his = taa_bilinear(t00, t10, t01, t11, wx, wy);
         }
-        // neighbourhood colour box, texelFetch (0 outside the image)                       :30-37
+        // neighbourhood colour box: the window itself
         rgb mn = cur, mx = cur;
 #pragma unroll
         for (int dx = -1; dx <= 1; dx++) {
 #pragma unroll
             for (int dy = -1; dy <= 1; dy++) {
                 const int x = i + dx, y = j + dy;
-                const bool inb = x >= 0 && y >= 0 && x < W && y < H;
-                const rgb q = c[dy < 0 ? sa : (dy == 0 ? sm : sb)][dx + 1];
-                const float nx = inb ? q.x : 0.0f, ny = inb ? q.y : 0.0f, nz = inb ? q.z : 0.0f;
-                mn.x = fminf(mn.x, nx); mn.y = fminf(mn.y, ny); mn.z = fminf(mn.z, nz);
-                mx.x = fmaxf(mx.x, nx); mx.y = fmaxf(mx.y, ny); mx.z = fmaxf(mx.z, nz);
+                taa_box(mn, mx, c[dy < 0 ? sa : (dy == 0 ? sm : sb)][dx + 1], x >= 0 && y >= 0 && x < W && y < H);
             }
         }
-        // normal check, NEAREST / REPEAT                                                   :40-45
-        float bf = 0.0f;
-        {
-            const int px = wrapi((int)floorf(u * (float)W), W), py = wrapi((int)floorf(v * (float)H), H);
-            const int cx = wrapi((int)floorf(ju * (float)W), W), cy = wrapi((int)floorf(jv * (float)H), H);
-            const uint2 pn = normal[(size_t)py * W + px];
-            const uint2 cn = (cx == px && cy == py) ? pn : normal[(size_t)cy * W + cx];   // sub-texel jitter: same texel
-            const float pnx = __half2float(__ushort_as_half((unsigned short)(pn.x & 0xffffu))), pny = __half2float(__ushort_as_half((unsigned short)(pn.x >> 16)));
-            const float pnz = __half2float(__ushort_as_half((unsigned short)(pn.y & 0xffffu)));
-            const float cnx = __half2float(__ushort_as_half((unsigned short)(cn.x & 0xffffu))), cny = __half2float(__ushort_as_half((unsigned short)(cn.x >> 16)));
-            const float cnz = __half2float(__ushort_as_half((unsigned short)(cn.y & 0xffffu)));
-            const float d = (pnz * cnz + pny * cny) + pnx * cnx;
-            if (d < 0.9f) bf = blendFactor * 0.2f;
-        }
-        // clipAABB (:13-19) then mix(history, current, blendFactor) (:51)
-        auto resolve = [&](float hh, float cc, float lo, float hi) -> float {
-            const float center = 0.5f * (hi + lo), extents = 0.5f * (hi - lo);
-            float clip = hh - center;
-            clip = fminf(fmaxf(clip, -extents), extents);
-            const float hc = center + clip;
-            return hc + bf * (cc - hc);
-        };
-        out[(size_t)j * W + i] = make_float4(resolve(his.x, cur.x, mn.x, mx.x), resolve(his.y, cur.y, mn.y, mx.y),
-                                             resolve(his.z, cur.z, mn.z, mx.z), 1.0f);
+        const float bf = taa_normal_blend(normal, W, H, u, v, ju, jv, blendFactor);
+        out[(size_t)j * W + i] = taa_resolve(his, cur, mn, mx, bf);
     }
 }
 
-#ifndef RT_TAA_WINDOW
-#define RT_TAA_WINDOW 1         // 0: the one-texel-per-lane kernel for every launch
-#endif
 hipError_t rt_launch_taa_resolve(const void *current, const void *history, const void *normal, void *out, int W, int H,
                                  float blend, float jx, float jy, hipStream_t s) {
     // (`out` must not alias the inputs in either form; frames of a few rows keep the one-texel-per-lane kernel)
-    if (RT_TAA_WINDOW && H >= 4 * RT_TAA_ROWS) {
+    if (H >= 4 * RT_TAA_ROWS) {
         dim3 grid((W + 63) / 64, (H + 4 * RT_TAA_ROWS - 1) / (4 * RT_TAA_ROWS));
         hipLaunchKernelGGL(rt_taa_resolve_rows_kernel, grid, dim3(256), 0, s, (const float4 *)current, (const float4 *)history,
                            (const uint2 *)normal, (float4 *)out, W, H, blend, jx, jy);
@@ -318,17 +293,21 @@ __device__ __forceinline__ float h2f_u(unsigned h) { return __half2float(__ushor
 __device__ __forceinline__ uint2 pack_half4(float r, float g, float b) {
     return make_uint2(cvt_pkrtz_u(r, g), cvt_pkrtz_u(b, 1.0f));
 }
+// brightness extract of one scene texel (brightness_extractFS.glsl:11-19) -> rgba16f
+__device__ __forceinline__ uint2 bloom_extract(float4 c, float threshold) {
+    const float brightness = (c.z * 0.0722f + c.y * 0.7152f) + c.x * 0.2126f;
+    return (brightness > threshold) ? pack_half4(c.x, c.y, c.z) : make_uint2(0u, 0x3c00u << 16);
+}
+// combine of one scene texel with its blurred rgba16f texel (bloom_combineFs.glsl:10-14)
+__device__ __forceinline__ float4 bloom_combine(float4 s, uint2 bl, float strength) {
+    return make_float4(s.x + h2f_u(bl.x) * strength, s.y + h2f_u(bl.x >> 16) * strength, s.z + h2f_u(bl.y) * strength, 1.0f);
+}
 
 }  // namespace
 
-// brightness extract (brightness_extractFS.glsl:11-19)
 __global__ __launch_bounds__(256) void rt_bloom_extract_kernel(const float4 *__restrict__ scene, uint2 *__restrict__ out,
                                                                size_t n, float threshold) {
-    for (size_t k = (size_t)blockIdx.x * 256 + threadIdx.x; k < n; k += (size_t)gridDim.x * 256) {
-        const float4 c = scene[k];
-        const float brightness = (c.z * 0.0722f + c.y * 0.7152f) + c.x * 0.2126f;
-        out[k] = (brightness > threshold) ? pack_half4(c.x, c.y, c.z) : make_uint2(0u, 0x3c00u << 16);
-    }
+    for (size_t k = (size_t)blockIdx.x * 256 + threadIdx.x; k < n; k += (size_t)gridDim.x * 256) out[k] = bloom_extract(scene[k], threshold);
 }
 
 // one separable 9-tap pass (gaussian_blurFs.glsl:8-26)
@@ -352,14 +331,9 @@ __global__ __launch_bounds__(256) void rt_bloom_blur_kernel(const uint2 *__restr
     out[(size_t)j * W + i] = pack_half4(r, g, b);
 }
 
-// combine (bloom_combineFs.glsl:10-14)
 __global__ __launch_bounds__(256) void rt_bloom_combine_kernel(const float4 *__restrict__ scene, const uint2 *__restrict__ bloom,
                                                                float4 *__restrict__ out, size_t n, float strength) {
-    for (size_t k = (size_t)blockIdx.x * 256 + threadIdx.x; k < n; k += (size_t)gridDim.x * 256) {
-        const float4 s = scene[k];
-        const uint2 bl = bloom[k];
-        out[k] = make_float4(s.x + h2f_u(bl.x) * strength, s.y + h2f_u(bl.x >> 16) * strength, s.z + h2f_u(bl.y) * strength, 1.0f);
-    }
+    for (size_t k = (size_t)blockIdx.x * 256 + threadIdx.x; k < n; k += (size_t)gridDim.x * 256) out[k] = bloom_combine(scene[k], bloom[k], strength);
 }
 
 // Fused horizontal+vertical pass pair (one blur "iteration pair" of ForwardShadingPipeline.cpp:207-216):
@@ -398,12 +372,6 @@ __device__ __forceinline__ void blur_window2(const rt_f2 (&r)[N + 8], const rt_f
     orr = ar; og = ag; ob = ab;
 }
 
-#ifndef RT_BLOOM_XCD
-#define RT_BLOOM_XCD 1      // XCD-aware tile order of the fused kernels (needs RT_BLOOM_TPW == 1)
-#endif
-#ifndef RT_BLOOM_TPW
-#define RT_BLOOM_TPW 1      // tiles per workgroup of the fused kernels (see rt_bloom_hv_kernel)
-#endif
 template <bool FIRST, bool LAST>
 __global__ __launch_bounds__(256) void rt_bloom_hv_kernel(const void *__restrict__ inV, const float4 *__restrict__ scene,
                                                           void *__restrict__ outV, int W, int H, float threshold, float strength) {
@@ -414,10 +382,8 @@ __global__ __launch_bounds__(256) void rt_bloom_hv_kernel(const void *__restrict
     uint2 *sh_ = sin_;
     // The patch is REQUESTED as one batch of NLD independent loads per thread into registers and written to LDS afterwards
     // (round 1 interleaved load -> ds_write per texel, which serialised the memory latency: 88 -> 72 us for the 1080p chain,
-    // 249 -> 226 us at 4K).  The tile loop also lets a workgroup walk several tiles with the next patch in flight during
-    // the two passes (RT_BLOOM_TPW tiles per workgroup): measured SLOWER -- 72 / 79 / 81 / 96 / 104 us at 1, 2, 3, 4, 6
-    // tiles per workgroup at 1080p -- the 1 350 one-tile workgroups are all co-resident and cover each other's phases
-    // better than fewer, longer-lived ones; the default stays one tile per workgroup.
+    // 249 -> 226 us at 4K).  One tile per workgroup: the 1 350 one-tile workgroups of a 1080p frame are all co-resident and cover
+    // each other's phases better than fewer, longer-lived ones.
     const int tilesX = (W + FX - 1) / FX, nTiles = tilesX * ((H + FY - 1) / FY);
     constexpr int NLD = (IW * IH) / 256;                               // patch texels per thread (9)
     static_assert(NLD * 256 == IW * IH, "whole patch in NLD loads per thread");
@@ -437,24 +403,18 @@ __global__ __launch_bounds__(256) void rt_bloom_hv_kernel(const void *__restrict
     // (one band of tiles per XCD: the aprons a tile shares with its neighbours come from the SAME L2, not from HBM once per XCD)
     int tile = RT_BLOOM_XCD ? rt_xcd_tile() : (int)blockIdx.x;
     if (tile < nTiles) request(tile);
-    for (; tile < nTiles; tile += (RT_BLOOM_TPW == 1 ? nTiles : (int)gridDim.x)) {      // (one trip when RT_BLOOM_TPW == 1)
+    // ONE trip (a workgroup past the last tile makes none).  Kept a loop, with the request a lambda ahead of it and the barrier at
+    // its end: as straight-line code the four instantiations compile to other schedules (12 to 32 instructions more or less), and
+    // the shipped code stays as it is.
+    for (; tile < nTiles; tile += nTiles) {
     const int x0 = (tile % tilesX) * FX, y0 = (tile / tilesX) * FY;
     // ---- the requested patch -> LDS
 #pragma unroll
     for (int j = 0; j < NLD; j++) {
         const int k = threadIdx.x + j * 256;
-        uint2 v;
-        if (FIRST) {     // brightness_extractFS.glsl:11-19 on the fly
-            const float4 c = preF[j];
-            const float brightness = (c.z * 0.0722f + c.y * 0.7152f) + c.x * 0.2126f;
-            v = (brightness > threshold) ? pack_half4(c.x, c.y, c.z) : make_uint2(0u, 0x3c00u << 16);
-        } else {
-            v = preH[j];
-        }
-        sin_[(k / IW) * IWP + (k % IW)] = v;
+        sin_[(k / IW) * IWP + (k % IW)] = FIRST ? bloom_extract(preF[j], threshold) : preH[j];      // FIRST: the extract on the fly
     }
     __syncthreads();
-    if (RT_BLOOM_TPW > 1 && tile + (int)gridDim.x < nTiles) request(tile + (int)gridDim.x);     // in flight during the two passes below
     {   // ---- horizontal pass: lane -> patch rows (rp, rp+16), 4 consecutive columns of each
         const int rp = threadIdx.x % (IH / 2), grp = threadIdx.x / (IH / 2);
         rt_f2 r[HSPAN + 8], g[HSPAN + 8], b[HSPAN + 8];
@@ -483,7 +443,7 @@ __global__ __launch_bounds__(256) void rt_bloom_hv_kernel(const void *__restrict
             r[c].x = h2f_u(v0.x); g[c].x = h2f_u(v0.x >> 16); b[c].x = h2f_u(v0.y);
             r[c].y = h2f_u(v1.x); g[c].y = h2f_u(v1.x >> 16); b[c].y = h2f_u(v1.y);
         }
-        __syncthreads();     // the horizontal result is in registers: the next tile's patch may overwrite the LDS array
+        __syncthreads();     // (the loop's: nothing writes the LDS array after it in the one trip)
 #pragma unroll
         for (int k = 0; k < VSPAN; k++) {
             const int y = y0 + seg * VSPAN + k;
@@ -495,18 +455,22 @@ __global__ __launch_bounds__(256) void rt_bloom_hv_kernel(const void *__restrict
                 const int x = x0 + lx + half * (FX / 2);
                 if (x >= W) continue;
                 const uint2 hv = half ? pack_half4(orr.y, og.y, ob.y) : pack_half4(orr.x, og.x, ob.x);   // the rgba16f store
-                if (LAST) {      // bloom_combineFs.glsl:10-14
-                    const float4 sc = scene[(size_t)y * W + x];
-                    ((float4 *)outV)[(size_t)y * W + x] = make_float4(sc.x + h2f_u(hv.x) * strength, sc.y + h2f_u(hv.x >> 16) * strength,
-                                                                      sc.z + h2f_u(hv.y) * strength, 1.0f);
-                } else {
-                    ((uint2 *)outV)[(size_t)y * W + x] = hv;
-                }
+                if (LAST) ((float4 *)outV)[(size_t)y * W + x] = bloom_combine(scene[(size_t)y * W + x], hv, strength);
+                else ((uint2 *)outV)[(size_t)y * W + x] = hv;
             }
         }
     }
-    }   // tiles of this workgroup
+    }   // (one trip)
 }
+
+namespace {
+// the fused kernel of one pass pair: FIRST reads the scene, LAST writes the combined image
+using BloomHvKernel = void (*)(const void *, const float4 *, void *, int, int, float, float);
+BloomHvKernel bloom_hv_kernel(bool first, bool last) {
+    return first ? (last ? rt_bloom_hv_kernel<true, true> : rt_bloom_hv_kernel<true, false>)
+                 : (last ? rt_bloom_hv_kernel<false, true> : rt_bloom_hv_kernel<false, false>);
+}
+}  // namespace
 
 hipError_t rt_launch_bloom(const void *scene, void *tmpA, void *tmpB, void *out, int W, int H, float threshold, float strength,
                            int iterations, hipStream_t s) {
@@ -518,7 +482,7 @@ hipError_t rt_launch_bloom(const void *scene, void *tmpA, void *tmpB, void *out,
     const int pairs = iterations / 2;
     const bool odd = (iterations & 1) != 0;
     const int nTilesF = ((W + FX - 1) / FX) * ((H + FY - 1) / FY);
-    dim3 fgrid(RT_BLOOM_XCD ? ((nTilesF + 7) / 8) * 8 : (nTilesF + RT_BLOOM_TPW - 1) / RT_BLOOM_TPW), grid((W + 63) / 64, (H + 3) / 4);
+    dim3 fgrid(RT_BLOOM_XCD ? ((nTilesF + 7) / 8) * 8 : nTilesF), grid((W + 63) / 64, (H + 3) / 4);
     if (pairs == 0) {            // 0 or 1 iterations: the unfused kernels
         hipLaunchKernelGGL(rt_bloom_extract_kernel, dim3(blocks), dim3(256), 0, s, sc, a, n, threshold);
         if (odd) { hipLaunchKernelGGL(rt_bloom_blur_kernel<true>, grid, dim3(256), 0, s, a, b, W, H); a = b; }
@@ -528,10 +492,7 @@ hipError_t rt_launch_bloom(const void *scene, void *tmpA, void *tmpB, void *out,
     for (int p = 0; p < pairs; p++) {
         const bool first = p == 0, last = (p == pairs - 1) && !odd;
         void *dst = last ? out : (void *)b;
-        if (first && last) hipLaunchKernelGGL((rt_bloom_hv_kernel<true, true>), fgrid, dim3(256), 0, s, (const void *)a, sc, dst, W, H, threshold, strength);
-        else if (first) hipLaunchKernelGGL((rt_bloom_hv_kernel<true, false>), fgrid, dim3(256), 0, s, (const void *)a, sc, dst, W, H, threshold, strength);
-        else if (last) hipLaunchKernelGGL((rt_bloom_hv_kernel<false, true>), fgrid, dim3(256), 0, s, (const void *)a, sc, dst, W, H, threshold, strength);
-        else hipLaunchKernelGGL((rt_bloom_hv_kernel<false, false>), fgrid, dim3(256), 0, s, (const void *)a, sc, dst, W, H, threshold, strength);
+        hipLaunchKernelGGL(bloom_hv_kernel(first, last), fgrid, dim3(256), 0, s, (const void *)a, sc, dst, W, H, threshold, strength);
         if (!last) { uint2 *t = a; a = b; b = t; }
     }
     if (odd) {                   // trailing horizontal pass, then the combine
@@ -550,15 +511,6 @@ hipError_t rt_launch_bloom(const void *scene, void *tmpA, void *tmpB, void *out,
 // (1.2 KB): wave-uniform, so they arrive as SGPR operands by s_load; a wave owns an 8x8 pixel tile so its
 // 64 x 64 depth gathers (4 B out of every 16 B texel) stay in a few L1/L2 lines.
 // =========================================================================================
-#ifndef RT_SSAO_UNROLL
-#define RT_SSAO_UNROLL 8
-#endif
-#ifndef RT_SSAO_XCD
-#define RT_SSAO_XCD 0             // 1: one contiguous image band per XCD.  Measured neutral at 1080p (387 vs 386 us) and
-#endif                            // 1.5 % slower at 4K: the kernel is VALU-bound, not L2-bound; kept as a switch.
-#ifndef RT_SSAO_TILE_W
-#define RT_SSAO_TILE_W 8          // wave tile width in pixels (height = 64 / width)
-#endif
 struct RtSsaoArgs {
     float samples[64][3];
     float projection[16], view[16];
@@ -585,10 +537,6 @@ __device__ __forceinline__ void ssao_nrm3(float x, float y, float z, float &ox, 
 __global__ __launch_bounds__(256) void rt_ssao_depth_kernel(const float4 *__restrict__ position, float *__restrict__ depth, size_t n) {
     for (size_t k = (size_t)blockIdx.x * 256 + threadIdx.x; k < n; k += (size_t)gridDim.x * 256) depth[k] = position[k].z;
 }
-
-#ifndef RT_SSAO_FASTDIV
-#define RT_SSAO_FASTDIV 1       // 0 = the compiler's IEEE divisions in the sample loop
-#endif
 
 // ssaoFs.glsl:27-44, the 64 kernel samples of one pixel.  FAST: divisions by rt_fastmath.h's fast paths; returns NaN when
 // any of them left its exact range (the caller then takes the IEEE instantiation).  The true sum is never NaN-free-checked:
@@ -646,17 +594,8 @@ __global__ __launch_bounds__(256) void rt_ssao_kernel(const float4 *__restrict__
     constexpr int TW = RT_SSAO_TILE_W, TH = 64 / TW;
     const int wave = threadIdx.x >> 6, ln = threadIdx.x & 63;
     const int W = a.W, H = a.H;
-    // XCD-aware block -> tile map: workgroup b runs on XCD b % 8, so give each XCD one contiguous band of the image
-    // (its 4 MB L2 then holds the band's depth neighbourhood instead of 1/8 of every neighbourhood of the frame)
     const int nbx = (W + 4 * TW - 1) / (4 * TW);
-#if RT_SSAO_XCD
-    const unsigned nb = gridDim.x, per = (nb + 7u) / 8u;
-    const unsigned lb = (blockIdx.x % 8u) * per + blockIdx.x / 8u;
-    if (lb >= nb) return;            // nb not a multiple of 8: the map below covers [0, nb) exactly once (see launch)
-#else
-    const unsigned lb = blockIdx.x;
-#endif
-    const int blkX = (int)(lb % (unsigned)nbx), blkY = (int)(lb / (unsigned)nbx);
+    const int blkX = (int)(blockIdx.x % (unsigned)nbx), blkY = (int)(blockIdx.x / (unsigned)nbx);
     const int i = blkX * (4 * TW) + wave * TW + (ln % TW), j = blkY * TH + (ln / TW);
     if (i >= W || j >= H) return;
     const float u = ((float)i + 0.5f) / (float)W, v = ((float)j + 0.5f) / (float)H;
@@ -721,11 +660,7 @@ hipError_t rt_launch_ssao(const void *position, const void *normal, void *depthP
     memcpy(a.noise, noise, (size_t)nW * nH * 4 * sizeof(float));
     a.nW = nW; a.nH = nH; a.W = W; a.H = H;
     constexpr int TW = RT_SSAO_TILE_W, TH = 64 / TW;
-    unsigned nBlocks = (unsigned)(((W + 4 * TW - 1) / (4 * TW)) * ((H + TH - 1) / TH));
-#if RT_SSAO_XCD
-    nBlocks = (nBlocks + 7u) / 8u * 8u;      // whole groups of 8 so that b -> (b % 8) * per + b / 8 is a bijection
-#endif
-    dim3 grid(nBlocks);
+    dim3 grid((unsigned)(((W + 4 * TW - 1) / (4 * TW)) * ((H + TH - 1) / TH)));
     const size_t n = (size_t)W * H;
     size_t blocks = (n + 255) / 256;
     if (blocks > 256 * 16) blocks = 256 * 16;

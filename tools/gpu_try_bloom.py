@@ -1,5 +1,5 @@
 """Build macro variants of the library on the GPU box and time the bloom chain with each (tools/bench_bloom.py), after the
-bloom GPU tests.  usage: python tools/gpu_try_bloom.py "name:-DRT_BLOOM_TPW=3" ..."""
+bloom GPU tests.  usage: python tools/gpu_try_bloom.py "name:-DRT_BLOOM_XCD=0" ..."""
 import os, subprocess, sys
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)

@@ -1,5 +1,5 @@
 """Build macro variants of the library on the GPU box and time the TAA resolve with each (tools/bench_taa.py), after the TAA
-GPU tests.  usage: python tools/gpu_try_taa.py "name:-DRT_TAA_XCD=0" ..."""
+GPU tests.  usage: python tools/gpu_try_taa.py "name:-DRT_TAA_ROWS=4" ..."""
 import os, subprocess, sys
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
