@@ -1026,6 +1026,82 @@ int rt_camera_rays_at(rt_context *ctx, const rt_params *p, const void *dPixels, 
 int rt_accum_add_at(rt_context *ctx, const void *dSamples, const void *dPixels, size_t n, void *dAccum, const rt_accum_desc *desc,
                     void *dState, void *hipStream);
 
+/* ---- first-hit-guided upsampling: shade at a fraction of the resolution, trace first hits at full resolution, reconstruct the full
+ *      frame by a joint bilateral filter that never mixes two surfaces, and re-shade exactly the pixels whose surface no
+ *      low-resolution ray saw.  The cost of a frame is almost all shading; first hits are cheap and exact.  Where rt_display_resample
+ *      -- a linear filter -- smears every silhouette across the two objects, this keeps it at full resolution.  Device buffers, all
+ *      caller-owned and 16-byte aligned:
+ *        dLow:      rgba32f, lowWidth*lowHeight -- a render's gColor at the low resolution, or a denoised plane;
+ *        dHitsLow, dHitsHigh: lowWidth*lowHeight and width*height rt_hit records (32 B) of rt_camera_rays -> rt_trace_rays(
+ *                   RT_QUERY_CLOSEST) for the low-resolution and the full-resolution rt_params of one view;
+ *        dOut:      rgba32f, width*height, written in full -- as it stands a valid input of every image stage;
+ *        dPixels:   rt_pixel, 8-byte aligned, room for `capacity` entries (may be NULL when capacity == 0): the HOLES;
+ *        dScratch:  rt_upsample_layout's scratchBytes (the same answer as rt_accum_select_layout's; content unspecified, need not be
+ *                   cleared);   dSelState: one rt_select_state (64 B), written whole.
+ *      Asynchronous on hipStream (NULL = the context's stream), no host synchronisation, and the context keeps no state of the
+ *      feature: the reconstruction, then rt_accum_select's scan and emit -- three launches (two when capacity == 0) in stream order.
+ *      All arithmetic is fp32, never fused, with IEEE divide and sqrt; every sum starts at +0 and adds the kept terms one by one in
+ *      the stated order.  max0, min1 and the normalisation n^ of a hit's normal are exactly rt_denoise's (GUIDE above), applied to the
+ *      records of both hit planes inside the kernel: no guide plane is needed.
+ *      POSITION of output pixel p = (x, y), in 64-bit integers (pixel centres of both grids over the same image; floor_div rounds
+ *        towards minus infinity):   numX = (2x + 1)*lowWidth - width;   ix0 = floor_div(numX, 2*width);
+ *        fx = (float)(numX - ix0*2*width) / (float)(2*width);   wx = {1.0f - fx, fx};   likewise numY, iy0, fy, wy with the heights.
+ *        ix0 lies in -1 .. lowWidth-1: the tap ix0 may be -1 and the tap ix0 + 1 may be lowWidth; 0 <= fx < 1.
+ *      A low texel is USABLE when all four channels are finite with |v| <= 2^48.  A tap q of p is DROPPED when it lies outside the
+ *        low image (no clamping), when its texel is not usable, or when object_q != object_p (the records' `object`, misses being
+ *        -1).  The index of a tap is formed only after the tap is known to lie inside the low image.  The normal weight of a tap is
+ *          wn = 1 when object_p < 0 (sky takes sky), otherwise c = min1(max0((n^p.x*n^q.x + n^p.y*n^q.y) + n^p.z*n^q.z)) squared
+ *          normalLog2Power times (c = c*c).
+ *      STAGE 1.  The 2x2 taps q = (ix0 + i, iy0 + j), j outer and i inner, with w = (wx[i]*wy[j]) * wn over the kept ones:
+ *          sw = sum(w);   when sw > 0 and sw >= minWeight:  out = sum(w*rgba_q) / sw per channel, alpha too.  p is INTERPOLATED.
+ *      STAGE 2.  Otherwise p is a HOLE.  The 4x4 taps q = (ix0 + i, iy0 + j), i, j = -1 .. 2, j outer and i inner, the same drop rule,
+ *          w = wn (1 for sky; a tap with wn == 0 contributes nothing):   sw = sum(w);   when sw > 0:  out = sum(w*rgba_q) / sw.
+ *      STAGE 3.  Otherwise p is an ORPHAN hole: out = the low texel (min(x*lowWidth / width, lowWidth - 1), min(y*lowHeight / height,
+ *          lowHeight - 1)) (integer division), copied as it stands, usable or not.
+ *      With the bound every sum stays finite: a weight is at most 1, so 16 terms of w*v stay below 2^52, and a quotient by sw is a
+ *      weighted mean up to rounding.  With lowWidth == width and lowHeight == height the position is exact (fx = fy = 0) and an
+ *      interpolated pixel is its own low texel, w*v / w.  minWeight 0 makes a hole of a pixel only when no tap carries weight.
+ *      HOLES.  dPixels receives the holes in exactly rt_accum_select's ORDER (tiles of 8 x 8 pixels in raster order, raster order
+ *        inside a tile): exactly the first nListed = min(nHoles, capacity) entries are written, nothing behind them is touched and
+ *        every store is checked against the capacity.  dSelState: nPixels = width*height; nSelected = the holes, whatever the
+ *        capacity; nListed; capacity (saturated at 2^32 - 1); overflow = nSelected > capacity; nCapped = the orphans among the holes.
+ *        A hole's value in dOut is a stand-in: the loop below replaces it with the pixel rt_render_to(pHigh) computes.  The result --
+ *        dOut, the list, the state -- is bit-identical from run to run.
+ *      rt_image_put_at: dImage[dPixels[k]] = dSamples[k] for k < n, 16 bytes each (dImage: rgba32f, width*height; dSamples: n
+ *        rgba32f, rt_shade_rays' colour; dPixels: n rt_pixel, 8-byte aligned).  An entry with x >= width or y >= height is skipped and
+ *        never forms an address.  n == 0 is a no-op; dSamples and dPixels may then be NULL.  With duplicates, which of the duplicate
+ *        samples a pixel keeps is unspecified, but every access stays inside the image.  One launch.
+ *      Refused before anything is enqueued, with RT_ERR_INVALID_ARG: NULL context, descriptor or required pointer; a pointer not
+ *      16-byte aligned (dPixels: 8); dOut, dPixels, dScratch or dSelState overlapping dLow, dHitsLow or dHitsHigh or each other; for
+ *      rt_image_put_at dSamples or dPixels overlapping dImage; width or height < 1; lowWidth outside 1..width, lowHeight outside
+ *      1..height; normalLog2Power outside 0..7; minWeight not finite or outside [0, 1]; non-zero reserved words.  RT_ERR_TOO_LARGE:
+ *      width*height > 2^31 - 1; n beyond one grid (2^31 - 1 workgroups of 256).  rt_upsample_layout refuses as rt_accum_select_layout
+ *      does.  The context stays usable after a refusal.  The loop of a frame, with pLow and pHigh the rt_params of one view at the two
+ *      sizes (DESIGN.md 31 has the measurements, stage by stage: at 2x per axis the loop costs more than rt_render_to(pHigh) alone on
+ *      the shipped scenes -- a low render is not a quarter of a full one, and rt_shade_rays has a floor however few holes it shades):
+ *          rt_render_to(ctx, &pLow, dLow, ...);
+ *          rt_camera_rays(ctx, &pLow, dRays, s);   rt_trace_rays(ctx, dRays, nLow, RT_QUERY_CLOSEST, dHitsLow, s);
+ *          rt_camera_rays(ctx, &pHigh, dRays, s);  rt_trace_rays(ctx, dRays, nHigh, RT_QUERY_CLOSEST, dHitsHigh, s);
+ *          rt_upsample(ctx, dLow, dHitsLow, dHitsHigh, dOut, &u, dPixels, capacity, dScratch, dSel, s);
+ *          an 8-byte read of dSel + offsetof(rt_select_state, nSelected): nSelected and nListed
+ *          rt_camera_rays_at(ctx, &pHigh, dPixels, nListed, dRays, s);
+ *          rt_shade_rays(ctx, &pHigh, dRays, dPixels, nListed, dSamples, NULL, NULL, s);
+ *          rt_image_put_at(ctx, dSamples, dPixels, nListed, dOut, width, height, s);
+ *      Afterwards every listed pixel of dOut holds rt_render_to(pHigh)'s bits and every other pixel is interpolated from low-resolution
+ *      pixels of its own object. */
+typedef struct rt_upsample_desc {
+    int32_t width, height;           /* the output, >= 1 */
+    int32_t lowWidth, lowHeight;     /* 1 <= lowWidth <= width, 1 <= lowHeight <= height; any ratio, per axis */
+    int32_t normalLog2Power;         /* 0..7, as rt_denoise_desc */
+    float minWeight;                 /* finite, 0..1: a pixel whose kept 2x2 weight is below it is a hole */
+    int32_t reserved[10];            /* zero */
+} rt_upsample_desc;                  /* 64 B */
+int rt_upsample_layout(int width, int height, size_t *scratchBytes);
+int rt_upsample(rt_context *ctx, const void *dLow, const void *dHitsLow, const void *dHitsHigh, void *dOut, const rt_upsample_desc *desc,
+                void *dPixels, size_t capacity, void *dScratch, void *dSelState, void *hipStream);
+int rt_image_put_at(rt_context *ctx, const void *dSamples, const void *dPixels, size_t n, void *dImage, int width, int height,
+                    void *hipStream);
+
 /* ---- multi-GPU strip helpers */
 /* Number of local rows a rank owns for interleaved strips. */
 int rt_strip_local_rows(int height, int stripRows, int stripCount, int stripIndex);

@@ -10,11 +10,6 @@ namespace {
 constexpr uint32_t kMaxSampleCap = 1u << 24;
 constexpr size_t kMaxListed = (size_t)0x7fffffff * 256;     // one grid of 256-lane workgroups
 
-inline int check_pixel_pointer(rt_context *c, const void *p, bool required) {
-    if ((!p && required) || ((uintptr_t)p & 7u)) return fail(c, RT_ERR_INVALID_ARG, required ? "the pixel list pointer must be non-NULL and 8-byte aligned" : "the pixel list pointer must be 8-byte aligned");
-    return RT_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -33,7 +28,7 @@ int rt_accum_select(rt_context *c, const void *dAccum, const rt_accum_desc *d, u
     RT_TRY(rt_validate_accum_desc(c, d, &rule));
     if (maxSamples < 1 || maxSamples > kMaxSampleCap) return fail(c, RT_ERR_INVALID_ARG, "maxSamples must be in 1..2^24");
     RT_TRY(rt_check_pointers(c, {{dAccum, "accumulator"}, {dScratch, "scratch"}, {dSelState, "select state"}}));
-    RT_TRY(check_pixel_pointer(c, dPixels, capacity != 0));
+    RT_TRY(rt_check_pixel_pointer(c, dPixels, capacity != 0));
     uint64_t npx;
     RT_TRY(rt_check_pixels(c, d->width, d->height, &npx));
     const DevRange accum = {dAccum, (size_t)npx * 32};
@@ -53,7 +48,7 @@ int rt_accum_add_at(rt_context *c, const void *dSamples, const void *dPixels, si
     RtAccumRule rule;
     RT_TRY(rt_validate_accum_desc(c, d, &rule));
     RT_TRY(rt_check_pointers(c, {{dSamples, "sample", n == 0}, {dAccum, "accumulator"}, {dState, "state"}}));
-    RT_TRY(check_pixel_pointer(c, dPixels, n != 0));
+    RT_TRY(rt_check_pixel_pointer(c, dPixels, n != 0));
     uint64_t npx;
     RT_TRY(rt_check_pixels(c, d->width, d->height, &npx));
     if (n > kMaxListed) return fail(c, RT_ERR_TOO_LARGE, "too many list entries in one call");

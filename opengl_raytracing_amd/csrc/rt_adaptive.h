@@ -20,7 +20,23 @@ inline size_t rt_select_scratch_bytes(int width, int height) {
     return kSelectScratchHeader + (((size_t)rt_select_tiles(width, height) * 8 + 15) & ~(size_t)15);
 }
 
-// rt_accum_select: judge (ballots and the workgroups' totals into scratch), scan (offsets, the select state), emit (the list) --
+// The grid every kernel of the selection is launched with, for a width x height image (width * height <= 2^31 - 1)
+struct RtSelectGrid {
+    unsigned tilesX, nTiles, nChunks, chunksPerWg, nWgs;
+    RtSelectGrid(int width, int height) {
+        tilesX = ((unsigned)width + kSelectTile - 1u) / kSelectTile;
+        nTiles = (unsigned)rt_select_tiles(width, height);
+        nChunks = (nTiles + kSelectTilesPerChunk - 1u) / kSelectTilesPerChunk;
+        chunksPerWg = (nChunks + kSelectMaxWgs - 1u) / kSelectMaxWgs;
+        nWgs = (nChunks + chunksPerWg - 1u) / chunksPerWg;                          // <= kSelectMaxWgs, none without a chunk
+    }
+};
+
+// The selection's second half, for any kernel that left one ballot per tile and the two totals of every workgroup of RtSelectGrid
+// in scratch (the judge below; rt_upsample.hip's reconstruction): scan (offsets, the select state), emit (the list) -- two launches
+// on s; the emit is left out when capacity == 0.
+hipError_t rt_launch_select_from_ballots(void *scratch, int width, int height, void *pixels, unsigned capacity, void *selState, hipStream_t s);
+// rt_accum_select: judge (ballots and the workgroups' totals into scratch), then rt_launch_select_from_ballots --
 // three launches on s; the emit is left out when capacity == 0.  capacity <= 2^32 - 1 (the caller saturates it).
 hipError_t rt_launch_accum_select(const void *accum, int width, int height, const RtAccumRule &rule, unsigned maxSamples, void *pixels,
                                   unsigned capacity, void *scratch, void *selState, hipStream_t s);

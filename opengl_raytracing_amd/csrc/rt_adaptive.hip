@@ -14,6 +14,7 @@
 //          of the chunk, scans their popcounts across its lanes, and for each of its 8 tiles a lane with its bit set stores
 //          (x, y) at offset + rank -- after checking that index against the capacity.  Consecutive entries are consecutive
 //          addresses.  The moments are not read again.
+//   Scan and emit know nothing of the judge but its ballots and totals: rt_launch_select_from_ballots runs them for rt_upsample.hip too.
 // ADD_AT is a scatter of one lane per list entry (the per-pixel arithmetic of rt_accum_add_kernel, to the letter), then the
 // statistics over every pixel -- rt_accum_add_kernel's second half on its own: per-wave LDS histograms behind rt_wave_hist_add,
 // counters in registers, one no-return integer atomic per workgroup and non-empty quantity, grid-stride -- then rt_accum.hip's solve.
@@ -263,20 +264,24 @@ __global__ __launch_bounds__(256) void rt_accum_stats_kernel(const f4 *__restric
 hipError_t rt_launch_accum_select(const void *accum, int width, int height, const RtAccumRule &rule, unsigned maxSamples, void *pixels,
                                   unsigned capacity, void *scratch, void *selState, hipStream_t s) {
     const unsigned w = (unsigned)width, h = (unsigned)height, nPixels = w * h;
-    const unsigned tilesX = (w + kTile - 1u) / kTile;
-    const unsigned nTiles = (unsigned)rt_select_tiles(width, height);
-    const unsigned nChunks = (nTiles + kTilesPerChunk - 1u) / kTilesPerChunk;
-    const unsigned chunksPerWg = (nChunks + kSelectMaxWgs - 1u) / kSelectMaxWgs;
-    const unsigned nWgs = (nChunks + chunksPerWg - 1u) / chunksPerWg;               // <= kSelectMaxWgs, none without a chunk
+    const RtSelectGrid g(width, height);
     unsigned *totals = (unsigned *)scratch;
     u64 *ballots = (u64 *)((char *)scratch + kSelectScratchHeader);
     const f4 *moments = (const f4 *)accum + nPixels;
-    hipLaunchKernelGGL(rt_select_judge_kernel, dim3(nWgs), dim3(256), 0, s, moments, w, h, tilesX, nTiles, nChunks, chunksPerWg, rule, maxSamples,
-                       ballots, totals);
-    hipLaunchKernelGGL(rt_select_scan_kernel, dim3(1), dim3(256), 0, s, totals, nWgs, nPixels, capacity, (unsigned *)selState);
+    hipLaunchKernelGGL(rt_select_judge_kernel, dim3(g.nWgs), dim3(256), 0, s, moments, w, h, g.tilesX, g.nTiles, g.nChunks, g.chunksPerWg, rule,
+                       maxSamples, ballots, totals);
+    return rt_launch_select_from_ballots(scratch, width, height, pixels, capacity, selState, s);
+}
+
+hipError_t rt_launch_select_from_ballots(void *scratch, int width, int height, void *pixels, unsigned capacity, void *selState, hipStream_t s) {
+    const unsigned nPixels = (unsigned)width * (unsigned)height;
+    const RtSelectGrid g(width, height);
+    unsigned *totals = (unsigned *)scratch;
+    const u64 *ballots = (const u64 *)((char *)scratch + kSelectScratchHeader);
+    hipLaunchKernelGGL(rt_select_scan_kernel, dim3(1), dim3(256), 0, s, totals, g.nWgs, nPixels, capacity, (unsigned *)selState);
     if (capacity)
-        hipLaunchKernelGGL(rt_select_emit_kernel, dim3(nWgs), dim3(256), 0, s, (const u64 *)ballots, (const unsigned *)totals, tilesX, nTiles, nChunks,
-                           chunksPerWg, (uint2 *)pixels, capacity);
+        hipLaunchKernelGGL(rt_select_emit_kernel, dim3(g.nWgs), dim3(256), 0, s, ballots, (const unsigned *)totals, g.tilesX, g.nTiles, g.nChunks,
+                           g.chunksPerWg, (uint2 *)pixels, capacity);
     return hipGetLastError();
 }
 

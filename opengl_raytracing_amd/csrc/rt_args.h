@@ -1,6 +1,6 @@
 // rt_args.h -- the argument checks the image stages' entry points share (rt_display.cpp, rt_jpeg.cpp, rt_accum.cpp, rt_denoise.cpp,
-// rt_resample.cpp): pointers, overlapping device ranges, the pixel limit, reserved words.  One definition each; an entry point
-// keeps its own order of checks.  Not part of the public ABI.
+// rt_resample.cpp, rt_adaptive.cpp, rt_upsample.cpp): pointers, overlapping device ranges, the pixel limit, reserved words.  One
+// definition each; an entry point keeps its own order of checks.  Not part of the public ABI.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -43,6 +43,12 @@ inline int rt_check_pointers(rt_context *c, std::initializer_list<RtPointerArg> 
     for (const RtPointerArg &a : args)
         if ((!a.p && !a.optional) || !rt_aligned16(a.p))
             return fail(c, RT_ERR_INVALID_ARG, (std::string("the ") + a.name + (a.optional ? " pointer must be 16-byte aligned" : " pointer must be non-NULL and 16-byte aligned")).c_str());
+    return RT_OK;
+}
+
+// A list of rt_pixel records: 8-byte aligned, and non-NULL where the call reads or writes an entry
+inline int rt_check_pixel_pointer(rt_context *c, const void *p, bool required) {
+    if ((!p && required) || ((uintptr_t)p & 7u)) return fail(c, RT_ERR_INVALID_ARG, required ? "the pixel list pointer must be non-NULL and 8-byte aligned" : "the pixel list pointer must be 8-byte aligned");
     return RT_OK;
 }
 

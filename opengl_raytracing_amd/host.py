@@ -143,6 +143,9 @@ def _signatures():
         "rt_accum_select": (ci, [vp, vp, accum, u32, vp, sz, vp, vp, vp]),
         "rt_camera_rays_at": (ci, [vp, params, vp, sz, vp, vp]),
         "rt_accum_add_at": (ci, [vp, vp, vp, sz, vp, accum, vp, vp]),
+        "rt_upsample_layout": (ci, [ci, ci, P(sz)]),
+        "rt_upsample": (ci, [vp, vp, vp, vp, vp, P(L.RtUpsampleDesc), vp, sz, vp, vp, vp]),
+        "rt_image_put_at": (ci, [vp, vp, vp, sz, vp, ci, ci, vp]),
         "rt_strip_local_rows": (ci, [ci, ci, ci, ci]),
         "rt_deinterleave": (ci, [vp, vp, vp, ci, ci, ci, ci, ci, sz, vp]),
         "rt_wire_bytes": (sz, [sz]),
@@ -461,6 +464,14 @@ def accum_select_layout(width, height):
     """The scratch bytes rt_accum_select needs for a width x height accumulator (rt_accum_select_layout).  Needs no GPU."""
     n = ctypes.c_size_t(0)
     _call("rt_accum_select_layout", int(width), int(height), ctypes.byref(n))
+    return n.value
+
+
+def upsample_layout(width, height):
+    """The scratch bytes rt_upsample needs for a width x height output (rt_upsample_layout; the same answer as
+    accum_select_layout's).  Needs no GPU."""
+    n = ctypes.c_size_t(0)
+    _call("rt_upsample_layout", int(width), int(height), ctypes.byref(n))
     return n.value
 
 
@@ -896,6 +907,30 @@ class RayTracer(_Handle):
         d = L.make_accum_desc(width, height, rel_error, lum_floor, min_samples, done_permille)
         self._launch(stream, "rt_accum_add_at", _dev_ptr(d_samples), _dev_ptr(d_pixels), int(n), _dev_ptr(d_accum), ctypes.byref(d),
                      _dev_ptr(d_state))
+
+    # ---- first-hit-guided upsampling (the loop: render low; first hits at both sizes; upsample; camera_rays_at -> shade_rays ->
+    # image_put_at on the holes) ----
+    upsample_layout = staticmethod(upsample_layout)
+
+    def upsample(self, d_low, d_hits_low, d_hits_high, d_out, d_pixels, capacity, d_scratch, d_sel_state, width, height, low_width,
+                 low_height, normal_log2_power=5, min_weight=0.25, stream=None):
+        """The low_width x low_height rgba32f surface d_low reconstructed at width x height into d_out (rt_upsample), guided by the
+        first hits of both sizes (d_hits_low, d_hits_high: trace_rays(camera_rays(params)) of the two rt_params): a pixel is
+        interpolated from the 2 x 2 low-resolution pixels of its own object, or is a hole -- filled from the 4 x 4 window as a
+        stand-in and listed at d_pixels (rt_pixel records in accum_select's tile order, the first min(holes, capacity) of them;
+        capacity 0 counts only and d_pixels may be None).  d_scratch: upsample_layout(width, height) bytes; d_sel_state receives the 64
+        bytes of rt_select_state (layout.SELECT_STATE_DTYPE): nSelected = the holes, nCapped = those without any pixel of their
+        object in the window.  accum_select_alloc allocates the three.  Raw device pointers or CUDA tensors; asynchronous on `stream`
+        (default torch.cuda.current_stream()), no host synchronisation."""
+        d = L.make_upsample_desc(width, height, low_width, low_height, normal_log2_power, min_weight)
+        self._launch(stream, "rt_upsample", _dev_ptr(d_low), _dev_ptr(d_hits_low), _dev_ptr(d_hits_high), _dev_ptr(d_out), ctypes.byref(d),
+                     _dev_ptr(d_pixels), int(capacity), _dev_ptr(d_scratch), _dev_ptr(d_sel_state))
+
+    def image_put_at(self, d_samples, d_pixels, n, d_image, width, height, stream=None):
+        """d_image[d_pixels[k]] = d_samples[k] for the n listed pixels (rt_image_put_at): shade_rays' colours of upsample's holes
+        into the width x height rgba32f surface.  An entry outside the image is skipped; n = 0 is a no-op (d_samples and d_pixels
+        may be None).  Raw device pointers or CUDA tensors; asynchronous on `stream` (default torch.cuda.current_stream())."""
+        self._launch(stream, "rt_image_put_at", _dev_ptr(d_samples), _dev_ptr(d_pixels), int(n), _dev_ptr(d_image), int(width), int(height))
 
     def accum_view(self, d_accum, d_out, width, height, mode="relerr", rel_error=0.02, lum_floor=2.0 ** -10, min_samples=16,
                    done_permille=950, stream=None):

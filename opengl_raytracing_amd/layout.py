@@ -416,6 +416,27 @@ assert all(SELECT_STATE_DTYPE.fields[k][1] == getattr(RtSelectState, k).offset f
 assert RtSelectState.nSelected.offset == SELECT_NSELECTED_OFFSET and RtSelectState.nListed.offset == 8
 
 
+# ---- first-hit-guided upsampling (rt_upsample / rt_image_put_at, include/rt_mi355.h) ---------------------------------------------
+UPSAMPLE_DEFAULTS = dict(normal_log2_power=5, min_weight=0.25)
+
+
+class RtUpsampleDesc(ctypes.Structure):
+    """``rt_upsample_desc``: the output's size, the low-resolution size, the normal weight's power, the least 2 x 2 weight of an
+    interpolated pixel."""
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("lowWidth", ctypes.c_int32), ("lowHeight", ctypes.c_int32),
+                ("normalLog2Power", ctypes.c_int32), ("minWeight", ctypes.c_float), ("reserved", ctypes.c_int32 * 10)]
+
+
+assert ctypes.sizeof(RtUpsampleDesc) == 64 and RtUpsampleDesc.minWeight.offset == 20 and RtUpsampleDesc.reserved.offset == 24
+
+
+def make_upsample_desc(width, height, low_width, low_height, normal_log2_power=5, min_weight=0.25):
+    d = RtUpsampleDesc()
+    d.width, d.height, d.lowWidth, d.lowHeight = int(width), int(height), int(low_width), int(low_height)
+    d.normalLog2Power, d.minWeight = int(normal_log2_power), float(min_weight)
+    return d
+
+
 # ---- denoising (rt_denoise_guide / rt_denoise, include/rt_mi355.h) ---------------------------------------------
 # one pixel of the guide plane: the upper half of an rt_hit, the normal normalised
 DENOISE_GUIDE_DTYPE = np.dtype({"names": ["n", "object"], "formats": [("<f4", 3), "<i4"], "offsets": [0, 12], "itemsize": 16})
