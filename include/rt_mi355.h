@@ -313,6 +313,64 @@ int rt_camera_rays(rt_context *ctx, const rt_params *p, void *dRays, void *hipSt
  * no scene set: RT_ERR_INVALID_ARG. */
 int rt_pick(rt_context *ctx, const rt_params *p, int px, int py, rt_hit *hit);
 
+/* ---- an opt-in acceleration structure behind rt_trace_rays and rt_pick.  Off by default: every query
+ *      then runs the brute-force kernels, which test every object.  Switched on, the host builds a bounding-volume hierarchy over
+ *      the objects' STORED boxes at every scene change, and the queries walk it.  The results are the brute-force ones bit for
+ *      bit, for every ray and every scene: the hierarchy only skips objects whose own stored-box test (the AABB cull above) would
+ *      fail, never anything "behind the current hit", so the set of objects that count does not change, and among equal t the
+ *      lower object index wins whatever the visiting order.  rt_shade_rays and the renders do not use it.
+ *
+ *   Structure.  A binary tree, median split on the box centres, stored in depth-first pre-order: the first child of inner node k is
+ *      node k + 1, and `skip` is the index of the first node behind k's subtree (the node count behind the last one), so a walk
+ *      needs no stack -- "descend" is k + 1, "skip" is nodes[k].skip.  `leaf` is 0xffffffff for an inner node, else first << 4 |
+ *      count: the leaf's objects are order[first .. first + count).  lo / hi: the exact union of the stored boxes below (an
+ *      inverted stored box counts as the swapped one).  Objects with a NaN or infinite bound, and objects whose box spans more
+ *      than largeFraction of the extent of all finite boxes on some axis (a floor, the walls of a room), are kept out of the tree
+ *      on the LOOSE list, which every ray tests as the brute-force kernels do.  order[] and loose[] together hold every object
+ *      index exactly once.
+ *   rt_accel_desc: zero = the default of every field.  enable: 0 switches the feature off.  leafSize: most objects of a leaf,
+ *      1..8 (default 4).  traversal: RT_ACCEL_WAVE walks the tree once per wavefront (nodes by scalar loads; for coherent rays),
+ *      RT_ACCEL_LANE once per ray; RT_ACCEL_AUTO (default) chooses per launch -- today always the per-ray form, the one that is
+ *      never slower than brute force from the default minObjects up whatever the rays; primary rays (rt_camera_rays) run another 2x
+ *      faster with RT_ACCEL_WAVE, which pays from 64 objects (DESIGN.md section 32 has the table).  rt_pick always uses the
+ *      per-wavefront form.  minObjects: scenes with fewer objects are served
+ *      by the brute-force kernels (default 1024), as are scenes whose tree would be empty.  largeFraction: default 0.5.
+ *   rt_set_accel: sticky for the context; NULL or enable == 0 switches it off.  While on, rt_set_scene rebuilds the structure
+ *      when the scene bytes change (an identical re-upload stays a no-op), and rt_set_accel itself builds at once when a scene is
+ *      loaded.  The upload is ordered like the scene's own.  RT_ERR_INVALID_ARG: an unknown traversal, a non-zero reserved word,
+ *      leafSize outside 0..8, a negative minObjects, a negative or non-finite largeFraction.
+ *   rt_accel_info: built (the current scene's queries walk a tree), nodes, leaves, depth, loose, bytes (of the device structure),
+ *      buildMs (host time of the last build and its check), builds (since rt_create), and how many query launches (rt_trace_rays
+ *      and rt_pick) went each way since rt_create: launchesAccel[0] per-wavefront, [1] per-ray, launchesBrute (counted only while
+ *      the feature is on).
+ *   rt_accel_build_host: the same build with no GPU and no context (enable and minObjects are not looked at).  nodes / order /
+ *      loose all NULL: only info is filled (nodes, loose and nObj - loose give the sizes).  Else the arrays are written;
+ *      RT_ERR_TOO_LARGE when a capacity (in elements) is too small or nObj > RT_MAX_OBJECTS. */
+#define RT_ACCEL_INNER 0xffffffffu   /* rt_accel_node.leaf of an inner node */
+typedef enum rt_accel_traversal { RT_ACCEL_AUTO = 0, RT_ACCEL_LANE = 1, RT_ACCEL_WAVE = 2 } rt_accel_traversal;
+typedef struct rt_accel_desc {
+    int32_t enable, leafSize, traversal, minObjects;
+    float largeFraction;
+    int32_t reserved[3];
+} rt_accel_desc;                     /* 32 B */
+typedef struct rt_accel_node { float lo[3]; uint32_t skip; float hi[3]; uint32_t leaf; } rt_accel_node;   /* 32 B */
+typedef struct rt_accel_report {
+    int32_t built, nodes, leaves, depth, loose, reserved0;
+    uint64_t bytes;
+    double buildMs;
+    uint64_t builds, launchesAccel[2], launchesBrute, reserved[3];
+} rt_accel_report;                   /* 96 B */
+int rt_set_accel(rt_context *ctx, const rt_accel_desc *desc);
+int rt_accel_info(rt_context *ctx, rt_accel_report *info);
+int rt_accel_build_host(const void *objects, int nObj, const rt_accel_desc *desc, rt_accel_node *nodes, size_t capNodes, uint32_t *order,
+                        size_t capOrder, uint32_t *loose, size_t capLoose, rt_accel_report *info);
+/* The check every structure passes before the context uploads it, on caller arrays (no GPU): RT_OK iff a walk may use them for these
+ * objects -- pre-order, every skip link strictly forward and equal to its subtree's end, the leaves within leafSize (1..8) and taking
+ * order[] in sequence, every object index below nObj and used exactly once across order[] and loose[], every node box finite and the
+ * exact union of its children's; else RT_ERR_INVALID_ARG.  It reads nothing outside the arrays whatever they hold. */
+int rt_accel_validate_host(const void *objects, int nObj, int leafSize, const rt_accel_node *nodes, size_t nNodes, const uint32_t *order,
+                           size_t nOrder, const uint32_t *loose, size_t nLoose);
+
 /* ---- ray shading on the scene of the last rt_set_scene: main() of raytracingCs.glsl (:509-584) on caller-supplied rays,
  *      for what a frame's pinhole camera cannot ask (cubemap / environment probes, panoramas, stereo, fisheye or
  *      orthographic views, re-shading a sparse set of pixels).  No reference counterpart.  Same fp32 arithmetic as the
@@ -1195,6 +1253,12 @@ RT_SA(sizeof(rt_ray) == 32 && offsetof(rt_ray, tMax) == 12 && offsetof(rt_ray, d
 RT_SA(sizeof(rt_hit) == 32 && offsetof(rt_hit, t) == 12 && offsetof(rt_hit, normal) == 16 && offsetof(rt_hit, object) == 28,
       "rt_hit layout");
 RT_SA(sizeof(rt_pixel) == 8 && offsetof(rt_pixel, y) == 4, "rt_pixel layout");
+RT_SA(sizeof(rt_accel_desc) == 32 && offsetof(rt_accel_desc, largeFraction) == 16 && offsetof(rt_accel_desc, reserved) == 20, "rt_accel_desc is 32 B");
+RT_SA(sizeof(rt_accel_node) == 32 && offsetof(rt_accel_node, skip) == 12 && offsetof(rt_accel_node, hi) == 16 && offsetof(rt_accel_node, leaf) == 28,
+      "rt_accel_node is 32 B");
+RT_SA(sizeof(rt_accel_report) == 96 && offsetof(rt_accel_report, bytes) == 24 && offsetof(rt_accel_report, buildMs) == 32 &&
+      offsetof(rt_accel_report, builds) == 40 && offsetof(rt_accel_report, launchesAccel) == 48 && offsetof(rt_accel_report, launchesBrute) == 64,
+      "rt_accel_report is 96 B");
 RT_SA(sizeof(rt_display_desc) == 32 && offsetof(rt_display_desc, flags) == 12 && offsetof(rt_display_desc, exposure) == 16,
       "rt_display_desc is 32 B");
 RT_SA(sizeof(rt_meter_desc) == 48 && offsetof(rt_meter_desc, adapt) == 20 && offsetof(rt_meter_desc, reserved) == 32,

@@ -173,6 +173,13 @@ int caller_stream(rt_context *c, void *hipStream, hipStream_t *out) {
     return RT_OK;
 }
 
+// Which traversal of the hierarchy an rt_trace_rays launch takes (1 = per ray, 0 = per wavefront; the index of
+// rt_accel_report.launchesAccel).  RT_ACCEL_AUTO is the per-ray form: the host cannot see whether a batch is coherent, and the
+// per-ray walk is the one that never lost to brute force from 1024 objects up (DESIGN.md section 32's table: 7.8-109x on primary
+// rays, 1.3-32x on incoherent ones), where the per-wavefront walk is 2x faster still on primary rays but 1.3x slower than brute
+// force on incoherent rays at 1024 objects.  A caller that knows its rays are coherent asks for RT_ACCEL_WAVE.
+int accel_lane(const rt_accel_desc &d) { return d.traversal == RT_ACCEL_WAVE ? 0 : 1; }
+
 // rt_render_to / rt_render_into_image
 int render_on(rt_context *c, const rt_params *p, void *dColor, void *dPosition, void *dNormal, void *hipStream, bool imageStores) {
     if (!c) return RT_ERR_INVALID_ARG;
@@ -248,6 +255,7 @@ int rt_set_scene(rt_context *c, const void *objects, int nObj, const void *light
     c->lastScene.clear();                  // (refilled at the end: a failed update must not look like the current scene)
     c->sceneGen++;
     c->firstHit.invalidate();              // changed bytes: the recorded first hits are another scene's (identical bytes keep them)
+    c->accel.built = false;                // ... and so is the hierarchy, until rt_accel_scene_changed below has built this scene's
     HIP_TRY(c, c->dObjects.grow(objBytes));
     HIP_TRY(c, c->dLights.grow(ltBytes));
     HIP_TRY(c, c->dCompiled.grow(rt_compiled_total_f4(nObj, nLt)));
@@ -281,6 +289,7 @@ int rt_set_scene(rt_context *c, const void *objects, int nObj, const void *light
         HIP_TRY(c, rt_launch_shadow_tables(c->dCompiled, nObj, nLt, c->dShadowTab, g, c->stream, c->stOnePhase, pcss));
         c->shadowTabValid = true;
     }
+    RT_TRY(rt_accel_scene_changed(c, objects, nObj));    // rt_set_accel: the new scene's hierarchy, uploaded on the same stream
     HIP_TRY(c, hipEventRecord(c->evScene, c->stream));   // foreign streams order behind this (rt_render_to)
     try {
         c->lastScene.resize(objBytes + ltBytes);
@@ -369,7 +378,14 @@ int rt_trace_rays(rt_context *c, const void *dRays, size_t nRays, int mode, void
     hipStream_t s;
     int rc = caller_stream(c, hipStream, &s);
     if (rc) return rc;
-    HIP_TRY(c, rt_launch_trace_rays((const float4 *)dRays, nRays, c->dCompiled, c->nObj, mode == RT_QUERY_ANY, dOut, s));
+    if (c->accel.built) {
+        const int lane = accel_lane(c->accel.desc);
+        HIP_TRY(c, rt_launch_trace_rays_accel((const float4 *)dRays, nRays, c->dCompiled, c->accel.dev, mode == RT_QUERY_ANY, lane, dOut, s));
+        c->accel.report.launchesAccel[lane]++;
+    } else {
+        HIP_TRY(c, rt_launch_trace_rays((const float4 *)dRays, nRays, c->dCompiled, c->nObj, mode == RT_QUERY_ANY, dOut, s));
+        if (c->accel.on) c->accel.report.launchesBrute++;
+    }
     SCHED_TRY(c, recordLaunch(s));
     return RT_OK;
 }
@@ -454,7 +470,13 @@ int rt_pick(rt_context *c, const rt_params *p, int px, int py, rt_hit *hit) {
     HIP_TRY(c, c->hPick.grow(1));
     RtFrame f;
     build_frame(c, &q, &f);
-    HIP_TRY(c, rt_launch_pick(f, c->dNoise, c->dCompiled, px, py, c->dPick, c->stream));
+    if (c->accel.built) {
+        HIP_TRY(c, rt_launch_pick_accel(f, c->dNoise, c->dCompiled, c->accel.dev, px, py, c->dPick, c->stream));
+        c->accel.report.launchesAccel[0]++;
+    } else {
+        HIP_TRY(c, rt_launch_pick(f, c->dNoise, c->dCompiled, px, py, c->dPick, c->stream));
+        if (c->accel.on) c->accel.report.launchesBrute++;
+    }
     HIP_TRY(c, hipMemcpyAsync(c->hPick, c->dPick, sizeof(rt_hit), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     memcpy(hit, c->hPick, sizeof(rt_hit));

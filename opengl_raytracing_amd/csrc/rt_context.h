@@ -12,6 +12,20 @@
 #include "rt_resample.h"
 #include "rt_sched.h"
 
+// rt_set_accel's state (rt_accel.cpp): the settings, the device copy of the current scene's structure and the counters of
+// rt_accel_info.  `built`: the queries of the current scene walk the tree (else they run the brute-force kernels).
+struct RtAccelState {
+    bool on = false, built = false;
+    rt_accel_desc desc = {};                   // resolved: no zero field
+    RtAccelDev dev;
+    DevBuf<uint8_t> dBuf;                      // nodes, order[], loose[]
+    PinnedBuf<uint8_t> hStage[2];              // double-buffered like the scene's: a buffer is rewritten only after its last copy has ended
+    DevEvent evStage[2];
+    bool stageUsed[2] = {false, false};
+    unsigned stageSeq = 0;
+    rt_accel_report report = {};
+};
+
 // Everything the context allocates is held by an owner (rt_devbuf.h): after rt_destroy has drained the streams, `delete`
 // releases it all.  The stream comes first so that it goes last.
 struct rt_context {
@@ -73,8 +87,13 @@ struct rt_context {
     ResampleTables resample;                   // rt_display_resample: the device copies of the two axis tables (rt_resample.h)
     DevBuf<uint8_t> dJpegScratch;              // rt_present_submit_jpeg: rt_jpeg_layout's scratch (YUV planes included) ...
     ScratchUse jpegUse;                        // ... and who ran last in it, on whichever stream
+    RtAccelState accel;                        // rt_set_accel: the hierarchy behind rt_trace_rays / rt_pick
     std::string err;
 };
+
+// rt_set_scene's hook (rt_accel.cpp): the structure of the new scene, uploaded on the context's stream.  Called between
+// waitForLaunches and the record of evScene.
+int rt_accel_scene_changed(rt_context *c, const void *objects, int nObj);
 
 inline int fail(rt_context *c, int code, const char *what, hipError_t e = hipSuccess) {
     if (c) {

@@ -107,6 +107,18 @@ hipError_t rt_launch_camera_rays(const RtFrame &f, const uint8_t *dNoise, float4
 hipError_t rt_launch_camera_rays_at(const RtFrame &f, const uint8_t *dNoise, const uint2 *dPixels, size_t n, float4 *dRays, hipStream_t s);
 hipError_t rt_launch_pick(const RtFrame &f, const uint8_t *dNoise, const float4 *dCompiled, int px, int py, float4 *dOut,
                           hipStream_t s);
+// The same queries through the threaded hierarchy (rt_accel.inc; rt_accel.h has the structure): nodes = 2 float4 per node
+// (lo, skip) (hi, leaf), order / loose = object indices.  lane: the per-ray traversal, else the per-wavefront one.  The host has
+// checked the structure (rt_accel_validate); the kernels' loops are bounded by nNodes whatever it holds.
+struct RtAccelDev {
+    const float4 *nodes = nullptr;
+    const unsigned *order = nullptr, *loose = nullptr;
+    int nNodes = 0, nLoose = 0;
+};
+hipError_t rt_launch_trace_rays_accel(const float4 *dRays, size_t nRays, const float4 *dCompiled, const RtAccelDev &acc, int anyHit, int lane,
+                                      void *dOut, hipStream_t s);
+hipError_t rt_launch_pick_accel(const RtFrame &f, const uint8_t *dNoise, const float4 *dCompiled, const RtAccelDev &acc, int px, int py,
+                                float4 *dOut, hipStream_t s);
 // rt_debug_device_math: one rt_device_math_op on n records of four words, one record per thread (rt_kernels.hip).
 hipError_t rt_launch_device_math(int op, const uint4 *dIn, uint4 *dOut, size_t n, hipStream_t s);
 // Ray shading (rt_shade.inc).  dRays: 2 float4 per ray (rt_ray); dPixels: one uint2 per ray, or null = rt_render_to(f.p)'s

@@ -1195,3 +1195,8 @@ hipError_t rt_launch_device_math(int op, const uint4 *dIn, uint4 *dOut, size_t n
 // Ray shading (rt_shade_rays): main() on caller-supplied rays, same helpers, separate kernel.
 // =========================================================================================
 #include "rt_shade.inc"
+
+// =========================================================================================
+// The queries through rt_set_accel's threaded hierarchy: rt_query.inc's helpers, separate kernels.
+// =========================================================================================
+#include "rt_accel.inc"

@@ -89,6 +89,10 @@ def _signatures():
         "rt_trace_rays": (ci, [vp, vp, sz, ci, vp, vp]),
         "rt_camera_rays": (ci, [vp, params, vp, vp]),
         "rt_pick": (ci, [vp, params, ci, ci, P(L.RtHit)]),
+        "rt_set_accel": (ci, [vp, P(L.RtAccelDesc)]),
+        "rt_accel_info": (ci, [vp, P(L.RtAccelReport)]),
+        "rt_accel_build_host": (ci, [vp, ci, P(L.RtAccelDesc), vp, sz, vp, sz, vp, sz, P(L.RtAccelReport)]),
+        "rt_accel_validate_host": (ci, [vp, ci, ci, vp, sz, vp, sz, vp, sz]),
         "rt_shade_rays": (ci, [vp, params, vp, vp, sz, vp, vp, vp, vp]),
         "rt_last_error": (cs, [vp]),
         "rt_generate_aabb": (ci, [vp, ci]),
@@ -510,6 +514,45 @@ def reproject_report(d_report):
     return d_report.cpu().numpy().view(np.uint8).reshape(-1)[:L.REPROJECT_REPORT_BYTES].view(L.REPROJECT_REPORT_DTYPE)[0]
 
 
+AccelStructure = collections.namedtuple("AccelStructure", "nodes order loose info")
+AccelStructure.__doc__ = """rt_accel_build_host's answer: nodes (layout.ACCEL_NODE_DTYPE records, depth-first pre-order), order and loose (uint32
+object indices: the leaves' slots, the objects outside the tree) and info (the counts, as accel_info's dict)."""
+
+
+def _accel_report(r):
+    """An rt_accel_report as a dict (launches_accel: (per-wavefront, per-ray))."""
+    return dict(built=bool(r.built), nodes=r.nodes, leaves=r.leaves, depth=r.depth, loose=r.loose, bytes=r.bytes, build_ms=r.buildMs,
+                builds=r.builds, launches_accel=tuple(r.launchesAccel), launches_brute=r.launchesBrute)
+
+
+def accel_build_host(objects, desc=None, **kw):
+    """The hierarchy RayTracer.set_accel builds for `objects` (OBJECT_DTYPE records), on the host (rt_accel_build_host) ->
+    AccelStructure.  `desc`: an RtAccelDesc, or make_accel_desc's keywords.  Needs no GPU."""
+    objects = np.ascontiguousarray(objects)
+    assert objects.dtype.itemsize == L.OBJECT_STRIDE
+    d = desc if desc is not None else L.make_accel_desc(**kw)
+    n, info = len(objects), L.RtAccelReport()
+    op = _ptr(objects) if n else None
+    _call("rt_accel_build_host", op, n, ctypes.byref(d), None, 0, None, 0, None, 0, ctypes.byref(info))
+    nodes = np.zeros(info.nodes, dtype=L.ACCEL_NODE_DTYPE)
+    order, loose = np.zeros(n - info.loose, dtype=np.uint32), np.zeros(info.loose, dtype=np.uint32)
+    _call("rt_accel_build_host", op, n, ctypes.byref(d), _ptr(nodes), len(nodes), _ptr(order), len(order), _ptr(loose), len(loose),
+          ctypes.byref(info))
+    return AccelStructure(nodes, order, loose, _accel_report(info))
+
+
+def accel_validate_host(objects, nodes, order, loose, leaf_size=4):
+    """True iff the arrays pass the check every structure passes before it is uploaded (rt_accel_validate_host).  Needs no GPU."""
+    objects, nodes = np.ascontiguousarray(objects), np.ascontiguousarray(nodes, dtype=L.ACCEL_NODE_DTYPE)
+    order, loose = np.ascontiguousarray(order, dtype=np.uint32), np.ascontiguousarray(loose, dtype=np.uint32)
+    p = lambda a: _ptr(a) if len(a) else None
+    rc = (_LIB or load_library()).entry["rt_accel_validate_host"](p(objects), len(objects), int(leaf_size), p(nodes), len(nodes), p(order), len(order),
+                                                                  p(loose), len(loose))
+    if rc not in (0, -1):
+        raise RtError(rc, "rt_accel_validate_host")
+    return rc == 0
+
+
 PickHit = collections.namedtuple("PickHit", "object t position normal")
 PickHit.__doc__ = """rt_pick's answer: object index (-1 = nothing under the pixel), hit distance (tMax on a miss), hit position and
 normal (float32[3] each; zero on a miss)."""
@@ -784,6 +827,23 @@ class RayTracer(_Handle):
         h = L.RtHit()
         self._call("rt_pick", ctypes.byref(params), int(x), int(y), ctypes.byref(h))
         return PickHit(h.object, h.t, np.array(h.position, dtype=np.float32), np.array(h.normal, dtype=np.float32))
+
+    def set_accel(self, desc=True, **kw):
+        """Switch the hierarchy behind trace_rays / pick on or off (rt_set_accel; sticky).  None / False: off.  True or keywords
+        (make_accel_desc's: leaf_size, traversal, min_objects, large_fraction): on; or an RtAccelDesc.  The results of the queries
+        do not change, bit for bit."""
+        if desc is None or desc is False:
+            self._call("rt_set_accel", None)
+            return
+        d = desc if isinstance(desc, L.RtAccelDesc) else L.make_accel_desc(**kw)
+        self._call("rt_set_accel", ctypes.byref(d))
+
+    def accel_info(self):
+        """rt_accel_info as a dict: built, nodes, leaves, depth, loose, bytes, build_ms, builds, launches_accel (per-wavefront,
+        per-ray), launches_brute."""
+        r = L.RtAccelReport()
+        self._call("rt_accel_info", ctypes.byref(r))
+        return _accel_report(r)
 
     def get_surfaces(self):
         """Device pointers (ints) of the context-owned gColor, gPosition, gNormal of the last rt_render."""

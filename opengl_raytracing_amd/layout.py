@@ -198,6 +198,40 @@ class RtHit(ctypes.Structure):
 assert ctypes.sizeof(RtRay) == RAY_DTYPE.itemsize == 32 and ctypes.sizeof(RtHit) == HIT_DTYPE.itemsize == 32
 
 
+# ---- the hierarchy behind the queries (rt_set_accel / rt_accel_info / rt_accel_build_host, include/rt_mi355.h) ----------------
+ACCEL_AUTO, ACCEL_LANE, ACCEL_WAVE = 0, 1, 2
+ACCEL_TRAVERSALS = {"auto": ACCEL_AUTO, "lane": ACCEL_LANE, "wave": ACCEL_WAVE}
+ACCEL_INNER = 0xFFFFFFFF       # rt_accel_node.leaf of an inner node; else first << 4 | count into order[]
+
+ACCEL_NODE_DTYPE = np.dtype({"names": ["lo", "skip", "hi", "leaf"], "formats": [("<f4", 3), "<u4", ("<f4", 3), "<u4"],
+                             "offsets": [0, 12, 16, 28], "itemsize": 32})
+
+
+class RtAccelDesc(ctypes.Structure):
+    """``rt_accel_desc``: zero = the default of every field."""
+    _fields_ = [("enable", ctypes.c_int32), ("leafSize", ctypes.c_int32), ("traversal", ctypes.c_int32), ("minObjects", ctypes.c_int32),
+                ("largeFraction", ctypes.c_float), ("reserved", ctypes.c_int32 * 3)]
+
+
+class RtAccelReport(ctypes.Structure):
+    """``rt_accel_report``: what rt_accel_info and rt_accel_build_host answer."""
+    _fields_ = [("built", ctypes.c_int32), ("nodes", ctypes.c_int32), ("leaves", ctypes.c_int32), ("depth", ctypes.c_int32),
+                ("loose", ctypes.c_int32), ("reserved0", ctypes.c_int32), ("bytes", ctypes.c_uint64), ("buildMs", ctypes.c_double),
+                ("builds", ctypes.c_uint64), ("launchesAccel", ctypes.c_uint64 * 2), ("launchesBrute", ctypes.c_uint64),
+                ("reserved", ctypes.c_uint64 * 3)]
+
+
+assert ctypes.sizeof(RtAccelDesc) == 32 and ctypes.sizeof(RtAccelReport) == 96 and ACCEL_NODE_DTYPE.itemsize == 32
+
+
+def make_accel_desc(enable=True, leaf_size=0, traversal="auto", min_objects=0, large_fraction=0.0):
+    """An rt_accel_desc; 0 keeps a field's default (leaf 4, minObjects 1024, largeFraction 0.5).  traversal: "auto", "lane", "wave" or a number."""
+    d = RtAccelDesc()
+    d.enable, d.leafSize, d.minObjects, d.largeFraction = int(bool(enable)), int(leaf_size), int(min_objects), float(large_fraction)
+    d.traversal = int(ACCEL_TRAVERSALS.get(traversal, traversal))
+    return d
+
+
 # ---- ray shading (rt_shade_rays, include/rt_mi355.h) ------------------------------------------
 PIXEL_DTYPE = np.dtype({"names": ["x", "y"], "formats": ["<u4", "<u4"], "offsets": [0, 4], "itemsize": 8})
 

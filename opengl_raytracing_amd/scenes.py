@@ -222,6 +222,24 @@ def make_scene(cfg, generate_aabb):
     return sc
 
 
+def sphere_cloud(n, seed, generate_aabb, floor=True):
+    """n seeded spheres (radius 0.3..1.2) uniform in a cube whose half edge 4 * n^(1/3) grows with n (constant density), plus a floor
+    plane under them: the scaling scene of the query hierarchy's tests and measurements (tools/bench_accel.py).  -> (objects, half edge)."""
+    rng = np.random.default_rng(seed)
+    half = 4.0 * max(n, 1) ** (1.0 / 3.0)
+    objs = L.default_objects(n + (1 if floor else 0))
+    objs["type"][:n] = L.SPHERE
+    objs["position"][:n] = rng.uniform(-half, half, (n, 3))
+    objs["radius"][:n] = rng.uniform(0.3, 1.2, n)
+    if floor:
+        objs[n]["type"] = L.PLANE
+        objs[n]["position"] = (0.0, -half - 2.0, 0.0)
+        objs[n]["normal"] = (0.0, 1.0, 0.0)
+        objs[n]["size"] = (4.0 * half, 4.0 * half)
+    generate_aabb(objs)
+    return objs, half
+
+
 def nan_parity_scene(generate_aabb):
     """Tiny scene that forces the reference's undefined-arithmetic corners
     (SURVEY.md A.1#12, a16, a17): roughness 0 (0/0 in the NDF), a light straight
