@@ -318,7 +318,8 @@ int rt_pick(rt_context *ctx, const rt_params *p, int px, int py, rt_hit *hit);
  *      the objects' STORED boxes at every scene change, and the queries walk it.  The results are the brute-force ones bit for
  *      bit, for every ray and every scene: the hierarchy only skips objects whose own stored-box test (the AABB cull above) would
  *      fail, never anything "behind the current hit", so the set of objects that count does not change, and among equal t the
- *      lower object index wins whatever the visiting order.  rt_shade_rays and the renders do not use it.
+ *      lower object index wins whatever the visiting order.  By default rt_shade_rays does not use it (rt_set_accel_shading
+ *      below switches that on); the renders never do.
  *
  *   Structure.  A binary tree, median split on the box centres, stored in depth-first pre-order: the first child of inner node k is
  *      node k + 1, and `skip` is the index of the first node behind k's subtree (the node count behind the last one), so a walk
@@ -370,6 +371,38 @@ int rt_accel_build_host(const void *objects, int nObj, const rt_accel_desc *desc
  * exact union of its children's; else RT_ERR_INVALID_ARG.  It reads nothing outside the arrays whatever they hold. */
 int rt_accel_validate_host(const void *objects, int nObj, int leafSize, const rt_accel_node *nodes, size_t nNodes, const uint32_t *order,
                            size_t nOrder, const uint32_t *loose, size_t nLoose);
+
+/* ---- the same hierarchy behind rt_shade_rays.  Off by default, also while rt_set_accel is on: rt_shade_rays
+ *      then launches the brute-force kernel, which tests every object for every closest-hit, shadow, PCSS-blocker and subsurface
+ *      ray.  Switched on, those four kinds of ray walk the tree rt_set_accel built (this switch builds nothing; the two switches
+ *      are independent and may be set in either order).  The colour, position and normal written are the brute-force kernel's,
+ *      bit for bit, for every ray and every scene: closest hits by the argument above; a shadow or blocker ray's answer is "some
+ *      object passes its own stored-box test at maxRayDistance and is hit with 0 < t < min(maxRayDistance, lightDistance)", the
+ *      walk tests nodes and gates objects at the first distance and accepts at the second, and an existential answer does not
+ *      depend on the visiting order.
+ *
+ *   rt_accel_shade_desc: zero = the default of every field.  enable: 0 switches the feature off.  traversal: rt_accel_traversal's
+ *      values, independent of rt_accel_desc's: RT_ACCEL_WAVE walks once per wavefront (the lanes still on a path share the walk),
+ *      RT_ACCEL_LANE once per ray; RT_ACCEL_AUTO (default) is the per-ray form, which from 256 objects up was faster than the
+ *      brute-force kernel on every measured ray set and from 1024 up faster than the per-wavefront form too; RT_ACCEL_WAVE pays
+ *      from 64 objects and is the faster form on camera frames and probes up to 256 (DESIGN.md section 33 has the table).
+ *      minObjects: scenes with fewer objects are shaded by the brute-force kernel (0 = the default, 256).  rt_set_accel has a
+ *      minObjects of its own (default 1024) below which it builds no tree: to shade smaller scenes through one, lower both.
+ *   rt_set_accel_shading: sticky for the context; NULL or enable == 0 switches it off.  RT_ERR_INVALID_ARG: a NULL context, an
+ *      unknown traversal, a non-zero reserved word, a negative minObjects.
+ *   rt_accel_shading_info: active (1 iff the next rt_shade_rays would walk the tree: the switch is on, rt_set_accel has built the
+ *      current scene's tree, and the scene has at least minObjects objects), traversal (the resolved one: RT_ACCEL_LANE or
+ *      RT_ACCEL_WAVE; 0 while off), and how many rt_shade_rays launches went each way since rt_create: launchesAccel[0]
+ *      per-wavefront, [1] per-ray, launchesBrute (counted only while this switch is on).  rt_accel_info's counters count queries
+ *      only. */
+#define RT_ACCEL_SHADE_DEFAULT_MIN_OBJECTS 256
+typedef struct rt_accel_shade_desc { int32_t enable, traversal, minObjects, reserved[5]; } rt_accel_shade_desc;   /* 32 B; zero = defaults */
+typedef struct rt_accel_shade_report {
+    int32_t active, traversal;
+    uint64_t launchesAccel[2], launchesBrute, reserved[2];
+} rt_accel_shade_report;             /* 48 B */
+int rt_set_accel_shading(rt_context *ctx, const rt_accel_shade_desc *desc);
+int rt_accel_shading_info(rt_context *ctx, rt_accel_shade_report *info);
 
 /* ---- ray shading on the scene of the last rt_set_scene: main() of raytracingCs.glsl (:509-584) on caller-supplied rays,
  *      for what a frame's pinhole camera cannot ask (cubemap / environment probes, panoramas, stereo, fisheye or
@@ -1259,6 +1292,10 @@ RT_SA(sizeof(rt_accel_node) == 32 && offsetof(rt_accel_node, skip) == 12 && offs
 RT_SA(sizeof(rt_accel_report) == 96 && offsetof(rt_accel_report, bytes) == 24 && offsetof(rt_accel_report, buildMs) == 32 &&
       offsetof(rt_accel_report, builds) == 40 && offsetof(rt_accel_report, launchesAccel) == 48 && offsetof(rt_accel_report, launchesBrute) == 64,
       "rt_accel_report is 96 B");
+RT_SA(sizeof(rt_accel_shade_desc) == 32 && offsetof(rt_accel_shade_desc, traversal) == 4 && offsetof(rt_accel_shade_desc, minObjects) == 8 &&
+      offsetof(rt_accel_shade_desc, reserved) == 12, "rt_accel_shade_desc is 32 B");
+RT_SA(sizeof(rt_accel_shade_report) == 48 && offsetof(rt_accel_shade_report, traversal) == 4 && offsetof(rt_accel_shade_report, launchesAccel) == 8 &&
+      offsetof(rt_accel_shade_report, launchesBrute) == 24 && offsetof(rt_accel_shade_report, reserved) == 32, "rt_accel_shade_report is 48 B");
 RT_SA(sizeof(rt_display_desc) == 32 && offsetof(rt_display_desc, flags) == 12 && offsetof(rt_display_desc, exposure) == 16,
       "rt_display_desc is 32 B");
 RT_SA(sizeof(rt_meter_desc) == 48 && offsetof(rt_meter_desc, adapt) == 20 && offsetof(rt_meter_desc, reserved) == 32,

@@ -450,8 +450,18 @@ int rt_shade_rays(rt_context *c, const rt_params *p, const void *dRays, const vo
     if ((rc = caller_stream(c, hipStream, &s))) return rc;
     RtFrame f;
     build_frame(c, p, &f);
-    HIP_TRY(c, rt_launch_shade_rays(f, c->dCompiled, c->dNoise, c->dSky, (const float4 *)dRays, (const uint2 *)dPixels, nRays,
-                                    (float4 *)dColor, (float4 *)dPosition, (uint2 *)dNormal, s));
+    // rt_set_accel_shading: the same kernel body over the tree.  The tree is read under the protocol above: this launch is
+    // recorded on s, rt_set_scene / rt_set_accel rebuild behind waitForLaunches, and the buffer grows only after drain().
+    if (c->accelShadeActive()) {
+        const int lane = c->accelShade.lane;
+        HIP_TRY(c, rt_launch_shade_rays_accel(f, c->dCompiled, c->accel.dev, lane, c->dNoise, c->dSky, (const float4 *)dRays,
+                                              (const uint2 *)dPixels, nRays, (float4 *)dColor, (float4 *)dPosition, (uint2 *)dNormal, s));
+        c->accelShade.launchesAccel[lane]++;
+    } else {
+        HIP_TRY(c, rt_launch_shade_rays(f, c->dCompiled, c->dNoise, c->dSky, (const float4 *)dRays, (const uint2 *)dPixels, nRays,
+                                        (float4 *)dColor, (float4 *)dPosition, (uint2 *)dNormal, s));
+        if (c->accelShade.on) c->accelShade.launchesBrute++;
+    }
     SCHED_TRY(c, recordLaunch(s));
     return RT_OK;
 }

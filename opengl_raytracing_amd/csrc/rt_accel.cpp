@@ -322,6 +322,38 @@ int rt_accel_info(rt_context *c, rt_accel_report *out) {
     return RT_OK;
 }
 
+// rt_shade_rays through the same tree (rt_accel_shade.inc).  Nothing is built or uploaded here: whether a launch walks the tree
+// is decided per launch from `accel.built` (rt_context::accelShadeActive), so the two switches commute.
+int rt_set_accel_shading(rt_context *c, const rt_accel_shade_desc *desc) {
+    if (!c) return RT_ERR_INVALID_ARG;
+    rt_accel_shade_desc d;
+    memset(&d, 0, sizeof d);
+    if (desc) d = *desc;
+    if (d.traversal != RT_ACCEL_AUTO && d.traversal != RT_ACCEL_LANE && d.traversal != RT_ACCEL_WAVE)
+        return fail(c, RT_ERR_INVALID_ARG, "rt_accel_shade_desc: unknown traversal");
+    for (int k = 0; k < 5; k++)
+        if (d.reserved[k]) return fail(c, RT_ERR_INVALID_ARG, "rt_accel_shade_desc: reserved words must be zero");
+    if (d.minObjects < 0) return fail(c, RT_ERR_INVALID_ARG, "rt_accel_shade_desc: negative minObjects");
+    RtAccelShadeState &S = c->accelShade;
+    S.on = desc && d.enable != 0;
+    // RT_ACCEL_AUTO: the per-ray walk (DESIGN.md section 33 has the measurement behind it and behind the default minObjects)
+    S.lane = d.traversal == RT_ACCEL_WAVE ? 0 : 1;
+    S.minObjects = d.minObjects ? d.minObjects : RT_ACCEL_SHADE_DEFAULT_MIN_OBJECTS;
+    return RT_OK;
+}
+
+int rt_accel_shading_info(rt_context *c, rt_accel_shade_report *out) {
+    if (!c || !out) return RT_ERR_INVALID_ARG;
+    const RtAccelShadeState &S = c->accelShade;
+    memset(out, 0, sizeof *out);
+    out->active = c->accelShadeActive() ? 1 : 0;
+    out->traversal = !S.on ? 0 : S.lane ? RT_ACCEL_LANE : RT_ACCEL_WAVE;
+    out->launchesAccel[0] = S.launchesAccel[0];
+    out->launchesAccel[1] = S.launchesAccel[1];
+    out->launchesBrute = S.launchesBrute;
+    return RT_OK;
+}
+
 int rt_accel_validate_host(const void *objects, int nObj, int leafSize, const rt_accel_node *nodes, size_t nNodes, const uint32_t *order,
                            size_t nOrder, const uint32_t *loose, size_t nLoose) {
     if (nObj < 0 || (nObj > 0 && !objects) || (nNodes && !nodes) || (nOrder && !order) || (nLoose && !loose)) return RT_ERR_INVALID_ARG;

@@ -26,6 +26,15 @@ struct RtAccelState {
     rt_accel_report report = {};
 };
 
+// rt_set_accel_shading's state (rt_accel.cpp): whether rt_shade_rays walks rt_set_accel's tree, by which traversal and from how
+// many objects, and the launch counters of rt_accel_shading_info.  It owns no structure: `accel.built` says whether there is one.
+struct RtAccelShadeState {
+    bool on = false;
+    int lane = 1;                              // resolved traversal: 1 = per ray, 0 = per wavefront (the index of launchesAccel)
+    int minObjects = RT_ACCEL_SHADE_DEFAULT_MIN_OBJECTS;
+    uint64_t launchesAccel[2] = {0, 0}, launchesBrute = 0;
+};
+
 // Everything the context allocates is held by an owner (rt_devbuf.h): after rt_destroy has drained the streams, `delete`
 // releases it all.  The stream comes first so that it goes last.
 struct rt_context {
@@ -88,6 +97,9 @@ struct rt_context {
     DevBuf<uint8_t> dJpegScratch;              // rt_present_submit_jpeg: rt_jpeg_layout's scratch (YUV planes included) ...
     ScratchUse jpegUse;                        // ... and who ran last in it, on whichever stream
     RtAccelState accel;                        // rt_set_accel: the hierarchy behind rt_trace_rays / rt_pick
+    RtAccelShadeState accelShade;              // rt_set_accel_shading: ... and, opted into separately, behind rt_shade_rays
+    // the next rt_shade_rays walks the tree
+    bool accelShadeActive() const { return accelShade.on && accel.built && nObj >= accelShade.minObjects; }
     std::string err;
 };
 

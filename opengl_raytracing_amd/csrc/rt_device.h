@@ -126,3 +126,8 @@ hipError_t rt_launch_device_math(int op, const uint4 *dIn, uint4 *dOut, size_t n
 hipError_t rt_launch_shade_rays(const RtFrame &f, const float4 *dCompiled, const uint8_t *dNoise, const uint16_t *dSky,
                                 const float4 *dRays, const uint2 *dPixels, size_t nRays, float4 *dColor, float4 *dPos,
                                 uint2 *dNormal, hipStream_t s);
+// ... and through the hierarchy (rt_accel_shade.inc; rt_set_accel_shading): the same kernel body, closest-hit, shadow, blocker
+// and subsurface rays by a walk of `acc`.  lane: the per-ray traversal, else the per-wavefront one.
+hipError_t rt_launch_shade_rays_accel(const RtFrame &f, const float4 *dCompiled, const RtAccelDev &acc, int lane, const uint8_t *dNoise,
+                                      const uint16_t *dSky, const float4 *dRays, const uint2 *dPixels, size_t nRays, float4 *dColor,
+                                      float4 *dPos, uint2 *dNormal, hipStream_t s);

@@ -470,6 +470,10 @@ struct LaneLds {
         tOut = minT;
         return hit;
     }
+    template <int COUNT>
+    __device__ __forceinline__ bool any(const Ray &r, float maxDist, float limit, unsigned &rays) const {
+        return lane_any<COUNT>(*this, nObj, r, maxDist, limit, rays);
+    }
 };
 
 #ifndef RT_V0_WAVES
@@ -1200,3 +1204,8 @@ hipError_t rt_launch_device_math(int op, const uint4 *dIn, uint4 *dOut, size_t n
 // The queries through rt_set_accel's threaded hierarchy: rt_query.inc's helpers, separate kernels.
 // =========================================================================================
 #include "rt_accel.inc"
+
+// =========================================================================================
+// Ray shading through the hierarchy (rt_set_accel_shading): rt_shade.inc's kernel body over rt_accel.inc's walks.
+// =========================================================================================
+#include "rt_accel_shade.inc"

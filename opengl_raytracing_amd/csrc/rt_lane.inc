@@ -7,6 +7,7 @@
 //   Rec rec(int i)                      object i's hot record, i wave-uniform (the traversal loops): h[k] is its float4 k
 //   bool shape(r, a, h, h0, h1, t)      shape_test of that object, whose first two float4 the caller holds
 //   int closest(r, maxDist, t)          intersectObjects (:155-196): the hit index or -1, t = minT
+//   bool any<COUNT>(r, maxDist, limit, rays)   a shadow / blocker ray's answer (lane_any's rule; LaneLds and ShadeScene call it)
 //   float4 light(int i, int k)          float4 k of light i's record, i wave-uniform
 //   float halton(which, i, base)        haltonSequence(i, base), i wave-uniform: entry i of table `which` (0: base 2, 1: base
 //                                       3), halton_eval beyond RT_HALTON_N
@@ -81,7 +82,7 @@ __device__ __forceinline__ float lane_pcf(const A &sc, const RtFrame &f, v3 orig
         v3 jd = (lightDir + (tangent * rx) * filterSize) + (bitangent * ry) * filterSize;
         if (ltype != 1) jd = normalize(jd);
         Ray sr; sr.o = origin; sr.d = jd;
-        bool occ = lane_any<COUNT>(sc, sc.nObj, sr, f.p.maxRayDistance, limit, rays);
+        bool occ = sc.template any<COUNT>(sr, f.p.maxRayDistance, limit, rays);
         shadow += occ ? 0.0f : 1.0f;
     }
     return shadow / (float)pcfSamples;
@@ -97,7 +98,7 @@ __device__ __forceinline__ float lane_pcss(const A &sc, const RtFrame &f, v3 ori
         float rr = sc.halton(1, i, 3) * 2.0f - 1.0f;
         v3 sd = (lightDir + splat(rr * searchSize)) + splat(rr * searchSize);
         Ray sr; sr.o = origin; sr.d = normalize(sd);
-        any |= lane_any<COUNT>(sc, sc.nObj, sr, f.p.maxRayDistance, limit, rays);
+        any |= sc.template any<COUNT>(sr, f.p.maxRayDistance, limit, rays);
     }
     if (!any) return 1.0f;
     return lane_pcf<COUNT>(sc, f, origin, ltype, pcfSamples, filterSize, lightDir, limit, jitterR, rays);

@@ -31,6 +31,10 @@ struct ShadeScene {
     __device__ __forceinline__ int closest(const Ray &r, float maxDist, float &t) const {
         return q_trace<false>(cmp, nObj, r, maxDist, true, t);
     }
+    template <int COUNT>
+    __device__ __forceinline__ bool any(const Ray &r, float maxDist, float limit, unsigned &rays) const {
+        return lane_any<COUNT>(*this, nObj, r, maxDist, limit, rays);
+    }
 };
 
 __device__ __forceinline__ ShadeScene sh_scene(const float4 *cmp, int nObj, int nLt) {

@@ -93,6 +93,8 @@ def _signatures():
         "rt_accel_info": (ci, [vp, P(L.RtAccelReport)]),
         "rt_accel_build_host": (ci, [vp, ci, P(L.RtAccelDesc), vp, sz, vp, sz, vp, sz, P(L.RtAccelReport)]),
         "rt_accel_validate_host": (ci, [vp, ci, ci, vp, sz, vp, sz, vp, sz]),
+        "rt_set_accel_shading": (ci, [vp, P(L.RtAccelShadeDesc)]),
+        "rt_accel_shading_info": (ci, [vp, P(L.RtAccelShadeReport)]),
         "rt_shade_rays": (ci, [vp, params, vp, vp, sz, vp, vp, vp, vp]),
         "rt_last_error": (cs, [vp]),
         "rt_generate_aabb": (ci, [vp, ci]),
@@ -844,6 +846,23 @@ class RayTracer(_Handle):
         r = L.RtAccelReport()
         self._call("rt_accel_info", ctypes.byref(r))
         return _accel_report(r)
+
+    def set_accel_shading(self, enable=True, traversal="auto", min_objects=0):
+        """Let shade_rays walk the hierarchy set_accel built (rt_set_accel_shading; sticky, off by default, independent of
+        set_accel's own switch and of the order of the two calls).  traversal: "auto", "lane", "wave"; min_objects: scenes with fewer
+        objects keep the brute-force kernel (0: the default).  The shaded surfaces do not change, bit for bit."""
+        if enable is None or enable is False:
+            self._call("rt_set_accel_shading", None)
+            return
+        d = enable if isinstance(enable, L.RtAccelShadeDesc) else L.make_accel_shade_desc(True, traversal, min_objects)
+        self._call("rt_set_accel_shading", ctypes.byref(d))
+
+    def accel_shading_info(self):
+        """rt_accel_shading_info as a dict: active (the next shade_rays walks the tree), traversal, launches_accel (per-wavefront,
+        per-ray), launches_brute (shade launches only; accel_info's counters count the queries)."""
+        r = L.RtAccelShadeReport()
+        self._call("rt_accel_shading_info", ctypes.byref(r))
+        return dict(active=bool(r.active), traversal=r.traversal, launches_accel=tuple(r.launchesAccel), launches_brute=r.launchesBrute)
 
     def get_surfaces(self):
         """Device pointers (ints) of the context-owned gColor, gPosition, gNormal of the last rt_render."""

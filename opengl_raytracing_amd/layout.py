@@ -232,6 +232,28 @@ def make_accel_desc(enable=True, leaf_size=0, traversal="auto", min_objects=0, l
     return d
 
 
+class RtAccelShadeDesc(ctypes.Structure):
+    """``rt_accel_shade_desc``: zero = the default of every field."""
+    _fields_ = [("enable", ctypes.c_int32), ("traversal", ctypes.c_int32), ("minObjects", ctypes.c_int32), ("reserved", ctypes.c_int32 * 5)]
+
+
+class RtAccelShadeReport(ctypes.Structure):
+    """``rt_accel_shade_report``: what rt_accel_shading_info answers."""
+    _fields_ = [("active", ctypes.c_int32), ("traversal", ctypes.c_int32), ("launchesAccel", ctypes.c_uint64 * 2),
+                ("launchesBrute", ctypes.c_uint64), ("reserved", ctypes.c_uint64 * 2)]
+
+
+assert ctypes.sizeof(RtAccelShadeDesc) == 32 and ctypes.sizeof(RtAccelShadeReport) == 48
+
+
+def make_accel_shade_desc(enable=True, traversal="auto", min_objects=0):
+    """An rt_accel_shade_desc; min_objects 0 keeps the default.  traversal: "auto", "lane", "wave" or a number."""
+    d = RtAccelShadeDesc()
+    d.enable, d.minObjects = int(bool(enable)), int(min_objects)
+    d.traversal = int(ACCEL_TRAVERSALS.get(traversal, traversal))
+    return d
+
+
 # ---- ray shading (rt_shade_rays, include/rt_mi355.h) ------------------------------------------
 PIXEL_DTYPE = np.dtype({"names": ["x", "y"], "formats": ["<u4", "<u4"], "offsets": [0, 4], "itemsize": 8})
 

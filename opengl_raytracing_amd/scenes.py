@@ -240,6 +240,50 @@ def sphere_cloud(n, seed, generate_aabb, floor=True):
     return objs, half
 
 
+def lit_cloud(n, seed, generate_aabb, floor=True):
+    """sphere_cloud's objects with materials that cycle through mirror / glass / diffuse, every 16th sphere subsurface, under three
+    lights placed from the cloud's half edge (a point light with PCF x 4, a directional light with PCF x 4, an area light with
+    PCSS x 4), seen from outside the cloud: the scaling scene of ray shading's tests and measurements (tools/bench_accel_shade.py)
+    -> Scene."""
+    objs, half = sphere_cloud(n, seed, generate_aabb, floor)
+    k = np.arange(n)
+    objs["albedo"][:n] = np.stack([0.55 + 0.4 * np.cos(k * 0.7), 0.55 + 0.4 * np.cos(k * 1.3 + 1.0), 0.55 + 0.4 * np.cos(k * 2.1 + 2.0)], -1)
+    mirror, glass, diffuse = k % 3 == 0, k % 3 == 1, k % 3 == 2
+    objs["diffuseStrength"][:n] = np.where(diffuse, 0.7, 0.0)
+    objs["metallic"][:n] = np.where(mirror, 1.0, 0.0)
+    objs["roughness"][:n] = np.where(diffuse, 0.6, 0.05)
+    objs["transparency"][:n] = np.where(glass, 0.9, 0.0)
+    objs["ior"][:n] = np.where(glass, 1.5, 1.0)
+    sss = k % 16 == 15
+    objs["diffuseStrength"][:n][sss] = 0.6
+    objs["transparency"][:n][sss] = 0.0
+    objs["subsurfaceScatter"][:n][sss] = 0.5
+    objs["subsurfaceColor"][:n][sss] = (1.0, 0.6, 0.5)
+    objs["scatterDistance"][:n][sss] = 0.8
+    if floor:
+        objs[n]["albedo"], objs[n]["roughness"], objs[n]["diffuseStrength"] = (0.8, 0.75, 0.7), 0.6, 0.5
+    return Scene(f"lit_cloud{n}", objs, cloud_lights(half), 960, 540, 4, cloud_camera(half))
+
+
+def cloud_lights(half):
+    """lit_cloud's three lights for a cloud of half edge `half`."""
+    lt = L.default_lights(3)
+    lt[0]["type"], lt[0]["position"], lt[0]["intensity"] = L.POINT, (0.3 * half, 1.5 * half, 0.4 * half), 2.0 * half * half
+    lt[0]["shadowType"], lt[0]["pcfSamples"] = L.SHADOW_PCF, 4
+    lt[1]["type"], lt[1]["direction"], lt[1]["intensity"] = L.DIRECTIONAL, (0.4, -1.0, -0.3), 2.0
+    lt[1]["shadowType"], lt[1]["pcfSamples"] = L.SHADOW_PCF, 4
+    lt[2]["type"], lt[2]["position"], lt[2]["direction"] = L.AREA, (-0.8 * half, 1.2 * half, 0.9 * half), (0.0, 1.0, 0.0)     # (+y lights what is below)
+    lt[2]["intensity"], lt[2]["shadowType"], lt[2]["pcfSamples"] = 6.0 * half * half, L.SHADOW_PCSS, 4
+    return lt
+
+
+def cloud_camera(half):
+    """A camera just outside the +z face of a cloud of half edge `half`, looking at its centre."""
+    cam = dict(CAMERA)
+    cam["cam_pos"] = (0.0, 0.25 * half, 1.3 * half)
+    return cam
+
+
 def nan_parity_scene(generate_aabb):
     """Tiny scene that forces the reference's undefined-arithmetic corners
     (SURVEY.md A.1#12, a16, a17): roughness 0 (0/0 in the NDF), a light straight
