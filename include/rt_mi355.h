@@ -212,6 +212,13 @@ int rt_debug_settled_tiles(rt_context *ctx, uint64_t out[2]);
 /* The cached window's flags, one byte per tile in row-major tile order (1 = settled); n must be out[0] of
  * rt_debug_settled_tiles (0 without a cache).  Both calls wait for the context's work in flight. */
 int rt_debug_settled_map(rt_context *ctx, uint8_t *flags, size_t n);
+/* Prefix replay (part of first-hit reuse; on unless the variant carries 0x1000 or RT_PREFIX_REPLAY=0 was set at rt_create): a
+ * tile none of whose paths reads the frame's bounce sample before depth K is the same bits up to the lighting of depth K for
+ * every frameCount, so the recording frame keeps each pixel's path state there and replaying frames resume the tile at depth
+ * K (capped at 7) instead of depth 0.  out[0] = settled tiles of the cached window, out[1 + K] = tiles that resume at depth
+ * K = 0 .. 7; the nine add up to the window's tile count, and are zeros while no recorded window is cached.  Waits for the
+ * context's work in flight. */
+int rt_debug_prefix_tiles(rt_context *ctx, uint64_t out[9]);
 
 /* Diagnostics of the last rt_count_rays launch: out[0] rays, out[1] wave-level ray packets,
  * out[2] candidate objects summed over packets (after packet culling), out[3] 64-object cull

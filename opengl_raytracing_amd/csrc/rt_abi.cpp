@@ -139,7 +139,8 @@ int launch_frame(rt_context *c, const rt_params *p, float4 *dColor, float4 *dPos
     if (timed) HIP_TRY(c, hipEventRecord(c->evStart, s));
     HIP_TRY(c, rt_launch_render(f, sc, dColor, dPos, dNormal, counter, c->variant, s, countMode, (int)mode,
                                 mode == RtFirstHit::NORMAL ? nullptr
-                                    : (void *)((uintptr_t)c->dFirstHit.ptr | (mode == RtFirstHit::RECORD && !c->settledOn() ? RT_FIRST_HIT_NO_SETTLED : 0))));
+                                    : (void *)((uintptr_t)c->dFirstHit.ptr | (mode == RtFirstHit::RECORD && !c->settledOn() ? RT_FIRST_HIT_NO_SETTLED : 0) |
+                                               (mode == RtFirstHit::RECORD && !c->prefixOn() ? RT_FIRST_HIT_NO_PREFIX : 0))));
     if (timed) {
         HIP_TRY(c, hipEventRecord(c->evStop, s));
         c->timed = true;
@@ -208,6 +209,7 @@ int rt_create(rt_context **out, int deviceId) {
     if (const char *e = getenv("RT_ST_BUILD")) c->stOnePhase = strcmp(e, "full") == 0;
     if (const char *e = getenv("RT_FIRST_HIT_REUSE")) c->firstHit.envOn = atoi(e) != 0;
     if (const char *e = getenv("RT_SETTLED_TILES")) c->settledEnvOn = atoi(e) != 0;
+    if (const char *e = getenv("RT_PREFIX_REPLAY")) c->prefixEnvOn = atoi(e) != 0;
     if (const char *e = getenv("RT_ST_GEOM")) {        // "Kcube,Kplan,NB": measurement override of the shadow-table geometry
         int kc = 0, kp = 0, nb = 0;
         if (sscanf(e, "%d,%d,%d", &kc, &kp, &nb) == 3 && kc >= 4 && kc <= 128 && kp >= 4 && kp <= 256 && nb >= 1 && nb <= 128)
@@ -563,12 +565,14 @@ int rt_count_rays_traced(rt_context *c, const rt_params *p, uint64_t *rays) { re
 
 int rt_set_variant(rt_context *c, int variant) {
     if (!c) return RT_ERR_INVALID_ARG;
-    // another kernel, or first-hit reuse (bit 10, 0x400 = off) or its settled tiles (bit 11, 0x800 = off) switched: the next
-    // frame is a normal one
-    const bool reuseOn = (variant & 0x400) == 0, settledOn = (variant & 0x800) == 0;
-    if ((variant & 0xff) != c->variant || reuseOn != c->firstHit.variantOn || settledOn != c->settledVariantOn) c->firstHit.invalidate();
+    // another kernel, or first-hit reuse (bit 10, 0x400 = off), its settled tiles (bit 11, 0x800 = off) or its prefix replay
+    // (bit 12, 0x1000 = off) switched: the next frame is a normal one
+    const bool reuseOn = (variant & 0x400) == 0, settledOn = (variant & 0x800) == 0, prefixOn = (variant & 0x1000) == 0;
+    if ((variant & 0xff) != c->variant || reuseOn != c->firstHit.variantOn || settledOn != c->settledVariantOn || prefixOn != c->prefixVariantOn)
+        c->firstHit.invalidate();
     c->firstHit.variantOn = reuseOn;
     c->settledVariantOn = settledOn;
+    c->prefixVariantOn = prefixOn;
     c->variant = variant & 0xff;
     c->sched.setMode(variant);         // bits 8 and 9: the tile order
     return RT_OK;
@@ -600,7 +604,19 @@ int rt_debug_settled_tiles(rt_context *c, uint64_t out[2]) {
     std::vector<uint8_t> flags;
     RT_TRY(settled_flags(c, &flags));
     out[0] = flags.size();
-    for (uint8_t v : flags) out[1] += v != 0;
+    for (uint8_t v : flags) out[1] += rt_prefix_flag_settled(v);
+    return RT_OK;
+}
+
+int rt_debug_prefix_tiles(rt_context *c, uint64_t out[9]) {
+    if (!c || !out) return RT_ERR_INVALID_ARG;
+    for (int k = 0; k < 9; k++) out[k] = 0;
+    std::vector<uint8_t> flags;
+    RT_TRY(settled_flags(c, &flags));
+    for (uint8_t v : flags) {
+        const int k = rt_prefix_flag_depth(v);
+        out[rt_prefix_flag_settled(v) ? 0 : 1 + (k < RT_PREFIX_CAP ? k : RT_PREFIX_CAP)]++;
+    }
     return RT_OK;
 }
 
@@ -609,7 +625,7 @@ int rt_debug_settled_map(rt_context *c, uint8_t *flags, size_t n) {
     std::vector<uint8_t> have;
     RT_TRY(settled_flags(c, &have));
     if (n != have.size()) return fail(c, RT_ERR_INVALID_ARG, "rt_debug_settled_map: n is not the cached window's tile count (rt_debug_settled_tiles)");
-    if (n) memcpy(flags, have.data(), n);
+    for (size_t i = 0; i < n; i++) flags[i] = rt_prefix_flag_settled(have[i]) ? 1 : 0;      // (the byte also carries the prefix depth)
     return RT_OK;
 }
 

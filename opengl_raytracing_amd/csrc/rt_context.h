@@ -72,6 +72,9 @@ struct rt_context {
     // rt_set_variant's bit 11 (0x800) switch them off
     bool settledEnvOn = true, settledVariantOn = true;
     bool settledOn() const { return settledEnvOn && settledVariantOn; }
+    // prefix replay, likewise: RT_PREFIX_REPLAY=0 at rt_create / rt_set_variant's bit 12 (0x1000) switch it off
+    bool prefixEnvOn = true, prefixVariantOn = true;
+    bool prefixOn() const { return prefixEnvOn && prefixVariantOn; }
     DevBuf<uint2> dBloom[2];                   // rgba16f ping-pong targets of rt_bloom
     DevBuf<float> dSsaoDepth;                  // gPosition.z plane of rt_ssao
     ScratchUse bloomUse, ssaoUse;              // who ran last in dBloom / dSsaoDepth, on whichever stream

@@ -91,6 +91,10 @@ hipError_t rt_launch_render(const RtFrame &f, const RtDeviceScene &sc, float4 *d
 // section 27: every tile's flag is then written as 0, which is all a replaying launch looks at): the buffer is aligned far
 // beyond that, and one more kernel argument would move the hidden arguments of every instantiation.
 #define RT_FIRST_HIT_NO_SETTLED ((uintptr_t)1)
+// Bit 1, likewise, switches prefix replay OFF: the recording launch writes no prefix record and every
+// tile's flag says K = 0 or settled, which is the buffer as section 27 left it.
+#define RT_FIRST_HIT_NO_PREFIX ((uintptr_t)2)
+#define RT_FIRST_HIT_SWITCHES (RT_FIRST_HIT_NO_SETTLED | RT_FIRST_HIT_NO_PREFIX)
 // Tile geometry of the packet kernel for a given scene size / window (so the ABI layer can size the
 // feedback buffers): workgroup threads, tile edge, tiles per row, total tiles.
 void rt_packet_geometry(int nObj, int regionW, int regionH, int *bt, int *tile, int *tilesX, int *nTiles);

@@ -52,7 +52,8 @@ inline RtFirstHitKey rt_first_hit_key(uint32_t sceneGen, uint32_t texGen, int nO
 //   colours  12 B/pixel  finalColor after depth 0                                           } packed: 20 B/pixel
 //   finals   32 B/pixel  what a settled tile stored to the three surfaces (section 27): two 16-byte halves,
 //                        (colour.xyz, position.x) and (position.y, position.z, the packed normal pair)
-//   flags    1 B/tile    1 = the 8x8 tile is settled, indexed by the window-local tile id tileY * tilesX + tileX
+//   flags    1 B/tile    1 = the 8x8 tile is settled, 1 + K = it resumes at depth K from prefix records (rt_prefix_flag, below),
+//                        indexed by the window-local tile id tileY * tilesX + tileX
 // Pixels are indexed window-locally, j * regionW + i.  Plain integer arithmetic: the kernel (render_packet), the ABI layer and
 // a host-only test (tests/test_settled_layout_host.py) all take the offsets from here.
 struct RtFirstHitLayout {
@@ -91,6 +92,62 @@ inline RtFirstHitLayout rt_first_hit_layout(int regionW, int regionH) {
     l.flags = rt_first_hit_flags_offset(regionW, regionH);
     l.bytes = rt_first_hit_bytes(regionW, regionH);
     return l;
+}
+
+// PREFIX REPLAY.  frameCount reaches a path only where a lane takes the diffuse branch of the
+// next-direction step (section 27's TAINT), so everything a tile does up to the first depth K at which one of its lanes is
+// tainted is the same bits for every frameCount.  Section 26 resumes every tile behind the lighting of depth 0; a tile with
+// K >= 1 resumes behind the lighting of depth K instead.  The tile's flag byte says which:
+//   0       K = 0: depth 0 is replayed from the (hits, colours) records (section 26)
+//   1       settled: the tile is copied out of its final records (section 27)
+//   1 + K   K = 1 .. RT_PREFIX_CAP: the bounce loop starts at depth K from the pixel's PREFIX record
+// Resuming at any depth <= K is exact, so K is capped: a tile that taints later (or, with settled tiles switched off, never)
+// resumes at the last depth it recorded.
+#define RT_PREFIX_CAP 7
+RT_FH_INLINE unsigned rt_prefix_flag(bool settled, int k) { return settled ? 1u : (k >= 1 ? 1u + (unsigned)(k < RT_PREFIX_CAP ? k : RT_PREFIX_CAP) : 0u); }
+RT_FH_INLINE bool rt_prefix_flag_settled(unsigned flag) { return flag == 1u; }
+RT_FH_INLINE int rt_prefix_flag_depth(unsigned flag) { return flag >= 2u ? (int)flag - 1 : 0; }      // 0 for K = 0 and for settled tiles
+// A prefix record is the parked path state as it stands behind the lighting of depth K and in front of the roulette: 13 dwords.
+//   w[0]       the hit object of depth K for a lane that is alive there, -1 for a lane whose path has ended
+//   w[1..3]    finalColor
+//   w[4..6]    P of the last hit
+//   w[7..12]   alive: throughput, then the incoming direction rd (N is recomputed from P and the hit object)
+//              ended: N of the last hit, then zeros
+// It lives in the 8 + 12 + 32 bytes the pixel already owns in the hits, colours and finals parts -- a K >= 1 tile needs neither
+// its depth-0 record nor a final record: w[0..1] -> hits, w[2..4] -> colours, w[5..12] -> finals.
+#define RT_PREFIX_DWORDS 13
+struct RtPrefixRecord { uint32_t w[RT_PREFIX_DWORDS]; };
+RT_FH_INLINE uint32_t rt_prefix_bits(float v) { uint32_t u; memcpy(&u, &v, 4); return u; }
+RT_FH_INLINE float rt_prefix_float(uint32_t u) { float v; memcpy(&v, &u, 4); return v; }
+RT_FH_INLINE RtPrefixRecord rt_prefix_pack(bool alive, int hit, const float fc[3], const float P[3], const float thrOrN[3], const float rd[3]) {
+    RtPrefixRecord r;
+    r.w[0] = alive ? (uint32_t)hit : 0xffffffffu;
+    for (int k = 0; k < 3; k++) {
+        r.w[1 + k] = rt_prefix_bits(fc[k]);
+        r.w[4 + k] = rt_prefix_bits(P[k]);
+        r.w[7 + k] = rt_prefix_bits(thrOrN[k]);
+        r.w[10 + k] = alive ? rt_prefix_bits(rd[k]) : 0u;
+    }
+    return r;
+}
+// returns alive; fills thr and rd for a lane that is, N for one that is not (the other outputs are left as they were)
+RT_FH_INLINE bool rt_prefix_unpack(const RtPrefixRecord &r, int nObj, int *hit, float fc[3], float P[3], float thr[3], float rd[3], float N[3]) {
+    const int h = (int)r.w[0];
+    const bool alive = h >= 0 && h < nObj;          // (a record never holds anything else; no gather may leave the scene)
+    *hit = alive ? h : -1;
+    for (int k = 0; k < 3; k++) {
+        fc[k] = rt_prefix_float(r.w[1 + k]);
+        P[k] = rt_prefix_float(r.w[4 + k]);
+        if (alive) { thr[k] = rt_prefix_float(r.w[7 + k]); rd[k] = rt_prefix_float(r.w[10 + k]); }
+        else N[k] = rt_prefix_float(r.w[7 + k]);
+    }
+    return alive;
+}
+// byte offset of dword d of pixel `at`'s prefix record in the buffer of a regionW x regionH window
+RT_FH_INLINE uint64_t rt_prefix_dword_offset(int regionW, int regionH, uint64_t at, int d) {
+    if (d < 2) return at * 8u + (uint64_t)d * 4u;
+    if (d < 5) return rt_first_hit_colours_offset(regionW, regionH) + at * 12u + (uint64_t)(d - 2) * 4u;
+    return rt_first_hit_finals_offset(regionW, regionH) + at * 32u + (uint64_t)(d - 5) * 4u;
 }
 
 struct RtFirstHit {

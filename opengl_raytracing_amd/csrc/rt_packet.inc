@@ -1320,7 +1320,7 @@ __device__ __forceinline__ float pk_pcf_shadow(const SceneLds &sc, int nObj, v3 
 __device__ __forceinline__ bool pk_replay_settled_tile(const RtFrame &f, int tileX, int tileY, const unsigned char *records, float4 *gColor,
                                                        float4 *gPosition, uint2 *gNormal) {
     const int tilesX = (f.p.regionW + 7) / 8;
-    if (__builtin_amdgcn_readfirstlane((int)records[rt_first_hit_flags_offset(f.p.regionW, f.p.regionH) + (size_t)(tileY * tilesX + tileX)]) == 0) return false;
+    if (!rt_prefix_flag_settled((unsigned)__builtin_amdgcn_readfirstlane((int)records[rt_first_hit_flags_offset(f.p.regionW, f.p.regionH) + (size_t)(tileY * tilesX + tileX)]))) return false;
     const int ln = threadIdx.x & 63;
     const int i = tileX * 8 + (ln & 7), j = tileY * 8 + (ln >> 3);
     if (i < f.p.regionW && j < f.p.regionH) {
@@ -1351,7 +1351,9 @@ __device__ __forceinline__ bool pk_replay_settled_tile(const RtFrame &f, int til
 // the closest-hit traversal, the light loop and the subsurface section, recomputes the shading point from them by the
 // expressions of the normal frame, and goes on with the next direction and depth 1 as ever.  Every value is copied bitwise or
 // recomputed by the identical expression, so the three frames are the same bits.  On top of that the recording frame marks the
-// SETTLED tiles and keeps their surface values, and the replaying frame copies those out (below; DESIGN.md section 27).
+// SETTLED tiles and keeps their surface values, and the replaying frame copies those out (below; DESIGN.md section 27); and it
+// keeps, for every tile that reaches depth 1 before one of its lanes reads the frame's bounce sample, the path state behind
+// the lighting of the last such depth, from which the replaying frame resumes the tile (PREFIX replay, DESIGN.md section 34).
 template <int COUNT, int BT, typename PROFILE, int FIRST = 0>
 __device__ __forceinline__ void render_packet(const RtFrame &f, const RtDeviceScene &dsc, const SceneLds &sc,
                                               float4 *gColor,
@@ -1395,7 +1397,7 @@ __device__ __forceinline__ void render_packet(const RtFrame &f, const RtDeviceSc
     // between lanes, so every access is volatile: no store may be dropped or forwarded to the load behind the loop (LDS
     // operations of one wave complete in order, and the workgroup is that one wave).
     [[maybe_unused]] volatile unsigned *const taintWord = (volatile unsigned *)sc.park - 4;
-    [[maybe_unused]] auto records = [&]() -> unsigned char * { return (unsigned char *)((uintptr_t)firstHit & ~RT_FIRST_HIT_NO_SETTLED); };
+    [[maybe_unused]] auto records = [&]() -> unsigned char * { return (unsigned char *)((uintptr_t)firstHit & ~RT_FIRST_HIT_SWITCHES); };
     if constexpr (FIRST == 1) *taintWord = 0u;
     int gxI, gyI;
     size_t outIdx;
@@ -1475,7 +1477,94 @@ __device__ __forceinline__ void render_packet(const RtFrame &f, const RtDeviceSc
         }
     };
 
-    for (int depth = 0; depth < f.p.maxRayDepth; ++depth) {
+    // PREFIX (DESIGN.md section 34; the record and the flag's encoding are rt_firsthit.h's).  FIRST == 1: behind the lighting of
+    // every depth 1 .. RT_PREFIX_CAP that the tile reaches untainted, each window lane overwrites its prefix record with the
+    // parked state as it stands there, and the taint word's low byte keeps that depth (bit 8 is the taint itself).
+    [[maybe_unused]] auto prefixRecord = [&](int depth_, bool alive_, int idx_) {
+        asm volatile("" ::: "memory");
+        const float *pk_ = sc.park + threadIdx.x;
+        const long long at = firstIndex();
+        if (at >= 0) {
+            const float *tn = pk_ + (alive_ ? 3 : 12) * BT;          // throughput, or N of the last hit where the path has ended
+            const pk_u2 w01 = {alive_ ? (unsigned)idx_ : 0xffffffffu, __float_as_uint(pk_[0 * BT])};
+            const pk_f4 a = {pk_[10 * BT], pk_[11 * BT], tn[0 * BT], tn[1 * BT]};
+            const pk_f4 b = {tn[2 * BT], alive_ ? pk_[6 * BT] : 0.0f, alive_ ? pk_[7 * BT] : 0.0f, alive_ ? pk_[8 * BT] : 0.0f};
+            float *col = (float *)(records() + rt_first_hit_colours_offset(f.p.regionW, f.p.regionH)) + 3 * at;
+            pk_f4 *fin = (pk_f4 *)(records() + rt_first_hit_finals_offset(f.p.regionW, f.p.regionH)) + 2 * at;
+            __builtin_nontemporal_store(w01, (pk_u2 *)records() + at);
+            __builtin_nontemporal_store(pk_[1 * BT], col + 0);
+            __builtin_nontemporal_store(pk_[2 * BT], col + 1);
+            __builtin_nontemporal_store(pk_[9 * BT], col + 2);
+            __builtin_nontemporal_store(a, fin);
+            __builtin_nontemporal_store(b, fin + 1);
+        }
+        *taintWord = (unsigned)depth_;
+    };
+    // FIRST == 2, a tile with K >= 1 (its flag; the kernel has tested it for `settled` already, it is loaded again here so that
+    // nothing stays live across the scene set-up): the PROLOGUE below stands for the bounces 0 .. K.  It parks the lane's prefix
+    // record -- finalColor, P, throughput and direction (alive) or N (ended) --, sets the hit of depth K up by the expressions
+    // of the loop's hit set-up (P is the record's, N and V follow from it), runs that depth's roulette and next direction,
+    // and the loop starts at depth K + 1: its body is, to the letter, what a K = 0 tile needs, and carries nothing for this.
+    int depth0 = 0;
+    if constexpr (FIRST == 2) {
+        const unsigned char *base = (const unsigned char *)firstHit;
+        int k = rt_prefix_flag_depth((unsigned)__builtin_amdgcn_readfirstlane(
+            (int)base[rt_first_hit_flags_offset(f.p.regionW, f.p.regionH) + (size_t)(sc.tileY * ((f.p.regionW + 7) / 8) + sc.tileX)]));
+        if (k > RT_PREFIX_CAP) k = RT_PREFIX_CAP;          // (a flag never holds more)
+        if (k > 0) {
+            const long long at = firstIndex();
+            float *pk_ = sc.park + threadIdx.x;
+            int idx = -1;
+            alive = false;
+            if (at >= 0) {
+                const uint2 w01 = firstHit[at];
+                const float *col = (const float *)(base + rt_first_hit_colours_offset(f.p.regionW, f.p.regionH)) + 3 * at;
+                const float4 *fin = (const float4 *)(base + rt_first_hit_finals_offset(f.p.regionW, f.p.regionH)) + 2 * at;
+                const float c0 = col[0], c1 = col[1], c2 = col[2];
+                const float4 a = fin[0], b = fin[1];
+                const int hitRec = (int)w01.x;
+                idx = (hitRec >= 0 && hitRec < nObj) ? hitRec : -1;      // (a record never holds anything else; no gather may leave the scene)
+                alive = idx >= 0;
+                pk_[0 * BT] = __uint_as_float(w01.y); pk_[1 * BT] = c0; pk_[2 * BT] = c1;
+                pk_[9 * BT] = c2; pk_[10 * BT] = a.x; pk_[11 * BT] = a.y;
+                float *tn = pk_ + (alive ? 3 : 12) * BT;
+                tn[0 * BT] = a.z; tn[1 * BT] = a.w; tn[2 * BT] = b.x;
+                if (alive) {
+                    ray.d = V3(b.y, b.z, b.w);
+                    P = V3(c2, a.x, a.y);
+                }
+            }
+            depth0 = f.p.maxRayDepth;          // nothing left to trace, unless ...
+            if (wave_any(alive) && k + 1 < f.p.maxRayDepth) {
+                const int ii = alive ? idx : 0;
+                const float4 hb = pk_bounds(sc, ii, 0), h2 = pk_lane_hot(sc, ii, 2), h3 = pk_lane_hot(sc, ii, 3);
+                const float4 m0 = pk_lane_mat(sc, ii, 0), m1 = pk_lane_mat(sc, ii, 1);
+                const v3 Ns = normalize(P - V3(h2));
+                N = (__float_as_int(hb.w) == 0) ? Ns : V3(h3);
+                const v3 V = normalize(-ray.d);
+                pk_[6 * BT] = ray.d.x; pk_[7 * BT] = ray.d.y; pk_[8 * BT] = ray.d.z;
+                if (alive) { pk_[12 * BT] = N.x; pk_[13 * BT] = N.y; pk_[14 * BT] = N.z; }
+                pk_[15 * BT] = V.x; pk_[16 * BT] = V.y; pk_[17 * BT] = V.z;
+                pk_[18 * BT] = m0.x; pk_[19 * BT] = m0.y; pk_[20 * BT] = m0.z;
+                pk_[22 * BT] = m1.x;
+                {
+                    const int depth = k;
+#include "rt_packet_bounce.inc"
+                }
+                rayBox = wave_box(ray.o, alive);
+                rayBoxFinite = box_finite(rayBox);
+                depth0 = k + 1;
+            } else if (wave_any(alive)) {       // (the last depth: its hit only has to leave N behind)
+                const int ii = alive ? idx : 0;
+                const float4 hb = pk_bounds(sc, ii, 0), h2 = pk_lane_hot(sc, ii, 2), h3 = pk_lane_hot(sc, ii, 3);
+                const v3 Ns = normalize(P - V3(h2));
+                N = (__float_as_int(hb.w) == 0) ? Ns : V3(h3);
+                if (alive) { pk_[12 * BT] = N.x; pk_[13 * BT] = N.y; pk_[14 * BT] = N.z; }
+            }
+        }
+    }
+
+    for (int depth = depth0; depth < f.p.maxRayDepth; ++depth) {
         if (!wave_any(alive)) {
             if constexpr (FIRST == 1) { if (depth == 0) { firstRecordHit(maxDist, -1); firstRecordColour(); } }
             break;
@@ -1773,58 +1862,16 @@ __device__ __forceinline__ void render_packet(const RtFrame &f, const RtDeviceSc
             pk_[0 * BT] = nf.x; pk_[1 * BT] = nf.y; pk_[2 * BT] = nf.z;
         }
         }
-        if constexpr (FIRST == 1) { if (depth == 0) firstRecordColour(); }
+        if constexpr (FIRST == 1) {
+            if (depth == 0) firstRecordColour();
+            else if (depth <= RT_PREFIX_CAP && ((uintptr_t)firstHit & RT_FIRST_HIT_NO_PREFIX) == 0 && __builtin_amdgcn_readfirstlane((int)*taintWord) < 0x100)
+                prefixRecord(depth, alive, idx);
+        }
         // After the last iteration nothing reads `alive`, `throughput` or the ray again, so its Russian roulette and bounce set-up
         // are dead (SURVEY.md A.1#17: at MAX_RAY_DEPTH = 4 the roulette can never change the output).
         if (depth + 1 >= f.p.maxRayDepth) break;
         {
-            const float4 mb = pk_lane_mat(sc, ii, 1);             // (roughness, diffuseStrength, ior, transparency)
-            const float diffuseStrength = mb.y, ior = mb.z, transparency = mb.w;
-            asm volatile("" ::: "memory");
-            float *pk_ = sc.park + threadIdx.x;
-            v3 thr = V3(pk_[3 * BT], pk_[4 * BT], pk_[5 * BT]);
-            const v3 rd = V3(pk_[6 * BT], pk_[7 * BT], pk_[8 * BT]);
-            const v3 Pb = V3(pk_[9 * BT], pk_[10 * BT], pk_[11 * BT]), Nb = V3(pk_[12 * BT], pk_[13 * BT], pk_[14 * BT]);
-            const v3 Vb = V3(pk_[15 * BT], pk_[16 * BT], pk_[17 * BT]), alb = V3(pk_[18 * BT], pk_[19 * BT], pk_[20 * BT]);
-            const float rough = pk_[22 * BT];
-            if (depth > 2) {   // Russian roulette (:544-549)
-                float dw = length(alb) * diffuseStrength;
-                float cp = fminf(fmaxf(thr.x, fmaxf(thr.y, thr.z)) * 0.95f + dw, 0.99f);
-                bool stop = false;
-                if (alive) {
-                    int rx_, ry_; size_t ro_;
-                    pixel(rx_, ry_, ro_);
-                    float rnd = random2((float)((unsigned)rx_ + (unsigned)depth), (float)((unsigned)ry_ + (unsigned)depth));
-                    stop = rnd > cp;
-                }
-                if (alive && !stop) thr = div3(thr, cp);
-                alive = alive && !stop;
-            }
-            // (alive lanes only: a dead lane gathered object 0's material)
-            if constexpr (FIRST == 1) { if (alive && diffuseStrength > 0.0f) *taintWord = 1u; }
-            // ---- next direction (:552-576).  Lanes whose path has ended get the same assignments (nothing reads their ray again):
-            // an unconditional write keeps the old origin / direction from staying live across the whole lighting section
-            Ray cur; cur.o = Pb; cur.d = rd;
-            v3 nd, no;
-            const float F = fresnel_schlick(fmaxf(dot(Vb, Nb), 0.0f), ior);
-            if (diffuseStrength > 0.0f) {
-                const int dd = depth < RT_MAX_DEPTH ? depth : RT_MAX_DEPTH - 1;
-                v3 sd = reflect(rd, Nb);
-                v3 hd = hemisphere_dir(V3(f.hemi[dd][0], f.hemi[dd][1], f.hemi[dd][2]), Nb);
-                nd = normalize(mix_fast(sd, hd, rough));
-                no = Pb + Nb * 0.001f;
-                thr = thr * (alb * diffuseStrength);
-            } else if (transparency > 0.0f) {
-                nd = calc_refraction(cur, Nb, ior);
-                no = Pb - Nb * 0.001f;
-                thr = thr * ((alb * (1.0f - F)) * transparency);
-            } else {
-                nd = reflect(rd, Nb);
-                no = Pb + Nb * 0.001f;
-                thr = thr * (alb * F);
-            }
-            ray.d = nd; ray.o = no;
-            if (alive) { pk_[3 * BT] = thr.x; pk_[4 * BT] = thr.y; pk_[5 * BT] = thr.z; }
+#include "rt_packet_bounce.inc"
         }
         rayBox = wave_box(ray.o, alive);
         rayBoxFinite = box_finite(rayBox);
@@ -1859,9 +1906,10 @@ __device__ __forceinline__ void render_packet(const RtFrame &f, const RtDeviceSc
     }
     if constexpr (FIRST == 1) {   // every exit of the bounce loop comes through here: the tile's flag, and a settled tile's final records
         asm volatile("" ::: "memory");
-        const bool settled = ((uintptr_t)firstHit & RT_FIRST_HIT_NO_SETTLED) == 0 && __builtin_amdgcn_readfirstlane((int)*taintWord) == 0;
+        const unsigned taint = (unsigned)__builtin_amdgcn_readfirstlane((int)*taintWord);      // bit 8: tainted; low byte: the depth of the last prefix record
+        const bool settled = ((uintptr_t)firstHit & RT_FIRST_HIT_NO_SETTLED) == 0 && taint < 0x100u;
         unsigned char *flags = records() + rt_first_hit_flags_offset(f.p.regionW, f.p.regionH);
-        if ((threadIdx.x & 63) == 0) flags[sc.tileY * ((f.p.regionW + 7) / 8) + sc.tileX] = settled ? 1 : 0;
+        if ((threadIdx.x & 63) == 0) flags[sc.tileY * ((f.p.regionW + 7) / 8) + sc.tileX] = (unsigned char)rt_prefix_flag(settled, (int)(taint & 0xffu));
         const long long at = firstIndex();
         if (settled && at >= 0) {
             pk_f4 *fin = (pk_f4 *)(records() + rt_first_hit_finals_offset(f.p.regionW, f.p.regionH)) + 2 * at;

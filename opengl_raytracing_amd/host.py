@@ -79,6 +79,7 @@ def _signatures():
         "rt_debug_first_hit": (ci, [vp, P(u64)]),
         "rt_debug_settled_tiles": (ci, [vp, P(u64)]),
         "rt_debug_settled_map": (ci, [vp, P(u8), sz]),
+        "rt_debug_prefix_tiles": (ci, [vp, P(u64)]),
         "rt_debug_stats": (ci, [vp, P(u64)]),
         "rt_debug_stats_ex": (ci, [vp, P(u64)]),
         "rt_debug_tile_costs": (ci, [vp, P(u32), ci, P(ci), P(ci)]),
@@ -1319,6 +1320,10 @@ class RayTracer(_Handle):
         flags = (ctypes.c_uint8 * max(n, 1))()
         self._call("rt_debug_settled_map", flags, n)
         return np.frombuffer(flags, dtype=np.uint8, count=n).copy()
+
+    def debug_prefix_tiles(self):
+        """[settled tiles, tiles that resume at depth K = 0 .. 7] of the cached first-hit window; zeros without a valid cache."""
+        return self._counters("rt_debug_prefix_tiles", 9)
 
     def deinterleave(self, d_src, d_dst, width, height, bytes_per_pixel, strip_rows, strip_count,
                      rank_stride_bytes, stream=None):

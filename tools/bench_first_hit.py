@@ -1,10 +1,11 @@
-"""First-hit reuse A/B inside one process (DESIGN.md sections 26 and 27): blocks of C2 frames in three arms -- `settled` (the
-default: reuse with settled tiles), `on` (reuse without them, rt_set_variant's bit 11) and `off` (no reuse, bit 10) -- alternate
-on one context, every frame between two events on the launch stream as in bench.py.  Then the two frames reuse could make
+"""First-hit reuse A/B inside one process (DESIGN.md sections 26, 27 and 34): blocks of C2 frames in four arms -- `prefix` (the
+default: reuse with settled tiles and prefix replay), `settled` (prefix replay off, rt_set_variant's bit 12), `on` (reuse without
+either, bits 11 and 12) and `off` (no reuse, bit 10) -- alternate on one context, every frame between two events on the launch stream as in bench.py.  Then the two frames reuse could make
 slower: the recording frame, and the frames of a camera that moves every frame with reuse on (which must never run anything but
 the normal kernel).
 
-  gain        the `on` frames' p90 lies below the `off` frames' p10; the `settled` frames' p90 below the `on` frames' p10
+  gain        the `on` frames' p90 lies below the `off` frames' p10; the `settled` frames' p90 below the `on` frames' p10; the
+              `prefix` frames' p90 below the `settled` frames' p10
   regression  the moving camera's median with reuse on, and the recording frames' median, lie within the [min, max] of the same
               moving views rendered with reuse off (the recording frame is also held to the still view's off frames)
 
@@ -18,7 +19,7 @@ from opengl_raytracing_amd import dist as D
 from opengl_raytracing_amd import host, scenes, layout as L
 
 OFF = 0x400
-ARMS = {"settled": 1, "on": 1 | 0x800, "off": 1 | OFF}      # rt_set_variant's argument of each arm
+ARMS = {"prefix": 1, "settled": 1 | 0x1000, "on": 1 | 0x800 | 0x1000, "off": 1 | OFF}      # rt_set_variant's argument of each arm
 
 
 def stats(ms):
@@ -64,6 +65,7 @@ def main():
     ms = {name: [] for name in ARMS}
     modes = {name: [] for name in ARMS}
     tiles = {name: [] for name in ARMS}
+    prefixes = {name: [] for name in ARMS}
     for b in range(a.blocks):
         for name in SB.alternating(list(ARMS), b):
             rt.set_variant(ARMS[name])
@@ -74,12 +76,16 @@ def main():
             ms[name] += timed([base] * a.frames)
             modes[name].append([x - y for x, y in zip(counts(), c0)])
             tiles[name].append(rt.debug_settled_tiles())
-    # the timed `settled` and `on` frames must all have replayed, the `off` frames all have run the normal kernel; only the
-    # `settled` arm may have found settled tiles, and it must have found some
-    assert all(m == [0, 0, a.frames] for m in modes["settled"] + modes["on"]), modes
+            prefixes[name].append(rt.debug_prefix_tiles())
+    # the timed `prefix`, `settled` and `on` frames must all have replayed, the `off` frames all have run the normal kernel; only
+    # the `prefix` and `settled` arms may have found settled tiles, the same ones, and must have found some; only the `prefix`
+    # arm may resume a tile behind depth 0, and it must do so for some
+    assert all(m == [0, 0, a.frames] for m in modes["prefix"] + modes["settled"] + modes["on"]), modes
     assert all(m == [a.frames, 0, 0] for m in modes["off"]), modes["off"]
     assert all(t[0] > 0 and t[1] > 0 for t in tiles["settled"]) and all(t[0] > 0 and t[1] == 0 for t in tiles["on"]), tiles
+    assert tiles["prefix"] == tiles["settled"], tiles
     assert all(t == [0, 0] for t in tiles["off"]), tiles["off"]
+    assert all(sum(h[2:]) > 0 for h in prefixes["prefix"]) and all(sum(h[2:]) == 0 for h in prefixes["settled"] + prefixes["on"] + prefixes["off"]), prefixes
 
     # a camera that moves every frame: the normal kernel only, with reuse on as with reuse off (the control: the same views)
     x0 = base.camPos[0]
@@ -108,9 +114,12 @@ def main():
     dc = [x - y for x, y in zip(counts(), c0)]
     assert dc == [120, 12, 24], dc
 
-    on, off, settled = stats(ms["on"]), stats(ms["off"]), stats(ms["settled"])
+    on, off, settled, prefix = stats(ms["on"]), stats(ms["off"]), stats(ms["settled"]), stats(ms["prefix"])
     mon, moff = stats(moving_ms["on"]), stats(moving_ms["off"])
     rec = {"config": f"C{a.cfg}", "size": [sc.width, sc.height], "blocks_each": a.blocks, "frames_per_block": a.frames, "warmup_per_block": a.warmup,
+           "prefix_ms": prefix, "prefix_tiles_settled_then_k0_to_k7": prefixes["prefix"][0],
+           "prefix_block_medians_ms": [round(float(np.median(ms["prefix"][i * a.frames:(i + 1) * a.frames])), 4) for i in range(a.blocks)],
+           "gain_prefix_p90_below_settled_p10": bool(prefix["p90"] < settled["p10"]),
            "settled_ms": settled, "settled_tiles_of_window": tiles["settled"][0],
            "settled_block_medians_ms": [round(float(np.median(ms["settled"][i * a.frames:(i + 1) * a.frames])), 4) for i in range(a.blocks)],
            "gain_settled_p90_below_on_p10": bool(settled["p90"] < on["p10"]),
@@ -126,11 +135,12 @@ def main():
            "note": "off spread = [min, max] of the reuse-off frames; the moving camera and the recording frame are held to the reuse-off "
                    "frames of the same moving views, the recording frame also to those of the still view"}
     SB.write_records(a.out, "tools/bench_first_hit.py", [rec], device=torch.cuda.get_device_name(0))
-    for key in ("settled_ms", "on_ms", "off_ms", "moving_camera_reuse_on_ms", "moving_camera_reuse_off_ms", "stop_and_go_normal_frames_before_recording_ms",
+    for key in ("prefix_ms", "settled_ms", "on_ms", "off_ms", "moving_camera_reuse_on_ms", "moving_camera_reuse_off_ms", "stop_and_go_normal_frames_before_recording_ms",
                 "recording_frame_ms", "replay_after_recording_ms"):
         print(f"{key:46s} {rec[key]}")
     print(f"{'settled_tiles_of_window':46s} {rec['settled_tiles_of_window']}")
-    for key in ("gain_settled_p90_below_on_p10", "gain_on_p90_below_off_p10", "moving_camera_within_off_spread", "recording_frame_within_off_spread",
+    print(f"{'prefix_tiles_settled_then_k0_to_k7':46s} {rec['prefix_tiles_settled_then_k0_to_k7']}")
+    for key in ("gain_prefix_p90_below_settled_p10", "gain_settled_p90_below_on_p10", "gain_on_p90_below_off_p10", "moving_camera_within_off_spread", "recording_frame_within_off_spread",
                 "recording_frame_within_still_view_off_spread"):
         print(f"{key:46s} {rec[key]}")
     rt.close()
