@@ -570,26 +570,39 @@ void rt_render_packet_kernel(const RtFrame f, const RtDeviceScene dsc, float4 *_
                              unsigned long long *rayCounter) {
     static_assert(FIRST == 0 || COUNT == 0, "a frame that records or replays first hits has no ray counter");
     static_assert(BT == 64 && COMPACT, "one-wave workgroups, only the AABBs staged in LDS");
-    if constexpr (FIRST == 2) {     // a settled tile of a replaying frame: copied out, costed, done
-        const unsigned tile_ = dsc.tileOrder ? dsc.tileOrder[blockIdx.x] : blockIdx.x;
-        if (tile_ < gridDim.x) {
-            const unsigned tilesX_ = (unsigned)(f.p.regionW + 7) / 8u;
-            const long long t0_ = clock64();
-            if (pk_replay_settled_tile(f, (int)(tile_ % tilesX_), (int)(tile_ / tilesX_), (const unsigned char *)rayCounter, gColor, gPosition, gNormal)) {
-                if (dsc.tileCost && (threadIdx.x & 63) == 0) {
-                    const unsigned c_ = (unsigned)(((unsigned long long)(clock64() - t0_)) >> 6);
-                    if (RT_FB_ACCUM) atomicAdd(&dsc.tileCost[tile_], c_);
-                    else dsc.tileCost[tile_] = c_;
-                }
-                return;
-            }
-        }
-    }
     extern __shared__ float4 lds[];
+    [[maybe_unused]] unsigned tileReplay = 0u;
+    if constexpr (FIRST == 2) {
+        // The start of a replaying frame's tile (rt_packet.inc has the two steps).  Its flag, its lanes'
+        // records and the bounds are requested together and the flag is fetched once: a settled tile (section 27) is copied
+        // out, costed, done; any other tile parks the rest behind one more wait, and render_packet finds the record and K in
+        // the parking area.
+        const unsigned tile_ = dsc.tileOrder ? dsc.tileOrder[blockIdx.x] : blockIdx.x;
+        if (tile_ >= gridDim.x) return;          // (the guard below, ahead of the first address formed from the tile)
+        tileReplay = tile_;
+        const unsigned tilesX_ = (unsigned)(f.p.regionW + 7) / 8u;
+        const int tileX_ = (int)(tile_ % tilesX_), tileY_ = (int)(tile_ / tilesX_);
+        const long long t0_ = clock64();
+        PkReplayLoads ld_;
+        pk_replay_request<BT, PROFILE::boundsLds>(f, dsc, tileX_, tileY_, (const unsigned char *)rayCounter, ld_);
+        const unsigned flag_ = (unsigned)__builtin_amdgcn_readfirstlane((int)ld_.flag);
+        if (rt_prefix_flag_settled(flag_)) {
+            pk_replay_settled_tile(f, tileX_, tileY_, (const unsigned char *)rayCounter, gColor, gPosition, gNormal);
+            if (dsc.tileCost && (threadIdx.x & 63) == 0) {
+                const unsigned c_ = (unsigned)(((unsigned long long)(clock64() - t0_)) >> 6);
+                if (RT_FB_ACCUM) atomicAdd(&dsc.tileCost[tile_], c_);
+                else dsc.tileCost[tile_] = c_;
+            }
+            return;
+        }
+        pk_replay_park<BT, PROFILE::boundsLds>(f, dsc, tileX_, tileY_, flag_, (const unsigned char *)rayCounter, lds, ld_);
+    }
     const int nAll = f.nObj * (RT_HOT_F4 + RT_MAT_F4) + f.nLt * RT_LGT_F4 + 2 * (RT_HALTON_N / 4);
     const int nF4 = PROFILE::boundsLds ? f.nObj * 2 : 0;          // float4 staged in LDS: the objects' two bounds float4
-    for (int i = threadIdx.x; i < nF4; i += BT) lds[i] = dsc.compiled[(i >> 1) * RT_HOT_F4 + (i & 1)];
-    __syncthreads();
+    if constexpr (FIRST != 2) {                   // (a replaying tile has staged them in pk_replay_park)
+        for (int i = threadIdx.x; i < nF4; i += BT) lds[i] = dsc.compiled[(i >> 1) * RT_HOT_F4 + (i & 1)];
+        __syncthreads();
+    }
     SceneLds sc;
     sc.compact = true;
     sc.boundsLds = PROFILE::boundsLds;
@@ -612,7 +625,7 @@ void rt_render_packet_kernel(const RtFrame f, const RtDeviceScene dsc, float4 *_
 
     // tile of this workgroup: longest-first order from the previous frame's measured costs, if any
     const int tilesX = (f.p.regionW + 7) / 8;
-    const unsigned tile = dsc.tileOrder ? dsc.tileOrder[blockIdx.x] : blockIdx.x;
+    const unsigned tile = FIRST == 2 ? tileReplay : dsc.tileOrder ? dsc.tileOrder[blockIdx.x] : blockIdx.x;
     // an order buffer is a permutation of [0, gridDim.x) by construction (identity-initialised, rewritten only by
     // rt_lpt_sort_kernel); the guard keeps a corrupted entry from turning into out-of-bounds tileCost / surface writes
     if (tile >= gridDim.x) return;

@@ -1312,15 +1312,13 @@ __device__ __forceinline__ float pk_pcf_shadow(const SceneLds &sc, int nObj, v3 
     }
 }
 
-// A replaying frame's SETTLED tile (DESIGN.md section 27; render_packet below has the rule and the recording side): the wave
-// loads its tile's flag, and where it is set every lane copies its final record to the three surfaces -- alpha and the zeros
+// A replaying frame's SETTLED tile (DESIGN.md section 27; render_packet below has the rule and the recording side): where the
+// tile's flag says so every lane copies its final record to the three surfaces -- alpha and the zeros
 // outside the image regenerated as at the end of render_packet -- and the tile is done.  Called at the very top of the kernel
 // with nothing but the kernel's arguments alive and sharing no value with render_packet: placed inside it, the early-out
 // cost the replaying instantiations 6-20 more spilled SGPRs over the whole bounce loop (C3 +2.5 %).
-__device__ __forceinline__ bool pk_replay_settled_tile(const RtFrame &f, int tileX, int tileY, const unsigned char *records, float4 *gColor,
+__device__ __forceinline__ void pk_replay_settled_tile(const RtFrame &f, int tileX, int tileY, const unsigned char *records, float4 *gColor,
                                                        float4 *gPosition, uint2 *gNormal) {
-    const int tilesX = (f.p.regionW + 7) / 8;
-    if (!rt_prefix_flag_settled((unsigned)__builtin_amdgcn_readfirstlane((int)records[rt_first_hit_flags_offset(f.p.regionW, f.p.regionH) + (size_t)(tileY * tilesX + tileX)]))) return false;
     const int ln = threadIdx.x & 63;
     const int i = tileX * 8 + (ln & 7), j = tileY * 8 + (ln >> 3);
     if (i < f.p.regionW && j < f.p.regionH) {
@@ -1340,7 +1338,89 @@ __device__ __forceinline__ bool pk_replay_settled_tile(const RtFrame &f, int til
             gNormal[out] = make_uint2(0u, 0u);
         }
     }
-    return true;
+}
+
+// Parking columns that hand a replaying tile's record from pk_replay_park to render_packet: (t, hit) of a K = 0 tile, the hit
+// object of a K >= 1 tile, and K itself (every lane its own copy: nothing travels between lanes, so no access is volatile).
+// They are V's columns, which the hit set-up of the first bounce that runs writes for every lane -- behind render_packet's
+// reads of these three.
+constexpr int PK_PARK_REC_T = 15, PK_PARK_REC_HIT = 16, PK_PARK_REC_K = 17;
+
+// The START of a replaying frame's tile (DESIGN.md section 35) is two steps around the kernel's settled test.
+// pk_replay_request issues, without waiting for any of them, the loads whose addresses need only the tile and the kernel's
+// arguments: the tile's flag byte, each window lane's (hits, colours) slots -- the whole record of a K = 0 tile, the first 20
+// bytes of a prefix record, nothing a settled tile wants (20 bytes per lane it loads for nothing, and 16 more where bounds
+// are staged) -- and the lane's share of the first 64 staged bounds.  The kernel waits for all of them together (the lanes
+// beyond the window have issued fewer loads, so no count short of zero says that the flag has come) and tests the flag.
+// pk_replay_park requests the finals slot where K >= 1,
+// finishes the staging and moves each piece from its load straight into the parking column render_packet wants it in:
+// nothing of the record is held in a register inside render_packet, whose bounce loop is what a K = 0 tile runs, and a tile
+// waits for memory once (K = 0) or twice (K >= 1) behind its tile id where it waited four or five times.  What a lane beyond the
+// window parks is what render_packet's own initialisation and the defaults of its loads gave it; such a lane forms no address.
+// Ends with the barrier behind the staging; shares no live value with render_packet (section 27's lesson).
+struct PkReplayLoads {
+    unsigned flag;          // the tile's flag byte (rt_firsthit.h has the encoding), as loaded: not yet uniform
+    uint2 w01;              // the hits slot: (t, hit) for K = 0, (hit, finalColor.x) for K >= 1
+    float c0, c1, c2;       // the colours slot
+    float4 bounds;          // float4 threadIdx.x of the staged bounds
+};
+template <int BT, bool BOUNDS_LDS>
+__device__ __forceinline__ void pk_replay_request(const RtFrame &f, const RtDeviceScene &dsc, int tileX, int tileY, const unsigned char *records,
+                                                  PkReplayLoads &ld) {
+    const int tilesX = (f.p.regionW + 7) / 8;
+    ld.flag = records[rt_first_hit_flags_offset(f.p.regionW, f.p.regionH) + (size_t)(tileY * tilesX + tileX)];
+    // (the bounds ahead of the record: the compiler waits for the record's first piece where the window's lanes rejoin the others,
+    // and by then everything is in flight)
+    ld.bounds = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (BOUNDS_LDS && (int)threadIdx.x < f.nObj * 2) ld.bounds = dsc.compiled[(threadIdx.x >> 1) * RT_HOT_F4 + (threadIdx.x & 1)];
+    const int ln = threadIdx.x & 63;
+    const int i = tileX * 8 + (ln & 7), j = tileY * 8 + (ln >> 3);
+    ld.w01 = make_uint2(0u, 0u);
+    ld.c0 = ld.c1 = ld.c2 = 0.0f;
+    if (i < f.p.regionW && j < f.p.regionH) {
+        const size_t at = (size_t)j * f.p.regionW + i;
+        const float *col = (const float *)(records + rt_first_hit_colours_offset(f.p.regionW, f.p.regionH)) + 3 * at;
+        ld.w01 = ((const uint2 *)records)[at];
+        ld.c0 = col[0]; ld.c1 = col[1]; ld.c2 = col[2];
+    }
+}
+template <int BT, bool BOUNDS_LDS>
+__device__ __forceinline__ void pk_replay_park(const RtFrame &f, const RtDeviceScene &dsc, int tileX, int tileY, unsigned flag,
+                                               const unsigned char *records, float4 *lds, const PkReplayLoads &ld) {
+    const int nF4 = BOUNDS_LDS ? f.nObj * 2 : 0;
+    float *pk_ = (float *)(lds + nF4 + 1) + threadIdx.x;          // (sc.park of the kernel)
+    int k = rt_prefix_flag_depth(flag);
+    if (k > RT_PREFIX_CAP) k = RT_PREFIX_CAP;          // (a flag never holds more)
+    const int ln = threadIdx.x & 63;
+    const int i = tileX * 8 + (ln & 7), j = tileY * 8 + (ln >> 3);
+    const bool inWindow = i < f.p.regionW && j < f.p.regionH;
+    float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f), b = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (k > 0 && inWindow) {
+        const float4 *fin = (const float4 *)(records + rt_first_hit_finals_offset(f.p.regionW, f.p.regionH)) + 2 * ((size_t)j * f.p.regionW + i);
+        a = fin[0]; b = fin[1];
+    }
+    if ((int)threadIdx.x < nF4) lds[threadIdx.x] = ld.bounds;
+    for (int s = threadIdx.x + BT; s < nF4; s += BT) lds[s] = dsc.compiled[(s >> 1) * RT_HOT_F4 + (s & 1)];
+    if (k > 0) {
+        const int hitRec = inWindow ? (int)ld.w01.x : -1;
+        const int hit = (hitRec >= 0 && hitRec < f.nObj) ? hitRec : -1;      // (a record never holds anything else; no gather may leave the scene)
+        const bool alive = hit >= 0;
+        pk_[0 * BT] = __uint_as_float(ld.w01.y); pk_[1 * BT] = ld.c0; pk_[2 * BT] = ld.c1;               // finalColor
+        pk_[3 * BT] = alive ? a.z : 1.0f; pk_[4 * BT] = alive ? a.w : 1.0f; pk_[5 * BT] = alive ? b.x : 1.0f;    // throughput
+        pk_[6 * BT] = b.y; pk_[7 * BT] = b.z; pk_[8 * BT] = b.w;                                         // the incoming direction, if alive
+        pk_[9 * BT] = ld.c2; pk_[10 * BT] = a.x; pk_[11 * BT] = a.y;                                     // P of the last hit
+        pk_[12 * BT] = alive ? 0.0f : a.z; pk_[13 * BT] = alive ? 0.0f : a.w; pk_[14 * BT] = alive ? 0.0f : b.x;   // N where the path has ended
+        pk_[PK_PARK_REC_HIT * BT] = __int_as_float(hit);
+    } else {
+        pk_[0 * BT] = ld.c0; pk_[1 * BT] = ld.c1; pk_[2 * BT] = ld.c2;         // finalColor after depth 0: the sky or zero where it missed
+        pk_[3 * BT] = 1.0f; pk_[4 * BT] = 1.0f; pk_[5 * BT] = 1.0f;            // throughput
+        pk_[9 * BT] = 0.0f; pk_[10 * BT] = 0.0f; pk_[11 * BT] = 0.0f;          // P, N of the last hit: undefined locals read as zero (A.3)
+        pk_[12 * BT] = 0.0f; pk_[13 * BT] = 0.0f; pk_[14 * BT] = 0.0f;
+        pk_[PK_PARK_REC_T * BT] = inWindow ? __uint_as_float(ld.w01.x) : f.p.maxRayDistance;          // a miss where there is no record
+        pk_[PK_PARK_REC_HIT * BT] = inWindow ? __uint_as_float(ld.w01.y) : __int_as_float(-1);
+    }
+    pk_[PK_PARK_REC_K * BT] = __int_as_float(k);
+    __syncthreads();
 }
 
 // main() of raytracingCs.glsl (:509-584) for one 64-lane packet of pixels.
@@ -1431,7 +1511,7 @@ __device__ __forceinline__ void render_packet(const RtFrame &f, const RtDeviceSc
     // less scratch traffic, which the paired subsurface probes it makes room for win back: 25.4 ms); PCSS profiles, with the
     // subsurface probes in pairs: C3 3.44 -> 3.39 ms, scratch 156 -> 68 B/lane (with single probes it was 3.73).
     v3 P = V3(0.0f, 0.0f, 0.0f), N = V3(0.0f, 0.0f, 0.0f);
-    {
+    if constexpr (FIRST != 2) {         // (a replaying tile's columns are filled already, record included: pk_replay_park)
         float *pk_ = sc.park + threadIdx.x;
         pk_[0 * BT] = 0.0f; pk_[1 * BT] = 0.0f; pk_[2 * BT] = 0.0f;            // finalColor
         pk_[3 * BT] = 1.0f; pk_[4 * BT] = 1.0f; pk_[5 * BT] = 1.0f;            // throughput
@@ -1500,39 +1580,22 @@ __device__ __forceinline__ void render_packet(const RtFrame &f, const RtDeviceSc
         }
         *taintWord = (unsigned)depth_;
     };
-    // FIRST == 2, a tile with K >= 1 (its flag; the kernel has tested it for `settled` already, it is loaded again here so that
-    // nothing stays live across the scene set-up): the PROLOGUE below stands for the bounces 0 .. K.  It parks the lane's prefix
-    // record -- finalColor, P, throughput and direction (alive) or N (ended) --, sets the hit of depth K up by the expressions
+    // FIRST == 2, a tile with K >= 1 (its parking column, where pk_replay_park has left the flag's depth: the flag is fetched
+    // from memory once per tile, and nothing stays live across the scene set-up): the PROLOGUE below stands for the bounces 0 .. K.
+    // The lane's prefix record -- finalColor, P, throughput and direction (alive) or N (ended) -- is parked already; the
+    // prologue sets the hit of depth K up by the expressions
     // of the loop's hit set-up (P is the record's, N and V follow from it), runs that depth's roulette and next direction,
     // and the loop starts at depth K + 1: its body is, to the letter, what a K = 0 tile needs, and carries nothing for this.
     int depth0 = 0;
     if constexpr (FIRST == 2) {
-        const unsigned char *base = (const unsigned char *)firstHit;
-        int k = rt_prefix_flag_depth((unsigned)__builtin_amdgcn_readfirstlane(
-            (int)base[rt_first_hit_flags_offset(f.p.regionW, f.p.regionH) + (size_t)(sc.tileY * ((f.p.regionW + 7) / 8) + sc.tileX)]));
-        if (k > RT_PREFIX_CAP) k = RT_PREFIX_CAP;          // (a flag never holds more)
+        float *pk_ = sc.park + threadIdx.x;
+        const int k = __builtin_amdgcn_readfirstlane(__float_as_int(pk_[PK_PARK_REC_K * BT]));
         if (k > 0) {
-            const long long at = firstIndex();
-            float *pk_ = sc.park + threadIdx.x;
-            int idx = -1;
-            alive = false;
-            if (at >= 0) {
-                const uint2 w01 = firstHit[at];
-                const float *col = (const float *)(base + rt_first_hit_colours_offset(f.p.regionW, f.p.regionH)) + 3 * at;
-                const float4 *fin = (const float4 *)(base + rt_first_hit_finals_offset(f.p.regionW, f.p.regionH)) + 2 * at;
-                const float c0 = col[0], c1 = col[1], c2 = col[2];
-                const float4 a = fin[0], b = fin[1];
-                const int hitRec = (int)w01.x;
-                idx = (hitRec >= 0 && hitRec < nObj) ? hitRec : -1;      // (a record never holds anything else; no gather may leave the scene)
-                alive = idx >= 0;
-                pk_[0 * BT] = __uint_as_float(w01.y); pk_[1 * BT] = c0; pk_[2 * BT] = c1;
-                pk_[9 * BT] = c2; pk_[10 * BT] = a.x; pk_[11 * BT] = a.y;
-                float *tn = pk_ + (alive ? 3 : 12) * BT;
-                tn[0 * BT] = a.z; tn[1 * BT] = a.w; tn[2 * BT] = b.x;
-                if (alive) {
-                    ray.d = V3(b.y, b.z, b.w);
-                    P = V3(c2, a.x, a.y);
-                }
+            const int idx = __float_as_int(pk_[PK_PARK_REC_HIT * BT]);
+            alive = idx >= 0;
+            if (alive) {
+                ray.d = V3(pk_[6 * BT], pk_[7 * BT], pk_[8 * BT]);
+                P = V3(pk_[9 * BT], pk_[10 * BT], pk_[11 * BT]);
             }
             depth0 = f.p.maxRayDepth;          // nothing left to trace, unless ...
             if (wave_any(alive) && k + 1 < f.p.maxRayDepth) {
@@ -1575,19 +1638,10 @@ __device__ __forceinline__ void render_packet(const RtFrame &f, const RtDeviceSc
         int idx;
         unsigned long long tHit = 0ull;
         if (replay) {
-            const long long at = firstIndex();
-            uint2 rec = make_uint2(__float_as_uint(maxDist), 0xffffffffu);
-            v3 recCol = V3(0.0f, 0.0f, 0.0f);
-            if (at >= 0) {
-                const float *col = (const float *)((const unsigned char *)firstHit + rt_first_hit_colours_offset(f.p.regionW, f.p.regionH)) + 3 * at;
-                rec = firstHit[at];
-                recCol = V3(col[0], col[1], col[2]);
-            }
-            const int hitRec = (int)rec.y;
+            const float *pk_ = sc.park + threadIdx.x;          // (t, hit) as pk_replay_park left them; finalColor after depth 0 stands in its columns
+            const int hitRec = __float_as_int(pk_[PK_PARK_REC_HIT * BT]);
             idx = (hitRec >= 0 && hitRec < nObj) ? hitRec : -1;          // (a record never holds anything else; no gather may leave the scene)
-            t = __uint_as_float(rec.x);
-            float *pk_ = sc.park + threadIdx.x;
-            pk_[0 * BT] = recCol.x; pk_[1 * BT] = recCol.y; pk_[2 * BT] = recCol.z;          // finalColor after depth 0: the sky or zero where it missed
+            t = pk_[PK_PARK_REC_T * BT];
         } else {
         const unsigned long long tTrace = pk_clock<COUNT>();
         idx = pk_trace_closest<COUNT>(sc, nObj, ray, alive, rayBox, rayBoxFinite, maxDist, t, rays);
