@@ -244,6 +244,23 @@ int rt_debug_tile_costs(rt_context *ctx, unsigned *out, int cap, int *nTiles, in
  * launch, raster tile order; *nTiles = capacity of the class buffer (>= that launch's tiles).  Measurement hook; synchronises. */
 int rt_debug_predicted_classes(rt_context *ctx, uint8_t *out, int cap, int *nTiles);
 
+/* The tile order the last packet-kernel rt_render / rt_render_to / rt_render_into_image launch was given, and who supplied
+ * it: out[k] = the tile workgroup k rendered (up to cap entries), *nTiles = that launch's tiles, *policy = 0 raster (no order
+ * buffer: out = 0 .. n-1), 1 measured (an adopted longest-first sort of the tile costs), 2 predicted (from the frame's own
+ * inputs), 3 the order of the frame's phase (frameCount mod 64).  Only in a context created with RT_DEBUG_TILE_ORDER=1 in the
+ * environment, which then copies every launch's order aside before the launch (the sorts rewrite the live buffers behind
+ * it); otherwise, and before the first such launch or after rt_set_variant, *nTiles = 0.  The copy is ONE buffer per
+ * context: it is the last launch's order only if the caller synchronises between frames.  Test hook; synchronises.  No
+ * reference counterpart. */
+int rt_debug_tile_order(rt_context *ctx, uint32_t *out, int cap, int *nTiles, int *policy);
+
+/* The longest-first sort of the measured order (256 linear cost bins, heaviest bin first, any order inside a bin) on
+ * caller-supplied costs: HOST arrays of nTiles entries, sorted in device buffers of the call's own on the context's stream;
+ * synchronises.  costs comes back as the kernel leaves it (cleared for the next accumulation), order[k] = the k-th tile to
+ * start, accum (may be NULL; in/out) += the costs read.  Touches no scheduler state.  RT_ERR_INVALID_ARG: NULL context,
+ * costs or order, nTiles outside [1, 2^20].  Test hook, no reference counterpart. */
+int rt_debug_lpt_sort(rt_context *ctx, uint32_t *costs, int nTiles, uint32_t *order, uint32_t *accum);
+
 /* The lights' SHADOW TABLES of the current scene (built by rt_set_scene for scenes of <= 256 objects; csrc/rt_shadowtab.inc):
  * per light 28 dwords of header -- (kind, base dword, K, NB) (invBinW, binMax, wlo, nmax^2) (pmin, qmin, invCell, cells)
  * (T0, eta) (B0, nmax) (light position or direction, binW) (base dword of the light's BLOCKER table or 0, its eta, -, -);

@@ -672,6 +672,22 @@ int rt_debug_tile_costs(rt_context *c, unsigned *out, int cap, int *nTiles, int 
     return RT_OK;
 }
 
+int rt_debug_tile_order(rt_context *c, uint32_t *out, int cap, int *nTiles, int *policy) {
+    if (!c || !out || cap < 0 || !nTiles || !policy) return RT_ERR_INVALID_ARG;
+    HIP_TRY(c, hipSetDevice(c->device));
+    SCHED_TRY(c, tileOrder(out, cap, nTiles, policy));
+    return RT_OK;
+}
+
+int rt_debug_lpt_sort(rt_context *c, uint32_t *costs, int nTiles, uint32_t *order, uint32_t *accum) {
+    if (!c) return RT_ERR_INVALID_ARG;
+    if (!costs || !order) return fail(c, RT_ERR_INVALID_ARG, "rt_debug_lpt_sort: NULL costs or order");
+    if (nTiles < 1 || nTiles > (1 << 20)) return fail(c, RT_ERR_INVALID_ARG, "rt_debug_lpt_sort: nTiles outside [1, 2^20]");
+    HIP_TRY(c, hipSetDevice(c->device));
+    SCHED_TRY(c, lptSortOf(costs, nTiles, order, accum));
+    return RT_OK;
+}
+
 const char *rt_last_error(rt_context *c) { return c ? c->err.c_str() : "NULL context"; }
 
 int rt_debug_mesa_math(const float *in, float *out, int n) {

@@ -29,6 +29,7 @@ void RtTileScheduler::init(hipStream_t contextStream) {
         if (v >= 1 && v <= 1024) fbPeriod = (unsigned)v;
     }
     if (const char *e = getenv("RT_DEBUG_PRED_CLASSES")) dbgWantCls = atoi(e) != 0;
+    if (const char *e = getenv("RT_DEBUG_TILE_ORDER")) dbgWantOrder = atoi(e) != 0;
     if (const char *e = getenv("RT_PRED_MIN_TILES")) predMinTiles = atoi(e);
     if (const char *e = getenv("RT_PHASE_ORDER")) phaseOn = atoi(e) != 0;
 }
@@ -38,6 +39,7 @@ void RtTileScheduler::setMode(int variant) {
     // predicted one (default)
     schedMode = (variant & 0x100) ? 0 : ((variant & 0x200) ? 1 : 2);
     fbTiles = 0;
+    dbgOrderTiles = 0;
 }
 
 // ---- stream protocol ----------------------------------------------------------------------------------------------------
@@ -210,7 +212,8 @@ hipError_t RtTileScheduler::tileCosts(unsigned *out, int cap, int *nTiles, int *
 hipError_t RtTileScheduler::predictedBegin(const RtFrame &f, RtDeviceScene &sc, hipStream_t s, unsigned long long inputsGen, const Plan &plan) {
     const int nTiles = plan.nTiles;
     const double work = (double)nTiles * (double)(f.p.maxRayDepth > 0 ? f.p.maxRayDepth : 1) * (double)(f.nObj > 0 ? f.nObj : 1);
-    if (nTiles < predMinTiles || f.nObj > RT_ST_MAX_OBJECTS || work > 3.0e8) return hipSuccess;
+    // (no objects: nothing to predict from -- every tile costs the same -- and the kernel stages the objects in LDS sized by nObj)
+    if (nTiles < predMinTiles || f.nObj <= 0 || f.nObj > RT_ST_MAX_OBJECTS || work > 3.0e8) return hipSuccess;
     // the inputs this frame's tile costs are a function of
     unsigned long long key = 1469598103934665603ull;
     auto mix = [&key](const void *in, size_t n) {
@@ -311,6 +314,57 @@ hipError_t RtTileScheduler::phaseEnd(const Plan &plan) {
     return hipSuccess;
 }
 
+// ---- the order a launch was given (rt_debug_tile_order; rt_sched.h has the why) ------------------------------------------------
+
+hipError_t RtTileScheduler::noteOrder(const RtDeviceScene &sc, hipStream_t s, int nTiles, const StreamRec *rec) {
+    // who supplied the order is read off the pointer begin() ended up with (no bookkeeping on the path of a context that never asks):
+    // the adopted measured buffer, this stream's prediction, else a phase's slice of dPhaseOrder
+    const unsigned *o = sc.tileOrder;
+    dbgOrderPolicy = !o ? 0 : (fbCur >= 0 && o == dTileOrder[fbCur].ptr) ? 1 : (o == rec->predOrder.ptr) ? 2 : 3;
+    dbgOrderTiles = nTiles;
+    if (!o) return hipSuccess;
+    if (!dDbgOrder.holds(nTiles)) {
+        SCHED_PASS(drain());           // copies into the old buffer may still be queued
+        SCHED_TRY(dDbgOrder.grow(nTiles));
+    }
+    // behind everything begin() has put on s for this order (the waits for its sort, the prediction), ahead of the launch
+    SCHED_TRY(hipMemcpyAsync(dDbgOrder, o, (size_t)nTiles * sizeof(unsigned), hipMemcpyDeviceToDevice, s));
+    return hipSuccess;
+}
+
+hipError_t RtTileScheduler::tileOrder(unsigned *out, int cap, int *nTiles, int *policy) {
+    *nTiles = 0;
+    *policy = 0;
+    if (!dbgWantOrder || dbgOrderTiles == 0) return hipSuccess;
+    SCHED_PASS(drain());
+    *nTiles = dbgOrderTiles;
+    *policy = dbgOrderPolicy;
+    const int n = dbgOrderTiles < cap ? dbgOrderTiles : cap;
+    if (dbgOrderPolicy == 0)
+        for (int i = 0; i < n; i++) out[i] = (unsigned)i;
+    else
+        SCHED_TRY(hipMemcpy(out, dDbgOrder, (size_t)n * sizeof(unsigned), hipMemcpyDeviceToHost));
+    return hipSuccess;
+}
+
+hipError_t RtTileScheduler::lptSortOf(unsigned *costs, int nTiles, unsigned *order, unsigned *accum) {
+    const size_t bytes = (size_t)nTiles * sizeof(unsigned);
+    DevBuf<unsigned> dCost, dSnap, dOrder, dAccum;
+    SCHED_TRY(dCost.grow(nTiles));
+    SCHED_TRY(dSnap.grow(nTiles));
+    SCHED_TRY(dOrder.grow(nTiles));
+    if (accum) SCHED_TRY(dAccum.grow(nTiles));
+    SCHED_TRY(hipMemcpyAsync(dCost, costs, bytes, hipMemcpyHostToDevice, own));
+    SCHED_TRY(hipMemsetAsync(dOrder, 0xFF, bytes, own));      // an entry the sort leaves unwritten is no tile id
+    if (accum) SCHED_TRY(hipMemcpyAsync(dAccum, accum, bytes, hipMemcpyHostToDevice, own));
+    SCHED_TRY(rt_launch_lpt_sort(dCost, dSnap, dOrder, nTiles, own, accum ? dAccum.ptr : nullptr));
+    SCHED_TRY(hipStreamSynchronize(own));
+    SCHED_TRY(hipMemcpy(costs, dCost, bytes, hipMemcpyDeviceToHost));
+    SCHED_TRY(hipMemcpy(order, dOrder, bytes, hipMemcpyDeviceToHost));
+    if (accum) SCHED_TRY(hipMemcpy(accum, dAccum, bytes, hipMemcpyDeviceToHost));
+    return hipSuccess;
+}
+
 // ---- one frame ------------------------------------------------------------------------------------------------------------
 
 hipError_t RtTileScheduler::begin(const RtFrame &f, RtDeviceScene &sc, hipStream_t s, bool packet, unsigned long long inputsGen, Plan *plan, int costClass) {
@@ -319,14 +373,23 @@ hipError_t RtTileScheduler::begin(const RtFrame &f, RtDeviceScene &sc, hipStream
     sc.tileOrder = nullptr;
     sc.tileCost = nullptr;
     SCHED_PASS(record(s, &plan->rec));
-    if (!(packet && schedMode != 0 && f.p.regionW > 0 && f.p.regionH > 0)) return hipSuccess;
+    if (!(packet && schedMode != 0 && f.p.regionW > 0 && f.p.regionH > 0)) {
+        if (dbgWantOrder && packet && f.p.regionW > 0 && f.p.regionH > 0) {      // raster mode: the launch still has an order to report
+            int bt = 0, tile = 0, tilesX = 0, nTiles = 0;
+            rt_packet_geometry(f.nObj, f.p.regionW, f.p.regionH, &bt, &tile, &tilesX, &nTiles);
+            SCHED_PASS(noteOrder(sc, s, nTiles, plan->rec));
+        }
+        return hipSuccess;
+    }
     int tile = 0;
     rt_packet_geometry(f.nObj, f.p.regionW, f.p.regionH, &plan->bt, &tile, &plan->tilesX, &plan->nTiles);
     bool newGeometry = false;
     SCHED_PASS(measuredBegin(sc, s, plan, &newGeometry));
     if (newGeometry) phaseForget();
     if (fbCur < 0 && schedMode == 2) SCHED_PASS(predictedBegin(f, sc, s, inputsGen, *plan));
-    return phaseBegin(f, sc, plan);
+    SCHED_PASS(phaseBegin(f, sc, plan));
+    if (dbgWantOrder) SCHED_PASS(noteOrder(sc, s, plan->nTiles, plan->rec));
+    return hipSuccess;
 }
 
 hipError_t RtTileScheduler::end(const Plan &plan, hipStream_t s) {

@@ -32,7 +32,7 @@ struct RtTileScheduler {
         bool sortAfter = false;                // the frame was scheduled: the measured order's bookkeeping runs after it
     };
 
-    void init(hipStream_t contextStream);      // + the environment overrides (RT_FB_PERIOD, RT_PRED_MIN_TILES, RT_PHASE_ORDER, RT_DEBUG_PRED_CLASSES)
+    void init(hipStream_t contextStream);      // + the environment overrides (RT_FB_PERIOD, RT_PRED_MIN_TILES, RT_PHASE_ORDER, RT_DEBUG_PRED_CLASSES, RT_DEBUG_TILE_ORDER)
     void setMode(int variant);                 // rt_set_variant's bits 8 and 9; forgets the geometry
 
     // ---- stream protocol
@@ -55,9 +55,13 @@ struct RtTileScheduler {
     hipError_t afterFirstHitRecord(hipStream_t s, StreamRec *rec);
     hipError_t beforeFirstHitReplay(hipStream_t s, StreamRec *rec);
 
-    // ---- debug read-outs (rt_debug_tile_costs, rt_debug_predicted_classes)
+    // ---- debug read-outs (rt_debug_tile_costs, rt_debug_predicted_classes, rt_debug_tile_order)
     hipError_t tileCosts(unsigned *out, int cap, int *nTiles, int *tilesX);
     hipError_t predictedClasses(unsigned char *out, int cap, int *nTiles);
+    hipError_t tileOrder(unsigned *out, int cap, int *nTiles, int *policy);
+    // rt_debug_lpt_sort: rt_launch_lpt_sort on the caller's host arrays, in device buffers of its own on the context's stream;
+    // synchronises.  Reads and writes nothing of the scheduler's (failedCall aside).
+    hipError_t lptSortOf(unsigned *costs, int nTiles, unsigned *order, unsigned *accum);
 
     const char *failedCall = "";               // the HIP call behind the last error returned
 
@@ -68,6 +72,7 @@ private:
     hipError_t phaseBegin(const RtFrame &f, RtDeviceScene &sc, Plan *plan);
     hipError_t phaseEnd(const Plan &plan);
     void phaseForget();
+    hipError_t noteOrder(const RtDeviceScene &sc, hipStream_t s, int nTiles, const StreamRec *rec);
 
     hipStream_t own = nullptr;                 // the context's stream: the periodic sort runs on it
     // schedMode 2 (default): tiles run longest-first by their MEASURED cost over the last frames of the same window geometry (the
@@ -101,6 +106,14 @@ private:
     bool dbgWantCls = false;                   // RT_DEBUG_PRED_CLASSES=1: predictions also store each tile's class
     const unsigned char *dbgPredCls = nullptr; // class buffer of the last predicted launch (rt_debug_predicted_classes)
     int dbgPredTiles = 0;
+
+    // ---- RT_DEBUG_TILE_ORDER=1: begin() ends by copying the order it chose (device to device, on the launch's stream, ahead of
+    // the launch) into dDbgOrder -- the sorts rewrite the live buffers behind the launch, phaseEnd the very one the frame read.
+    // One buffer per context: the read-out means the last launch's order only if the caller synchronises between frames.
+    bool dbgWantOrder = false;
+    DevBuf<unsigned> dDbgOrder;
+    int dbgOrderTiles = 0;                     // tiles of the last packet launch begin() saw (0 = none since init / setMode)
+    int dbgOrderPolicy = 0;                    // who supplied its order: 0 raster (nothing copied), 1 measured, 2 predicted, 3 phase
 
     // ---- per-phase orders.  Free-running frameCount (the reference with TAA on, ForwardShadingPipeline.cpp:254): frameCount
     // enters the frame through hammersley(depth*64 + frameCount, 64) (:557) -- the bounce sample ALL pixels share -- whose azimuth

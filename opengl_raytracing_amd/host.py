@@ -84,6 +84,8 @@ def _signatures():
         "rt_debug_stats_ex": (ci, [vp, P(u64)]),
         "rt_debug_tile_costs": (ci, [vp, P(u32), ci, P(ci), P(ci)]),
         "rt_debug_predicted_classes": (ci, [vp, vp, ci, P(ci)]),
+        "rt_debug_tile_order": (ci, [vp, P(u32), ci, P(ci), P(ci)]),
+        "rt_debug_lpt_sort": (ci, [vp, P(u32), ci, P(u32), P(u32)]),
         "rt_debug_shadow_tables": (ci, [vp, vp, sz, P(sz), P(ci)]),
         "rt_debug_mesa_math": (ci, [vp, vp, ci]),
         "rt_debug_device_math": (ci, [vp, ci, vp, vp, sz, vp]),
@@ -1283,6 +1285,29 @@ class RayTracer(_Handle):
         n = ctypes.c_int(0)
         self._call("rt_debug_predicted_classes", _ptr(out), n_tiles, ctypes.byref(n))
         return out
+
+    def tile_order(self):
+        """(order uint32[nTiles], policy) of the last packet launch (rt_debug_tile_order): order[k] = the tile workgroup k rendered,
+        policy 0 raster / 1 measured / 2 predicted / 3 phase.  An empty order unless the context was created with
+        RT_DEBUG_TILE_ORDER=1; the last launch's only if the caller synchronises between frames."""
+        n, policy = ctypes.c_int(0), ctypes.c_int(0)
+        probe = np.zeros(1, dtype=np.uint32)
+        self._call("rt_debug_tile_order", _typed(probe, ctypes.c_uint32), 0, ctypes.byref(n), ctypes.byref(policy))
+        out = np.zeros(max(n.value, 1), dtype=np.uint32)
+        self._call("rt_debug_tile_order", _typed(out, ctypes.c_uint32), n.value, ctypes.byref(n), ctypes.byref(policy))
+        return out[:n.value], policy.value
+
+    def lpt_sort(self, costs, accum=None):
+        """rt_lpt_sort_kernel on the given tile costs (rt_debug_lpt_sort) -> (order uint32[n], costs as the kernel leaves them,
+        accum + costs or None).  The arguments are not modified."""
+        u32p = lambda a: _typed(a, ctypes.c_uint32)
+        costs = np.array(costs, dtype=np.uint32).reshape(-1)
+        order = np.zeros(costs.size, dtype=np.uint32)
+        if accum is not None:
+            accum = np.array(accum, dtype=np.uint32).reshape(-1)
+            assert accum.size == costs.size
+        self._call("rt_debug_lpt_sort", u32p(costs), costs.size, u32p(order), u32p(accum) if accum is not None else None)
+        return order, costs, accum
 
     def shadow_tables(self):
         """(dwords uint32[n], words per cell) of the current scene's shadow tables (headers + cells), or (None, 0)."""

@@ -125,6 +125,26 @@ def test_null_context(tracer):
 
 
 @pytest.mark.gpu
+def test_scheduler_hook_refusals(ctx):
+    """rt_debug_tile_order and rt_debug_lpt_sort (the hooks of tests/test_sched.py): NULL pointers and tile counts outside
+    [1, 2^20].  The read-out's refusals leave no text, as those of the other two scheduler read-outs."""
+    e, c = ctx.lib.entry, ctx.ctx
+    buf = (ctypes.c_uint32 * 4)()
+    n, policy = ctypes.c_int(0), ctypes.c_int(0)
+    assert e["rt_debug_tile_order"](None, buf, 4, ctypes.byref(n), ctypes.byref(policy)) == INVALID
+    for args in ((None, 4, ctypes.byref(n), ctypes.byref(policy)), (buf, -1, ctypes.byref(n), ctypes.byref(policy)),
+                 (buf, 4, None, ctypes.byref(policy)), (buf, 4, ctypes.byref(n), None)):
+        assert e["rt_debug_tile_order"](c, *args) == INVALID, args
+    assert e["rt_debug_lpt_sort"](None, buf, 4, buf, None) == INVALID
+    order = (ctypes.c_uint32 * 4)()
+    for args in ((None, 4, order, None), (buf, 4, None, None), (None, 4, None, buf)):
+        ctx.refused("rt_debug_lpt_sort", args, INVALID, "rt_debug_lpt_sort: NULL costs or order")
+    for bad in (0, -1, (1 << 20) + 1, -(1 << 31)):
+        ctx.refused("rt_debug_lpt_sort", (buf, bad, order, None), INVALID, "rt_debug_lpt_sort: nTiles outside [1, 2^20]")
+    assert list(buf) == [0, 0, 0, 0] and list(order) == [0, 0, 0, 0]
+
+
+@pytest.mark.gpu
 def test_taa_resolve_refusals(ctx, dev):
     valid = dict(cur=dev["a"], his=dev["b"], nrm=dev["n"], out=dev["c"], w=W, h=H, blend=0.1, jx=0.0, jy=0.0, stream=None)
     bad = dict(cur=(None,), his=(None,), nrm=(None,), out=(None,), w=(0, -1), h=(0, -1))
