@@ -189,6 +189,23 @@ int rt_count_rays(rt_context *ctx, const rt_params *p, uint64_t *rays);
  * lanes whose light term is +-0 or NaN for every finite shadow value, blocker rays after the first blocker; DESIGN.md
  * section 4 items 6-8).  <= rt_count_rays; equal for variant 0.  Synchronises. */
 int rt_count_rays_traced(rt_context *ctx, const rt_params *p, uint64_t *rays);
+/* Both of them, with the instrumented build's frame made visible.  mode = 1 counts the reference's rays (rt_count_rays), mode = 2
+ * the traced ones (rt_count_rays_traced); any other mode is refused.  dColor / dPosition / dNormal are DEVICE surfaces sized like
+ * rt_render_to's (regionW*regionH*16, *16, *8 bytes) that receive the frame the instrumented launch renders -- the same bits as
+ * rt_render_to's in both modes, which is what makes the skipped rays provably dead -- or all three NULL: the frame then goes into
+ * scratch that is freed again.  Runs on the context's stream and synchronises.  Never records or replays first hits, and leaves
+ * the cached ones, rt_debug_first_hit and rt_debug_prefix_tiles as they were.
+ *
+ * The traced count, exactly.  Primary, bounce and subsurface rays always count.  Per hit point and light with shadowType 1 or 2:
+ *   lit = pcfSamples < 1 (the shadow factor is 0/0 then: nothing is skipped), or otherwise both
+ *         max(dot(N, normalize(lightDir)), 0) > 0 and some channel of (color * attenuation) * intensity neither +-0 nor NaN;
+ *   an unlit point traces no shadow ray for that light;
+ *   a lit point under PCSS traces its 16 blocker rays in groups of G: a group is traced whole if no blocker was found before its
+ *         first ray, and no group after that.  G is the launched kernel's blocker rays per traversal: RT_PK_BLOCKER_GROUP (4) in
+ *         every packet kernel of a scene with a PCSS light, 1 otherwise; rt_debug_stats_ex reports it in out[31];
+ *   a lit point traces the PCF rays the reference traces (pcfSamples each; under PCSS only where a blocker was found).
+ * Variant 0 ignores the mode: its traced count is the reference count. */
+int rt_count_rays_to(rt_context *ctx, const rt_params *p, int mode, void *dColor, void *dPosition, void *dNormal, uint64_t *rays);
 
 /* Kernel variant: 1 (default) = wavefront-packet kernel (packet culling, scalar-fed traversal),
  * 0 = exhaustive per-lane loop over all objects.  Both produce bit-identical surfaces; the switch
@@ -220,9 +237,9 @@ int rt_debug_settled_map(rt_context *ctx, uint8_t *flags, size_t n);
  * context's work in flight. */
 int rt_debug_prefix_tiles(rt_context *ctx, uint64_t out[9]);
 
-/* Diagnostics of the last rt_count_rays launch: out[0] rays, out[1] wave-level ray packets,
- * out[2] candidate objects summed over packets (after packet culling), out[3] 64-object cull
- * passes.  [1..3] are zero for variant 0 (no packet culling). */
+/* Diagnostics of the last rt_count_rays / rt_count_rays_traced / rt_count_rays_to launch: out[0] rays (the total that call
+ * returned), out[1] wave-level ray packets, out[2] candidate objects summed over packets (after packet culling, or from a
+ * light's shadow table), out[3] 64-object cull passes.  [1..3] are zero for variant 0 (no packet culling). */
 int rt_debug_stats(rt_context *ctx, uint64_t out[4]);
 /* The same plus packet-coherence diagnostics of the packet kernel: out[4..7] packets whose direction boxes leave 3 / 2 / 1 / 0
  * axes usable for culling (an axis is lost when the packet's directions straddle zero on it), out[8] packets that cannot be
@@ -233,7 +250,17 @@ int rt_debug_stats(rt_context *ctx, uint64_t out[4]);
  * candidates entering / leaving the per-lane cull level of a light's PCF rays; timers build only: out[22] candidate trips of
  * the PCF sample loops, out[23] those in which some lane passes the slab test, out[24] lanes passing, out[25] sample groups, out[26] the whole
  * light loop, out[27] the subsurface section, out[28] PCSS blocker searches, out[29] hit shading set-up, out[30] roulette + next
- * direction (clocks). */
+ * direction (clocks); out[31] the blocker group G of that launch (rt_count_rays_to; written by the host, 1 for variant 0).
+ * Relations that hold for every launch: the counters are sums of integers over waves, so two launches of the same frame give
+ * the same out[0..11], out[20] and out[21]; out[21] <= out[20]; variant 0 leaves out[1..30] zero; out[12..19] and out[22..30]
+ * are zero unless built with -DRT_PK_TIMERS=1.  Packets whose candidates come from a light's shadow table (PCF and blocker
+ * rays of scenes that have tables) are counted in out[1] and out[2] only: no direction box is formed and no cull pass made for
+ * them, so they appear in none of out[3..11].  Hence out[4] + ... + out[8] <= out[1] and out[9] + out[10] <= out[2], with
+ * equality when no table served the launch; out[11] <= 64 * (out[4] + ... + out[8]) <= 64 * out[1]; out[0] <= 64 * out[1] (a
+ * packet carries at most one ray per lane); out[11] >= the window's pixels inside the image (every primary ray is a lane of a
+ * boxed packet); a mode-2 launch's out[0], out[1] and out[11] never exceed the mode-1 launch's of the same frame (the skips only
+ * take packets and lanes away); and a packet-kernel launch
+ * on a scene with objects in view has out[1], out[2], out[3] > 0 (the primary rays' packets are never table-driven). */
 int rt_debug_stats_ex(rt_context *ctx, uint64_t out[32]);
 /* Measured cost (shader clock cycles / 64, summed over the tile's waves) of every workgroup tile of the
  * last feedback-scheduled rt_render / rt_render_to launch, in raster tile order; synchronises.  Writes up

@@ -111,7 +111,8 @@ RtFirstHit::Mode first_hit_mode(rt_context *c, const RtFirstHitKey &key) {
 // The launches of one frame (launch(), below, is what the entry points call): the first-hit mode, the scheduler's plan, the
 // render kernel between the timing events.
 int launch_frame(rt_context *c, const rt_params *p, float4 *dColor, float4 *dPos, uint2 *dNormal,
-                 unsigned long long *counter, hipStream_t s, bool timed, int countMode, bool imageStores, bool reusable) {
+                 unsigned long long *counter, hipStream_t s, bool timed, int countMode, bool imageStores, bool reusable,
+                 int *blockerGroup) {
     RtFrame f;
     build_frame(c, p, &f);
     f.imageStores = imageStores ? 1 : 0;
@@ -140,7 +141,8 @@ int launch_frame(rt_context *c, const rt_params *p, float4 *dColor, float4 *dPos
     HIP_TRY(c, rt_launch_render(f, sc, dColor, dPos, dNormal, counter, c->variant, s, countMode, (int)mode,
                                 mode == RtFirstHit::NORMAL ? nullptr
                                     : (void *)((uintptr_t)c->dFirstHit.ptr | (mode == RtFirstHit::RECORD && !c->settledOn() ? RT_FIRST_HIT_NO_SETTLED : 0) |
-                                               (mode == RtFirstHit::RECORD && !c->prefixOn() ? RT_FIRST_HIT_NO_PREFIX : 0))));
+                                               (mode == RtFirstHit::RECORD && !c->prefixOn() ? RT_FIRST_HIT_NO_PREFIX : 0)),
+                                blockerGroup));
     if (timed) {
         HIP_TRY(c, hipEventRecord(c->evStop, s));
         c->timed = true;
@@ -157,10 +159,11 @@ int launch_frame(rt_context *c, const rt_params *p, float4 *dColor, float4 *dPos
 // One frame.  Whatever goes wrong in a launch that could have recorded or replayed (a refusal, a failed HIP call) leaves the
 // first-hit state empty: the next frame is a normal one.
 int launch(rt_context *c, const rt_params *p, float4 *dColor, float4 *dPos, uint2 *dNormal,
-           unsigned long long *counter, hipStream_t s, bool timed, int countMode = 1, bool imageStores = false) {
+           unsigned long long *counter, hipStream_t s, bool timed, int countMode = 1, bool imageStores = false,
+           int *blockerGroup = nullptr) {
     // instrumented launches and the exhaustive kernel always trace the whole frame and leave the cache as it is
     const bool reusable = c->variant == 1 && !counter;
-    const int rc = launch_frame(c, p, dColor, dPos, dNormal, counter, s, timed, countMode, imageStores, reusable);
+    const int rc = launch_frame(c, p, dColor, dPos, dNormal, counter, s, timed, countMode, imageStores, reusable, blockerGroup);
     if (rc != RT_OK && reusable) c->firstHit.invalidate();
     return rc;
 }
@@ -538,30 +541,44 @@ int rt_last_kernel_ms(rt_context *c, float *ms) {
     return RT_OK;
 }
 
-static int count_rays_impl(rt_context *c, const rt_params *p, uint64_t *rays, int countMode) {
+// The instrumented builds of the render kernel (rt_launch_render's countMode): the frame into the caller's surfaces or, with
+// none, into scratch that is freed again; the ray total and the diagnostics of rt_debug_stats_ex.  The launch never records
+// or replays first hits and leaves the cached ones as they are (launch()).
+int rt_count_rays_to(rt_context *c, const rt_params *p, int mode, void *dColor, void *dPosition, void *dNormal, uint64_t *rays) {
     if (!c || !rays) return RT_ERR_INVALID_ARG;
+    *rays = 0;
+    if (mode != 1 && mode != 2) return fail(c, RT_ERR_INVALID_ARG, "rt_count_rays_to: mode must be 1 (reference rays) or 2 (traced rays)");
     int rc = validate_params(c, p);
     if (rc) return rc;
+    const bool own = !dColor && !dPosition && !dNormal;
+    if (!own && (!dColor || !dPosition || !dNormal)) return fail(c, RT_ERR_INVALID_ARG, "rt_count_rays_to: all three surfaces or none");
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t npx = (size_t)p->regionW * p->regionH;
     DevBuf<float4> col, pos;
     DevBuf<uint2> nrm;
-    hipError_t e = col.grow(npx);
-    if (e == hipSuccess) e = pos.grow(npx);
-    if (e == hipSuccess) e = nrm.grow(npx);
-    if (e != hipSuccess) return fail(c, RT_ERR_HIP, "hipMalloc (ray count scratch)", e);
+    if (own) {
+        hipError_t e = col.grow(npx);
+        if (e == hipSuccess) e = pos.grow(npx);
+        if (e == hipSuccess) e = nrm.grow(npx);
+        if (e != hipSuccess) return fail(c, RT_ERR_HIP, "hipMalloc (ray count scratch)", e);
+        dColor = col.ptr;
+        dPosition = pos.ptr;
+        dNormal = nrm.ptr;
+    }
+    int group = 1;
     if (hipMemsetAsync(c->dRayCounter, 0, 32 * sizeof(unsigned long long), c->stream) != hipSuccess) rc = RT_ERR_HIP;
-    if (!rc) rc = launch(c, p, col, pos, nrm, c->dRayCounter, c->stream, false, countMode);
+    if (!rc) rc = launch(c, p, (float4 *)dColor, (float4 *)dPosition, (uint2 *)dNormal, c->dRayCounter, c->stream, false, mode, false, &group);
     unsigned long long v[32] = {};
     if (!rc && (hipStreamSynchronize(c->stream) != hipSuccess ||
                 hipMemcpy(v, c->dRayCounter, sizeof v, hipMemcpyDeviceToHost) != hipSuccess))
         rc = fail(c, RT_ERR_HIP, "ray counter readback");
+    v[31] = (unsigned long long)group;       // written here, not by the kernel: the launched instantiation's blocker group
     *rays = v[0];
     for (int k = 0; k < 32; k++) c->lastStats[k] = v[k];
     return rc;
 }
-int rt_count_rays(rt_context *c, const rt_params *p, uint64_t *rays) { return count_rays_impl(c, p, rays, 1); }
-int rt_count_rays_traced(rt_context *c, const rt_params *p, uint64_t *rays) { return count_rays_impl(c, p, rays, 2); }
+int rt_count_rays(rt_context *c, const rt_params *p, uint64_t *rays) { return rt_count_rays_to(c, p, 1, nullptr, nullptr, nullptr, rays); }
+int rt_count_rays_traced(rt_context *c, const rt_params *p, uint64_t *rays) { return rt_count_rays_to(c, p, 2, nullptr, nullptr, nullptr, rays); }
 
 int rt_set_variant(rt_context *c, int variant) {
     if (!c) return RT_ERR_INVALID_ARG;

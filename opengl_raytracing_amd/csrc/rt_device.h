@@ -85,7 +85,10 @@ hipError_t rt_launch_compile_scene(const uint8_t *dObjects, int nObj, const uint
                                    float4 *dCompiled, hipStream_t s);
 hipError_t rt_launch_render(const RtFrame &f, const RtDeviceScene &sc, float4 *dColor, float4 *dPos,
                             uint2 *dNormal, unsigned long long *dRayCounter, int variant, hipStream_t s, int countMode = 1,
-                            int firstMode = 0, void *dFirstHit = nullptr);
+                            int firstMode = 0, void *dFirstHit = nullptr, int *blockerGroup = nullptr);
+// (blockerGroup, optional: receives how many of pcssShadow's blocker rays the launched instantiation takes per traversal --
+// RT_PK_BLOCKER_GROUP in the profiles with blockerPairs / blockerTab, 1 in the others and in the exhaustive kernel; the
+// granularity at which a countMode-2 launch stops a lane's blocker search.)
 // (the record buffer of a regionW x regionH window, render_packet FIRST != 0: rt_first_hit_bytes() and the offsets of its parts
 // are rt_firsthit.h's.)  Bit 0 of the dFirstHit pointer a RECORDING launch passes switches settled tiles OFF (DESIGN.md
 // section 27: every tile's flag is then written as 0, which is all a replaying launch looks at): the buffer is aligned far

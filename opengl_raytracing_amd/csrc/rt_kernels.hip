@@ -917,7 +917,8 @@ hipError_t rt_launch_shadow_tables(const float4 *dCompiled, int nObj, int nLt, u
 // depth 0 from them (rt_first_hit_bytes(regionW, regionH) bytes; render_packet).
 hipError_t rt_launch_render(const RtFrame &f, const RtDeviceScene &sc, float4 *dColor, float4 *dPos,
                             uint2 *dNormal, unsigned long long *dRayCounter, int variant, hipStream_t s, int countMode,
-                            int firstMode, void *dFirstHit) {
+                            int firstMode, void *dFirstHit, int *blockerGroup) {
+    if (blockerGroup) *blockerGroup = 1;
     if (f.p.regionW <= 0 || f.p.regionH <= 0) return hipSuccess;
     if (firstMode != 0 && (firstMode < 0 || firstMode > 2 || variant != 1 || dRayCounter || !dFirstHit || f.p.maxRayDepth < 1)) return hipErrorInvalidValue;
     if (variant != 1 && (f.nObj > RT_EXHAUSTIVE_MAX_OBJECTS || f.nLt > RT_EXHAUSTIVE_MAX_LIGHTS)) return hipErrorInvalidValue;      // (the ABI refuses first)
@@ -933,6 +934,7 @@ hipError_t rt_launch_render(const RtFrame &f, const RtDeviceScene &sc, float4 *d
         unsigned long long *const firstArg = (unsigned long long *)dFirstHit;      // (the records travel in the counter's argument: rt_render_packet_kernel)
 #define RT_LAUNCH_PK(PROFILE_)                                                                                                        \
         do {                                                                                                                          \
+            if (blockerGroup) *blockerGroup = (PROFILE_::blockerPairs || PROFILE_::blockerTab) ? RT_PK_BLOCKER_GROUP : 1;             \
             if (dRayCounter && countMode == 2) hipLaunchKernelGGL((rt_render_packet_kernel<2, 64, true, PROFILE_>), grid, dim3(64), ldsBytes, s, f, sc, dColor, dPos, dNormal, dRayCounter); \
             else if (dRayCounter) hipLaunchKernelGGL((rt_render_packet_kernel<1, 64, true, PROFILE_>), grid, dim3(64), ldsBytes, s, f, sc, dColor, dPos, dNormal, dRayCounter);            \
             else if (firstMode == 1) hipLaunchKernelGGL((rt_render_packet_kernel<0, 64, true, PROFILE_, 1>), grid, dim3(64), ldsBytes, s, f, sc, dColor, dPos, dNormal, firstArg);    \

@@ -1149,7 +1149,9 @@ __device__ __forceinline__ float pk_pcf_shadow(const SceneLds &sc, int nObj, v3 
     if (splitLight) pk_stat<COUNT>(sc, 17, tMasks - tSetup);       // [17] masks of split packets
 #endif
     for (int s0 = 0; s0 < pcfSamples; s0 += GROUPN) {
-        pk_stat<COUNT>(sc, 25, 1);                                               // [25] sample groups
+#if RT_PK_TIMERS
+        pk_stat<COUNT>(sc, 25, 1);                                               // [25] sample groups (timers build only, like [22..24])
+#endif
         Ray sr[GROUPN];
         v3 inv[GROUPN];
         float a[GROUPN];
@@ -1258,11 +1260,12 @@ __device__ __forceinline__ float pk_pcf_shadow(const SceneLds &sc, int nObj, v3 
         } else {
             mask = light_mask(bmn, bmx, base + lane < nObj, bnan);
         }
-        if (NWT == 0)
+        if (NWT == 0) {       // (a table-driven light is booked above, in [1] and [2] only: it has no direction box and makes no cull pass)
         pk_stat<COUNT>(sc, 2, (unsigned long long)__builtin_popcountll(mask) * (unsigned long long)pcfSamples);
         pk_stat<COUNT>(sc, (pk.cull && pk.okx && pk.oky && pk.okz) ? 9 : 10, (unsigned long long)__builtin_popcountll(mask) * (unsigned long long)pcfSamples);
         pk_stat<COUNT>(sc, 3, 1);
-        if (NWT == 0 && base == 0) pk_stat<COUNT>(sc, 1, (unsigned long long)pcfSamples);
+        if (base == 0) pk_stat<COUNT>(sc, 1, (unsigned long long)pcfSamples);
+        }
         if (mask == 0ull) continue;
         for (int s = 0; s < pcfSamples; s++) {
             bool todo = need && !((occBits >> (s & 31)) & 1u);

@@ -75,6 +75,7 @@ def _signatures():
         "rt_last_kernel_ms": (ci, [vp, P(cf)]),
         "rt_count_rays": (ci, [vp, params, P(u64)]),
         "rt_count_rays_traced": (ci, [vp, params, P(u64)]),
+        "rt_count_rays_to": (ci, [vp, params, ci, vp, vp, vp, P(u64)]),
         "rt_set_variant": (ci, [vp, ci]),
         "rt_debug_first_hit": (ci, [vp, P(u64)]),
         "rt_debug_settled_tiles": (ci, [vp, P(u64)]),
@@ -887,6 +888,15 @@ class RayTracer(_Handle):
         """Rays the production kernel traverses (keeps its dead-ray skips); <= count_rays."""
         n = ctypes.c_uint64()
         self._call("rt_count_rays_traced", ctypes.byref(params), ctypes.byref(n))
+        return n.value
+
+    def count_rays_to(self, params, mode, d_color=None, d_position=None, d_normal=None):
+        """The instrumented launch of mode 1 (reference rays) or 2 (traced rays) with its frame rendered into caller-owned
+        device surfaces (raw device pointers as ints or CUDA tensors, sized like render_to's; all three or none) -> the ray
+        total (rt_count_rays_to).  On the context's stream; synchronises."""
+        n = ctypes.c_uint64()
+        self._call("rt_count_rays_to", ctypes.byref(params), int(mode), _dev_ptr(d_color), _dev_ptr(d_position), _dev_ptr(d_normal),
+                   ctypes.byref(n))
         return n.value
 
     def taa_resolve(self, d_current, d_history, d_normal, d_out, width, height, blend, jx, jy, stream=None):

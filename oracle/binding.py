@@ -30,6 +30,8 @@ def load():
         vp, ci = ctypes.c_void_p, ctypes.c_int
         lib.orc_render.argtypes = [vp, ci, vp, ci, vp, vp, ci, ci, vp, ci, vp, vp, vp, ctypes.POINTER(ctypes.c_uint64), ci]
         lib.orc_render.restype = ci
+        lib.orc_render_traced.argtypes = lib.orc_render.argtypes + [ci, ctypes.POINTER(ctypes.c_uint64), vp]
+        lib.orc_render_traced.restype = ci
         lib.orc_generate_aabb.argtypes = [vp, ci]
         lib.orc_generate_aabb.restype = None
         lib.orc_halton.argtypes = [vp, vp, vp, ci]
@@ -48,15 +50,18 @@ def _ptr(a):
     return a.ctypes.data_as(ctypes.c_void_p) if a is not None else None
 
 
-def render(scene, params, nthreads=0):
+def render(scene, params, nthreads=0, blocker_group=None, blocker_hist=False):
     """CPU restatement of one dispatch.  -> (gColor f32[h,w,4], gPosition f32[h,w,4],
-    gNormal f16[h,w,4], rays)."""
+    gNormal f16[h,w,4], rays); with blocker_group (1, 2, 4, 8 or 16) a fifth item follows: the rays a skip-exact tracer
+    traverses that takes pcssShadow's blocker rays blocker_group per traversal (rt_oracle.h, orc_render_traced); with
+    blocker_hist a sixth: uint64[17], the blocker searches of lit points by the ray that found their first blocker ([16]: none)."""
     lib = load()
     w, h = params.regionW, params.regionH
     col = np.zeros((h, w, 4), dtype=np.float32)
     pos = np.zeros((h, w, 4), dtype=np.float32)
     nrm = np.zeros((h, w, 4), dtype=np.float16)
-    rays = ctypes.c_uint64(0)
+    rays, traced = ctypes.c_uint64(0), ctypes.c_uint64(0)
+    hist = np.zeros(17, dtype=np.uint64)
     objs = np.ascontiguousarray(scene.objects)
     lts = np.ascontiguousarray(scene.lights)
     noise = np.ascontiguousarray(scene.noise) if scene.noise is not None else None
@@ -65,14 +70,17 @@ def render(scene, params, nthreads=0):
     # limiter); every parity test against the HIP path leaves it 0 -- anything else is refused rather than silently honoured
     if not 0 <= int(params.reserved0) <= 7:
         raise ValueError(f"params.reserved0 = {params.reserved0}: not a set of oracle diagnostic bits")
-    rc = lib.orc_render(_ptr(objs), len(objs), _ptr(lts), len(lts), ctypes.byref(params),
-                        _ptr(noise), noise.shape[1] if noise is not None else 0,
-                        noise.shape[0] if noise is not None else 0,
-                        _ptr(sky), sky.shape[1] if sky is not None else 0,
-                        _ptr(col), _ptr(pos), _ptr(nrm), ctypes.byref(rays), nthreads)
+    rc = lib.orc_render_traced(_ptr(objs), len(objs), _ptr(lts), len(lts), ctypes.byref(params),
+                               _ptr(noise), noise.shape[1] if noise is not None else 0,
+                               noise.shape[0] if noise is not None else 0,
+                               _ptr(sky), sky.shape[1] if sky is not None else 0,
+                               _ptr(col), _ptr(pos), _ptr(nrm), ctypes.byref(rays), nthreads,
+                               1 if blocker_group is None else int(blocker_group), ctypes.byref(traced), _ptr(hist))
     if rc:
         raise RuntimeError(f"orc_render failed: {rc}")
-    return col, pos, nrm, rays.value
+    if blocker_group is None:
+        return col, pos, nrm, rays.value
+    return (col, pos, nrm, rays.value, traced.value) + ((hist,) if blocker_hist else ())
 
 
 def generate_aabb(objects):

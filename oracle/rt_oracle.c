@@ -280,6 +280,14 @@ typedef struct {
     /* per-pixel state */
     uint32_t gidx, gidy;
     uint64_t rays;
+    /* The traced count: the rays a tracer traverses that skips exactly the shadow and PCSS-blocker rays which cannot reach a
+     * pixel (the HIP packet kernel's rule, restated in computeLighting / pcssShadow below).  blockerGroup = blocker rays per
+     * traversal of that tracer (1, 2, 4, 8 or 16); lit = the current light can reach this shading point's pixel;
+     * untraced = the rays being counted now are ones such a tracer skips. */
+    uint64_t traced;
+    int blockerGroup, lit, untraced;
+    /* ... and where the blocker searches of lit points end: [i] = searches whose first blocker is ray i, [16] = none found */
+    uint64_t firstBlocker[17];
 } Ctx;
 
 typedef struct { v3 origin, direction; } Ray; /* :13-18; energy/depth are dead (A.1#21) */
@@ -418,6 +426,7 @@ static int intersectObjects(Ctx *c, const Ray *r, Mat *hitMat, v3 *hitNormal, fl
     float minT = c->p->maxRayDistance;
     int hit = 0;
     c->rays++;
+    if (!c->untraced) c->traced++;
     LIM_FOR(int i = 0, i < c->nObj, i++) {
         const Obj *o = &c->objs[i];
         if (!intersectAABB(c, r, o->bmin, o->bmax)) continue;
@@ -516,6 +525,7 @@ static float pcfShadow(Ctx *c, v3 point, v3 normal, const Lgt *l, v3 lightDir, f
     v3 tangent = normalize3(cross3(lightDir, V3(0, 1, 0)));
     v3 bitangent = cross3(lightDir, tangent);
     float jr = sample_noise(c); /* .rg of an R8 texture = (r, 0) */
+    c->untraced = !c->lit;      /* traced count: PCF rays where the reference traces them and the point is lit */
     LIM_FOR(int i = 0, i < l->pcfSamples, i++) {
         float filterSize = l->shadowSoftness * 0.005f;
         float rx = fract1(halton(i, 2) + jr);
@@ -531,14 +541,18 @@ static float pcfShadow(Ctx *c, v3 point, v3 normal, const Lgt *l, v3 lightDir, f
         if (l->type == 0 || l->type == 2) occ = occ && (t < lightDistance);
         shadow += occ ? 0.0f : 1.0f;
     }
+    c->untraced = 0;
     return shadow / (float)l->pcfSamples;
 }
 
 /* pcssShadow  :400-440 */
 static float pcssShadow(Ctx *c, v3 point, v3 normal, const Lgt *l, v3 lightDir, float lightDistance) {
-    int blockerCount = 0;
+    int blockerCount = 0, first = 16;
     float searchSize = l->lightSize * 0.1f;
     LIM_FOR(int i = 0, i < 16, i++) {
+        /* traced count: the blocker rays only feed `blockerCount == 0`, so the search may stop at the first blocker; a tracer
+         * that takes them blockerGroup per traversal traces a group whole if no blocker was found before its first ray */
+        if (i % c->blockerGroup == 0) c->untraced = !(c->lit && blockerCount == 0);
         float rr = halton(i, 3) * 2.0f - 1.0f;
         v3 sd = add3(add3(lightDir, splat3(rr * searchSize)), splat3(rr * searchSize));
         Ray sr;
@@ -548,7 +562,10 @@ static float pcssShadow(Ctx *c, v3 point, v3 normal, const Lgt *l, v3 lightDir, 
         int occ = intersectObjects(c, &sr, &tm, &tn, &t);
         if (l->type != 1) occ = occ && (t < lightDistance);
         if (occ) blockerCount++;
+        if (occ && first == 16) first = i;
     }
+    if (c->lit) c->firstBlocker[first]++;
+    c->untraced = 0;
     if (blockerCount == 0) return 1.0f;
     return pcfShadow(c, point, normal, l, lightDir, lightDistance);
 }
@@ -605,6 +622,15 @@ static v3 computeLighting(Ctx *c, v3 P, v3 N, const Mat *m, v3 V) {
             v3 ln = normalize3(l->direction);
             float lc = fmaxf(dot3(lightDir, ln), 0.0f);
             attenuation *= lc;
+        }
+        /* traced count: computePBR ends in `... * radiance * NdotL` (:251-252) and the shadow factor multiplies that (:500), so
+         * where NdotL is 0 or the radiance is +-0 or NaN in every channel the product is the same for every finite factor and
+         * the light's shadow rays cannot reach the pixel.  A PCF of zero samples is 0/0 (:396), not finite: no skip then. */
+        c->lit = 1;
+        if ((l->shadowType == 1 || l->shadowType == 2) && l->pcfSamples >= 1) {
+            v3 rad = scale3(scale3(l->color, attenuation), l->intensity);
+            int shines = (rad.x != 0.0f && rad.x == rad.x) || (rad.y != 0.0f && rad.y == rad.y) || (rad.z != 0.0f && rad.z == rad.z);
+            c->lit = shines && fmaxf(dot3(N, normalize3(lightDir)), 0.0f) > 0.0f;
         }
         float shadowFactor = calculateShadow(c, P, N, lightDir, lightDistance, l);
         v3 L = normalize3(lightDir);
@@ -717,6 +743,15 @@ static void shade_pixel(Ctx *c, float *color, float *pos, uint16_t *nrm) {
 int orc_render(const void *objects, int nObj, const void *lights, int nLt, const orc_params *p,
                const uint8_t *noise, int noiseW, int noiseH, const uint16_t *sky, int skySize,
                float *gColor, float *gPosition, uint16_t *gNormal, uint64_t *rayCount, int nthreads) {
+    return orc_render_traced(objects, nObj, lights, nLt, p, noise, noiseW, noiseH, sky, skySize, gColor, gPosition, gNormal, rayCount,
+                             nthreads, 1, NULL, NULL);
+}
+
+int orc_render_traced(const void *objects, int nObj, const void *lights, int nLt, const orc_params *p,
+                      const uint8_t *noise, int noiseW, int noiseH, const uint16_t *sky, int skySize,
+                      float *gColor, float *gPosition, uint16_t *gNormal, uint64_t *rayCount, int nthreads,
+                      int blockerGroup, uint64_t *tracedCount, uint64_t *firstBlocker) {
+    if (blockerGroup != 1 && blockerGroup != 2 && blockerGroup != 4 && blockerGroup != 8 && blockerGroup != 16) return -1;
     if (!p || nObj < 0 || nLt < 0 || p->regionW < 0 || p->regionH < 0) return -1;
     if (p->stripRows <= 0) return -1;
     if (p->stripCycleRows > 0) {
@@ -728,14 +763,14 @@ int orc_render(const void *objects, int nObj, const void *lights, int nLt, const
     Lgt *lts = malloc(sizeof(Lgt) * (size_t)(nLt > 0 ? nLt : 1));
     for (int i = 0; i < nObj; i++) decode_object((const uint8_t *)objects + (size_t)i * 176, &objs[i]);
     for (int i = 0; i < nLt; i++) decode_light((const uint8_t *)lights + (size_t)i * 96, &lts[i]);
-    uint64_t total = 0;
+    uint64_t total = 0, totalTraced = 0, hist[17] = {0};
     const int diag_pow = p->reserved0 & 1, diag_lim = (p->reserved0 >> 1) & 1, diag_sss = (p->reserved0 >> 2) & 1;      /* diagnostics (see pow5, loop_end) */
 #ifdef _OPENMP
     if (nthreads > 0) omp_set_num_threads(nthreads);
 #else
     (void)nthreads;
 #endif
-#pragma omp parallel for schedule(dynamic, 1) reduction(+ : total)
+#pragma omp parallel for schedule(dynamic, 1) reduction(+ : total, totalTraced)
     for (int j = 0; j < p->regionH; j++) {
         Ctx c;
         g_mesa_pow = diag_pow;
@@ -744,6 +779,8 @@ int orc_render(const void *objects, int nObj, const void *lights, int nLt, const
         c.objs = objs; c.nObj = nObj; c.lts = lts; c.nLt = nLt; c.p = p;
         c.noise = noise; c.noiseW = noiseW; c.noiseH = noiseH;
         c.sky = sky; c.skySize = skySize; c.rays = 0;
+        c.traced = 0; c.blockerGroup = blockerGroup; c.lit = 1; c.untraced = 0;
+        memset(c.firstBlocker, 0, sizeof c.firstBlocker);
         int ly = p->y0 + j;
         int gy = (ly / p->stripRows) * cycleRows + offsetRows + ly % p->stripRows;
         for (int i = 0; i < p->regionW; i++) {
@@ -757,8 +794,13 @@ int orc_render(const void *objects, int nObj, const void *lights, int nLt, const
             shade_pixel(&c, gColor + o, gPosition + o, gNormal + o);
         }
         total += c.rays;
+        totalTraced += c.traced;
+#pragma omp critical
+        for (int k = 0; k < 17; k++) hist[k] += c.firstBlocker[k];
     }
     if (rayCount) *rayCount = total;
+    if (tracedCount) *tracedCount = totalTraced;
+    if (firstBlocker) memcpy(firstBlocker, hist, sizeof hist);
     free(objs); free(lts);
     return 0;
 }

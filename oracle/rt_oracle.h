@@ -56,6 +56,21 @@ int orc_render(const void *objects, int nObj, const void *lights, int nLt,
                const uint16_t *sky, int skySize, float *gColor, float *gPosition,
                uint16_t *gNormal, uint64_t *rayCount, int nthreads);
 
+/* The same render, which also counts the rays a SKIP-EXACT tracer traverses (tracedCount, optional): primary, bounce and
+ * subsurface rays always; per hit point and light with shadowType 1 or 2, with
+ *   lit = pcfSamples < 1, or max(dot(N, normalize(lightDir)), 0) > 0 and some channel of (color * attenuation) * intensity
+ *         is neither +-0 nor NaN,
+ * no shadow ray where lit is false; where it is true the PCF rays the reference traces, and pcssShadow's 16 blocker rays in
+ * groups of blockerGroup (1, 2, 4, 8 or 16; anything else is refused): a group is traced whole if no blocker was found before
+ * its first ray, and none after that.  tracedCount <= rayCount, and it grows with blockerGroup.
+ * firstBlocker (optional, 17 entries): how the blocker searches of lit points end -- [i] = searches whose first blocker is ray i,
+ * [16] = searches that find none. */
+int orc_render_traced(const void *objects, int nObj, const void *lights, int nLt,
+                      const orc_params *p, const uint8_t *noise, int noiseW, int noiseH,
+                      const uint16_t *sky, int skySize, float *gColor, float *gPosition,
+                      uint16_t *gNormal, uint64_t *rayCount, int nthreads, int blockerGroup, uint64_t *tracedCount,
+                      uint64_t *firstBlocker);
+
 /* GenerateAABBForObject (/root/reference/src/SceneIO.h:75-104) applied in place to
  * n 176-byte Object records. */
 void orc_generate_aabb(void *objects, int n);
