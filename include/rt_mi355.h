@@ -423,6 +423,45 @@ int rt_accel_build_host(const void *objects, int nObj, const rt_accel_desc *desc
 int rt_accel_validate_host(const void *objects, int nObj, int leafSize, const rt_accel_node *nodes, size_t nNodes, const uint32_t *order,
                            size_t nOrder, const uint32_t *loose, size_t nLoose);
 
+/* ---- who builds the hierarchy.  RT_ACCEL_BUILD_HOST (default): one host thread, median splits, the check
+ *      above before the upload -- everything as described so far.  RT_ACCEL_BUILD_DEVICE: HIP kernels on the context's stream build
+ *      the SAME structure (rt_accel_node in pre-order with skip links, order[], loose[]) over another topology, a linear BVH:
+ *      the host only classifies (loose[] is the host builder's, for the same bytes and desc), the device sorts the tree's objects
+ *      by (30-bit Morton code of the box centre, object index), cuts the sequence into leaves of leafSize (within a leaf ascending
+ *      object index), and builds the binary radix tree over the leaves' keys; every box is the exact union of the stored boxes
+ *      below, as before.  The hierarchy only culls, so queries and shading answer the same bits through either tree; the Morton
+ *      tree is coarser (slower to walk) and far cheaper to build from a few thousand objects up -- for scenes that change every
+ *      frame.  A device-built structure is not run through the host check; what keeps the walks inside their arrays whatever the
+ *      device wrote is stated in DESIGN.md section 36.
+ *
+ *   rt_set_accel_builder: sticky, independent of rt_set_accel and of the order of the two calls.  A change while rt_set_accel is on
+ *      and a scene is loaded rebuilds at once (ordered like rt_set_accel's own rebuild); the same value again does nothing.
+ *      RT_ERR_INVALID_ARG: a NULL context, an unknown value.  A HIP failure during a device build is RT_ERR_HIP, and the queries
+ *      are served by brute force until the next build.
+ *   rt_accel_build_info: builder (of the structure that stands; 0 while none does), buildsHost / buildsDevice (since rt_create;
+ *      their sum is rt_accel_info's builds), hostMs (the last build's host time inside the call: the host build and its check, or
+ *      the classification and the enqueue of the device build), deviceMs (the last device build between the two events around it;
+ *      0 after a host build; the first request after a build waits for it).
+ *   rt_accel_info after a device build: nodes, leaves, loose, bytes and builds are known at once; depth is fetched from the device
+ *      on the first request, which waits for the build; buildMs is hostMs.
+ *   rt_accel_read: the structure that stands on the device, from either builder, copied to the host; it waits for the context's
+ *      stream.  info: rt_accel_info's.  nodes / order / loose all NULL: only info (nodes, loose and nObj - loose give the sizes).
+ *      Else the arrays are written; RT_ERR_TOO_LARGE when a capacity (in elements) is too small.  While nothing is built info is
+ *      all zeros and nothing is written. */
+typedef enum rt_accel_builder { RT_ACCEL_BUILD_HOST = 0, RT_ACCEL_BUILD_DEVICE = 1 } rt_accel_builder;
+int rt_set_accel_builder(rt_context *ctx, int builder);
+typedef struct rt_accel_build_report {
+    int32_t builder;        /* of the structure that stands; 0 while none is built */
+    int32_t reserved0;
+    uint64_t buildsHost, buildsDevice;
+    double hostMs;          /* last build: host time inside the call (classification + enqueue, or the host build) */
+    double deviceMs;        /* last device build between its two events; 0 for a host build; the call waits for it */
+    uint64_t reserved[3];
+} rt_accel_build_report;             /* 64 B */
+int rt_accel_build_info(rt_context *ctx, rt_accel_build_report *info);
+int rt_accel_read(rt_context *ctx, rt_accel_node *nodes, size_t capNodes, uint32_t *order, size_t capOrder,
+                  uint32_t *loose, size_t capLoose, rt_accel_report *info);
+
 /* ---- the same hierarchy behind rt_shade_rays.  Off by default, also while rt_set_accel is on: rt_shade_rays
  *      then launches the brute-force kernel, which tests every object for every closest-hit, shadow, PCSS-blocker and subsurface
  *      ray.  Switched on, those four kinds of ray walk the tree rt_set_accel built (this switch builds nothing; the two switches
@@ -1343,6 +1382,9 @@ RT_SA(sizeof(rt_accel_node) == 32 && offsetof(rt_accel_node, skip) == 12 && offs
 RT_SA(sizeof(rt_accel_report) == 96 && offsetof(rt_accel_report, bytes) == 24 && offsetof(rt_accel_report, buildMs) == 32 &&
       offsetof(rt_accel_report, builds) == 40 && offsetof(rt_accel_report, launchesAccel) == 48 && offsetof(rt_accel_report, launchesBrute) == 64,
       "rt_accel_report is 96 B");
+RT_SA(sizeof(rt_accel_build_report) == 64 && offsetof(rt_accel_build_report, buildsHost) == 8 && offsetof(rt_accel_build_report, buildsDevice) == 16 &&
+      offsetof(rt_accel_build_report, hostMs) == 24 && offsetof(rt_accel_build_report, deviceMs) == 32 &&
+      offsetof(rt_accel_build_report, reserved) == 40, "rt_accel_build_report is 64 B");
 RT_SA(sizeof(rt_accel_shade_desc) == 32 && offsetof(rt_accel_shade_desc, traversal) == 4 && offsetof(rt_accel_shade_desc, minObjects) == 8 &&
       offsetof(rt_accel_shade_desc, reserved) == 12, "rt_accel_shade_desc is 32 B");
 RT_SA(sizeof(rt_accel_shade_report) == 48 && offsetof(rt_accel_shade_report, traversal) == 4 && offsetof(rt_accel_shade_report, launchesAccel) == 8 &&

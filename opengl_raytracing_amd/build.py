@@ -17,7 +17,8 @@ ORACLE_LIB = os.path.join(ORACLE_DIR, "liboracle_rt.so")
 
 SOURCES = ["rt_kernels.hip", "rt_post.hip", "rt_display.hip", "rt_abi.cpp", "rt_display.cpp", "rt_present.cpp", "rt_resample.hip", "rt_resample.cpp", "rt_sched.cpp", "rt_host.cpp",
            "rt_mgpu.cpp", "rt_accum.hip", "rt_accum.cpp", "rt_denoise.hip", "rt_denoise.cpp", "rt_reproject.hip",
-           "rt_reproject.cpp", "rt_adaptive.hip", "rt_adaptive.cpp", "rt_upsample.hip", "rt_upsample.cpp", "rt_jpeg.hip", "rt_jpeg.cpp", "rt_post.cpp", "rt_wire.cpp", "rt_accel.cpp"]
+           "rt_reproject.cpp", "rt_adaptive.hip", "rt_adaptive.cpp", "rt_upsample.hip", "rt_upsample.cpp", "rt_jpeg.hip", "rt_jpeg.cpp", "rt_post.cpp", "rt_wire.cpp", "rt_accel.cpp",
+           "rt_accel_build.hip"]
 # every header and include file of csrc/ plus the public header: nothing to keep by hand, so no stale build from a forgotten one
 HEADERS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".inc"))) + [os.path.join(REPO, "include", "rt_mi355.h")]
 

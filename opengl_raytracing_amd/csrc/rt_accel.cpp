@@ -1,5 +1,6 @@
 // rt_accel.cpp -- the host side of the threaded hierarchy (rt_accel.h): the build, the check, and the entry points
-// rt_set_accel / rt_accel_info / rt_accel_build_host of include/rt_mi355.h.  The kernels are rt_accel.inc's.
+// rt_set_accel / rt_accel_info / rt_accel_build_host of include/rt_mi355.h.  The kernels are rt_accel.inc's.  Also the host side
+// of the device builder (rt_set_accel_builder / rt_accel_build_info / rt_accel_read; rt_accel_build.h has its kernels' interface).
 #include "rt_accel.h"
 
 #include <math.h>
@@ -9,7 +10,10 @@
 #include <chrono>
 #include <new>
 
+#include "rt_accel_build.h"
 #include "rt_context.h"
+
+static_assert(RT_AB_MAX_LEAF == RT_ACCEL_MAX_LEAF, "the device builder sorts a leaf in RT_ACCEL_MAX_LEAF registers");
 
 namespace {
 
@@ -119,10 +123,16 @@ bool rt_accel_resolve_desc(const rt_accel_desc *desc, rt_accel_desc *out, const 
     return true;
 }
 
-void rt_accel_build(const void *objects, int nObj, const rt_accel_desc &desc, RtAccelBuild *out) {
-    out->clear();
-    if (nObj <= 0) return;
-    std::vector<Box> box((size_t)nObj);
+namespace {
+
+// The linear pass both builders start with: every object's ordered stored box, and who goes where.  LOOSE: no finite box, or
+// "large" -- on some axis the box spans more than largeFraction of the whole scene's extent (the floor and the walls of a room:
+// most rays pass their box test anyway, and in a tree they would stretch every ancestor).  Both lists come out ascending.
+// centres (may be null): the per-axis minimum [0..2] and maximum [3..5] of the tree objects' box centres, in double.
+void classify(const void *objects, int nObj, const rt_accel_desc &desc, std::vector<Box> *boxes, std::vector<uint32_t> *tree,
+              std::vector<uint32_t> *loose, double *centres) {
+    std::vector<Box> &box = *boxes;
+    box.resize((size_t)nObj);
     std::vector<uint8_t> finite((size_t)nObj);
     // the union of every finite box, in double: a difference of two floats cannot overflow there
     double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
@@ -134,14 +144,32 @@ void rt_accel_build(const void *objects, int nObj, const rt_accel_desc &desc, Rt
             if (box[i].hi[a] > hi[a]) hi[a] = box[i].hi[a];
         }
     }
-    // LOOSE: no finite box, or "large" -- on some axis the box spans more than largeFraction of the whole scene's extent (the
-    // floor and the walls of a room: most rays pass their box test anyway, and in a tree they would stretch every ancestor)
+    if (centres)
+        for (int a = 0; a < 3; a++) {
+            centres[a] = INFINITY;
+            centres[3 + a] = -INFINITY;
+        }
     for (int i = 0; i < nObj; i++) {
         bool large = !finite[i];
         for (int a = 0; a < 3 && !large; a++)
             large = (double)box[i].hi[a] - (double)box[i].lo[a] > (double)desc.largeFraction * (hi[a] - lo[a]);
-        (large ? out->loose : out->order).push_back((uint32_t)i);
+        (large ? loose : tree)->push_back((uint32_t)i);
+        if (large || !centres) continue;
+        for (int a = 0; a < 3; a++) {
+            const double c = 0.5 * ((double)box[i].lo[a] + (double)box[i].hi[a]);
+            if (c < centres[a]) centres[a] = c;
+            if (c > centres[3 + a]) centres[3 + a] = c;
+        }
     }
+}
+
+}  // namespace
+
+void rt_accel_build(const void *objects, int nObj, const rt_accel_desc &desc, RtAccelBuild *out) {
+    out->clear();
+    if (nObj <= 0) return;
+    std::vector<Box> box;
+    classify(objects, nObj, desc, &box, &out->order, &out->loose, nullptr);
     if (out->order.empty()) return;
     out->nodes.reserve(2 * out->order.size());
     Builder b{box, out->order, out->nodes, desc.leafSize};
@@ -238,6 +266,90 @@ void fill_report(const RtAccelBuild &b, double ms, rt_accel_report *r) {
     r->buildMs = ms;
 }
 
+// RT_ACCEL_BUILD_DEVICE (rt_accel_build.h): the host classifies, uploads the two index lists and enqueues
+// the kernels, all on the context's stream, where the host builder's upload would run.  dObjects holds this scene's records: the
+// caller's upload of them is ahead on the same stream.  Every size is known here, so RtAccelDev and the report are filled at once;
+// only the depth comes back from the device (rt_accel_info).  A HIP failure leaves `built` false.
+int accel_build_device(rt_context *c, const void *objects, int nObj) {
+    RtAccelState &A = c->accel;
+    rt_accel_report &r = A.report;
+    const auto t0 = std::chrono::steady_clock::now();
+    auto elapsed = [&] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); };
+    std::vector<uint32_t> tree, loose;
+    double centres[6];
+    bool ok = true;
+    try {
+        std::vector<Box> box;
+        classify(objects, nObj, A.desc, &box, &tree, &loose, centres);
+    } catch (const std::bad_alloc &) {
+        ok = false;
+    }
+    r.builds++;
+    A.buildsDevice++;
+    A.deviceMs = 0.0;
+    A.deviceMsPending = A.depthPending = false;
+    if (!ok || tree.empty()) {                 // nothing for a tree: brute force serves, as with the host builder
+        r.buildMs = A.hostMs = elapsed();
+        return RT_OK;
+    }
+    RtAccelBuildParams P;
+    for (int a = 0; a < 3; a++) {
+        P.cmin[a] = centres[a];
+        P.scale[a] = centres[3 + a] > centres[a] ? 1024.0 / (centres[3 + a] - centres[a]) : 0.0;
+    }
+    P.nObj = nObj;
+    P.nTree = (int)tree.size();
+    P.leafSize = A.desc.leafSize;
+    P.nLeaves = (P.nTree + P.leafSize - 1) / P.leafSize;
+    P.nNodes = 2 * P.nLeaves - 1;
+    const size_t nodeBytes = (size_t)P.nNodes * sizeof(rt_accel_node), orderBytes = tree.size() * sizeof(uint32_t),
+                 looseBytes = loose.size() * sizeof(uint32_t), bytes = nodeBytes + orderBytes + looseBytes;
+    const size_t scratchBytes = RtAccelBuildScratch::carve(nullptr, P.nTree, P.leafSize, nullptr);
+    if (!A.dBuf.holds(bytes) || !A.dBuildScratch.holds(scratchBytes)) {
+        SCHED_TRY(c, drain());                 // queries on any stream may still read the structure about to be freed, a build the scratch
+        HIP_TRY(c, A.dBuf.grow(bytes));
+        HIP_TRY(c, A.dBuildScratch.grow(scratchBytes));
+    }
+    RtAccelBuildScratch S;
+    RtAccelBuildScratch::carve(A.dBuildScratch, P.nTree, P.leafSize, &S);
+    uint8_t *dOrder = A.dBuf.ptr + nodeBytes, *dLoose = dOrder + orderBytes;
+    HIP_TRY(c, A.evBuild[0].create(hipEventDefault));
+    HIP_TRY(c, A.evBuild[1].create(hipEventDefault));
+    HIP_TRY(c, A.evDepth.create(hipEventDisableTiming));
+    HIP_TRY(c, A.hDepth.grow(1));
+    const int k = (int)(A.stageSeq++ & 1u);
+    if (A.stageUsed[k]) HIP_TRY(c, hipEventSynchronize(A.evStage[k]));      // the copy out of this staging buffer two uploads ago
+    HIP_TRY(c, A.hStage[k].grow(orderBytes + looseBytes));
+    memcpy(A.hStage[k], tree.data(), orderBytes);
+    if (looseBytes) memcpy(A.hStage[k] + orderBytes, loose.data(), looseBytes);
+    HIP_TRY(c, hipEventRecord(A.evBuild[0], c->stream));
+    HIP_TRY(c, hipMemcpyAsync(S.vals[0], A.hStage[k], orderBytes, hipMemcpyHostToDevice, c->stream));
+    if (looseBytes) HIP_TRY(c, hipMemcpyAsync(dLoose, A.hStage[k] + orderBytes, looseBytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, A.evStage[k].create(hipEventDisableTiming));
+    HIP_TRY(c, hipEventRecord(A.evStage[k], c->stream));
+    A.stageUsed[k] = true;
+    HIP_TRY(c, rt_launch_accel_build(c->dObjects, P, S, (float4 *)A.dBuf.ptr, (uint32_t *)dOrder, c->stream));
+    HIP_TRY(c, hipEventRecord(A.evBuild[1], c->stream));
+    HIP_TRY(c, hipMemcpyAsync(A.hDepth, S.depth, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipEventRecord(A.evDepth, c->stream));
+    A.deviceMsPending = A.depthPending = true;
+    A.dev.nodes = (const float4 *)A.dBuf.ptr;
+    A.dev.order = (const unsigned *)dOrder;
+    A.dev.loose = (const unsigned *)dLoose;
+    A.dev.nNodes = P.nNodes;
+    A.dev.nLoose = (int)loose.size();
+    A.nOrder = P.nTree;
+    A.builtBy = RT_ACCEL_BUILD_DEVICE;
+    r.nodes = P.nNodes;
+    r.leaves = P.nLeaves;
+    r.loose = (int32_t)loose.size();
+    r.bytes = bytes;
+    r.buildMs = A.hostMs = elapsed();
+    A.built = true;
+    r.built = 1;
+    return RT_OK;
+}
+
 // The context's structure for the scene `objects` (the bytes rt_set_scene was given), uploaded on the context's stream.  The
 // caller has ordered that stream behind every launch that may still read the old structure (waitForLaunches) and records
 // evScene behind this.  A scene the tree is not for -- too small, nothing but loose objects -- and a structure that cannot be
@@ -249,12 +361,17 @@ int accel_upload(rt_context *c, const void *objects, int nObj) {
     r.built = r.nodes = r.leaves = r.depth = r.loose = 0;
     r.bytes = 0;
     if (!A.on || nObj < A.desc.minObjects || nObj <= 0) return RT_OK;
+    if (A.builder == RT_ACCEL_BUILD_DEVICE) return accel_build_device(c, objects, nObj);
     RtAccelBuild b;
     double ms = 0.0;
     const char *why = nullptr;
     const bool ok = build_checked(objects, nObj, A.desc, &b, &ms, &why);
     r.builds++;
     r.buildMs = ms;
+    A.buildsHost++;
+    A.hostMs = ms;
+    A.deviceMs = 0.0;
+    A.deviceMsPending = A.depthPending = false;
     if (!ok || b.nodes.empty()) return RT_OK;
     fill_report(b, ms, &r);
     const size_t nodeBytes = b.nodes.size() * sizeof(rt_accel_node), orderBytes = b.order.size() * sizeof(uint32_t),
@@ -278,8 +395,22 @@ int accel_upload(rt_context *c, const void *objects, int nObj) {
     A.dev.loose = (const unsigned *)(A.dBuf.ptr + nodeBytes + orderBytes);
     A.dev.nNodes = (int)b.nodes.size();
     A.dev.nLoose = (int)b.loose.size();
+    A.nOrder = (int)b.order.size();
+    A.builtBy = RT_ACCEL_BUILD_HOST;
     A.built = true;
     r.built = 1;
+    return RT_OK;
+}
+
+// rt_set_accel / rt_set_accel_builder with a scene loaded: the structure of the current scene under the new settings, at once
+int rebuild_now(rt_context *c) {
+    const size_t objBytes = (size_t)c->nObj * RT_OBJECT_STRIDE;
+    if (!c->dCompiled || c->lastScene.size() < objBytes) return RT_OK;      // no scene (bytes) yet: built by the next rt_set_scene that changes them
+    HIP_TRY(c, hipSetDevice(c->device));
+    SCHED_TRY(c, waitForLaunches(c->stream));
+    const int rc = accel_upload(c, c->lastScene.data(), c->nObj);
+    if (rc) return rc;
+    HIP_TRY(c, hipEventRecord(c->evScene, c->stream));      // foreign streams order behind the upload (caller_stream)
     return RT_OK;
 }
 
@@ -306,19 +437,67 @@ int rt_set_accel(rt_context *c, const rt_accel_desc *desc) {
         A.report.bytes = 0;
         return RT_OK;
     }
-    const size_t objBytes = (size_t)c->nObj * RT_OBJECT_STRIDE;
-    if (!c->dCompiled || c->lastScene.size() < objBytes) return RT_OK;      // no scene (bytes) yet: built by the next rt_set_scene that changes them
-    HIP_TRY(c, hipSetDevice(c->device));
-    SCHED_TRY(c, waitForLaunches(c->stream));
-    const int rc = accel_upload(c, c->lastScene.data(), c->nObj);
-    if (rc) return rc;
-    HIP_TRY(c, hipEventRecord(c->evScene, c->stream));      // foreign streams order behind the upload (caller_stream)
-    return RT_OK;
+    return rebuild_now(c);
 }
 
 int rt_accel_info(rt_context *c, rt_accel_report *out) {
     if (!c || !out) return RT_ERR_INVALID_ARG;
-    *out = c->accel.report;
+    RtAccelState &A = c->accel;
+    if (A.built && A.depthPending) {           // a device build: the depth is the one word only the device knows
+        HIP_TRY(c, hipSetDevice(c->device));
+        HIP_TRY(c, hipEventSynchronize(A.evDepth));
+        A.report.depth = (int32_t)A.hDepth[0];
+        A.depthPending = false;
+    }
+    *out = A.report;
+    return RT_OK;
+}
+
+int rt_set_accel_builder(rt_context *c, int builder) {
+    if (!c) return RT_ERR_INVALID_ARG;
+    if (builder != RT_ACCEL_BUILD_HOST && builder != RT_ACCEL_BUILD_DEVICE) return fail(c, RT_ERR_INVALID_ARG, "rt_set_accel_builder: unknown builder");
+    RtAccelState &A = c->accel;
+    if (builder == A.builder) return RT_OK;
+    A.builder = builder;
+    return A.on ? rebuild_now(c) : RT_OK;
+}
+
+int rt_accel_build_info(rt_context *c, rt_accel_build_report *out) {
+    if (!c || !out) return RT_ERR_INVALID_ARG;
+    RtAccelState &A = c->accel;
+    if (A.deviceMsPending) {
+        float ms = 0.0f;
+        HIP_TRY(c, hipSetDevice(c->device));
+        HIP_TRY(c, hipEventSynchronize(A.evBuild[1]));
+        HIP_TRY(c, hipEventElapsedTime(&ms, A.evBuild[0], A.evBuild[1]));
+        A.deviceMs = ms;
+        A.deviceMsPending = false;
+    }
+    memset(out, 0, sizeof *out);
+    out->builder = A.built ? A.builtBy : 0;
+    out->buildsHost = A.buildsHost;
+    out->buildsDevice = A.buildsDevice;
+    out->hostMs = A.hostMs;
+    out->deviceMs = A.deviceMs;
+    return RT_OK;
+}
+
+int rt_accel_read(rt_context *c, rt_accel_node *nodes, size_t capNodes, uint32_t *order, size_t capOrder, uint32_t *loose, size_t capLoose,
+                  rt_accel_report *info) {
+    if (!c || !info) return RT_ERR_INVALID_ARG;
+    RtAccelState &A = c->accel;
+    memset(info, 0, sizeof *info);
+    if (!A.built) return RT_OK;
+    RT_TRY(rt_accel_info(c, info));
+    const size_t nNodes = (size_t)A.dev.nNodes, nOrder = (size_t)A.nOrder, nLoose = (size_t)A.dev.nLoose;
+    if (!nodes && !order && !loose) return RT_OK;      // the sizes only
+    if (capNodes < nNodes || capOrder < nOrder || capLoose < nLoose) return fail(c, RT_ERR_TOO_LARGE, "rt_accel_read: a capacity is too small");
+    if ((nNodes && !nodes) || (nOrder && !order) || (nLoose && !loose)) return fail(c, RT_ERR_INVALID_ARG, "rt_accel_read: a NULL array");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));       // the upload, or the build
+    if (nNodes) HIP_TRY(c, hipMemcpy(nodes, A.dev.nodes, nNodes * sizeof(rt_accel_node), hipMemcpyDeviceToHost));
+    if (nOrder) HIP_TRY(c, hipMemcpy(order, A.dev.order, nOrder * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (nLoose) HIP_TRY(c, hipMemcpy(loose, A.dev.loose, nLoose * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return RT_OK;
 }
 

@@ -1,6 +1,7 @@
 // rt_accel.h -- the threaded bounding-volume hierarchy behind rt_trace_rays / rt_pick (rt_set_accel; include/rt_mi355.h;
 // DESIGN.md section 32): the structure, its host build and the check every structure passes before it is uploaded.  Plain
-// C++, no HIP: rt_accel_build_host runs the same code with no GPU.  The traversal kernels are rt_accel.inc's.
+// C++, no HIP: rt_accel_build_host runs the same code with no GPU.  The traversal kernels are rt_accel.inc's.  A second builder
+// of the same structure, on the device and without the check, is rt_accel_build.h's (rt_set_accel_builder).
 //
 // The hierarchy only CULLS: a node may be skipped iff every object below it fails its own stored-box test (aabb_test).  So a
 // node's box is the exact union of its objects' stored boxes (min / max of floats do not round; an inverted stored box counts

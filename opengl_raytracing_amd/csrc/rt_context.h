@@ -24,6 +24,15 @@ struct RtAccelState {
     bool stageUsed[2] = {false, false};
     unsigned stageSeq = 0;
     rt_accel_report report = {};
+    int nOrder = 0;                            // entries of the standing structure's order[] (rt_accel_read)
+    // rt_set_accel_builder: who builds, who built what stands, and the device builder's own state
+    int builder = RT_ACCEL_BUILD_HOST, builtBy = RT_ACCEL_BUILD_HOST;
+    uint64_t buildsHost = 0, buildsDevice = 0;
+    double hostMs = 0.0, deviceMs = 0.0;
+    DevBuf<uint8_t> dBuildScratch;             // RtAccelBuildScratch's parts: sort ping-pong, histograms, leaf boxes and keys, ranges, parents
+    DevEvent evBuild[2], evDepth;              // around the last device build; behind the copy of its depth word
+    PinnedBuf<uint32_t> hDepth;
+    bool deviceMsPending = false, depthPending = false;      // fetched on first request (rt_accel_build_info, rt_accel_info)
 };
 
 // rt_set_accel_shading's state (rt_accel.cpp): whether rt_shade_rays walks rt_set_accel's tree, by which traversal and from how

@@ -115,8 +115,9 @@ hipError_t rt_launch_camera_rays_at(const RtFrame &f, const uint8_t *dNoise, con
 hipError_t rt_launch_pick(const RtFrame &f, const uint8_t *dNoise, const float4 *dCompiled, int px, int py, float4 *dOut,
                           hipStream_t s);
 // The same queries through the threaded hierarchy (rt_accel.inc; rt_accel.h has the structure): nodes = 2 float4 per node
-// (lo, skip) (hi, leaf), order / loose = object indices.  lane: the per-ray traversal, else the per-wavefront one.  The host has
-// checked the structure (rt_accel_validate); the kernels' loops are bounded by nNodes whatever it holds.
+// (lo, skip) (hi, leaf), order / loose = object indices.  lane: the per-ray traversal, else the per-wavefront one.  The host
+// builder's structure has passed rt_accel_validate; the device builder's (rt_accel_build.h) is bounded by construction; the
+// kernels' loops are bounded by nNodes whatever it holds.
 struct RtAccelDev {
     const float4 *nodes = nullptr;
     const unsigned *order = nullptr, *loose = nullptr;

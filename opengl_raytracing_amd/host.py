@@ -97,6 +97,9 @@ def _signatures():
         "rt_accel_info": (ci, [vp, P(L.RtAccelReport)]),
         "rt_accel_build_host": (ci, [vp, ci, P(L.RtAccelDesc), vp, sz, vp, sz, vp, sz, P(L.RtAccelReport)]),
         "rt_accel_validate_host": (ci, [vp, ci, ci, vp, sz, vp, sz, vp, sz]),
+        "rt_set_accel_builder": (ci, [vp, ci]),
+        "rt_accel_build_info": (ci, [vp, P(L.RtAccelBuildReport)]),
+        "rt_accel_read": (ci, [vp, vp, sz, vp, sz, vp, sz, P(L.RtAccelReport)]),
         "rt_set_accel_shading": (ci, [vp, P(L.RtAccelShadeDesc)]),
         "rt_accel_shading_info": (ci, [vp, P(L.RtAccelShadeReport)]),
         "rt_shade_rays": (ci, [vp, params, vp, vp, sz, vp, vp, vp, vp]),
@@ -850,6 +853,33 @@ class RayTracer(_Handle):
         r = L.RtAccelReport()
         self._call("rt_accel_info", ctypes.byref(r))
         return _accel_report(r)
+
+    def set_accel_builder(self, builder="host"):
+        """Who builds set_accel's hierarchy (rt_set_accel_builder; sticky, "host" by default): "host", one host thread and median
+        splits; "device", HIP kernels on the context's stream and a Morton-code tree -- the same answers from every query, a
+        build that no longer grows on the CPU.  A change while the feature is on and a scene is loaded rebuilds at once."""
+        self._call("rt_set_accel_builder", int(L.ACCEL_BUILDERS.get(builder, builder)))
+
+    def accel_build_info(self):
+        """rt_accel_build_info as a dict: builder (of the structure that stands: "host" / "device", None while none does),
+        builds_host, builds_device, host_ms and device_ms of the last build (device_ms waits for it; 0 after a host build)."""
+        r = L.RtAccelBuildReport()
+        self._call("rt_accel_build_info", ctypes.byref(r))
+        built = self.accel_info()["built"]
+        return dict(builder=("host", "device")[r.builder] if built else None, builds_host=r.buildsHost, builds_device=r.buildsDevice,
+                    host_ms=r.hostMs, device_ms=r.deviceMs)
+
+    def accel_read(self):
+        """The structure that stands on the device, from either builder, read back (rt_accel_read; waits for the context's stream)
+        -> AccelStructure, as accel_build_host answers; empty arrays while nothing is built."""
+        info = L.RtAccelReport()
+        self._call("rt_accel_read", None, 0, None, 0, None, 0, ctypes.byref(info))
+        n_order = (info.bytes - 32 * info.nodes) // 4 - info.loose          # bytes: 32 per node, 4 per object
+        nodes = np.zeros(info.nodes, dtype=L.ACCEL_NODE_DTYPE)
+        order, loose = np.zeros(n_order, dtype=np.uint32), np.zeros(info.loose, dtype=np.uint32)
+        if info.built:
+            self._call("rt_accel_read", _ptr(nodes), len(nodes), _ptr(order), len(order), _ptr(loose), len(loose), ctypes.byref(info))
+        return AccelStructure(nodes, order, loose, _accel_report(info))
 
     def set_accel_shading(self, enable=True, traversal="auto", min_objects=0):
         """Let shade_rays walk the hierarchy set_accel built (rt_set_accel_shading; sticky, off by default, independent of

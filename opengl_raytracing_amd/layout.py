@@ -232,6 +232,20 @@ def make_accel_desc(enable=True, leaf_size=0, traversal="auto", min_objects=0, l
     return d
 
 
+# ---- who builds it (rt_set_accel_builder / rt_accel_build_info) ----
+ACCEL_BUILD_HOST, ACCEL_BUILD_DEVICE = 0, 1
+ACCEL_BUILDERS = {"host": ACCEL_BUILD_HOST, "device": ACCEL_BUILD_DEVICE}
+
+
+class RtAccelBuildReport(ctypes.Structure):
+    """``rt_accel_build_report``: what rt_accel_build_info answers."""
+    _fields_ = [("builder", ctypes.c_int32), ("reserved0", ctypes.c_int32), ("buildsHost", ctypes.c_uint64), ("buildsDevice", ctypes.c_uint64),
+                ("hostMs", ctypes.c_double), ("deviceMs", ctypes.c_double), ("reserved", ctypes.c_uint64 * 3)]
+
+
+assert ctypes.sizeof(RtAccelBuildReport) == 64
+
+
 class RtAccelShadeDesc(ctypes.Structure):
     """``rt_accel_shade_desc``: zero = the default of every field."""
     _fields_ = [("enable", ctypes.c_int32), ("traversal", ctypes.c_int32), ("minObjects", ctypes.c_int32), ("reserved", ctypes.c_int32 * 5)]
