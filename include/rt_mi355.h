@@ -370,7 +370,7 @@ int rt_pick(rt_context *ctx, const rt_params *p, int px, int py, rt_hit *hit);
  *      bit, for every ray and every scene: the hierarchy only skips objects whose own stored-box test (the AABB cull above) would
  *      fail, never anything "behind the current hit", so the set of objects that count does not change, and among equal t the
  *      lower object index wins whatever the visiting order.  By default rt_shade_rays does not use it (rt_set_accel_shading
- *      below switches that on); the renders never do.
+ *      below switches that on), and neither do the renders (rt_set_accel_render, further below, switches that on).
  *
  *   Structure.  A binary tree, median split on the box centres, stored in depth-first pre-order: the first child of inner node k is
  *      node k + 1, and `skip` is the index of the first node behind k's subtree (the node count behind the last one), so a walk
@@ -493,6 +493,50 @@ typedef struct rt_accel_shade_report {
 } rt_accel_shade_report;             /* 48 B */
 int rt_set_accel_shading(rt_context *ctx, const rt_accel_shade_desc *desc);
 int rt_accel_shading_info(rt_context *ctx, rt_accel_shade_report *info);
+
+/* ---- the same hierarchy behind the frames: rt_render, rt_render_to, rt_render_into_image, and rt_frame through rt_render
+ *      (DESIGN.md section 37).  Off by default, also while the two switches above are on: a frame then runs the packet kernel,
+ *      which has shadow tables up to 256 objects and 64 lights and above that tests every object for every closest-hit, shadow,
+ *      blocker and subsurface ray.  Switched on, a frame of a scene whose tree stands is rendered by a kernel of its own -- one
+ *      wavefront per 8x8 pixel tile, the per-lane path tracer rt_shade_rays runs, camera ray and noise sample taken from the
+ *      frame -- whose four kinds of ray walk the tree.  It writes the same three surfaces in the same formats and layouts (window,
+ *      local rows, both strip rules, rt_render_into_image's stores, all-zero records for window pixels outside the image), and
+ *      every value is the packet kernel's bit for bit, by the two arguments above.  This switch builds nothing: it uses the tree
+ *      rt_set_accel built, from either builder, and is independent of the other three switches and of the order of the calls.
+ *
+ *   rt_accel_render_desc: zero = the default of every field.  enable: 0 switches the feature off.  traversal:
+ *      RT_ACCEL_RENDER_LANE walks once per ray and RT_ACCEL_RENDER_WAVE once per wavefront, as in rt_shade_rays;
+ *      RT_ACCEL_RENDER_SPLIT takes the depth-0 closest hit -- the 64 coherent primary rays of a tile -- by one per-wavefront walk
+ *      and every later ray by the per-ray walks; RT_ACCEL_RENDER_AUTO (default) is the per-ray form: measured from 1025 objects
+ *      up, LANE and SPLIT lie within each other's spread on every scene and both are 1.2-2.2x faster than WAVE (section 37).
+ *      rt_accel_traversal keeps its three values: rt_set_accel and rt_set_accel_shading refuse 3.  minObjects: scenes with
+ *      fewer objects keep the packet kernel (0 = RT_ACCEL_RENDER_DEFAULT_MIN_OBJECTS, the smallest measured scene from which
+ *      AUTO beat the packet kernel beyond both spreads: 3.4x there, 5.7x at 16386 objects; at 1026 the two were level, at 258
+ *      and below the packet kernel, which has shadow tables up to 256 objects, is 1.6-9.5x faster); rt_set_accel has a minObjects
+ *      of its own (default 1024) below which there is no tree.
+ *   rt_set_accel_render: sticky for the context; NULL or enable == 0 switches it off.  RT_ERR_INVALID_ARG: a NULL context, an
+ *      unknown traversal, a non-zero reserved word, a negative minObjects.
+ *   Which frames take it: those for which `active` holds, except the exhaustive cross-check kernel (rt_set_variant's variant 0)
+ *      and every instrumented launch (rt_count_rays*), which stay what they were.  A frame through the tree neither records nor
+ *      replays first hits and leaves that cache and rt_debug_first_hit's counts as it found them; it takes no part in the tile
+ *      scheduler (orders, costs and predicted classes of the packet frames are untouched); rt_last_kernel_ms times it, and scene
+ *      and texture uploads order behind it like behind any frame.  rt_mgpu_* has no accel API and never takes it.
+ *   rt_accel_render_info: active (1 iff the next plain frame would walk the tree: the switch is on, rt_set_accel has built the
+ *      current scene's tree, and the scene has at least minObjects objects), traversal (the resolved one, never AUTO; 0 while
+ *      off), minObjects (the resolved one), and how many frames went each way since rt_create: launchesAccel[0] per-wavefront,
+ *      [1] per-ray (the order of the other two reports), [2] SPLIT; launchesPacket: frames that took the existing kernels while
+ *      this switch was on.  rt_accel_info's and rt_accel_shading_info's counters do not count frames. */
+typedef enum rt_accel_render_traversal {
+    RT_ACCEL_RENDER_AUTO = 0, RT_ACCEL_RENDER_LANE = 1, RT_ACCEL_RENDER_WAVE = 2, RT_ACCEL_RENDER_SPLIT = 3
+} rt_accel_render_traversal;
+#define RT_ACCEL_RENDER_DEFAULT_MIN_OBJECTS 4098
+typedef struct rt_accel_render_desc { int32_t enable, traversal, minObjects, reserved[5]; } rt_accel_render_desc;   /* 32 B; zero = defaults */
+typedef struct rt_accel_render_report {
+    int32_t active, traversal, minObjects, reserved0;
+    uint64_t launchesAccel[3], launchesPacket, reserved[2];
+} rt_accel_render_report;            /* 64 B */
+int rt_set_accel_render(rt_context *ctx, const rt_accel_render_desc *desc);
+int rt_accel_render_info(rt_context *ctx, rt_accel_render_report *info);
 
 /* ---- ray shading on the scene of the last rt_set_scene: main() of raytracingCs.glsl (:509-584) on caller-supplied rays,
  *      for what a frame's pinhole camera cannot ask (cubemap / environment probes, panoramas, stereo, fisheye or
@@ -1389,6 +1433,12 @@ RT_SA(sizeof(rt_accel_shade_desc) == 32 && offsetof(rt_accel_shade_desc, travers
       offsetof(rt_accel_shade_desc, reserved) == 12, "rt_accel_shade_desc is 32 B");
 RT_SA(sizeof(rt_accel_shade_report) == 48 && offsetof(rt_accel_shade_report, traversal) == 4 && offsetof(rt_accel_shade_report, launchesAccel) == 8 &&
       offsetof(rt_accel_shade_report, launchesBrute) == 24 && offsetof(rt_accel_shade_report, reserved) == 32, "rt_accel_shade_report is 48 B");
+RT_SA(sizeof(rt_accel_render_desc) == 32 && offsetof(rt_accel_render_desc, traversal) == 4 && offsetof(rt_accel_render_desc, minObjects) == 8 &&
+      offsetof(rt_accel_render_desc, reserved) == 12, "rt_accel_render_desc is 32 B");
+RT_SA(sizeof(rt_accel_render_report) == 64 && offsetof(rt_accel_render_report, traversal) == 4 && offsetof(rt_accel_render_report, minObjects) == 8 &&
+      offsetof(rt_accel_render_report, launchesAccel) == 16 && offsetof(rt_accel_render_report, launchesPacket) == 40 &&
+      offsetof(rt_accel_render_report, reserved) == 48, "rt_accel_render_report is 64 B");
+RT_SA(RT_ACCEL_RENDER_DEFAULT_MIN_OBJECTS >= 257, "up to 256 objects the packet kernel has its shadow tables");
 RT_SA(sizeof(rt_display_desc) == 32 && offsetof(rt_display_desc, flags) == 12 && offsetof(rt_display_desc, exposure) == 16,
       "rt_display_desc is 32 B");
 RT_SA(sizeof(rt_meter_desc) == 48 && offsetof(rt_meter_desc, adapt) == 20 && offsetof(rt_meter_desc, reserved) == 32,

@@ -124,6 +124,24 @@ int launch_frame(rt_context *c, const rt_params *p, float4 *dColor, float4 *dPos
     if (!c->dCompiled) return fail(c, RT_ERR_INVALID_ARG, "rt_set_scene has not been called");
     if (c->variant != 1 && (c->nObj > RT_EXHAUSTIVE_MAX_OBJECTS || c->nLt > RT_EXHAUSTIVE_MAX_LIGHTS))
         return fail(c, RT_ERR_TOO_LARGE, "the exhaustive cross-check kernel stages the scene in LDS: at most 512 objects / 64 lights (use the default kernel)");
+    // rt_set_accel_render: a plain frame of a scene whose tree stands is rt_accel_render.inc's.  It keeps out
+    // of the first-hit cache and of the tile scheduler -- no key, no plan, no count, as an instrumented launch keeps out of the
+    // cache -- but its launch is recorded, so the uploads order behind it.  With the switch off nothing here differs.
+    if (c->accelRender.on) {
+        if (c->variant == 1 && !counter && c->accelRenderActive()) {
+            const int traversal = c->accelRender.traversal;
+            if (timed) HIP_TRY(c, hipEventRecord(c->evStart, s));
+            HIP_TRY(c, rt_launch_render_accel(f, c->dCompiled, c->accel.dev, traversal, c->dNoise, c->dSky, dColor, dPos, dNormal, s));
+            if (timed) {
+                HIP_TRY(c, hipEventRecord(c->evStop, s));
+                c->timed = true;
+            }
+            SCHED_TRY(c, recordLaunch(s));
+            c->accelRender.launchesAccel[traversal == RT_ACCEL_RENDER_WAVE ? 0 : traversal == RT_ACCEL_RENDER_LANE ? 1 : 2]++;
+            return RT_OK;
+        }
+        c->accelRender.launchesPacket++;
+    }
     RtFirstHit::Mode mode = RtFirstHit::NORMAL;
     RtFirstHitKey key;
     // (with reuse switched off nothing below differs from a context that never had it)

@@ -1,6 +1,7 @@
 // rt_accel.cpp -- the host side of the threaded hierarchy (rt_accel.h): the build, the check, and the entry points
 // rt_set_accel / rt_accel_info / rt_accel_build_host of include/rt_mi355.h.  The kernels are rt_accel.inc's.  Also the host side
-// of the device builder (rt_set_accel_builder / rt_accel_build_info / rt_accel_read; rt_accel_build.h has its kernels' interface).
+// of the device builder (rt_set_accel_builder / rt_accel_build_info / rt_accel_read; rt_accel_build.h has its kernels' interface),
+// and the two switches that let other launches walk the same tree: rt_set_accel_shading and rt_set_accel_render.
 #include "rt_accel.h"
 
 #include <math.h>
@@ -530,6 +531,40 @@ int rt_accel_shading_info(rt_context *c, rt_accel_shade_report *out) {
     out->launchesAccel[0] = S.launchesAccel[0];
     out->launchesAccel[1] = S.launchesAccel[1];
     out->launchesBrute = S.launchesBrute;
+    return RT_OK;
+}
+
+// The frames through the same tree (rt_accel_render.inc).  Nothing is built or uploaded here either: whether a frame walks the
+// tree is decided per launch (rt_context::accelRenderActive, launch_frame in rt_abi.cpp), so the switches commute.
+int rt_set_accel_render(rt_context *c, const rt_accel_render_desc *desc) {
+    if (!c) return RT_ERR_INVALID_ARG;
+    rt_accel_render_desc d;
+    memset(&d, 0, sizeof d);
+    if (desc) d = *desc;
+    if (d.traversal != RT_ACCEL_RENDER_AUTO && d.traversal != RT_ACCEL_RENDER_LANE && d.traversal != RT_ACCEL_RENDER_WAVE &&
+        d.traversal != RT_ACCEL_RENDER_SPLIT)
+        return fail(c, RT_ERR_INVALID_ARG, "rt_accel_render_desc: unknown traversal");
+    for (int k = 0; k < 5; k++)
+        if (d.reserved[k]) return fail(c, RT_ERR_INVALID_ARG, "rt_accel_render_desc: reserved words must be zero");
+    if (d.minObjects < 0) return fail(c, RT_ERR_INVALID_ARG, "rt_accel_render_desc: negative minObjects");
+    RtAccelRenderState &S = c->accelRender;
+    S.on = desc && d.enable != 0;
+    // RT_ACCEL_RENDER_AUTO: the per-ray walk.  SPLIT and LANE tie within their spreads on every measured scene from 1025 objects up and
+    // both beat WAVE there, so the established form stays (DESIGN.md section 37 has the table, also behind the default minObjects)
+    S.traversal = d.traversal == RT_ACCEL_RENDER_AUTO ? RT_ACCEL_RENDER_LANE : d.traversal;
+    S.minObjects = d.minObjects ? d.minObjects : RT_ACCEL_RENDER_DEFAULT_MIN_OBJECTS;
+    return RT_OK;
+}
+
+int rt_accel_render_info(rt_context *c, rt_accel_render_report *out) {
+    if (!c || !out) return RT_ERR_INVALID_ARG;
+    const RtAccelRenderState &S = c->accelRender;
+    memset(out, 0, sizeof *out);
+    out->active = c->accelRenderActive() ? 1 : 0;
+    out->traversal = S.on ? S.traversal : 0;
+    out->minObjects = S.minObjects;
+    for (int k = 0; k < 3; k++) out->launchesAccel[k] = S.launchesAccel[k];
+    out->launchesPacket = S.launchesPacket;
     return RT_OK;
 }
 

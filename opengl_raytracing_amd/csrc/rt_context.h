@@ -44,6 +44,15 @@ struct RtAccelShadeState {
     uint64_t launchesAccel[2] = {0, 0}, launchesBrute = 0;
 };
 
+// rt_set_accel_render's state (rt_accel.cpp): whether plain frames walk rt_set_accel's tree (rt_accel_render.inc), by which
+// traversal and from how many objects, and the frame counters of rt_accel_render_info.  It owns no structure either.
+struct RtAccelRenderState {
+    bool on = false;
+    int traversal = RT_ACCEL_RENDER_LANE;      // resolved: RT_ACCEL_RENDER_LANE, _WAVE or _SPLIT
+    int minObjects = RT_ACCEL_RENDER_DEFAULT_MIN_OBJECTS;
+    uint64_t launchesAccel[3] = {0, 0, 0}, launchesPacket = 0;      // [0] per-wavefront, [1] per-ray, [2] SPLIT
+};
+
 // Everything the context allocates is held by an owner (rt_devbuf.h): after rt_destroy has drained the streams, `delete`
 // releases it all.  The stream comes first so that it goes last.
 struct rt_context {
@@ -112,6 +121,9 @@ struct rt_context {
     RtAccelShadeState accelShade;              // rt_set_accel_shading: ... and, opted into separately, behind rt_shade_rays
     // the next rt_shade_rays walks the tree
     bool accelShadeActive() const { return accelShade.on && accel.built && nObj >= accelShade.minObjects; }
+    RtAccelRenderState accelRender;            // rt_set_accel_render: ... and, opted into separately again, behind the frames
+    // the next plain frame (packet variant, no ray counter) walks the tree
+    bool accelRenderActive() const { return accelRender.on && accel.built && nObj >= accelRender.minObjects; }
     std::string err;
 };
 

@@ -139,3 +139,8 @@ hipError_t rt_launch_shade_rays(const RtFrame &f, const float4 *dCompiled, const
 hipError_t rt_launch_shade_rays_accel(const RtFrame &f, const float4 *dCompiled, const RtAccelDev &acc, int lane, const uint8_t *dNoise,
                                       const uint16_t *dSky, const float4 *dRays, const uint2 *dPixels, size_t nRays, float4 *dColor,
                                       float4 *dPos, uint2 *dNormal, hipStream_t s);
+// A frame through the hierarchy (rt_accel_render.inc; rt_set_accel_render): rt_render_kernel's surfaces -- window, strips,
+// imageStores, zero records outside the image -- by the per-lane path tracer over `acc`.  traversal: RT_ACCEL_RENDER_LANE, _WAVE
+// or _SPLIT (the resolved one).
+hipError_t rt_launch_render_accel(const RtFrame &f, const float4 *dCompiled, const RtAccelDev &acc, int traversal, const uint8_t *dNoise,
+                                  const uint16_t *dSky, float4 *dColor, float4 *dPos, uint2 *dNormal, hipStream_t s);

@@ -1224,3 +1224,8 @@ hipError_t rt_launch_device_math(int op, const uint4 *dIn, uint4 *dOut, size_t n
 // Ray shading through the hierarchy (rt_set_accel_shading): rt_shade.inc's kernel body over rt_accel.inc's walks.
 // =========================================================================================
 #include "rt_accel_shade.inc"
+
+// =========================================================================================
+// Whole frames through the hierarchy (rt_set_accel_render): rt_render_kernel's pixel map and stores over the same walks.
+// =========================================================================================
+#include "rt_accel_render.inc"

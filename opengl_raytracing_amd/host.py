@@ -102,6 +102,8 @@ def _signatures():
         "rt_accel_read": (ci, [vp, vp, sz, vp, sz, vp, sz, P(L.RtAccelReport)]),
         "rt_set_accel_shading": (ci, [vp, P(L.RtAccelShadeDesc)]),
         "rt_accel_shading_info": (ci, [vp, P(L.RtAccelShadeReport)]),
+        "rt_set_accel_render": (ci, [vp, P(L.RtAccelRenderDesc)]),
+        "rt_accel_render_info": (ci, [vp, P(L.RtAccelRenderReport)]),
         "rt_shade_rays": (ci, [vp, params, vp, vp, sz, vp, vp, vp, vp]),
         "rt_last_error": (cs, [vp]),
         "rt_generate_aabb": (ci, [vp, ci]),
@@ -897,6 +899,25 @@ class RayTracer(_Handle):
         r = L.RtAccelShadeReport()
         self._call("rt_accel_shading_info", ctypes.byref(r))
         return dict(active=bool(r.active), traversal=r.traversal, launches_accel=tuple(r.launchesAccel), launches_brute=r.launchesBrute)
+
+    def set_accel_render(self, enable=True, traversal="auto", min_objects=0):
+        """Let the frames (render, render_to, render_into_image, frame) walk the hierarchy set_accel built (rt_set_accel_render;
+        sticky, off by default, independent of the other accel switches and of the order of the calls).  traversal: "auto", "lane",
+        "wave", "split" (primary rays per wavefront, every later ray per ray); min_objects: scenes with fewer objects keep the
+        packet kernel (0: the default).  The surfaces do not change, bit for bit."""
+        if enable is None or enable is False:
+            self._call("rt_set_accel_render", None)
+            return
+        d = enable if isinstance(enable, L.RtAccelRenderDesc) else L.make_accel_render_desc(True, traversal, min_objects)
+        self._call("rt_set_accel_render", ctypes.byref(d))
+
+    def accel_render_info(self):
+        """rt_accel_render_info as a dict: active (the next plain frame walks the tree), traversal and min_objects (resolved),
+        launches_accel (per-wavefront, per-ray, split), launches_packet (frames that kept the existing kernels while the switch was on)."""
+        r = L.RtAccelRenderReport()
+        self._call("rt_accel_render_info", ctypes.byref(r))
+        return dict(active=bool(r.active), traversal=r.traversal, min_objects=r.minObjects, launches_accel=tuple(r.launchesAccel),
+                    launches_packet=r.launchesPacket)
 
     def get_surfaces(self):
         """Device pointers (ints) of the context-owned gColor, gPosition, gNormal of the last rt_render."""

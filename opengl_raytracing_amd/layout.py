@@ -268,6 +268,34 @@ def make_accel_shade_desc(enable=True, traversal="auto", min_objects=0):
     return d
 
 
+# ---- the frames through the hierarchy (rt_set_accel_render / rt_accel_render_info) ----
+ACCEL_RENDER_AUTO, ACCEL_RENDER_LANE, ACCEL_RENDER_WAVE, ACCEL_RENDER_SPLIT = 0, 1, 2, 3
+ACCEL_RENDER_TRAVERSALS = {"auto": ACCEL_RENDER_AUTO, "lane": ACCEL_RENDER_LANE, "wave": ACCEL_RENDER_WAVE, "split": ACCEL_RENDER_SPLIT}
+ACCEL_RENDER_DEFAULT_MIN_OBJECTS = 4098
+
+
+class RtAccelRenderDesc(ctypes.Structure):
+    """``rt_accel_render_desc``: zero = the default of every field."""
+    _fields_ = [("enable", ctypes.c_int32), ("traversal", ctypes.c_int32), ("minObjects", ctypes.c_int32), ("reserved", ctypes.c_int32 * 5)]
+
+
+class RtAccelRenderReport(ctypes.Structure):
+    """``rt_accel_render_report``: what rt_accel_render_info answers."""
+    _fields_ = [("active", ctypes.c_int32), ("traversal", ctypes.c_int32), ("minObjects", ctypes.c_int32), ("reserved0", ctypes.c_int32),
+                ("launchesAccel", ctypes.c_uint64 * 3), ("launchesPacket", ctypes.c_uint64), ("reserved", ctypes.c_uint64 * 2)]
+
+
+assert ctypes.sizeof(RtAccelRenderDesc) == 32 and ctypes.sizeof(RtAccelRenderReport) == 64
+
+
+def make_accel_render_desc(enable=True, traversal="auto", min_objects=0):
+    """An rt_accel_render_desc; min_objects 0 keeps the default.  traversal: "auto", "lane", "wave", "split" or a number."""
+    d = RtAccelRenderDesc()
+    d.enable, d.minObjects = int(bool(enable)), int(min_objects)
+    d.traversal = int(ACCEL_RENDER_TRAVERSALS.get(traversal, traversal))
+    return d
+
+
 # ---- ray shading (rt_shade_rays, include/rt_mi355.h) ------------------------------------------
 PIXEL_DTYPE = np.dtype({"names": ["x", "y"], "formats": ["<u4", "<u4"], "offsets": [0, 4], "itemsize": 8})
 
