@@ -288,6 +288,24 @@ int rt_debug_tile_order(rt_context *ctx, uint32_t *out, int cap, int *nTiles, in
  * costs or order, nTiles outside [1, 2^20].  Test hook, no reference counterpart. */
 int rt_debug_lpt_sort(rt_context *ctx, uint32_t *costs, int nTiles, uint32_t *order, uint32_t *accum);
 
+/* TILE SPLIT: a replaying frame (first-hit reuse) on the measured tile order runs its heaviest tiles as
+ * P = 2 .. 4 one-wave jobs that divide the tile's lighting among themselves; the pixels are the same bits.  RT_TILE_SPLIT=0 in
+ * the environment at rt_create switches it off, RT_DEBUG_SPLIT_PARTS=2|3|4 makes every plan split every tile it can into that
+ * many parts (tests).  rt_debug_split_tiles: out[t] = P of tile t (raster tile order, up to cap entries; 0 = the tile ran whole)
+ * in the last replaying launch, *nTiles = that launch's tiles, 0 before the first one; a launch that ran without a plan reports
+ * zeros.  A settled tile listed with a P was copied out by its first job alone.  Test hook; synchronises.  No reference counterpart. */
+int rt_debug_split_tiles(rt_context *ctx, uint8_t *out, int cap, int *nTiles);
+
+/* The split plan's rule on caller-supplied HOST arrays: order[k] = the k-th tile to start and costs[t] = tile t's cost (nTiles
+ * entries each), waveSlots = the resident wave slots the costs' sum is divided by, depth / nLt = the frame's maxRayDepth and
+ * lights, forceParts = 0 or RT_DEBUG_SPLIT_PARTS' value, prevParts (may be NULL) = the plan in use.  Out: parts[t] = P or 0,
+ * slot[t] = a split tile's scratch slot, extra[1536] = the jobs beyond each split tile's first (tile | part << 28; entries
+ * beyond counts[0] are 0xffffffff), counts = (extra jobs, split tiles).  Touches no scheduler state; synchronises.
+ * RT_ERR_INVALID_ARG: NULL context or array, nTiles outside [1, 2^20], depth outside [0, 32], forceParts not 0, 2, 3 or 4.
+ * Test hook, no reference counterpart. */
+int rt_debug_split_plan(rt_context *ctx, const uint32_t *order, const uint32_t *costs, int nTiles, uint32_t waveSlots, int depth, int nLt,
+                        int forceParts, const uint8_t *prevParts, uint8_t *parts, uint32_t *slot, uint32_t *extra, uint32_t counts[2]);
+
 /* The lights' SHADOW TABLES of the current scene (built by rt_set_scene for scenes of <= 256 objects; csrc/rt_shadowtab.inc):
  * per light 28 dwords of header -- (kind, base dword, K, NB) (invBinW, binMax, wlo, nmax^2) (pmin, qmin, invCell, cells)
  * (T0, eta) (B0, nmax) (light position or direction, binW) (base dword of the light's BLOCKER table or 0, its eta, -, -);

@@ -155,12 +155,14 @@ int launch_frame(rt_context *c, const rt_params *p, float4 *dColor, float4 *dPos
                        mode == RtFirstHit::REPLAY ? 1 : 0));
     if (mode == RtFirstHit::RECORD) SCHED_TRY(c, beforeFirstHitRecord(s));
     if (mode == RtFirstHit::REPLAY) SCHED_TRY(c, beforeFirstHitReplay(s, plan.rec));
+    const RtSplitDesc *split = nullptr;          // a replaying frame whose heaviest tiles run in parts, or null
+    if (mode == RtFirstHit::REPLAY) SCHED_TRY(c, splitFor(plan, sc, c->dFirstHit.ptr, s, &split));
     if (timed) HIP_TRY(c, hipEventRecord(c->evStart, s));
     HIP_TRY(c, rt_launch_render(f, sc, dColor, dPos, dNormal, counter, c->variant, s, countMode, (int)mode,
                                 mode == RtFirstHit::NORMAL ? nullptr
                                     : (void *)((uintptr_t)c->dFirstHit.ptr | (mode == RtFirstHit::RECORD && !c->settledOn() ? RT_FIRST_HIT_NO_SETTLED : 0) |
                                                (mode == RtFirstHit::RECORD && !c->prefixOn() ? RT_FIRST_HIT_NO_PREFIX : 0)),
-                                blockerGroup));
+                                blockerGroup, split));
     if (timed) {
         HIP_TRY(c, hipEventRecord(c->evStop, s));
         c->timed = true;
@@ -720,6 +722,27 @@ int rt_debug_lpt_sort(rt_context *c, uint32_t *costs, int nTiles, uint32_t *orde
     if (nTiles < 1 || nTiles > (1 << 20)) return fail(c, RT_ERR_INVALID_ARG, "rt_debug_lpt_sort: nTiles outside [1, 2^20]");
     HIP_TRY(c, hipSetDevice(c->device));
     SCHED_TRY(c, lptSortOf(costs, nTiles, order, accum));
+    return RT_OK;
+}
+
+int rt_debug_split_tiles(rt_context *c, uint8_t *out, int cap, int *nTiles) {
+    if (!c || !out || cap < 0 || !nTiles) return RT_ERR_INVALID_ARG;
+    HIP_TRY(c, hipSetDevice(c->device));
+    SCHED_TRY(c, splitTiles(out, cap, nTiles));
+    return RT_OK;
+}
+
+int rt_debug_split_plan(rt_context *c, const uint32_t *order, const uint32_t *costs, int nTiles, uint32_t waveSlots, int depth, int nLt, int forceParts,
+                        const uint8_t *prevParts, uint8_t *parts, uint32_t *slot, uint32_t *extra, uint32_t counts[2]) {
+    if (!c) return RT_ERR_INVALID_ARG;
+    if (!order || !costs || !parts || !slot || !extra || !counts) return fail(c, RT_ERR_INVALID_ARG, "rt_debug_split_plan: NULL array");
+    if (nTiles < 1 || nTiles > (1 << 20)) return fail(c, RT_ERR_INVALID_ARG, "rt_debug_split_plan: nTiles outside [1, 2^20]");
+    if (depth < 0 || depth > RT_MAX_DEPTH || nLt < 0 || nLt > 1024 || forceParts < 0 || forceParts > RT_SPLIT_MAX_PARTS || forceParts == 1)
+        return fail(c, RT_ERR_INVALID_ARG, "rt_debug_split_plan: depth, nLt or forceParts out of range");
+    HIP_TRY(c, hipSetDevice(c->device));
+    std::vector<unsigned short> slots((size_t)nTiles);
+    SCHED_TRY(c, splitPlanOf(order, costs, nTiles, waveSlots, depth, nLt, forceParts, prevParts, parts, slots.data(), extra, counts));
+    for (int i = 0; i < nTiles; i++) slot[i] = slots[(size_t)i];
     return RT_OK;
 }
 

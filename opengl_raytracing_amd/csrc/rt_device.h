@@ -85,7 +85,7 @@ hipError_t rt_launch_compile_scene(const uint8_t *dObjects, int nObj, const uint
                                    float4 *dCompiled, hipStream_t s);
 hipError_t rt_launch_render(const RtFrame &f, const RtDeviceScene &sc, float4 *dColor, float4 *dPos,
                             uint2 *dNormal, unsigned long long *dRayCounter, int variant, hipStream_t s, int countMode = 1,
-                            int firstMode = 0, void *dFirstHit = nullptr, int *blockerGroup = nullptr);
+                            int firstMode = 0, void *dFirstHit = nullptr, int *blockerGroup = nullptr, const struct RtSplitDesc *dSplit = nullptr);
 // (blockerGroup, optional: receives how many of pcssShadow's blocker rays the launched instantiation takes per traversal --
 // RT_PK_BLOCKER_GROUP in the profiles with blockerPairs / blockerTab, 1 in the others and in the exhaustive kernel; the
 // granularity at which a countMode-2 launch stops a lane's blocker search.)
@@ -98,13 +98,51 @@ hipError_t rt_launch_render(const RtFrame &f, const RtDeviceScene &sc, float4 *d
 // tile's flag says K = 0 or settled, which is the buffer as section 27 left it.
 #define RT_FIRST_HIT_NO_PREFIX ((uintptr_t)2)
 #define RT_FIRST_HIT_SWITCHES (RT_FIRST_HIT_NO_SETTLED | RT_FIRST_HIT_NO_PREFIX)
+
+// ---- TILE SPLIT: a replaying frame's heaviest tiles run as P one-wave jobs that share the path geometry
+// and divide the lighting units (depth, light) and (depth, subsurface section) among themselves; the job that ends last adds up.
+#define RT_SPLIT_MAX_TILES 512                            // S: tiles split per frame at most
+#define RT_SPLIT_MAX_PARTS 4                              // P <= 4
+#define RT_SPLIT_EXTRA_BLOCKS (3 * RT_SPLIT_MAX_TILES)    // E: workgroups ahead of the tiles' own, one per extra job (the host never reads the count)
+#define RT_SPLIT_UNITS_PER_PART 32                        // a tile of more than 32 P units stays whole
+// Frames of more tiles than this per resident wave slot are launched whole: their longest tile is a small part of a slot's load
+// (C3 and C4, 21-25 tiles per slot: no tile above the plan's target; C2, 6.3: some 300), and a launch with a plan runs the
+// kernel that carries the split's code, which costs the whole tiles 3-10 %
+#define RT_SPLIT_MAX_TILES_PER_SLOT 16
+// g, the share of a heavy replaying tile's time that every part repeats (the start, closest hits, hit set-up, roulette, next
+// direction), in 1/256.  Measured (profiles/tile_split_bench.json, "geometry_share"): the section timers on windows of the 300
+// heaviest C2 tiles give 0.14-0.16 for whole frames, whose depth-0 lighting a replaying tile does not have; the ten heaviest
+// replaying tiles cost 1.89 times as much in four parts as whole, which is g = (1.89 - 1) / 3 = 0.30 -- the figure used.
+#define RT_SPLIT_G256 76
+// A split tile's scratch slot, in dwords, for frames of `depth` bounces and nLt lights: 64 of header (dword 0 = the arrival
+// counter), then SoA columns of 64 lanes -- 4 per unit (x, y, z, and for a subsurface unit the lane's needs-it bit), 4 per depth
+// (throughput, then bit 0 alive / bit 1 a miss that adds the sky), 4 for that sky term.
+RT_FH_INLINE unsigned rt_split_units(int depth, int nLt) { return (unsigned)depth * (unsigned)(nLt + 1); }
+RT_FH_INLINE size_t rt_split_slot_dwords(int depth, int nLt) { return 64u + ((size_t)rt_split_units(depth, nLt) * 4u + (size_t)depth * 4u + 4u) * 64u; }
+struct RtSplitDesc {
+    const unsigned char *records;      // the first-hit record buffer
+    const unsigned char *parts;        // [nTiles] P of a split tile, 0 of any other
+    const unsigned short *slot;        // [nTiles] a split tile's scratch slot, < RT_SPLIT_MAX_TILES
+    const unsigned *extra;             // [RT_SPLIT_EXTRA_BLOCKS] the jobs beyond part 0, heaviest tile first: tile | part << 28
+    const unsigned *counts;            // [0] extra jobs, [1] split tiles
+    float *scratch;                    // [RT_SPLIT_MAX_TILES] slots of rt_split_slot_dwords() each
+};
+// The plan of the order buffer `order` (rt_sched.cpp launches it behind the sort that wrote the order): walks it heaviest first.
+// forceParts: RT_DEBUG_SPLIT_PARTS; prevParts (may be null): the plan in use, whose split tiles stay split.
+hipError_t rt_launch_split_plan(const unsigned *dOrder, const unsigned *dCost, int nTiles, unsigned waveSlots, int depth, int nLt, int forceParts,
+                                const unsigned char *dPrevParts, unsigned char *dParts, unsigned short *dSlot, unsigned *dExtra,
+                                unsigned *dCounts, unsigned epoch, unsigned *hSeen, hipStream_t s);      // hSeen (pinned, may be null): (split tiles, epoch)
+hipError_t rt_launch_split_desc(RtSplitDesc *dDesc, const RtSplitDesc &v, hipStream_t s);
+// resident waves per SIMD of the packet-kernel instantiation rt_launch_render picks for this frame
+int rt_packet_profile_waves(const RtFrame &f, const RtDeviceScene &sc);
 // Tile geometry of the packet kernel for a given scene size / window (so the ABI layer can size the
 // feedback buffers): workgroup threads, tile edge, tiles per row, total tiles.
 void rt_packet_geometry(int nObj, int regionW, int regionH, int *bt, int *tile, int *tilesX, int *nTiles);
 // Heavy-first tile order predicted from the frame's own inputs (rt_predict_tiles_kernel): no history involved.
 hipError_t rt_launch_predict_order(const RtFrame &f, const RtDeviceScene &sc, int tilesX, int nTiles, unsigned *dSeg, int segStride,
                                    unsigned *dCursors, unsigned *dNextCursors, unsigned char *dCls, unsigned *dOrder, hipStream_t s);
-hipError_t rt_launch_lpt_sort(unsigned *dCost, unsigned *dSnap, unsigned *dOrder, int nTiles, hipStream_t s, unsigned *dAccum = nullptr);
+hipError_t rt_launch_lpt_sort(unsigned *dCost, unsigned *dSnap, unsigned *dOrder, int nTiles, hipStream_t s, unsigned *dAccum = nullptr,
+                              unsigned *dKeep = nullptr);      // dKeep (optional): the costs as read, for the split plan
 hipError_t rt_launch_iota(unsigned *dOrder, int n, hipStream_t s);      // dOrder[i] = i (identity tile order)
 // Ray queries (rt_query.inc).  dRays / dOut: 2 float4 per ray / hit (rt_ray / rt_hit), anyHit: one int per ray.
 hipError_t rt_launch_trace_rays(const float4 *dRays, size_t nRays, const float4 *dCompiled, int nObj, int anyHit, void *dOut,

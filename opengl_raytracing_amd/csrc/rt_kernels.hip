@@ -557,7 +557,7 @@ __global__ RT_V0_BOUNDS void rt_render_kernel(const RtFrame f, const RtDeviceSce
 //   LIGHT / HEAVY profiles                             0.404    4.84    8.15    43.2
 // BT and COMPACT are 64 and true in every instantiation; the parameters stay because the kernels' names carry them.
 // FIRST: 0 = the frame as ever, 1 = it also records every pixel's first hit into firstHit, 2 = depth 0 replayed from firstHit
-// (render_packet).  The records come in the `rayCounter` argument, which the launches that reuse (never
+// (render_packet), 3 = the same replay launched with a split plan (section 38; 2 stays the kernel it was).  The records come in the `rayCounter` argument, which the launches that reuse (never
 // instrumented: COUNT = 0) have no other use for: one more kernel argument moves the hidden arguments behind it, and FIRST = 0
 // has to stay, to the byte, the kernel it was.
 #ifndef RT_FB_ACCUM
@@ -597,9 +597,62 @@ void rt_render_packet_kernel(const RtFrame f, const RtDeviceScene dsc, float4 *_
         }
         pk_replay_park<BT, PROFILE::boundsLds>(f, dsc, tileX_, tileY_, flag_, (const unsigned char *)rayCounter, lds, ld_);
     }
+    if constexpr (FIRST == 3) {
+        // TILE SPLIT: the same start for a replaying frame that is launched with a split plan.  The
+        // argument is an RtSplitDesc, which holds the records; the grid is RT_SPLIT_EXTRA_BLOCKS workgroups for the plan's
+        // extra jobs (tile, part >= 1) -- those beyond the plan's count end here -- and then one per tile in the order, which is
+        // the tile's part 0.  A job leaves its part, the tile's P and its scratch slot in the counter slot's four words of
+        // LDS, where render_packet reads them when it needs them (P = 1: the tile is whole).
+        const unsigned tilesX_ = (unsigned)(f.p.regionW + 7) / 8u, nTiles_ = tilesX_ * ((unsigned)(f.p.regionH + 7) / 8u);
+        const RtSplitDesc *const desc_ = (const RtSplitDesc *)rayCounter;
+        const unsigned char *const records_ = desc_->records;
+        unsigned block_ = blockIdx.x, part_ = 0u;
+        if (block_ < (unsigned)RT_SPLIT_EXTRA_BLOCKS) {
+            if (block_ >= desc_->counts[0]) return;
+            part_ = desc_->extra[block_];
+            if ((part_ >> 28) == 0u) return;          // (no job: part 0 is the tile's own workgroup)
+        } else {
+            block_ -= (unsigned)RT_SPLIT_EXTRA_BLOCKS;
+        }
+        if (block_ >= nTiles_ && part_ == 0u) return;          // (a grid is never larger; ahead of the order's entry)
+        const unsigned tile_ = part_ ? (part_ & 0x0fffffffu) : dsc.tileOrder ? dsc.tileOrder[block_] : block_;
+        part_ >>= 28;
+        if (tile_ >= nTiles_) return;          // (the guard below, ahead of the first address formed from the tile)
+        tileReplay = tile_;
+        unsigned parts_ = desc_->parts[tile_], slot_ = desc_->slot[tile_];
+        const int tileX_ = (int)(tile_ % tilesX_), tileY_ = (int)(tile_ / tilesX_);
+        const long long t0_ = clock64();
+        PkReplayLoads ld_;
+        pk_replay_request<BT, PROFILE::boundsLds>(f, dsc, tileX_, tileY_, records_, ld_);
+        const unsigned flag_ = (unsigned)__builtin_amdgcn_readfirstlane((int)ld_.flag);
+        parts_ = (unsigned)__builtin_amdgcn_readfirstlane((int)parts_);
+        slot_ = (unsigned)__builtin_amdgcn_readfirstlane((int)slot_);
+        // every bound ahead of every address formed from them; a tile the plan did not split has part 0 alone
+        if (parts_ < 2u || parts_ > (unsigned)RT_SPLIT_MAX_PARTS || slot_ >= (unsigned)RT_SPLIT_MAX_TILES || f.p.maxRayDepth > RT_MAX_DEPTH) parts_ = 1u;
+        if (part_ >= parts_) return;
+        if (rt_prefix_flag_settled(flag_)) {
+            if (part_ != 0u) return;          // (a settled tile is copied out by its part 0 and has nothing to divide)
+            pk_replay_settled_tile(f, tileX_, tileY_, records_, gColor, gPosition, gNormal);
+            if (dsc.tileCost && (threadIdx.x & 63) == 0) {
+                const unsigned c_ = (unsigned)(((unsigned long long)(clock64() - t0_)) >> 6);
+                if (RT_FB_ACCUM) atomicAdd(&dsc.tileCost[tile_], c_);
+                else dsc.tileCost[tile_] = c_;
+            }
+            return;
+        }
+        {
+            volatile unsigned *w_ = (volatile unsigned *)(lds + (PROFILE::boundsLds ? f.nObj * 2 : 0));
+            const uintptr_t at_ = parts_ > 1u ? (uintptr_t)(desc_->scratch + (size_t)slot_ * rt_split_slot_dwords(f.p.maxRayDepth, f.nLt)) : (uintptr_t)0;
+            w_[0] = 0u;                          // the depths whose lighting this job has passed (pk_split_*)
+            w_[1] = part_ | (parts_ << 8);
+            w_[2] = (unsigned)at_;
+            w_[3] = (unsigned)((unsigned long long)at_ >> 32);
+        }
+        pk_replay_park<BT, PROFILE::boundsLds>(f, dsc, tileX_, tileY_, flag_, records_, lds, ld_);
+    }
     const int nAll = f.nObj * (RT_HOT_F4 + RT_MAT_F4) + f.nLt * RT_LGT_F4 + 2 * (RT_HALTON_N / 4);
     const int nF4 = PROFILE::boundsLds ? f.nObj * 2 : 0;          // float4 staged in LDS: the objects' two bounds float4
-    if constexpr (FIRST != 2) {                   // (a replaying tile has staged them in pk_replay_park)
+    if constexpr (FIRST < 2) {                    // (a replaying tile has staged them in pk_replay_park)
         for (int i = threadIdx.x; i < nF4; i += BT) lds[i] = dsc.compiled[(i >> 1) * RT_HOT_F4 + (i & 1)];
         __syncthreads();
     }
@@ -625,10 +678,14 @@ void rt_render_packet_kernel(const RtFrame f, const RtDeviceScene dsc, float4 *_
 
     // tile of this workgroup: longest-first order from the previous frame's measured costs, if any
     const int tilesX = (f.p.regionW + 7) / 8;
-    const unsigned tile = FIRST == 2 ? tileReplay : dsc.tileOrder ? dsc.tileOrder[blockIdx.x] : blockIdx.x;
+    const unsigned tile = FIRST >= 2 ? tileReplay : dsc.tileOrder ? dsc.tileOrder[blockIdx.x] : blockIdx.x;
     // an order buffer is a permutation of [0, gridDim.x) by construction (identity-initialised, rewritten only by
     // rt_lpt_sort_kernel); the guard keeps a corrupted entry from turning into out-of-bounds tileCost / surface writes
-    if (tile >= gridDim.x) return;
+    if constexpr (FIRST == 3) {          // (a split launch's grid holds the extra jobs too: the bound is the region's tile count)
+        if (tile >= (unsigned)tilesX * ((unsigned)(f.p.regionH + 7) / 8u)) return;
+    } else {
+        if (tile >= gridDim.x) return;
+    }
     sc.tileX = (int)(tile % (unsigned)tilesX);
     sc.tileY = (int)(tile / (unsigned)tilesX);
     const long long t0 = clock64();
@@ -910,6 +967,16 @@ hipError_t rt_launch_shadow_tables(const float4 *dCompiled, int nObj, int nLt, u
     return hipGetLastError();
 }
 
+// Which packet-kernel profile a frame runs (rt_launch_render's instantiation and rt_packet_profile_waves read it here; the
+// ...S twin where the scene has a PCSS light).  Scenes without shadow tables (more than RT_ST_MAX_OBJECTS objects or
+// RT_ST_MAX_LIGHTS lights: rt_set_scene builds none) run the profile that finds the lights' candidates per packet.
+enum { PK_PROFILE_HUGE = 0, PK_PROFILE_LIGHT = 1, PK_PROFILE_HEAVY1 = 2, PK_PROFILE_HEAVY = 3 };
+static int pk_profile_of(const RtFrame &f, const RtDeviceScene &sc) {
+    const bool noTab = PkLight::tabWords > 0 && f.nObj > 0 && f.nLt > 0 && (!sc.shadowTab || f.nObj > RT_ST_MAX_OBJECTS);
+    const bool light = f.nObj <= RT_PK_LIGHT_SCENE && !(f.nObj > 0 && f.nLt > 0 && !sc.shadowTab);
+    return noTab ? PK_PROFILE_HUGE : light ? PK_PROFILE_LIGHT : f.nObj <= 64 ? PK_PROFILE_HEAVY1 : PK_PROFILE_HEAVY;
+}
+
 // countMode (only with dRayCounter): 1 = instrumented build that traces every ray the REFERENCE traces (its count is the
 // unit count R of the metric), 2 = instrumented build that keeps the production kernel's provably-dead-ray skips
 // (its count is what the timed kernel actually traverses).
@@ -917,7 +984,7 @@ hipError_t rt_launch_shadow_tables(const float4 *dCompiled, int nObj, int nLt, u
 // depth 0 from them (rt_first_hit_bytes(regionW, regionH) bytes; render_packet).
 hipError_t rt_launch_render(const RtFrame &f, const RtDeviceScene &sc, float4 *dColor, float4 *dPos,
                             uint2 *dNormal, unsigned long long *dRayCounter, int variant, hipStream_t s, int countMode,
-                            int firstMode, void *dFirstHit, int *blockerGroup) {
+                            int firstMode, void *dFirstHit, int *blockerGroup, const RtSplitDesc *dSplit) {
     if (blockerGroup) *blockerGroup = 1;
     if (f.p.regionW <= 0 || f.p.regionH <= 0) return hipSuccess;
     if (firstMode != 0 && (firstMode < 0 || firstMode > 2 || variant != 1 || dRayCounter || !dFirstHit || f.p.maxRayDepth < 1)) return hipErrorInvalidValue;
@@ -927,11 +994,20 @@ hipError_t rt_launch_render(const RtFrame &f, const RtDeviceScene &sc, float4 *d
         int bt, tile, tilesX, nTiles;
         rt_packet_geometry(f.nObj, f.p.regionW, f.p.regionH, &bt, &tile, &tilesX, &nTiles);
         dim3 grid(nTiles);
-        const bool light = bt == 64 && f.nObj <= RT_PK_LIGHT_SCENE && !(f.nObj > 0 && f.nLt > 0 && !sc.shadowTab);
+        const int profile = pk_profile_of(f, sc);
+        const bool light = profile == PK_PROFILE_LIGHT;
         // LDS: the AABBs (2 float4 per object) + the 16-byte counter slot + the profile's parking area
         const size_t ldsBytes = ((size_t)((light || PkHeavy::boundsLds) ? f.nObj * 2 : 0) + 1) * sizeof(float4) +
                                 (size_t)PK_PARK_FLOATS * bt * sizeof(float);
-        unsigned long long *const firstArg = (unsigned long long *)dFirstHit;      // (the records travel in the counter's argument: rt_render_packet_kernel)
+        unsigned long long *firstArg = (unsigned long long *)dFirstHit;      // (the records travel in the counter's argument: rt_render_packet_kernel)
+        // a replaying launch with a split plan: the descriptor, which holds the records, travels in their
+        // place, and the plan's extra jobs get RT_SPLIT_EXTRA_BLOCKS workgroups ahead of the tiles' own
+        if (dSplit && firstMode == 2) {
+            if (((uintptr_t)dSplit & 15u) || f.p.maxRayDepth > RT_MAX_DEPTH) return hipErrorInvalidValue;
+            firstArg = (unsigned long long *)dSplit;
+            grid = dim3((unsigned)nTiles + (unsigned)RT_SPLIT_EXTRA_BLOCKS);
+            firstMode = 3;
+        }
 #define RT_LAUNCH_PK(PROFILE_)                                                                                                        \
         do {                                                                                                                          \
             if (blockerGroup) *blockerGroup = (PROFILE_::blockerPairs || PROFILE_::blockerTab) ? RT_PK_BLOCKER_GROUP : 1;             \
@@ -939,20 +1015,18 @@ hipError_t rt_launch_render(const RtFrame &f, const RtDeviceScene &sc, float4 *d
             else if (dRayCounter) hipLaunchKernelGGL((rt_render_packet_kernel<1, 64, true, PROFILE_>), grid, dim3(64), ldsBytes, s, f, sc, dColor, dPos, dNormal, dRayCounter);            \
             else if (firstMode == 1) hipLaunchKernelGGL((rt_render_packet_kernel<0, 64, true, PROFILE_, 1>), grid, dim3(64), ldsBytes, s, f, sc, dColor, dPos, dNormal, firstArg);    \
             else if (firstMode == 2) hipLaunchKernelGGL((rt_render_packet_kernel<0, 64, true, PROFILE_, 2>), grid, dim3(64), ldsBytes, s, f, sc, dColor, dPos, dNormal, firstArg);    \
+            else if (firstMode == 3) hipLaunchKernelGGL((rt_render_packet_kernel<0, 64, true, PROFILE_, 3>), grid, dim3(64), ldsBytes, s, f, sc, dColor, dPos, dNormal, firstArg);    \
             else hipLaunchKernelGGL((rt_render_packet_kernel<0, 64, true, PROFILE_>), grid, dim3(64), ldsBytes, s, f, sc, dColor, dPos, dNormal, dRayCounter);                             \
         } while (0)
-        // scenes without shadow tables (more than RT_ST_MAX_OBJECTS objects or RT_ST_MAX_LIGHTS lights: rt_set_scene builds none)
-        // run the profile that finds the lights' candidates per packet
-        const bool noTab = PkLight::tabWords > 0 && f.nObj > 0 && f.nLt > 0 && (!sc.shadowTab || f.nObj > RT_ST_MAX_OBJECTS);
         if (f.anyPcss) {
-            if (noTab) RT_LAUNCH_PK(PkHugeS);
-            else if (light) RT_LAUNCH_PK(PkLightS);
-            else if (f.nObj <= 64) RT_LAUNCH_PK(PkHeavy1S);
+            if (profile == PK_PROFILE_HUGE) RT_LAUNCH_PK(PkHugeS);
+            else if (profile == PK_PROFILE_LIGHT) RT_LAUNCH_PK(PkLightS);
+            else if (profile == PK_PROFILE_HEAVY1) RT_LAUNCH_PK(PkHeavy1S);
             else RT_LAUNCH_PK(PkHeavyS);
         } else {
-            if (noTab) RT_LAUNCH_PK(PkHuge);
-            else if (light) RT_LAUNCH_PK(PkLight);
-            else if (f.nObj <= 64) RT_LAUNCH_PK(PkHeavy1);
+            if (profile == PK_PROFILE_HUGE) RT_LAUNCH_PK(PkHuge);
+            else if (profile == PK_PROFILE_LIGHT) RT_LAUNCH_PK(PkLight);
+            else if (profile == PK_PROFILE_HEAVY1) RT_LAUNCH_PK(PkHeavy1);
             else RT_LAUNCH_PK(PkHeavy);
         }
 #undef RT_LAUNCH_PK
@@ -997,6 +1071,12 @@ hipError_t rt_launch_predict_order(const RtFrame &f, const RtDeviceScene &sc, in
     return hipGetLastError();
 }
 
+int rt_packet_profile_waves(const RtFrame &f, const RtDeviceScene &sc) {
+    constexpr int waves[4] = {PkHuge::waves, PkLight::waves, PkHeavy1::waves, PkHeavy::waves};
+    constexpr int wavesS[4] = {PkHugeS::waves, PkLightS::waves, PkHeavy1S::waves, PkHeavyS::waves};
+    return (f.anyPcss ? wavesS : waves)[pk_profile_of(f, sc)];
+}
+
 void rt_packet_geometry(int nObj, int regionW, int regionH, int *bt, int *tile, int *tilesX, int *nTiles) {
     (void)nObj;         // one-wave workgroups / 8x8-pixel tiles for every scene size (the 256-thread shape is retired)
     *bt = 64;
@@ -1012,8 +1092,10 @@ void rt_packet_geometry(int nObj, int regionW, int regionH, int *bt, int *tile, 
 // snapshot: `order` is always a permutation of the tiles.  Costs are cleared for the next accumulation.
 // `accum` (optional): the costs read here are also added to a second cost buffer (the per-phase sorts of a free-running
 // frameCount feed the all-phase average this way, rt_abi.cpp).
+// `keep` (optional): the costs as read, which the split plan behind a replaying frame's sort works on (rt_split_plan_kernel).
 __global__ __launch_bounds__(1024) void rt_lpt_sort_kernel(unsigned *__restrict__ cost, unsigned *__restrict__ snap,
-                                                           unsigned *__restrict__ order, int nTiles, unsigned *__restrict__ accum) {
+                                                           unsigned *__restrict__ order, int nTiles, unsigned *__restrict__ accum,
+                                                           unsigned *__restrict__ keep) {
     __shared__ unsigned bins[256];
     __shared__ unsigned maxCost;
     if (threadIdx.x < 256) bins[threadIdx.x] = 0;
@@ -1023,6 +1105,7 @@ __global__ __launch_bounds__(1024) void rt_lpt_sort_kernel(unsigned *__restrict_
     for (int i = threadIdx.x; i < nTiles; i += 1024) {
         const unsigned c = __hip_atomic_load(&cost[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         snap[i] = c;
+        if (keep) keep[i] = c;
         if (accum) atomicAdd(&accum[i], c);
         mx = max(mx, c);
     }
@@ -1066,9 +1149,102 @@ hipError_t rt_launch_iota(unsigned *dOrder, int n, hipStream_t s) {
     return hipGetLastError();
 }
 
-hipError_t rt_launch_lpt_sort(unsigned *dCost, unsigned *dSnap, unsigned *dOrder, int nTiles, hipStream_t s, unsigned *dAccum) {
+hipError_t rt_launch_lpt_sort(unsigned *dCost, unsigned *dSnap, unsigned *dOrder, int nTiles, hipStream_t s, unsigned *dAccum, unsigned *dKeep) {
     if (nTiles <= 0) return hipSuccess;
-    hipLaunchKernelGGL(rt_lpt_sort_kernel, dim3(1), dim3(1024), 0, s, dCost, dSnap, dOrder, nTiles, dAccum);
+    hipLaunchKernelGGL(rt_lpt_sort_kernel, dim3(1), dim3(1024), 0, s, dCost, dSnap, dOrder, nTiles, dAccum, dKeep);
+    return hipGetLastError();
+}
+
+// The SPLIT PLAN of a replaying frame, one workgroup behind the sort that wrote `order`.  target = the
+// costs' sum / the device's resident wave slots: what a slot carries when the frame divides evenly.  The order is walked from
+// its head; a tile is split when its cost exceeds the target (or it is split in the plan in use: its cost is then the sum of
+// its parts', and it stays split) into the fewest parts P with cost (g + (1 - g) / P) <= target, at most RT_SPLIT_MAX_PARTS and
+// at most the units a K = 0 tile of this frame can have; the first RT_SPLIT_MAX_TILES such tiles get a scratch slot each, in
+// walking order, and their parts beyond 0 the extra jobs, in the same order.  Integer arithmetic throughout (g = RT_SPLIT_G256 /
+// 256), so that tests/test_tile_split.py restates it exactly.  forceParts (RT_DEBUG_SPLIT_PARTS): every tile is split into that many.
+__global__ __launch_bounds__(1024) void rt_split_plan_kernel(const unsigned *__restrict__ order, const unsigned *__restrict__ cost, int nTiles,
+                                                             unsigned waveSlots, int depth, int nLt, int forceParts,
+                                                             const unsigned char *__restrict__ prevParts, unsigned char *__restrict__ parts,
+                                                             unsigned short *__restrict__ slot, unsigned *__restrict__ extra,
+                                                             unsigned *__restrict__ counts, unsigned epoch, unsigned *__restrict__ hostSeen) {
+    __shared__ unsigned long long sum;
+    __shared__ unsigned scan[1024];
+    __shared__ unsigned base;         // tiles that want a split (high half) and their extra jobs (low half) in the chunks walked so far
+    __shared__ unsigned nSplit, nExtra;
+    if (threadIdx.x == 0) { sum = 0ull; base = 0u; nSplit = 0u; nExtra = 0u; }
+    __syncthreads();
+    unsigned long long mine = 0ull;
+    for (int i = threadIdx.x; i < nTiles; i += 1024) { mine += cost[i]; parts[i] = 0; slot[i] = 0; }
+    atomicAdd(&sum, mine);
+    __syncthreads();
+    const unsigned long long target = sum / (waveSlots ? waveSlots : 1u);
+    // what a K = 0 tile can own: the units of the depths behind the replayed one; and what the scratch layout takes
+    const unsigned unitsOwn = depth > 1 ? rt_split_units(depth - 1, nLt) : 0u, unitsAll = rt_split_units(depth, nLt);
+    unsigned cap = unitsOwn < (unsigned)RT_SPLIT_MAX_PARTS ? unitsOwn : (unsigned)RT_SPLIT_MAX_PARTS;
+    if (depth > RT_MAX_DEPTH) cap = 0u;
+    for (int r0 = 0; r0 < nTiles; r0 += 1024) {
+        const int r = r0 + (int)threadIdx.x;
+        unsigned tile = 0u, P = 0u;
+        if (r < nTiles) {
+            tile = order[r];
+            if (tile < (unsigned)nTiles) {
+                const unsigned long long c = cost[tile];
+                const unsigned prev = prevParts ? prevParts[tile] : 0u;
+                if (forceParts >= 2) P = (unsigned)forceParts;
+                else if (c > target || prev >= 2u) {
+                    P = 2u;
+                    while (P < (unsigned)RT_SPLIT_MAX_PARTS && c * (RT_SPLIT_G256 * P + (256u - RT_SPLIT_G256)) > target * 256ull * P) P++;
+                    if (prev > P) P = prev;
+                }
+                if (P > cap) P = cap;
+                if (P < 2u || unitsAll > (unsigned)RT_SPLIT_UNITS_PER_PART * P) P = 0u;
+            }
+        }
+        // inclusive scan of (split << 16 | extra jobs) over the chunk
+        const unsigned v = P ? ((1u << 16) | (P - 1u)) : 0u;
+        scan[threadIdx.x] = v;
+        __syncthreads();
+        for (int o = 1; o < 1024; o <<= 1) {
+            const unsigned a = (int)threadIdx.x >= o ? scan[threadIdx.x - o] : 0u;
+            __syncthreads();
+            scan[threadIdx.x] += a;
+            __syncthreads();
+        }
+        const unsigned before = base + scan[threadIdx.x] - v;
+        const unsigned mySlot = before >> 16, myExtra = before & 0xffffu;
+        if (P && mySlot < (unsigned)RT_SPLIT_MAX_TILES && myExtra + (P - 1u) <= (unsigned)RT_SPLIT_EXTRA_BLOCKS) {
+            parts[tile] = (unsigned char)P;
+            slot[tile] = (unsigned short)mySlot;
+            for (unsigned k = 1; k < P; k++) extra[myExtra + k - 1u] = tile | (k << 28);
+            atomicMax(&nSplit, mySlot + 1u);          // (the tiles that get a slot are a prefix of the walk: so are their jobs)
+            atomicMax(&nExtra, myExtra + P - 1u);
+        }
+        __syncthreads();
+        if (threadIdx.x == 1023) base += scan[1023];
+        __syncthreads();
+        if ((base >> 16) >= (unsigned)RT_SPLIT_MAX_TILES) break;          // (uniform: every slot is taken)
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        counts[0] = nExtra; counts[1] = nSplit;
+        if (hostSeen) {          // two words of pinned host memory that the scheduler reads without waiting (rt_sched.h): the epoch last
+            hostSeen[0] = nSplit;
+            __hip_atomic_store(&hostSeen[1], epoch, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+    }
+}
+__global__ void rt_split_desc_kernel(RtSplitDesc *__restrict__ out, const RtSplitDesc v) { *out = v; }
+
+hipError_t rt_launch_split_plan(const unsigned *dOrder, const unsigned *dCost, int nTiles, unsigned waveSlots, int depth, int nLt, int forceParts,
+                                const unsigned char *dPrevParts, unsigned char *dParts, unsigned short *dSlot, unsigned *dExtra,
+                                unsigned *dCounts, unsigned epoch, unsigned *hSeen, hipStream_t s) {
+    if (nTiles <= 0) return hipSuccess;
+    hipLaunchKernelGGL(rt_split_plan_kernel, dim3(1), dim3(1024), 0, s, dOrder, dCost, nTiles, waveSlots, depth, nLt, forceParts, dPrevParts, dParts,
+                       dSlot, dExtra, dCounts, epoch, hSeen);
+    return hipGetLastError();
+}
+hipError_t rt_launch_split_desc(RtSplitDesc *dDesc, const RtSplitDesc &v, hipStream_t s) {
+    hipLaunchKernelGGL(rt_split_desc_kernel, dim3(1), dim3(1), 0, s, dDesc, v);
     return hipGetLastError();
 }
 

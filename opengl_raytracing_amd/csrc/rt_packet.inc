@@ -1482,6 +1482,34 @@ __device__ __forceinline__ void render_packet(const RtFrame &f, const RtDeviceSc
     [[maybe_unused]] volatile unsigned *const taintWord = (volatile unsigned *)sc.park - 4;
     [[maybe_unused]] auto records = [&]() -> unsigned char * { return (unsigned char *)((uintptr_t)firstHit & ~RT_FIRST_HIT_SWITCHES); };
     if constexpr (FIRST == 1) *taintWord = 0u;
+    // TILE SPLIT (FIRST == 3: a replaying frame launched with a split plan, DESIGN.md section 38).  The tile is run by P one-wave jobs, this one being `part` (P = 1: the tile
+    // is whole, and nothing below does anything).  Every job traces the whole path geometry -- closest hits, hit set-up,
+    // roulette, next direction: deterministic, so all of them hold the same bits -- but evaluates only the lighting UNITS it
+    // owns: unit d * (nLt + 1) + li is light li of depth d, li = nLt that depth's subsurface section, and a job owns the units
+    // u with u mod P == part.  A split job adds nothing into finalColor: it stores each owned unit's v3 into the tile's scratch
+    // slot (rt_device.h has the layout), part 0 also what the sums need of each depth, and the job that arrives last at the
+    // slot's counter replays the additions in the source's order (below, ahead of the surface stores).  The kernel has left
+    // (the depths passed, part | P << 8, the slot's address) in the four words of the counter slot, which a replaying
+    // launch has no other use for: nothing of this stays in a register across the shadow rays.
+    [[maybe_unused]] volatile unsigned *const splitWord = (volatile unsigned *)sc.park - 4;
+    // (part | P << 8 is fetched once per depth: a word of LDS read inside the light loop would wait for the light's scalar loads too)
+    [[maybe_unused]] auto splitState = [&]() -> unsigned { return (unsigned)__builtin_amdgcn_readfirstlane((int)splitWord[1]); };
+    [[maybe_unused]] auto splitOwns = [&](unsigned pw, int depth_, int li_) -> bool {          // wave-uniform
+        const unsigned P_ = pw >> 8, u = (unsigned)depth_ * (unsigned)(f.nLt + 1) + (unsigned)li_;
+        const unsigned q = P_ == 3u ? (u * 43691u) >> 17 : u >> (P_ >> 1);       // u / P for P = 1 .. 4, u < 2^15
+        return u - q * P_ == (pw & 0xffu);
+    };
+    // column c of unit u (u < 0: of depth -1 - u's record, or -33: the sky term's) in the slot, this lane's entry
+    [[maybe_unused]] auto splitSlot = [&]() -> unsigned long long {
+        return ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)splitWord[3]) << 32) |
+               (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)splitWord[2]);
+    };
+    [[maybe_unused]] auto splitColumn = [&](int u, int c) -> float * {
+        const unsigned long long at = splitSlot();
+        const unsigned units = rt_split_units(f.p.maxRayDepth, f.nLt);
+        const unsigned col = u >= 0 ? (unsigned)u * 4u : u == -33 ? (units + (unsigned)f.p.maxRayDepth) * 4u : (units + (unsigned)(-1 - u)) * 4u;
+        return (float *)at + 64u + (col + (unsigned)c) * 64u + (threadIdx.x & 63);
+    };
     int gxI, gyI;
     size_t outIdx;
     const bool inWindow0 = pixel(gxI, gyI, outIdx);
@@ -1514,7 +1542,7 @@ __device__ __forceinline__ void render_packet(const RtFrame &f, const RtDeviceSc
     // less scratch traffic, which the paired subsurface probes it makes room for win back: 25.4 ms); PCSS profiles, with the
     // subsurface probes in pairs: C3 3.44 -> 3.39 ms, scratch 156 -> 68 B/lane (with single probes it was 3.73).
     v3 P = V3(0.0f, 0.0f, 0.0f), N = V3(0.0f, 0.0f, 0.0f);
-    if constexpr (FIRST != 2) {         // (a replaying tile's columns are filled already, record included: pk_replay_park)
+    if constexpr (FIRST < 2) {         // (a replaying tile's columns are filled already, record included: pk_replay_park)
         float *pk_ = sc.park + threadIdx.x;
         pk_[0 * BT] = 0.0f; pk_[1 * BT] = 0.0f; pk_[2 * BT] = 0.0f;            // finalColor
         pk_[3 * BT] = 1.0f; pk_[4 * BT] = 1.0f; pk_[5 * BT] = 1.0f;            // throughput
@@ -1590,7 +1618,7 @@ __device__ __forceinline__ void render_packet(const RtFrame &f, const RtDeviceSc
     // of the loop's hit set-up (P is the record's, N and V follow from it), runs that depth's roulette and next direction,
     // and the loop starts at depth K + 1: its body is, to the letter, what a K = 0 tile needs, and carries nothing for this.
     int depth0 = 0;
-    if constexpr (FIRST == 2) {
+    if constexpr (FIRST >= 2) {
         float *pk_ = sc.park + threadIdx.x;
         const int k = __builtin_amdgcn_readfirstlane(__float_as_int(pk_[PK_PARK_REC_K * BT]));
         if (k > 0) {
@@ -1635,11 +1663,14 @@ __device__ __forceinline__ void render_packet(const RtFrame &f, const RtDeviceSc
             if constexpr (FIRST == 1) { if (depth == 0) { firstRecordHit(maxDist, -1); firstRecordColour(); } }
             break;
         }
-        bool replay = false;            // this bounce comes from the record: wave-uniform, and false wherever FIRST != 2
-        if constexpr (FIRST == 2) replay = depth == 0;
+        bool replay = false;            // this bounce comes from the record: wave-uniform, and false wherever FIRST < 2
+        if constexpr (FIRST >= 2) replay = depth == 0;
         float t;
         int idx;
         unsigned long long tHit = 0ull;
+        [[maybe_unused]] bool skyMiss = false;          // (FIRST == 3: this lane's miss of a split tile adds the sky)
+        [[maybe_unused]] unsigned pw = 0x100u;          // (FIRST == 3: part | P << 8 of this job)
+        if constexpr (FIRST == 3) pw = splitState();
         if (replay) {
             const float *pk_ = sc.park + threadIdx.x;          // (t, hit) as pk_replay_park left them; finalColor after depth 0 stands in its columns
             const int hitRec = __float_as_int(pk_[PK_PARK_REC_HIT * BT]);
@@ -1655,12 +1686,35 @@ __device__ __forceinline__ void render_packet(const RtFrame &f, const RtDeviceSc
             if (missed && f.p.useSkybox && dsc.sky) {
                 float *pk_ = sc.park + threadIdx.x;
                 const v3 fc = V3(pk_[0 * BT], pk_[1 * BT], pk_[2 * BT]), thr = V3(pk_[3 * BT], pk_[4 * BT], pk_[5 * BT]);
+                if constexpr (FIRST == 3) {
+                    // (a lane misses once, and nothing is added for it afterwards: a split tile has one sky term per lane)
+                    const v3 term = thr * sample_cube(dsc.sky, f.skySize, ray.d);
+                    if ((pw >> 8) > 1u) {
+                        skyMiss = true;
+                        if ((pw & 0xffu) == 0u) { *splitColumn(-33, 0) = term.x; *splitColumn(-33, 1) = term.y; *splitColumn(-33, 2) = term.z; }
+                    } else {
+                        const v3 nf = fc + term;
+                        pk_[0 * BT] = nf.x; pk_[1 * BT] = nf.y; pk_[2 * BT] = nf.z;
+                    }
+                } else {
                 const v3 nf = fc + thr * sample_cube(dsc.sky, f.skySize, ray.d);
                 pk_[0 * BT] = nf.x; pk_[1 * BT] = nf.y; pk_[2 * BT] = nf.z;
+                }
             }
         }
         }
         alive = alive && idx >= 0;          // a miss ends the path (:533)
+        if constexpr (FIRST == 3) {
+            if (!replay) {
+                *splitWord = *splitWord | (1u << (depth & 31));          // (every lane the same word: this depth's lighting is passed)
+                if ((pw >> 8) > 1u && (pw & 0xffu) == 0u) {              // part 0: what the sums need of this depth
+                    asm volatile("" ::: "memory");
+                    const float *pk_ = sc.park + threadIdx.x;
+                    *splitColumn(-1 - depth, 0) = pk_[3 * BT]; *splitColumn(-1 - depth, 1) = pk_[4 * BT]; *splitColumn(-1 - depth, 2) = pk_[5 * BT];
+                    *splitColumn(-1 - depth, 3) = __uint_as_float((alive ? 1u : 0u) | (skyMiss ? 2u : 0u));
+                }
+            }
+        }
         if constexpr (FIRST == 1) { if (depth == 0) firstRecordHit(t, alive ? idx : -1); }
         if (!wave_any(alive)) {
             if constexpr (FIRST == 1) { if (depth == 0) firstRecordColour(); }
@@ -1717,6 +1771,7 @@ __device__ __forceinline__ void render_packet(const RtFrame &f, const RtDeviceSc
         const unsigned long long tLights = pk_clock<COUNT>();
         pk_stat<COUNT>(sc, 29, tLights - tHit);                                  // [29] hit shading set-up (normal, material, origin box, parking)
         for (int li = 0; li < f.nLt; li++) {
+            if constexpr (FIRST == 3) { if (!splitOwns(pw, depth, li)) continue; }          // (a whole tile owns every unit)
             const int lb4 = sc.lgtF4Base + li * RT_LGT_F4;
             const float4 l0 = uni_load4(sc, lb4), l1 = uni_load4(sc, lb4 + 1), l2 = uni_load4(sc, lb4 + 2), l3 = uni_load4(sc, lb4 + 3);
             const int ltype = __builtin_amdgcn_readfirstlane(__float_as_int(l0.w));
@@ -1856,14 +1911,30 @@ __device__ __forceinline__ void render_packet(const RtFrame &f, const RtDeviceSc
             } else {
             radiance = (V3(l2) * attenuation) * l1.w;
             }
+            if constexpr (FIRST == 3) {
+                const v3 term = compute_pbr<PROFILE::fastPbr>(ml, Nl, Vl, L, H, radiance, alive) * shadowFactor;
+                if ((pw >> 8) > 1u) {
+                    const int u = depth * (f.nLt + 1) + li;
+                    *splitColumn(u, 0) = term.x; *splitColumn(u, 1) = term.y; *splitColumn(u, 2) = term.z;
+                } else {
+                    Lo = Lo + term;
+                }
+            } else {
             Lo = Lo + compute_pbr<PROFILE::fastPbr>(ml, Nl, Vl, L, H, radiance, alive) * shadowFactor;
+            }
         }
         const unsigned long long tSss = pk_clock<COUNT>();
         pk_stat<COUNT>(sc, 26, tSss - tLights);                                  // [26] the whole light loop
         // ---- computeSubsurfaceScattering (:316-339), entered if any lane needs it
         const float4 m2 = pk_lane_mat(sc, ii, 2);          // (subsurfaceColor, subsurfaceScatter)
         const bool needSss = alive && m2.w > 0.0f;
-        if (wave_any(needSss)) {
+        bool enterSss = wave_any(needSss);
+        if constexpr (FIRST == 3) {          // the subsurface section is the depth's unit nLt; its owner in a split tile also keeps which lanes it is for
+            const bool owns = splitOwns(pw, depth, f.nLt);
+            enterSss = enterSss && owns;
+            if (owns && (pw >> 8) > 1u) *splitColumn(depth * (f.nLt + 1) + f.nLt, 3) = __uint_as_float(needSss ? 1u : 0u);
+        }
+        if (enterSss) {
             const float scatterDistance = pk_lane_mat(sc, ii, 3).x;
             v3 sss = V3(0.0f, 0.0f, 0.0f);
             if constexpr (PROFILE::sssGroup > 1) {       // the four probes PROFILE::sssGroup per traversal
@@ -1907,11 +1978,23 @@ __device__ __forceinline__ void render_packet(const RtFrame &f, const RtDeviceSc
                     sss = sss + V3(pk_lane_mat(sc, si, 0)) * att;
                 }
             }
+            if constexpr (FIRST == 3) {
+                const v3 term = ((sss * V3(m2)) * m2.w) / 4.0f;
+                if ((pw >> 8) > 1u) {
+                    const int u = depth * (f.nLt + 1) + f.nLt;
+                    if (needSss) { *splitColumn(u, 0) = term.x; *splitColumn(u, 1) = term.y; *splitColumn(u, 2) = term.z; }
+                } else if (needSss) {
+                    Lo = Lo + term;
+                }
+            } else {
             if (needSss) Lo = Lo + ((sss * V3(m2)) * m2.w) / 4.0f;
+            }
         }
         tAfter = pk_clock<COUNT>();
         pk_stat<COUNT>(sc, 27, tAfter - tSss);                                 // [27] subsurface section
-        if (alive) {        // finalColor += throughput * Lo, in place
+        bool addLo = alive;
+        if constexpr (FIRST == 3) addLo = alive && (pw >> 8) == 1u;          // (a split tile's sums are made at its end)
+        if (addLo) {        // finalColor += throughput * Lo, in place
             asm volatile("" ::: "memory");
             float *pk_ = sc.park + threadIdx.x;
             const v3 fc = V3(pk_[0 * BT], pk_[1 * BT], pk_[2 * BT]), thr = V3(pk_[3 * BT], pk_[4 * BT], pk_[5 * BT]);
@@ -1949,6 +2032,42 @@ __device__ __forceinline__ void render_packet(const RtFrame &f, const RtDeviceSc
         finalColor = V3(pk_[0 * BT], pk_[1 * BT], pk_[2 * BT]);
         P = V3(pk_[9 * BT], pk_[10 * BT], pk_[11 * BT]);
         N = V3(pk_[12 * BT], pk_[13 * BT], pk_[14 * BT]);
+    }
+    if constexpr (FIRST == 3) {
+        const unsigned P_ = splitState() >> 8;
+        if (P_ > 1u) {
+            // A split tile's job has stored its units (part 0 the depths' records too): an agent-scope release -- L2 is per
+            // XCD, and the jobs of a tile run wherever they were dispatched -- behind a wait for every store, then ONE add on the
+            // slot's counter.  Every job but the last to arrive ends here; no job ever waits for another.  The last one puts
+            // the counter back for the next frame, makes the acquire that its loads below sit behind, and adds up in the
+            // source's order: per depth Lo = 0, + each light's term, + the subsurface term where the lane needs it, then
+            // finalColor + throughput * Lo where the lane is alive; the sky term where the lane's miss adds it.
+            unsigned *const counter = (unsigned *)splitSlot();
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            unsigned seen = 0u;
+            if ((threadIdx.x & 63) == 0) seen = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            seen = (unsigned)__builtin_amdgcn_readfirstlane((int)seen);
+            if (seen != P_ - 1u) return;
+            if ((threadIdx.x & 63) == 0) __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+            const unsigned passed = (unsigned)__builtin_amdgcn_readfirstlane((int)splitWord[0]);
+            for (int d = 0; d < f.p.maxRayDepth && d < RT_MAX_DEPTH; d++) {
+                if (!((passed >> d) & 1u)) continue;
+                const unsigned bits = __float_as_uint(*splitColumn(-1 - d, 3));
+                if (bits & 2u) finalColor = finalColor + V3(*splitColumn(-33, 0), *splitColumn(-33, 1), *splitColumn(-33, 2));
+                if (bits & 1u) {
+                    const v3 thr = V3(*splitColumn(-1 - d, 0), *splitColumn(-1 - d, 1), *splitColumn(-1 - d, 2));
+                    v3 Lo = V3(0.0f, 0.0f, 0.0f);
+                    const int u0 = d * (f.nLt + 1);
+                    for (int li = 0; li < f.nLt; li++) Lo = Lo + V3(*splitColumn(u0 + li, 0), *splitColumn(u0 + li, 1), *splitColumn(u0 + li, 2));
+                    if (__float_as_uint(*splitColumn(u0 + f.nLt, 3)) & 1u)
+                        Lo = Lo + V3(*splitColumn(u0 + f.nLt, 0), *splitColumn(u0 + f.nLt, 1), *splitColumn(u0 + f.nLt, 2));
+                    finalColor = finalColor + thr * Lo;
+                }
+            }
+        }
     }
     if (inWindow) {
         if (inImageS) {

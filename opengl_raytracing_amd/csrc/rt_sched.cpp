@@ -32,6 +32,17 @@ void RtTileScheduler::init(hipStream_t contextStream) {
     if (const char *e = getenv("RT_DEBUG_TILE_ORDER")) dbgWantOrder = atoi(e) != 0;
     if (const char *e = getenv("RT_PRED_MIN_TILES")) predMinTiles = atoi(e);
     if (const char *e = getenv("RT_PHASE_ORDER")) phaseOn = atoi(e) != 0;
+    if (const char *e = getenv("RT_TILE_SPLIT")) splitOn = atoi(e) != 0;
+    if (const char *e = getenv("RT_DEBUG_SPLIT_PARTS")) {
+        const int v = atoi(e);
+        if (v >= 2 && v <= RT_SPLIT_MAX_PARTS) splitForce = v;
+    }
+    // the resident wave slots a frame fills are SIMDs x the kernel's waves per SIMD; a CDNA compute unit has four SIMDs
+    int dev = 0, cus = 0;
+    if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0)
+        simds = 4u * (unsigned)cus;
+    else
+        (void)hipGetLastError();
 }
 
 void RtTileScheduler::setMode(int variant) {
@@ -122,8 +133,26 @@ hipError_t RtTileScheduler::measuredBegin(RtDeviceScene &sc, hipStream_t s, Plan
         fbTiles = 0;
         fbCur = -1;
         sortPending = false;
+        planValid[0] = planValid[1] = false;
+        splitEpoch++;
         for (DevBuf<unsigned> *b : {&dTileCost, &dTileSnap, &dTileOrder[0], &dTileOrder[1]}) SCHED_TRY(b->release());
         for (DevBuf<unsigned> *b : {&dTileCost, &dTileSnap, &dTileOrder[0], &dTileOrder[1]}) SCHED_TRY(b->grow(nTiles));
+        // the split plans live and die with the orders they belong to (a context with the split off never makes one)
+        SCHED_TRY(dCostKeep.release());
+        for (int k = 0; k < 2; k++) { SCHED_TRY(dSplitParts[k].release()); SCHED_TRY(dSplitSlot[k].release()); }
+        if (splitOn) {
+            if (!hSplitSeen) {
+                SCHED_TRY(hSplitSeen.grow(2));
+                hSplitSeen.ptr[0] = hSplitSeen.ptr[1] = 0u;
+            }
+            SCHED_TRY(dCostKeep.grow(nTiles));
+            for (int k = 0; k < 2; k++) {
+                SCHED_TRY(dSplitParts[k].grow(nTiles));
+                SCHED_TRY(dSplitSlot[k].grow(nTiles));
+                SCHED_TRY(dSplitExtra[k].grow(RT_SPLIT_EXTRA_BLOCKS));
+                SCHED_TRY(dSplitCounts[k].grow(2));
+            }
+        }
     }
     *newGeometry = !(fbTiles == nTiles && fbTilesX == plan->tilesX && fbBt == plan->bt && fbClass == plan->costClass);
     if (*newGeometry) {
@@ -140,6 +169,8 @@ hipError_t RtTileScheduler::measuredBegin(RtDeviceScene &sc, hipStream_t s, Plan
         fbCur = -1;
         sortPending = false;
         fbAge = 0;
+        planValid[0] = planValid[1] = false;          // the feedback restarts: so does the split
+        splitEpoch++;
     } else if (sortPending) {
         // The sort runs on the context's own stream, beside the frames; its order is adopted by the first launch
         // issued after it has completed, so no render stream waits for a sort in steady state.
@@ -178,7 +209,28 @@ hipError_t RtTileScheduler::measuredEnd(const Plan &plan) {
         // the buffer about to be rewritten was last read before the previous adoption: every stream's last
         // launch (this one included) is after those reads, and gives the sort this frame's costs
         SCHED_PASS(waitForLaunches(own, true));
-        SCHED_TRY(rt_launch_lpt_sort(dTileCost, dTileSnap, dTileOrder[next], plan.nTiles, own));
+        // replaying frames: the split plan of the new order, behind the sort and ahead of its event -- adopted with the order
+        // (a frame of more units than any split takes gets no plan at all)
+        // Not for frames in flight on several streams, which fill each other's tails, nor while frameCount advances: the order is
+        // then the all-phase average, the tiles that are long in one frame are not the ones that are long on average, and the
+        // split only added its work (measured: the first free-running period +8.5 %, two frames in flight +2 % with plans made
+        // that no launch used).  RT_DEBUG_SPLIT_PARTS plans regardless of frameCount.
+        const bool planned = splitOn && plan.costClass == 1 && plan.sameStream && (freeRun == 0 || splitForce) && simds > 0 && plan.waves > 0 && dCostKeep.holds(plan.nTiles) && hSplitSeen &&
+                             plan.depth >= 2 && plan.depth <= RT_MAX_DEPTH &&
+                             rt_split_units(plan.depth, plan.nLt) <= (unsigned)(RT_SPLIT_UNITS_PER_PART * RT_SPLIT_MAX_PARTS) &&
+                             (unsigned)plan.nTiles <= (unsigned)RT_SPLIT_MAX_TILES_PER_SLOT * simds * (unsigned)plan.waves;
+        SCHED_TRY(rt_launch_lpt_sort(dTileCost, dTileSnap, dTileOrder[next], plan.nTiles, own, nullptr, planned ? dCostKeep.ptr : nullptr));
+        planValid[next] = false;
+        if (planned) {
+            const int cur = fbCur >= 0 && planValid[fbCur] && planDepth[fbCur] == plan.depth && planNLt[fbCur] == plan.nLt ? fbCur : -1;
+            SCHED_TRY(rt_launch_split_plan(dTileOrder[next], dCostKeep, plan.nTiles, simds * (unsigned)plan.waves, plan.depth, plan.nLt, splitForce,
+                                           cur >= 0 ? dSplitParts[cur].ptr : nullptr, dSplitParts[next], dSplitSlot[next], dSplitExtra[next],
+                                           dSplitCounts[next], splitEpoch, hSplitSeen, own));
+            planValid[next] = true;
+            planDepth[next] = plan.depth;
+            planNLt[next] = plan.nLt;
+            planGen[next] = ++planCount;
+        }
         SCHED_TRY(evSort[next].create(hipEventDisableTiming));
         SCHED_TRY(hipEventRecord(evSort[next], own));
         fbNext = next;
@@ -190,6 +242,94 @@ hipError_t RtTileScheduler::measuredEnd(const Plan &plan) {
     fbTilesX = plan.tilesX;
     fbBt = plan.bt;
     fbClass = plan.costClass;
+    return hipSuccess;
+}
+
+// ---- tile split (rt_sched.h has the rule) ----------------------------------------------------------------------------------
+
+hipError_t RtTileScheduler::splitFor(const Plan &plan, const RtDeviceScene &sc, const void *records, hipStream_t s, const RtSplitDesc **out) {
+    *out = nullptr;
+    dbgSplitK = -1;
+    dbgSplitTiles = plan.nTiles;
+    const int k = fbCur;
+    if (!(splitOn && plan.sortAfter && plan.costClass == 1 && plan.sameStream && k >= 0 && planValid[k] && sc.tileOrder == dTileOrder[k].ptr &&
+          planDepth[k] == plan.depth && planNLt[k] == plan.nLt && plan.depth >= 2 && plan.depth <= RT_MAX_DEPTH && records))
+        return hipSuccess;
+    if (rt_split_units(plan.depth, plan.nLt) > (unsigned)(RT_SPLIT_UNITS_PER_PART * RT_SPLIT_MAX_PARTS)) return hipSuccess;
+    if (freeRun != 0 && !splitForce) return hipSuccess;          // (frameCount advances: measuredEnd has the why)
+    const volatile unsigned *seen = hSplitSeen.ptr;          // (split tiles, epoch) of the plan kernel that ran last
+    if (!(seen && seen[1] == splitEpoch && seen[0] > 0u)) return hipSuccess;
+    StreamRec *rec = plan.rec;
+    const size_t need = (size_t)RT_SPLIT_MAX_TILES * rt_split_slot_dwords(plan.depth, plan.nLt);
+    if (rec->splitRefused && need >= rec->splitRefused) return hipSuccess;          // (could not be had before: not asked for again)
+    if (!rec->splitScratch.holds(need) || !rec->splitDesc) {
+        // (a launch of this stream may still be working in a smaller scratch)
+        if (rec->splitScratch.ptr) SCHED_TRY(hipStreamSynchronize(s));
+        hipError_t e = rec->splitScratch.grow(need);
+        if (e == hipSuccess) e = rec->splitDesc.grow(2);
+        // every slot's arrival counter starts at zero, and the job that arrives last puts it back
+        if (e == hipSuccess) e = hipMemsetAsync(rec->splitScratch.ptr, 0, need * sizeof(float), s);
+        if (e != hipSuccess) {          // no scratch to be had: the frame runs whole, as it does without a first-hit buffer
+            (void)hipGetLastError();
+            (void)rec->splitScratch.release();
+            rec->splitRefused = need;
+            return hipSuccess;
+        }
+    }
+    if (rec->descGen[k] != planGen[k] || rec->descRecords[k] != records || rec->descScratch[k] != rec->splitScratch.ptr) {
+        RtSplitDesc d;
+        d.records = (const unsigned char *)records;
+        d.parts = dSplitParts[k];
+        d.slot = dSplitSlot[k];
+        d.extra = dSplitExtra[k];
+        d.counts = dSplitCounts[k];
+        d.scratch = rec->splitScratch;
+        // on the launch's stream: behind the stream's earlier launches that read this descriptor, ahead of this one
+        SCHED_TRY(rt_launch_split_desc(rec->splitDesc.ptr + k, d, s));
+        rec->descGen[k] = planGen[k];
+        rec->descRecords[k] = records;
+        rec->descScratch[k] = rec->splitScratch.ptr;
+    }
+    *out = rec->splitDesc.ptr + k;
+    dbgSplitK = k;
+    return hipSuccess;
+}
+
+hipError_t RtTileScheduler::splitTiles(unsigned char *out, int cap, int *nTiles) {
+    *nTiles = 0;
+    if (dbgSplitK == -2) return hipSuccess;
+    SCHED_PASS(drain());
+    *nTiles = dbgSplitTiles;
+    const int n = dbgSplitTiles < cap ? dbgSplitTiles : cap;
+    if (dbgSplitK < 0 || !dSplitParts[dbgSplitK].holds(dbgSplitTiles)) memset(out, 0, (size_t)n);
+    else SCHED_TRY(hipMemcpy(out, dSplitParts[dbgSplitK], (size_t)n, hipMemcpyDeviceToHost));
+    return hipSuccess;
+}
+
+hipError_t RtTileScheduler::splitPlanOf(const unsigned *order, const unsigned *costs, int nTiles, unsigned waveSlots, int depth, int nLt, int forceParts,
+                                        const unsigned char *prevParts, unsigned char *parts, unsigned short *slot, unsigned *extra, unsigned *counts) {
+    const size_t n = (size_t)nTiles;
+    DevBuf<unsigned> dOrder, dCost, dExtra, dCounts;
+    DevBuf<unsigned char> dPrev, dParts;
+    DevBuf<unsigned short> dSlot;
+    SCHED_TRY(dOrder.grow(n));
+    SCHED_TRY(dCost.grow(n));
+    SCHED_TRY(dParts.grow(n));
+    SCHED_TRY(dSlot.grow(n));
+    SCHED_TRY(dExtra.grow(RT_SPLIT_EXTRA_BLOCKS));
+    SCHED_TRY(dCounts.grow(2));
+    if (prevParts) SCHED_TRY(dPrev.grow(n));
+    SCHED_TRY(hipMemcpyAsync(dOrder, order, n * sizeof(unsigned), hipMemcpyHostToDevice, own));
+    SCHED_TRY(hipMemcpyAsync(dCost, costs, n * sizeof(unsigned), hipMemcpyHostToDevice, own));
+    if (prevParts) SCHED_TRY(hipMemcpyAsync(dPrev, prevParts, n, hipMemcpyHostToDevice, own));
+    SCHED_TRY(hipMemsetAsync(dExtra, 0xFF, RT_SPLIT_EXTRA_BLOCKS * sizeof(unsigned), own));      // an entry the plan leaves unwritten is no job
+    SCHED_TRY(rt_launch_split_plan(dOrder, dCost, nTiles, waveSlots, depth, nLt, forceParts, prevParts ? dPrev.ptr : nullptr, dParts, dSlot, dExtra,
+                                   dCounts, 0u, nullptr, own));
+    SCHED_TRY(hipStreamSynchronize(own));
+    SCHED_TRY(hipMemcpy(parts, dParts, n, hipMemcpyDeviceToHost));
+    SCHED_TRY(hipMemcpy(slot, dSlot, n * sizeof(unsigned short), hipMemcpyDeviceToHost));
+    SCHED_TRY(hipMemcpy(extra, dExtra, RT_SPLIT_EXTRA_BLOCKS * sizeof(unsigned), hipMemcpyDeviceToHost));
+    SCHED_TRY(hipMemcpy(counts, dCounts, 2 * sizeof(unsigned), hipMemcpyDeviceToHost));
     return hipSuccess;
 }
 
@@ -373,6 +513,11 @@ hipError_t RtTileScheduler::begin(const RtFrame &f, RtDeviceScene &sc, hipStream
     sc.tileOrder = nullptr;
     sc.tileCost = nullptr;
     SCHED_PASS(record(s, &plan->rec));
+    if (packet) {
+        plan->sameStream = haveLastPacket && lastPacketStream == s;
+        lastPacketStream = s;
+        haveLastPacket = true;
+    }
     if (!(packet && schedMode != 0 && f.p.regionW > 0 && f.p.regionH > 0)) {
         if (dbgWantOrder && packet && f.p.regionW > 0 && f.p.regionH > 0) {      // raster mode: the launch still has an order to report
             int bt = 0, tile = 0, tilesX = 0, nTiles = 0;
@@ -383,6 +528,9 @@ hipError_t RtTileScheduler::begin(const RtFrame &f, RtDeviceScene &sc, hipStream
     }
     int tile = 0;
     rt_packet_geometry(f.nObj, f.p.regionW, f.p.regionH, &plan->bt, &tile, &plan->tilesX, &plan->nTiles);
+    plan->depth = f.p.maxRayDepth;
+    plan->nLt = f.nLt;
+    plan->waves = rt_packet_profile_waves(f, sc);
     bool newGeometry = false;
     SCHED_PASS(measuredBegin(sc, s, plan, &newGeometry));
     if (newGeometry) phaseForget();

@@ -22,6 +22,14 @@ struct RtTileScheduler {
         unsigned long long predKey = 0;
         bool predValid = false;
         int predSet = 0;
+        // tile split (below): the scratch slots of this stream's split launches -- frames on different streams never share them --
+        // and the two descriptors its launches pass, one per plan buffer, with what each was last written from
+        DevBuf<float> splitScratch;
+        size_t splitRefused = 0;               // a scratch of this many floats could not be had on this stream
+        DevBuf<RtSplitDesc> splitDesc;
+        unsigned descGen[2] = {0, 0};
+        const void *descRecords[2] = {nullptr, nullptr};
+        const void *descScratch[2] = {nullptr, nullptr};
     };
     // What begin() decided for one launch; end() takes it back.
     struct Plan {
@@ -30,9 +38,12 @@ struct RtTileScheduler {
         int costClass = 0;                     // what the frame's tile costs are comparable with: 0 = whole frames, 1 = first-hit replays
         int phase = -1;                        // frameCount mod 64 when the frame records into (and sorts) its phase's buffers
         bool sortAfter = false;                // the frame was scheduled: the measured order's bookkeeping runs after it
+        int depth = 0, nLt = 0;                // the frame's maxRayDepth and lights, and the resident waves per SIMD of its kernel:
+        int waves = 0;                         // what a split plan made behind this frame is made for
+        bool sameStream = false;               // the context's previous packet launch was on this stream too
     };
 
-    void init(hipStream_t contextStream);      // + the environment overrides (RT_FB_PERIOD, RT_PRED_MIN_TILES, RT_PHASE_ORDER, RT_DEBUG_PRED_CLASSES, RT_DEBUG_TILE_ORDER)
+    void init(hipStream_t contextStream);      // + the environment overrides (RT_FB_PERIOD, RT_PRED_MIN_TILES, RT_PHASE_ORDER, RT_DEBUG_PRED_CLASSES, RT_DEBUG_TILE_ORDER, RT_TILE_SPLIT, RT_DEBUG_SPLIT_PARTS)
     void setMode(int variant);                 // rt_set_variant's bits 8 and 9; forgets the geometry
 
     // ---- stream protocol
@@ -55,6 +66,15 @@ struct RtTileScheduler {
     hipError_t afterFirstHitRecord(hipStream_t s, StreamRec *rec);
     hipError_t beforeFirstHitReplay(hipStream_t s, StreamRec *rec);
 
+    // ---- TILE SPLIT (rt_device.h has the device side).  Behind every sort of a replaying frame's costs
+    // (cost class 1, measured order) the plan kernel decides, on the context's stream and ahead of the sort's event, which tiles
+    // of the new order run as P one-wave jobs: the plan is double-buffered with the order and adopted with it -- the same event,
+    // the same seenGen wait.  A new geometry or cost class drops both plans, as it drops the orders.  splitFor(), between
+    // begin() and the launch of a REPLAYING frame: the descriptor to launch with, or null -- no plan for the order in use, a
+    // phase's or a predicted order, the previous packet launch on another stream (frames in flight on several streams fill each
+    // other's tails, and would only pay the split's extra work), no scratch to be had (no error: the frame runs whole).
+    hipError_t splitFor(const Plan &plan, const RtDeviceScene &sc, const void *records, hipStream_t s, const RtSplitDesc **out);
+
     // ---- debug read-outs (rt_debug_tile_costs, rt_debug_predicted_classes, rt_debug_tile_order)
     hipError_t tileCosts(unsigned *out, int cap, int *nTiles, int *tilesX);
     hipError_t predictedClasses(unsigned char *out, int cap, int *nTiles);
@@ -62,6 +82,13 @@ struct RtTileScheduler {
     // rt_debug_lpt_sort: rt_launch_lpt_sort on the caller's host arrays, in device buffers of its own on the context's stream;
     // synchronises.  Reads and writes nothing of the scheduler's (failedCall aside).
     hipError_t lptSortOf(unsigned *costs, int nTiles, unsigned *order, unsigned *accum);
+
+    // rt_debug_split_tiles: P per tile (0 = whole) of the plan the last replaying launch ran with; *nTiles = 0 before any
+    hipError_t splitTiles(unsigned char *out, int cap, int *nTiles);
+    // rt_debug_split_plan: rt_launch_split_plan on the caller's host arrays (order, costs; prevParts may be null), in device
+    // buffers of its own on the context's stream; synchronises.  counts = (extra jobs, split tiles).
+    hipError_t splitPlanOf(const unsigned *order, const unsigned *costs, int nTiles, unsigned waveSlots, int depth, int nLt, int forceParts,
+                           const unsigned char *prevParts, unsigned char *parts, unsigned short *slot, unsigned *extra, unsigned *counts);
 
     const char *failedCall = "";               // the HIP call behind the last error returned
 
@@ -100,6 +127,30 @@ private:
     unsigned fbAge = 0;                        // frames since that geometry was first seen
     unsigned adoptGen = 0;                     // bumped whenever fbCur changes to a freshly sorted buffer
     unsigned fbPeriod = 32;                    // re-sort period in frames (RT_FB_PERIOD overrides, for measurements)
+
+    // ---- tile split
+    bool splitOn = true;                       // RT_TILE_SPLIT=0 clears it: no plan is made, every replaying frame is the whole-tile one
+    int splitForce = 0;                        // RT_DEBUG_SPLIT_PARTS=2|3|4: every tile the layout takes is split into that many (tests)
+    unsigned simds = 0;                        // SIMDs of the device (init): the plan's target is the costs' sum / (simds x waves)
+    DevBuf<unsigned> dCostKeep;                // the costs the last sort read
+    DevBuf<unsigned char> dSplitParts[2];      // the plan of dTileOrder[k]: P per tile,
+    DevBuf<unsigned short> dSplitSlot[2];      // a split tile's scratch slot,
+    DevBuf<unsigned> dSplitExtra[2];           // the jobs beyond part 0
+    DevBuf<unsigned> dSplitCounts[2];          // and how many (extra jobs, split tiles)
+    // Whether the plans of the current feedback epoch split anything, as the device last said: (split tiles, epoch), two words of
+    // pinned host memory that every plan kernel writes and nobody waits for.  A launch takes the split kernel only once a plan
+    // of ITS epoch has been seen to split a tile -- the kernel that carries the split's code costs the whole tiles a few per
+    // cent, and a frame whose plans split nothing must not pay it.  The host may run many frames ahead of the device: those
+    // frames run whole; split tiles stay split within an epoch, so a count once seen above zero stays above zero.
+    PinnedBuf<unsigned> hSplitSeen;
+    unsigned splitEpoch = 1;                   // bumped whenever the feedback restarts (0 is no epoch's)
+    bool planValid[2] = {false, false};
+    int planDepth[2] = {0, 0}, planNLt[2] = {0, 0};
+    unsigned planGen[2] = {0, 0}, planCount = 0;
+    hipStream_t lastPacketStream = nullptr;    // the stream of the context's previous packet launch
+    bool haveLastPacket = false;
+    int dbgSplitK = -2;                        // plan buffer of the last replaying launch (-1: it ran whole, -2: there was none)
+    int dbgSplitTiles = 0;
 
     // ---- predicted order
     int predMinTiles = 49152;                  // frames of at least this many tiles get a predicted order while no measured one exists (RT_PRED_MIN_TILES)

@@ -87,6 +87,8 @@ def _signatures():
         "rt_debug_predicted_classes": (ci, [vp, vp, ci, P(ci)]),
         "rt_debug_tile_order": (ci, [vp, P(u32), ci, P(ci), P(ci)]),
         "rt_debug_lpt_sort": (ci, [vp, P(u32), ci, P(u32), P(u32)]),
+        "rt_debug_split_tiles": (ci, [vp, P(u8), ci, P(ci)]),
+        "rt_debug_split_plan": (ci, [vp, P(u32), P(u32), ci, u32, ci, ci, ci, P(u8), P(u8), P(u32), P(u32), P(u32)]),
         "rt_debug_shadow_tables": (ci, [vp, vp, sz, P(sz), P(ci)]),
         "rt_debug_mesa_math": (ci, [vp, vp, ci]),
         "rt_debug_device_math": (ci, [vp, ci, vp, vp, sz, vp]),
@@ -1369,6 +1371,34 @@ class RayTracer(_Handle):
             assert accum.size == costs.size
         self._call("rt_debug_lpt_sort", u32p(costs), costs.size, u32p(order), u32p(accum) if accum is not None else None)
         return order, costs, accum
+
+    def split_tiles(self):
+        """P per tile (uint8[nTiles], raster tile order; 0 = the tile ran whole) of the last replaying launch's split plan
+        (rt_debug_split_tiles); empty before the first replaying launch."""
+        n = ctypes.c_int(0)
+        probe = np.zeros(1, dtype=np.uint8)
+        self._call("rt_debug_split_tiles", _typed(probe, ctypes.c_uint8), 0, ctypes.byref(n))
+        out = np.zeros(max(n.value, 1), dtype=np.uint8)
+        self._call("rt_debug_split_tiles", _typed(out, ctypes.c_uint8), n.value, ctypes.byref(n))
+        return out[:n.value]
+
+    def split_plan(self, order, costs, wave_slots, depth, n_lights, force_parts=0, prev_parts=None):
+        """rt_split_plan_kernel on the given order and costs (rt_debug_split_plan) -> (parts uint8[n], slot uint32[n],
+        extra uint32[1536], (extra jobs, split tiles))."""
+        order = np.ascontiguousarray(order, dtype=np.uint32).reshape(-1)
+        costs = np.ascontiguousarray(costs, dtype=np.uint32).reshape(-1)
+        assert order.size == costs.size
+        parts, slot = np.zeros(order.size, dtype=np.uint8), np.zeros(order.size, dtype=np.uint32)
+        extra, counts = np.zeros(1536, dtype=np.uint32), np.zeros(2, dtype=np.uint32)
+        prev = None
+        if prev_parts is not None:
+            prev_parts = np.ascontiguousarray(prev_parts, dtype=np.uint8).reshape(-1)
+            assert prev_parts.size == order.size
+            prev = _typed(prev_parts, ctypes.c_uint8)
+        self._call("rt_debug_split_plan", _typed(order, ctypes.c_uint32), _typed(costs, ctypes.c_uint32), order.size, int(wave_slots), int(depth),
+                   int(n_lights), int(force_parts), prev, _typed(parts, ctypes.c_uint8), _typed(slot, ctypes.c_uint32),
+                   _typed(extra, ctypes.c_uint32), _typed(counts, ctypes.c_uint32))
+        return parts, slot, extra, (int(counts[0]), int(counts[1]))
 
     def shadow_tables(self):
         """(dwords uint32[n], words per cell) of the current scene's shadow tables (headers + cells), or (None, 0)."""
