@@ -79,6 +79,7 @@ hipError_t RtTileScheduler::record(hipStream_t s, StreamRec **out) {
     m->predValid = false;
     m->seenGen = 0;                // adoptGen starts at 1 with the first adoption: a new stream always orders itself
     m->seenFirst = 0;              // (firstGen likewise)
+    m->splitStride = 0;            // a recycled record's scratch is another stream's: this one zeroes it before its first split
     SCHED_TRY(hipEventRecord(m->last, s));
     *out = m;
     return hipSuccess;
@@ -260,21 +261,28 @@ hipError_t RtTileScheduler::splitFor(const Plan &plan, const RtDeviceScene &sc, 
     const volatile unsigned *seen = hSplitSeen.ptr;          // (split tiles, epoch) of the plan kernel that ran last
     if (!(seen && seen[1] == splitEpoch && seen[0] > 0u)) return hipSuccess;
     StreamRec *rec = plan.rec;
-    const size_t need = (size_t)RT_SPLIT_MAX_TILES * rt_split_slot_dwords(plan.depth, plan.nLt);
+    const size_t stride = rt_split_slot_dwords(plan.depth, plan.nLt);
+    const size_t need = (size_t)RT_SPLIT_MAX_TILES * stride;
     if (rec->splitRefused && need >= rec->splitRefused) return hipSuccess;          // (could not be had before: not asked for again)
     if (!rec->splitScratch.holds(need) || !rec->splitDesc) {
         // (a launch of this stream may still be working in a smaller scratch)
         if (rec->splitScratch.ptr) SCHED_TRY(hipStreamSynchronize(s));
+        rec->splitStride = 0;
         hipError_t e = rec->splitScratch.grow(need);
         if (e == hipSuccess) e = rec->splitDesc.grow(2);
-        // every slot's arrival counter starts at zero, and the job that arrives last puts it back
-        if (e == hipSuccess) e = hipMemsetAsync(rec->splitScratch.ptr, 0, need * sizeof(float), s);
         if (e != hipSuccess) {          // no scratch to be had: the frame runs whole, as it does without a first-hit buffer
             (void)hipGetLastError();
             (void)rec->splitScratch.release();
             rec->splitRefused = need;
             return hipSuccess;
         }
+    }
+    if (rec->splitStride != stride) {
+        // Every slot's arrival counter starts at zero, and the job that arrives last puts it back -- at ITS stride.  A frame of
+        // another depth or light count finds slot j's counter at j * stride, in what the earlier frames left of their columns.
+        // On the launch's stream: behind the stream's earlier split launches, ahead of the descriptor and of this one.
+        SCHED_TRY(hipMemsetAsync(rec->splitScratch.ptr, 0, need * sizeof(float), s));
+        rec->splitStride = stride;
     }
     if (rec->descGen[k] != planGen[k] || rec->descRecords[k] != records || rec->descScratch[k] != rec->splitScratch.ptr) {
         RtSplitDesc d;

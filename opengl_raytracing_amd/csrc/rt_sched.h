@@ -25,6 +25,8 @@ struct RtTileScheduler {
         // tile split (below): the scratch slots of this stream's split launches -- frames on different streams never share them --
         // and the two descriptors its launches pass, one per plan buffer, with what each was last written from
         DevBuf<float> splitScratch;
+        size_t splitStride = 0;                // rt_split_slot_dwords() of the launches whose counters it holds at zero (0: nobody's;
+                                               // under another stride the counters lie in old column data: splitFor zeroes it first)
         size_t splitRefused = 0;               // a scratch of this many floats could not be had on this stream
         DevBuf<RtSplitDesc> splitDesc;
         unsigned descGen[2] = {0, 0};
