@@ -1387,7 +1387,13 @@ int rt_wire_unpack(rt_context *ctx, const void *dWire, size_t rankStrideBytes, s
  *      access; csrc/rt_mgpu.cpp) -- no gather buffer, no collective.  Asynchronous: the root context's stream (returned by
  *      rt_mgpu_get_surfaces) is ordered behind every device's stores, so work enqueued on it afterwards sees the whole frame;
  *      rt_mgpu_sync / rt_mgpu_readback wait for it.  p describes the WHOLE frame (identity window and strip fields).
- *      rt_mgpu_last_ms: duration of every device's share of the last frame (HIP events on its stream). */
+ *      rt_mgpu_last_ms: duration of every device's share of the last frame (HIP events on its stream).
+ *      A refused rt_mgpu_render changes nothing: parameters that are not a whole frame's, a maxRayDepth outside [0, 32] or a
+ *      handle without a scene are turned down before the handle is touched, so the surfaces, the size rt_mgpu_readback copies
+ *      and the frame rt_mgpu_last_ms times stay those of the last good frame (none, RT_ERR_NO_SURFACES, on a fresh handle).
+ *      rt_mgpu_context: the context of device slot `slot` (0 <= slot < rt_mgpu_device_count), BORROWED -- the handle keeps
+ *      ownership, rt_destroy on it is an error of the caller's.  For tests and instrumentation (the rt_debug_* read-outs of one
+ *      device's share); RT_ERR_INVALID_ARG: NULL m or out, slot out of range. */
 typedef struct rt_mgpu rt_mgpu;
 int rt_mgpu_create(rt_mgpu **out, const int *deviceIds, int nDevices);
 int rt_mgpu_destroy(rt_mgpu *m);
@@ -1402,6 +1408,7 @@ int rt_mgpu_get_surfaces(rt_mgpu *m, void **dColor, void **dPosition, void **dNo
 int rt_mgpu_readback(rt_mgpu *m, float *gColor, float *gPosition, uint16_t *gNormal);
 int rt_mgpu_last_ms(rt_mgpu *m, float *perDeviceMs, int cap);
 const char *rt_mgpu_last_error(rt_mgpu *m);
+int rt_mgpu_context(rt_mgpu *m, int slot, rt_context **out);
 
 #ifdef __cplusplus
 }

@@ -181,6 +181,7 @@ def _signatures():
         "rt_mgpu_readback": (ci, [vp, vp, vp, vp]),
         "rt_mgpu_last_ms": (ci, [vp, P(cf), ci]),
         "rt_mgpu_last_error": (cs, [vp]),
+        "rt_mgpu_context": (ci, [vp, ci, P(vp)]),
     }
 
 
@@ -1459,6 +1460,19 @@ class RayTracer(_Handle):
                    _dev_ptr(stream))
 
 
+class _BorrowedRayTracer(RayTracer):
+    """A RayTracer view of a context somebody else owns (MultiGpuRayTracer.context): every method works on it, close() and the
+    garbage collector only let go of it -- rt_destroy is the owner's.  It is valid as long as its owner is open."""
+
+    def __init__(self, lib, ctx):
+        self.lib, self.ctx = lib, ctx
+        self._size = None
+        self._present_tickets = {}
+
+    def close(self):
+        self.ctx = None
+
+
 class MultiGpuRayTracer(_Handle):
     """rt_mgpu_*: one frame on N devices from one process; the devices' kernels store their strips straight into device 0's frame
     (include/rt_mi355.h).  `devices` may repeat an id (the N-way plan on one GPU)."""
@@ -1470,10 +1484,15 @@ class MultiGpuRayTracer(_Handle):
         self.n = len(devices)
         self._call("rt_mgpu_set_strip_rows", strip_rows)
 
-    def load(self, scene):
-        objects, lights = np.ascontiguousarray(scene.objects), np.ascontiguousarray(scene.lights)
+    def set_scene(self, objects, lights):
+        """rt_mgpu_set_scene alone: the per-frame upload, asynchronous on every context's stream (load() also sets the
+        textures, which waits for every frame in flight)."""
+        objects, lights = np.ascontiguousarray(objects), np.ascontiguousarray(lights)
         self._call("rt_mgpu_set_scene", _ptr(objects) if len(objects) else None, len(objects),
                    _ptr(lights) if len(lights) else None, len(lights))
+
+    def load(self, scene):
+        self.set_scene(scene.objects, scene.lights)
         if scene.noise is None:
             self._call("rt_mgpu_set_noise", None, 0, 0)
         else:
@@ -1486,7 +1505,30 @@ class MultiGpuRayTracer(_Handle):
         self._call("rt_mgpu_render", ctypes.byref(params))
         self._size = (params.width, params.height)
 
+    def readback(self):
+        if self._size is None:             # no frame of this handle's yet: the library says so (RT_ERR_NO_SURFACES)
+            self._call("rt_mgpu_readback", None, None, None)
+        return super().readback()
+
     def last_ms(self):
         out = (ctypes.c_float * self.n)()
         self._call("rt_mgpu_last_ms", out, self.n)
         return list(out)
+
+    def set_strip_rows(self, n):
+        """Rows per strip of the frames from now on (rt_mgpu_set_strip_rows)."""
+        self._call("rt_mgpu_set_strip_rows", int(n))
+
+    def get_surfaces(self):
+        """Device pointers (ints) of the root's full-frame gColor, gPosition, gNormal, and the root stream (a hipStream_t as an
+        int): work enqueued on it sees the whole last frame, and the next frame overwrites the surfaces only behind that work."""
+        dc, dp, dn, s = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
+        self._call("rt_mgpu_get_surfaces", ctypes.byref(dc), ctypes.byref(dp), ctypes.byref(dn), ctypes.byref(s))
+        return dc.value, dp.value, dn.value, s.value
+
+    def context(self, slot):
+        """Device slot `slot`'s context as a RayTracer that does not own it (rt_mgpu_context): for the debug_* read-outs of one
+        device's share.  Valid while this handle is open; closing the view destroys nothing."""
+        c = ctypes.c_void_p()
+        self._call("rt_mgpu_context", int(slot), ctypes.byref(c))
+        return _BorrowedRayTracer(self.lib, c)

@@ -38,8 +38,11 @@ def test_n_way_frame_equals_single_device_render(host, cfg, size):
 
 
 def test_scene_updates_and_consumers_between_n_way_frames(host, oracle):
-    """Per-frame rt_mgpu_set_scene (the reference re-uploads its SSBOs every frame) and frames issued back to back without a sync:
-    every frame shows the scene that was current when it was issued; a consumer on the root stream sees whole frames."""
+    """Per-frame scene updates on one handle (the reference re-uploads its SSBOs every frame): six frames, two scenes taken in turn
+    through load(), each frame read back -- which waits for it -- and compared with the oracle's frame of the scene that was
+    current when it was issued; then a window that is not the whole frame is refused.  Nothing here is in flight while the next
+    frame is issued and nothing is enqueued on the root stream: frames issued back to back with a consumer there are
+    tests/test_mgpu_frames.py's."""
     import ctypes
     a = scenes.make_scene(2, host.generate_aabb)
     b = scenes.make_scene(2, host.generate_aabb)
